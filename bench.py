@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- HMC leapfrog steps/s on a 256^3 grid (BASELINE.json metric), one chain per GPU.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 A "step" is one leapfrog step (HMC.cc:284-365 body: half kick, M^-1 p, drift, one full force evaluation,
@@ -10,6 +10,15 @@ half kick).  The timed region is ONE trajectory of exactly K steps through the C
 input grids already resident in HBM, bracketed by barrier + torch.cuda.synchronize().  Each rank runs its own
 independent chain (weak scaling); the only collective is the epsilon-statistics all-gather (one 520-byte packet
 per rank per sample, bchmc_eps_exchange; RCCL).  Rank 0 prints one JSON line.
+
+A plain run sets up, warms up, times the K steps, writes the outputs of the timed trajectory if --dump-outputs is
+given and prints the line: `value` (steps/s), `ms_per_step` (wall milliseconds of one timed step) and the roofline
+fraction of the timed trajectory itself.  --full adds everything that takes work of its own: the per-kernel HIP-event
+pass, the `sustained` trajectory, the CPU baseline with `parity_at_size`, the probe of the library's RCCL transport on
+multi-rank runs and the roofline figures read from the committed profiles.
+
+The inputs are the same from run to run for the same arguments: seeded host fields, and mock data from the forward
+model of the truth field on a deterministic-mode handle (fixed-point mass assignment, bitwise repeatable).
 
 `python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment launches its own N ranks: the parent
 process starts N children (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_ADDR=127.0.0.1 / MASTER_PORT set) before it
@@ -27,6 +36,8 @@ sys.path.insert(0, ROOT)
 
 ALGO_BYTES_PER_CELL_STEP = 544  # 68 real arrays x 8 B per leapfrog step (default force path)
 HBM_PEAK_GBS = 8000.0           # MI355X_MICROARCH.md: HBM3E 8 TB/s spec
+DUMP_MAX_CELLS = 1 << 21        # --dump-outputs: cells per array at most (2 arrays x 16 MB in float64)
+DUMP_SEED = 2024                # --dump-outputs: Philox seed of the sampled cells
 
 
 def parse():
@@ -42,17 +53,23 @@ def parse():
     ap.add_argument("--mk", type=int, default=3, help="masskernel 0 NGP / 1 CIC / 2 TSC / 3 SPH (default; anything else is a "
                                                       "separate line, never the headline)")
     ap.add_argument("--calc-h", type=int, default=2, help="likelihood-force variant 0..3 (default 2; mk != 3 needs 0 or 1)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: per-kernel breakdown, sustained "
+                         "trajectory, CPU baseline + parity at size, RCCL-transport probe (N > 1), profile roofline figures")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed trajectory returned (q1, p1, steps_done) as DIR/<name>.npy, float64; grids "
+                         "above %d cells: the same fixed, seeded sample of cells in every run" % DUMP_MAX_CELLS)
     ap.add_argument("--sustained", type=float, default=3.0,
-                    help="N = 1: additionally run ONE trajectory long enough for about this many seconds and report it as "
-                         "`sustained` next to the headline (untimed part of the run; 0 switches it off)")
+                    help="with --full and N = 1: additionally run ONE trajectory long enough for about this many seconds and "
+                         "report it as `sustained` next to the headline (untimed part of the run; 0 switches it off)")
     ap.add_argument("--no-rccl-probe", action="store_true",
-                    help="N > 1 on nccl: skip the untimed ncclAllGather through the library's own RCCL transport")
+                    help="with --full, N > 1 on nccl: skip the untimed ncclAllGather through the library's own RCCL transport")
     ap.add_argument("--force-rccl-probe", action="store_true",
                     help="rehearsal: run that probe whatever the backend (two ranks on one device make RCCL refuse: the "
                          "error path)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-nx", type=int, default=0, help="grid of the CPU-baseline sample (default: same as --nx)")
-    ap.add_argument("--no-kernel-profile", action="store_true")
+    ap.add_argument("--no-kernel-profile", action="store_true", help="with --full: skip the per-kernel pass")
     ap.add_argument("--fp32", action="store_true", help="fp32 field arrays (BASELINE config 5); tolerance re-stated")
     ap.add_argument("--chains-per-gpu", type=int, default=1, choices=[1, 2],
                     help="2: additionally measure the throughput mode -- two chains per GPU on disjoint halves of the "
@@ -96,6 +113,23 @@ def _rel_l2(a, b):
     import numpy as np
     a, b = np.asarray(a).ravel(), np.asarray(b).ravel()
     return float(np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-300))
+
+
+def dump_outputs(directory, q1, p1, done):
+    """--dump-outputs: what a caller of the timed path receives -- the end state q1, p1 (float64 device arrays) and the
+    number of steps done -- as <directory>/<name>.npy.  Above DUMP_MAX_CELLS cells both arrays are sampled at the same
+    DUMP_MAX_CELLS cells, drawn without replacement by a Philox generator seeded with DUMP_SEED and sorted."""
+    import numpy as np
+    import torch
+    os.makedirs(directory, exist_ok=True)
+    n = q1.numel()
+    if n > DUMP_MAX_CELLS:
+        cells = np.sort(np.random.Generator(np.random.Philox(DUMP_SEED)).choice(n, DUMP_MAX_CELLS, replace=False))
+        idx = torch.from_numpy(cells).to(q1.device)
+        q1, p1 = q1.index_select(0, idx), p1.index_select(0, idx)
+    for name, a in (("q1", q1), ("p1", p1)):
+        np.save(os.path.join(directory, name + ".npy"), a.cpu().numpy().astype(np.float64))
+    np.save(os.path.join(directory, "steps_done.npy"), np.array([done], dtype=np.float64))
 
 
 def cpu_baseline(params, case_arrays, q0, p0, eps, reps=3):
@@ -358,16 +392,28 @@ def main():
     ring = EpsRing()
 
     f = inputs.make_fields(params)
-    engine = Engine(params, device=local_rank, precision=1 if args.fp32 else 0)
-    engine.upload(signal_PS=f["signal_PS"], mass_f=f["mass_f"])
-    # mock data: forward model of the truth field on the GPU, then the reference's noise model
+    precision = 1 if args.fp32 else 0
+    # mock data: forward model of the truth field on the GPU, then the reference's noise model.  The mock data come from
+    # a deterministic-mode handle of its own (fixed-point mass assignment), so that the inputs of the timed path are
+    # bitwise the same in every run with the same arguments.
+    rsd_fwd = rsd if params.likelihood == 1 else 0
+    placeholders = dict(nobs=np.zeros(params.N), window=np.ones(params.N), noise=np.ones(params.N))
     if params.likelihood != 3:
-        engine.upload(nobs=np.zeros(params.N), window=np.ones(params.N), noise=np.ones(params.N))
-        engine.forward(f["truth"], rsd if params.likelihood == 1 else 0)
-        dX = engine.fetch("deltaX").reshape((params.Nx,) * 3)
+        fwd = Engine(params, device=local_rank, precision=precision, deterministic=1)
+        fwd.upload(signal_PS=f["signal_PS"], mass_f=f["mass_f"], **placeholders)
+        fwd.forward(f["truth"], rsd_fwd)
+        dX = fwd.fetch("deltaX").reshape((params.Nx,) * 3)
+        fwd.close()
     else:
         dX = np.zeros((params.Nx,) * 3)
     window, noise, nobs = inputs.mock_observations(params, dX, delta_lag=f["truth"])
+    engine = Engine(params, device=local_rank, precision=precision)
+    engine.upload(signal_PS=f["signal_PS"], mass_f=f["mass_f"])
+    if params.likelihood != 3:
+        # the same forward pass on the timed handle, result unused: it leaves the handle as it always was before the
+        # warm-up (the binning's record slots sized at this sync point)
+        engine.upload(**placeholders)
+        engine.forward(f["truth"], rsd_fwd)
     engine.upload(window=window, noise=noise, nobs=nobs)
     arrays = dict(signal_PS=f["signal_PS"], mass_f=f["mass_f"], window=window, noise=noise, nobs=nobs)
 
@@ -429,20 +475,23 @@ def main():
                                 collective["ranks_seen"] == list(range(world)) and collective["records"] == world)
     else:
         collective["ok"] = collective["ranks_seen"] == [0] and collective["records"] == 1
-    if distributed and ((args.backend == "nccl" and not args.single_device and not args.no_rccl_probe) or
+    if done != args.steps:
+        print("bench.py: runaway guard fired after %d of %d steps" % (done, args.steps), file=sys.stderr)
+    finite = bool(torch.isfinite(q1).all().item() and torch.isfinite(p1).all().item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, q1, p1, done)   # before any later pass of --full overwrites q1 / p1
+
+    if distributed and ((args.full and args.backend == "nccl" and not args.single_device and not args.no_rccl_probe) or
                         args.force_rccl_probe):
         try:
             collective["rccl_native"] = rccl_native_probe(dist, dev, rank, world, eps, args.steps,
                                                           timeout_s=20.0 if args.force_rccl_probe else 90.0)
         except Exception as e:  # the probe must never cost the measurement
             collective["rccl_native"] = dict(ok=False, error="%s: %s" % (type(e).__name__, e))
-    if done != args.steps:
-        print("bench.py: runaway guard fired after %d of %d steps" % (done, args.steps), file=sys.stderr)
-    finite = bool(torch.isfinite(q1).all().item() and torch.isfinite(p1).all().item())
 
     # ---- per-kernel HIP-event breakdown (separate, untimed pass) -------------------------------------
     kernels = dominant = None
-    if not args.no_kernel_profile:
+    if args.full and not args.no_kernel_profile:
         ksteps = min(args.steps, 10)
         engine.profile(True)
         engine.leapfrog_device(q0, p0, q1, p1, eps, ksteps)
@@ -459,7 +508,7 @@ def main():
                         if dom in ("k_scatter_sph", "k_gather_sph") else "hbm")
 
     sustained = None
-    if args.sustained > 0 and world == 1:
+    if args.full and args.sustained > 0 and world == 1:
         sustained = sustained_run(engine, q0, p0, q1, p1, eps, 1e3 * wall / args.steps, args.sustained, torch)
     throughput_mode = None
     if args.chains_per_gpu == 2 and world == 1:
@@ -472,7 +521,7 @@ def main():
         algo = ALGO_BYTES_PER_CELL_STEP // (2 if args.fp32 else 1)  # 272 N bytes per step with fp32 fields
         achieved = algo * N * args.steps / (gpu_ms * 1e-3) / 1e9  # per GPU, device time
         traffic, traffic_src = (pmc_traffic(params.Nx, "fp32" if args.fp32 else "fp64")
-                                if (rsd and params.likelihood == 1 and headline_variant) else (None, None))
+                                if (args.full and rsd and params.likelihood == 1 and headline_variant) else (None, None))
         out = {
             "metric": "HMC leapfrog steps/sec on %d^3 grid" % params.Nx + ("" if headline_variant else
                                                                         " (variant mk=%d calc_h=%d: not the headline)" % (args.mk, args.calc_h)),
@@ -517,15 +566,15 @@ def main():
                 "dominant_kernel": dominant,
                 "kernels": kernels,
                 # the two particle-mesh kernels are fp64-VALU bound, not HBM bound: reported against 78.6 TFLOP/s
-                "valu": valu_roofline() if (rsd and params.likelihood == 1 and not args.fp32 and params.Nx == 256 and
-                                            headline_variant) else None,
+                "valu": valu_roofline() if (args.full and rsd and params.likelihood == 1 and not args.fp32 and
+                                            params.Nx == 256 and headline_variant) else None,
             },
         }
         if throughput_mode is not None:
             out["throughput_mode"] = throughput_mode
         if sustained is not None:
             out["sustained"] = sustained
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             cpu_params = params
             cq0, cp0, carr = f["q0"], p0_host, arrays
             if args.cpu_nx and args.cpu_nx != params.Nx:

@@ -8,7 +8,7 @@ steps=10
 export TMPDIR=/tmp
 out=gpurun_out
 mkdir -p $out
-python3 bench.py --steps 100 --warmup 10 "$@" > $out/${tag}_bench.json 2> $out/${tag}_bench.err
+python3 bench.py --full --steps 100 --warmup 10 "$@" > $out/${tag}_bench.json 2> $out/${tag}_bench.err
 tail -c 600 $out/${tag}_bench.json; echo
 rocprofv3 --kernel-trace --stats -d $out/${tag}_stats -o st --output-format csv -- python3 bench.py --steps 20 --warmup 2 --no-cpu-baseline --sustained 0 --no-kernel-profile "$@" > $out/${tag}_stats.log 2>&1
 cp $(find $out/${tag}_stats -name '*kernel_stats.csv' | head -1) $out/${tag}_kernel_stats.csv

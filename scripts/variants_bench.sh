@@ -4,7 +4,7 @@
 tag=${1:-r03}; out=gpurun_out; mkdir -p $out
 export TMPDIR=/tmp
 line() {  # name, env, bench args
-  env $2 timeout -k 10 400 python3 bench.py --steps 40 --warmup 4 --no-cpu-baseline --sustained 0 $3 2>$out/vb.err > $out/vb.json || { echo "FAILED $1"; tail -3 $out/vb.err; return; }
+  env $2 timeout -k 10 400 python3 bench.py --full --steps 40 --warmup 4 --no-cpu-baseline --sustained 0 $3 2>$out/vb.err > $out/vb.json || { echo "FAILED $1"; tail -3 $out/vb.err; return; }
   python3 - "$1" $out/vb.json <<'PY'
 import json, sys
 d = json.load(open(sys.argv[2]))

@@ -170,3 +170,26 @@ def test_bench_refuses_more_ranks_than_gpus():
                        env={k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")})
     assert r.returncode == 2
     assert b"refusing to run" in r.stderr and r.stdout.strip() == b""
+
+
+def test_bench_dump_outputs_writes_a_fixed_sample(tmp_path):
+    """`bench.py --dump-outputs DIR`: q1 / p1 / steps_done as float64 .npy; above DUMP_MAX_CELLS cells both arrays are
+    sampled at the same cells in every run, below it they are written whole (CPU tensors stand in for device ones)."""
+    import importlib.util
+    import torch
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    n = bench.DUMP_MAX_CELLS + 4096
+    q = torch.arange(n, dtype=torch.float64)
+    p = -q
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), q, p, 7)
+    qa, qb = np.load(tmp_path / "a" / "q1.npy"), np.load(tmp_path / "b" / "q1.npy")
+    pa = np.load(tmp_path / "a" / "p1.npy")
+    assert qa.dtype == np.float64 and qa.shape == (bench.DUMP_MAX_CELLS,) and np.array_equal(qa, qb)
+    assert np.array_equal(pa, -qa) and np.all(np.diff(qa) > 0) and qa[-1] < n   # same distinct cells, sorted
+    assert np.load(tmp_path / "a" / "steps_done.npy").tolist() == [7.0]
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= 64 << 20
+    bench.dump_outputs(str(tmp_path / "small"), q[:1000], p[:1000], 7)
+    assert np.array_equal(np.load(tmp_path / "small" / "q1.npy"), np.arange(1000.0))

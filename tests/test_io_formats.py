@@ -11,20 +11,23 @@ from tests.util import GOLDEN_DIR
 EXPECTED = [18012.18201, 280.22, 300021.850, 3.14, 2., 333888., 807520.20, 170412.0]  # test/io_array.cpp:67-74
 
 
-def test_read_array_reads_the_reference_fixture():
-    a = bio.read_array(os.path.join(GOLDEN_DIR, "reference_io_array"), 8)  # extension added like the reference does
+def test_read_array_reads_the_reference_fixture(monkeypatch):
+    # a bare name: the extension rule looks for a '.' anywhere in the name, so a dotted directory would defeat it
+    monkeypatch.chdir(GOLDEN_DIR)
+    a = bio.read_array("reference_io_array", 8)  # extension added like the reference does
     assert a.tolist() == EXPECTED
 
 
-def test_write_read_round_trip_and_byte_identity(tmp_path):
+def test_write_read_round_trip_and_byte_identity(tmp_path, monkeypatch):
     """test/io_array.cpp:34-59 (round trip), plus: our writer reproduces the reference file byte for byte."""
-    fn = str(tmp_path / "arr")
+    monkeypatch.chdir(tmp_path)  # bare names, as in the reference's test: the temporary directory may hold a '.'
+    fn = "arr"
     bio.write_array(fn, np.array(EXPECTED))
     assert os.path.exists(fn + ".dat")
     assert open(fn + ".dat", "rb").read() == open(os.path.join(GOLDEN_DIR, "reference_io_array.dat"), "rb").read()
     assert bio.read_array(fn, 8).tolist() == EXPECTED
     with pytest.raises(RuntimeError):
-        bio.read_array(str(tmp_path / "missing"), 8)
+        bio.read_array("missing", 8)
     with pytest.raises(RuntimeError):
         bio.read_array(fn, 9)
     assert bio.add_extension_if_missing("a.b") == "a.b" and bio.add_extension_if_missing("a") == "a.dat"

@@ -1,9 +1,11 @@
 """Boundary conformance against the reference's REAL headers.
 
 barlib cannot be compiled in this image (fftw3.h / gsl are absent), so the C++ host layer is compiled against
-``HamilView`` / ``HamilNumericalView`` and the barlib-side shim in INTEGRATION.md is a listing.  This test reads
-``/root/reference/barlib/include/struct_hamil.h``, ``struct_main.h``, ``curses_funcs.h`` and ``src/HMC.cc`` as TEXT (no
-code from the tree is imported, built or copied; nothing travels to the GPU box, where the test is skipped) and asserts
+``HamilView`` / ``HamilNumericalView`` and the barlib-side shim in INTEGRATION.md is a listing.  The reference's
+``barlib/include/struct_hamil.h``, ``struct_main.h``, ``curses_funcs.h`` and ``src/HMC.cc`` were read as TEXT by
+``parse_reference`` below (no code from the tree is imported, built or copied) into the data fixture
+``tests/golden/reference_headers.json`` -- member tables, function-pointer names, four signatures, the call order in
+HamiltonianMC; ``tests/golden/make_reference_headers.py`` regenerates it -- and this test asserts
 
   * every member of HamilNumericalView / HamilView that claims to be a HAMIL_NUMERICAL / HAMIL_DATA member exists
     upstream under that name with that type (input pointers may add ``const``); members the shim adds are listed here
@@ -14,15 +16,18 @@ code from the tree is imported, built or copied; nothing travels to the GPU box,
   * the four function signatures the listing replaces equal the ones in HMC.cc (return type, name, parameter types);
   * the step-size keys of EpsAdaptConfig are NUMERICAL / HAMIL_NUMERICAL members of the same type.
 """
+import json
 import os
 import re
 
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference/barlib"
-
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason="the reference tree is only present in the build container")
+FIXTURE = os.path.join(ROOT, "tests", "golden", "reference_headers.json")
+STRUCTS = (("struct_hamil.h", "HAMIL_NUMERICAL"), ("struct_hamil.h", "HAMIL_DATA"), ("struct_main.h", "NUMERICAL"),
+           ("struct_main.h", "OBSERVATIONAL"), ("struct_main.h", "DATA"), ("curses_funcs.h", "CURSES_STRUCT"))
+LISTING_FUNCTIONS = ("Hamiltonian_EoM", "delta_Hamiltonian", "kinetic_term", "psi")
+STATE_ARRAYS = ("signali", "signalf", "momentai", "momentaf")
 
 
 def _strip_comments(text):
@@ -87,18 +92,40 @@ def _read(*parts):
         return f.read()
 
 
+def _function_pointers(text):
+    return sorted(set(re.findall(r"\(\s*\*\s*(\w+)\s*\)", text)))
+
+
+def _call_order(hmc):
+    """HamiltonianMC's back-to-back Hamiltonian_EoM / delta_Hamiltonian calls (HMC.cc:455-459): their array arguments
+    and the state arrays assigned between the two calls; None when the two calls are not found in sequence."""
+    m = re.search(r"Hamiltonian_EoM\s*\(\s*hd\s*,([^;]*?),\s*seed\s*,\s*data\s*\)\s*;(.*?)delta_Hamiltonian\s*\(\s*hd\s*,([^;]*?),\s*data\s*\)",
+                  hmc, flags=re.S)
+    if not m:
+        return None
+    norm = lambda s: [a.strip() for a in s.split(",")]  # noqa: E731
+    written = re.findall(r"\b(%s)\b[^;]*=" % "|".join(STATE_ARRAYS), m.group(2))
+    return dict(eom_args=norm(m.group(1)), dh_args=norm(m.group(3)), arrays_written_between=sorted(set(written)))
+
+
+def parse_reference(barlib):
+    """The fixture's content, from the ``barlib`` directory of a reference checkout."""
+    text = {h: _strip_comments(_read(barlib, "include", h)) for h in ("struct_hamil.h", "struct_main.h", "curses_funcs.h")}
+    hmc = _strip_comments(_read(barlib, "src", "HMC.cc"))
+    return dict(structs={name: _members(_struct_body(text[h], name)) for h, name in STRUCTS},
+                function_pointers={h: _function_pointers(text[h]) for h in ("struct_hamil.h", "struct_main.h")},
+                signatures={fn: _signature(hmc, fn) for fn in LISTING_FUNCTIONS},
+                call_order=_call_order(hmc))
+
+
 @pytest.fixture(scope="module")
 def ref():
-    hamil = _strip_comments(_read(REF, "include", "struct_hamil.h"))
-    main = _strip_comments(_read(REF, "include", "struct_main.h"))
-    curses = _strip_comments(_read(REF, "include", "curses_funcs.h"))
-    return dict(HAMIL_NUMERICAL=_members(_struct_body(hamil, "HAMIL_NUMERICAL")),
-                HAMIL_DATA=_members(_struct_body(hamil, "HAMIL_DATA")),
-                NUMERICAL=_members(_struct_body(main, "NUMERICAL")),
-                OBSERVATIONAL=_members(_struct_body(main, "OBSERVATIONAL")),
-                DATA=_members(_struct_body(main, "DATA")),
-                CURSES_STRUCT=_members(_struct_body(curses, "CURSES_STRUCT")),
-                hmc=_strip_comments(_read(REF, "src", "HMC.cc")))
+    with open(FIXTURE) as f:
+        d = json.load(f)
+    out = dict(d["structs"])
+    out.update(function_pointers=d["function_pointers"], call_order=d["call_order"],
+               signatures={fn: (r, list(params)) for fn, (r, params) in d["signatures"].items()})
+    return out
 
 
 @pytest.fixture(scope="module")
@@ -167,10 +194,9 @@ def test_view_members_are_hamil_data_members_or_declared_additions(ref, ours):
     assert seen_additions == SHIM_ONLY_VIEW & set(ours["view"]), "stale entry in SHIM_ONLY_VIEW"
     assert ref["NUMERICAL"]["likelihood"] == "int" == ours["view"]["likelihood"]
     # the five plugin function pointers the likelihood enum stands for exist in both structs (struct_main.h:66-72)
-    hamil_txt = _strip_comments(_read(REF, "include", "struct_hamil.h"))
-    main_txt = _strip_comments(_read(REF, "include", "struct_main.h"))
+    fp = ref["function_pointers"]
     for fn in ("partial_f_delta_x_log_like", "log_like", "grad_f_delta_x_comp", "log_prior", "grad_log_prior"):
-        assert re.search(r"\(\s*\*\s*%s\s*\)" % fn, hamil_txt) and re.search(r"\(\s*\*\s*%s\s*\)" % fn, main_txt)
+        assert fn in fp["struct_hamil.h"] and fn in fp["struct_main.h"]
 
 
 def test_eps_adapt_keys_are_reference_members(ref, ours):
@@ -196,7 +222,7 @@ def _signature(text, name):
 
 @pytest.mark.parametrize("fn", ["Hamiltonian_EoM", "delta_Hamiltonian", "kinetic_term", "psi"])
 def test_listing_signatures_equal_the_reference(ref, ours, fn):
-    assert _signature(ours["listing"], fn) == _signature(ref["hmc"], fn)
+    assert _signature(ours["listing"], fn) == ref["signatures"][fn]
 
 
 def test_listing_touches_only_existing_members_and_declared_entry_points(ref, ours):
@@ -231,10 +257,7 @@ def test_listing_touches_only_existing_members_and_declared_entry_points(ref, ou
 def test_call_order_the_shim_relies_on(ref):
     """HamiltonianMC calls Hamiltonian_EoM and delta_Hamiltonian back to back on the same four arrays (HMC.cc:455-459):
     the contract behind bchmc_leapfrog_dh / HamilView::reuse_eom_energies."""
-    m = re.search(r"Hamiltonian_EoM\s*\(\s*hd\s*,([^;]*?),\s*seed\s*,\s*data\s*\)\s*;(.*?)delta_Hamiltonian\s*\(\s*hd\s*,([^;]*?),\s*data\s*\)",
-                  ref["hmc"], flags=re.S)
-    assert m, "HamiltonianMC no longer calls the two functions in sequence"
-    norm = lambda s: [a.strip() for a in s.split(",")]  # noqa: E731
-    assert norm(m.group(1)) == norm(m.group(3)) and len(norm(m.group(1))) == 4
-    between = m.group(2)
-    assert not re.search(r"\b(signali|signalf|momentai|momentaf)\b[^;]*=", between), "the arrays are written in between"
+    co = ref["call_order"]
+    assert co, "HamiltonianMC no longer calls the two functions in sequence"
+    assert co["eom_args"] == co["dh_args"] and len(co["eom_args"]) == 4
+    assert not co["arrays_written_between"], "the arrays are written in between"
