@@ -14,6 +14,7 @@
 #include <rocprofiler-sdk-roctx/roctx.h>
 
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -93,6 +94,18 @@ struct bchmc_handle {
   int *stop = nullptr;
   unsigned long long *steps_done = nullptr;
   double *h_part = nullptr;                          // pinned host staging for partials
+  // draw_momenta from a GSL mt19937 state (mt_draw.hpp), set up on the first such draw: S words per segment, B
+  // segments, C = B S words per pass, G Gaussians per draw
+  struct MtDraw {
+    long long S = 0, C = 0, G = 0;
+    int B = 0;
+    uint32_t *poly = nullptr, *win = nullptr, *words = nullptr, *st = nullptr;
+    unsigned long long *nz = nullptr, *nzoff = nullptr, *acc = nullptr, *accoff = nullptr, *lastend = nullptr;
+    unsigned long long *res = nullptr;  // 8 counters + the 624-word end state
+    unsigned long long *h_io = nullptr; // pinned mirror of res (the input window goes out through its state words)
+    double *gauss = nullptr;
+    double setup_ms = 0.;
+  } mt;
   double *spec_bins = nullptr;                       // measure_spectrum's 3 * n_bin accumulators
   size_t spec_cap = 0;
   // host-array entry points: caller arrays are pageable, so they cross PCIe through two pinned staging chunks
@@ -1981,6 +1994,32 @@ struct Pipe {
     return store_real(h, src, d_out);
   }
 
+  // Momenta from the Gaussians of an exact draw (mt_draw.hpp): cp = G of create_GARFIELD placed directly (the R2C of
+  // its C2R / N), plus R2C[sqrt(mass_r) g] for a real-space mass -- what bchmc_chain_set_momenta makes of
+  // draw_momenta's array.
+  static int mt_place(bchmc_handle *h) {
+    const long long N = h->g.N, Nh = h->g.Nhp;
+    const int n = h->g.n;
+    ProfScope ps(h, BCHMC_K_OTHER);
+    HIPCHK(hipMemsetAsync(h->cp, 0, 2 * (size_t)Nh * sizeof(T), h->stream));
+    if (h->mass_fs) {
+      const long long cells = (long long)(n / 2 + 1) * (n / 2 + 1) * (n / 2 + 1);
+      const double amp = (double)N * (double)N / (h->g.L * h->g.L * h->g.L);  // random.cpp:88-90
+      k_mt_place<T><<<nblk_stride(cells), 256, 0, h->stream>>>(n, h->g.nhp, h->mt.gauss, R(h->in_arr[BCHMC_F_MASS_F]),
+                                                               amp, C(h->cp));
+      HIPCHK(hipGetLastError());
+    }
+    if (h->mass_rs) {
+      k_mt_real_space<T><<<nblk_stride(N), 256, 0, h->stream>>>(N, h->mt.gauss + (h->mass_fs ? 2 * N : 0),
+                                                                R(h->in_arr[BCHMC_F_MASS_R]), R(h->iop));
+      HIPCHK(hipGetLastError());
+      CHK(fft_exec(h, h->r2c1, h->iop, h->tC, BCHMC_K_FFT_R2C));
+      k_color_momenta<T><<<nblk_stride(Nh), 256, 0, h->stream>>>(Nh, C(h->tC), nullptr, C(h->cp), 1);
+      HIPCHK(hipGetLastError());
+    }
+    return BCHMC_OK;
+  }
+
   static int upload(bchmc_handle *h, bchmc_field field, const double *d_src) {
     CHK(load_real(h, d_src, R(h->in_arr[field])));
     const double normFS = h->g.L * h->g.L * h->g.L / (double)h->g.N;  // FOURIER_DEF_2, HMC_help.cc:25-27
@@ -2035,6 +2074,151 @@ int validate_config(const bchmc_config *c, std::string &why) {
     return BCHMC_ERR_ARG;
   }
   return BCHMC_OK;
+}
+
+// ---- draw_momenta from a GSL mt19937 state (mt_draw.hpp) ------------------------------------------------------------
+const mt_host::Phi &mt_phi() {
+  static std::once_flag once;
+  static mt_host::Phi phi;
+  std::call_once(once, [] { phi = mt_host::make_phi(); });
+  return phi;
+}
+
+// GSL state `steps` outputs later.  mti = (Q - 1) mod 624 + 1 for the position Q = mti_in + steps: GSL regenerates a
+// block when the next output needs it, so after any output 1 <= mti <= 624; mt[] = the 624 words from Q - mti on.
+int mt_jump_gsl(const uint32_t *mt_in, int32_t mti_in, uint64_t steps, uint32_t *mt_out, int32_t *mti_out) {
+  if (mti_in < 0 || mti_in > kMtN) return BCHMC_ERR_ARG;
+  if (steps == 0) {
+    std::memmove(mt_out, mt_in, kMtN * sizeof(uint32_t));
+    *mti_out = mti_in;
+    return BCHMC_OK;
+  }
+  const unsigned long long Q = (unsigned long long)mti_in + steps, mo = (Q - 1) % kMtN + 1, base = Q - mo;
+  if (base == 0) {
+    std::memmove(mt_out, mt_in, kMtN * sizeof(uint32_t));
+  } else {
+    const mt_host::Phi &phi = mt_phi();
+    if (!phi.ok) return BCHMC_ERR_STATE;
+    uint32_t tmp[kMtN];
+    mt_host::window_ahead(phi, mt_in, base, tmp);  // mt_in is the window at position 0
+    std::memcpy(mt_out, tmp, sizeof tmp);
+  }
+  *mti_out = (int32_t)mo;
+  return BCHMC_OK;
+}
+
+// Once per handle: segment length S, segments B, the jump polynomials x^(b S - 1) mod phi (b = 1 .. B-1), buffers.
+// Capacity per pass: 2.546 words per Gaussian (4/pi pairs of 2 words per accepted one) + 12 sigma + 4 blocks.
+// BCHMC_MT_SEGMENT_WORDS / BCHMC_MT_CAPACITY (tests) set S and the capacity.
+int mt_setup(bchmc_handle *h) {
+  auto &m = h->mt;
+  if (m.words) return BCHMC_OK;
+  const auto t0 = std::chrono::steady_clock::now();
+  const mt_host::Phi &phi = mt_phi();
+  if (!phi.ok) return h->fail(BCHMC_ERR_STATE, "MT19937 characteristic polynomial: Berlekamp-Massey did not give degree 19937");
+  const long long N = h->g.N;
+  m.G = (h->mass_fs ? 2 * N : 0) + (h->mass_rs ? N : 0);
+  double cap = std::ceil(2.546 * (double)m.G + 12. * 1.18 * std::sqrt((double)m.G)) + 4. * kMtN;
+  if (const char *v = std::getenv("BCHMC_MT_CAPACITY")) cap = std::max(2. * kMtN, std::atof(v));
+  int ncu = 256;
+  HIPCHK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, h->c.device));
+  auto round624 = [](double w) { return (long long)std::ceil(w / kMtN) * kMtN; };
+  long long S = std::max(round624(cap / std::max(ncu, 1)), 4LL * kMtN);
+  if (const char *v = std::getenv("BCHMC_MT_SEGMENT_WORDS")) S = std::max(round624(std::atof(v)), (long long)kMtN);
+  const long long B = (long long)std::ceil(cap / (double)S);
+  if (B * S >= (1LL << 32) || B > (1 << 20))
+    return h->fail(BCHMC_ERR_UNSUPPORTED, "exact momentum draw: %lld words per pass exceed 32-bit positions", B * S);
+  m.S = S, m.B = (int)B, m.C = B * S;
+  std::vector<uint32_t> polys((size_t)std::max<long long>(B - 1, 1) * kMtPolyWords, 0);
+  if (B > 1) {
+    mt_host::Poly p = mt_host::xpow(phi, (unsigned long long)S - 1);
+    const mt_host::Poly J = B > 2 ? mt_host::xpow(phi, (unsigned long long)S) : p;
+    for (long long b = 1; b < B; b++) {
+      mt_host::to_words(p, polys.data() + (size_t)(b - 1) * kMtPolyWords);
+      if (b + 1 < B) p = mt_host::mulmod(phi, p, J);
+    }
+  }
+  CHK(dev_alloc(h, &m.poly, polys.size()));
+  CHK(dev_alloc(h, &m.win, (size_t)34 * kMtN));
+  CHK(dev_alloc(h, &m.words, (size_t)m.C));
+  CHK(dev_alloc(h, &m.st, (size_t)kMtN));
+  for (unsigned long long **p : {&m.nz, &m.nzoff, &m.acc, &m.accoff, &m.lastend}) CHK(dev_alloc(h, p, (size_t)B));
+  CHK(dev_alloc(h, &m.res, (size_t)8 + kMtN / 2));
+  CHK(dev_alloc(h, &m.gauss, (size_t)std::max(m.G, 1LL)));
+  HIPCHK(hipHostMalloc((void **)&m.h_io, (8 + kMtN / 2) * sizeof(unsigned long long)));
+  HIPCHK(hipMemcpyAsync(m.poly, polys.data(), polys.size() * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_mt_segments), hipFuncAttributeMaxDynamicSharedMemorySize,
+                             (int)kMtSegLds));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  m.setup_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return BCHMC_OK;
+}
+
+// One pass: C words from the window at position P (counted from mt[0] of the caller's state), Gaussians
+// gauss[done ..) up to the G - done still needed.  Leaves res on the host in m.h_io.
+int mt_pass(bchmc_handle *h, const uint32_t *win, unsigned long long P, long long done) {
+  auto &m = h->mt;
+  ProfScope ps(h, BCHMC_K_OTHER);
+  uint32_t *io_st = reinterpret_cast<uint32_t *>(m.h_io + 8);
+  std::memcpy(io_st, win, kMtN * sizeof(uint32_t));
+  HIPCHK(hipMemcpyAsync(m.st, io_st, kMtN * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemsetAsync(m.res, 0, 8 * sizeof(unsigned long long), h->stream));
+  k_mt_window<<<1, kMtThreads, 0, h->stream>>>(m.st, m.win, 34);
+  k_mt_segments<<<m.B, kMtThreads, kMtSegLds, h->stream>>>(m.win, m.poly, m.S, m.words, m.nz);
+  k_mt_scan<<<1, kMtThreads, 0, h->stream>>>(m.nz, m.B, m.nzoff, m.res, 4, nullptr);
+  k_mt_pairs<false><<<m.B, kMtThreads, 0, h->stream>>>(m.words, m.C, m.S, m.nzoff, nullptr, m.acc, m.lastend, 0,
+                                                        nullptr, m.res);
+  k_mt_scan<<<1, kMtThreads, 0, h->stream>>>(m.acc, m.B, m.accoff, m.res, 0, m.lastend);
+  k_mt_pairs<true><<<m.B, kMtThreads, 0, h->stream>>>(m.words, m.C, m.S, m.nzoff, m.accoff, nullptr, nullptr,
+                                                       m.G - done, m.gauss + done, m.res);
+  k_mt_final<<<1, 640, 0, h->stream>>>(m.words, m.C, P, m.res, reinterpret_cast<uint32_t *>(m.res + 8));
+  HIPCHK(hipGetLastError());
+  return BCHMC_OK;
+}
+
+int mt_draw(bchmc_handle *h, uint32_t *mt, int32_t *mti, uint64_t *words_used) {
+  CHK(mt_setup(h));
+  auto &m = h->mt;
+  const int32_t mti_in = *mti;
+  uint32_t win[kMtN];
+  mt_host::gsl_to_window(mt, mti_in, win);
+  unsigned long long P = (unsigned long long)mti_in;
+  long long done = 0;
+  for (int pass = 0;; pass++) {
+    CHK(mt_pass(h, win, P, done));
+    // placed now, so that it runs while the host waits; a continuation pass places again
+    if (pass == 0) CHK(DISPATCH(h, mt_place(h)));
+    HIPCHK(hipMemcpyAsync(m.h_io, m.res, (8 + kMtN / 2) * sizeof(unsigned long long), hipMemcpyDeviceToHost,
+                          h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    const unsigned long long got = m.h_io[0];
+    if ((long long)got >= m.G - done) {
+      const unsigned long long used = P + m.h_io[2] - (unsigned long long)mti_in;
+      if (m.h_io[3]) {
+        const unsigned long long Q = P + m.h_io[2];
+        std::memcpy(mt, m.h_io + 8, kMtN * sizeof(uint32_t));
+        *mti = (int32_t)((Q - 1) % kMtN + 1);
+      } else {  // end state outside the last pass's buffer: jump there from the caller's state
+        uint32_t out[kMtN];
+        int32_t mo = 0;
+        if (mt_jump_gsl(mt, mti_in, used, out, &mo)) return h->fail(BCHMC_ERR_STATE, "MT19937 jump failed");
+        std::memcpy(mt, out, sizeof out);
+        *mti = mo;
+      }
+      if (words_used) *words_used = used;
+      if (pass > 0) CHK(DISPATCH(h, mt_place(h)));
+      return BCHMC_OK;
+    }
+    // the pass ran out of words (a far statistical tail, or a capacity set small on purpose): continue the stream
+    // after its last complete pair
+    const unsigned long long E = m.h_io[1];
+    if (E == 0) return h->fail(BCHMC_ERR_STATE, "exact momentum draw: a pass of %lld words held no complete pair", m.C);
+    done += (long long)got;
+    uint32_t next[kMtN];
+    mt_host::window_ahead(mt_phi(), win, E, next);
+    std::memcpy(win, next, sizeof next);
+    P += E;
+  }
 }
 
 }  // namespace
@@ -2394,6 +2578,11 @@ void bchmc_destroy(bchmc_handle *h) {
   for (int f = 0; f < 6; f++)
     if (h->in_arr[f]) (void)hipFree(h->in_arr[f]);
   if (h->h_part) (void)hipHostFree(h->h_part);
+  for (void *p : {(void *)h->mt.poly, (void *)h->mt.win, (void *)h->mt.words, (void *)h->mt.st, (void *)h->mt.nz,
+                  (void *)h->mt.nzoff, (void *)h->mt.acc, (void *)h->mt.accoff, (void *)h->mt.lastend,
+                  (void *)h->mt.res, (void *)h->mt.gauss})
+    if (p) (void)hipFree(p);
+  if (h->mt.h_io) (void)hipHostFree(h->mt.h_io);
   if (h->copy_stream) (void)hipStreamDestroy(h->copy_stream);
   if (h->ev_q) (void)hipEventDestroy(h->ev_q);
   if (h->h_slots) (void)hipHostFree(h->h_slots);
@@ -2654,6 +2843,30 @@ int bchmc_chain_draw_momenta(bchmc_handle *h, uint64_t seed, uint64_t attempt) {
   CHK(DISPATCH(h, chain_alloc(h)));
   CHK(DISPATCH(h, chain_draw(h, seed, attempt)));
   h->have_cp = true;
+  return BCHMC_OK;
+}
+
+int bchmc_chain_draw_momenta_mt19937(bchmc_handle *h, uint32_t mt[624], int32_t *mti, uint64_t *words_used) {
+  if (!h || !mt || !mti) return BCHMC_ERR_ARG;
+  if (*mti < 0 || *mti > 624) return h->fail(BCHMC_ERR_ARG, "mti = %d outside [0, 624]", (int)*mti);
+  ENTER(h);
+  if (h->mass_fs && !h->have[BCHMC_F_MASS_F]) return h->fail(BCHMC_ERR_STATE, "mass_f was never uploaded");
+  if (h->mass_rs && !h->have[BCHMC_F_MASS_R]) return h->fail(BCHMC_ERR_STATE, "mass_r was never uploaded");
+  CHK(DISPATCH(h, chain_alloc(h)));
+  CHK(mt_draw(h, mt, mti, words_used));
+  h->have_cp = true;
+  return BCHMC_OK;
+}
+
+int bchmc_mt19937_jump(const uint32_t mt_in[624], int32_t mti_in, uint64_t steps, uint32_t mt_out[624],
+                       int32_t *mti_out) {
+  if (!mt_in || !mt_out || !mti_out) return BCHMC_ERR_ARG;
+  return mt_jump_gsl(mt_in, mti_in, steps, mt_out, mti_out);
+}
+
+int bchmc_garfield_walk_index(uint32_t n, uint32_t i, uint32_t j, uint32_t k, uint64_t *index) {
+  if (!index || n < 2 || (n & 1) || n > (1u << 20) || i >= n || j >= n || k >= n) return BCHMC_ERR_ARG;
+  *index = mt_walk_index((int)n, (int)i, (int)j, (int)k);
   return BCHMC_OK;
 }
 

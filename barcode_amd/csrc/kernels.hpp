@@ -17,6 +17,7 @@
 #include "kspace_force.hpp"  // Force assembly, fused step boundary, rollback, Parseval energies, element-wise helpers, GRF likelihood
 #include "variants.hpp"  // NGP / CIC / TSC mass assignment and the calc_h 0 / 3 likelihood-force variants
 #include "rng.hpp"  // Philox4x32-10 momentum draw
+#include "mt_draw.hpp"  // draw_momenta from the caller's GSL mt19937 stream: jump-ahead segments, polar pairs, walk placement
 #include "tiles.hpp"  // Tile-sorted particle-mesh path: binning, scan, LDS scatter / gather kernels
 #include "tiles_low.hpp"  // NGP / CIC / TSC mass assignment and calc_h = 3's TSC interpolation on the same records
 #include "alpt.hpp"  // ALPT displacement (Lag2Eul_non_zeldovich)

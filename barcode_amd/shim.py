@@ -17,7 +17,7 @@ _lib = None
 
 SHIM_EXPORTS = ("bchmc_shim_Hamiltonian_EoM", "bchmc_shim_delta_Hamiltonian", "bchmc_shim_gradient_psi",
                 "bchmc_shim_measure_spectrum", "bchmc_shim_chain_set_state", "bchmc_shim_chain_get_state",
-                "bchmc_shim_HamiltonianMC", "bchmc_shim_release", "bchmc_shim_sizeof_view",
+                "bchmc_shim_HamiltonianMC", "bchmc_shim_HamiltonianMC_mt19937", "bchmc_shim_release", "bchmc_shim_sizeof_view",
                 "bchmc_shim_sizeof_numerical", "bchmc_shim_sizeof_attempt_log",
                 "bchmc_shim_HamiltonianMC_scripted", "bchmc_shim_kinetic_term", "bchmc_shim_psi",
                 "bchmc_shim_eps_create", "bchmc_shim_eps_destroy", "bchmc_shim_eps_append", "bchmc_shim_eps_records",
@@ -82,6 +82,8 @@ class AttemptLog(C.Structure):
 
 
 UNIFORM_FN = C.CFUNCTYPE(C.c_double, C.c_void_p)
+# bchmc_shim::mt19937_state_fn: void (*)(void *rng_state, uint32_t mt[624], int32_t *mti, int store)
+MT_STATE_FN = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_int32), C.c_int)
 
 
 def load():
@@ -108,6 +110,8 @@ def load():
     lib.bchmc_shim_chain_get_state.argtypes = [hv, _dp, C.c_char_p, sz]
     lib.bchmc_shim_HamiltonianMC.argtypes = [hv, UNIFORM_FN, C.c_void_p, C.c_uint64, ul, C.POINTER(ul),
                                              C.POINTER(AttemptLog), ul, C.POINTER(ul), C.c_char_p, sz]
+    lib.bchmc_shim_HamiltonianMC_mt19937.argtypes = [hv, UNIFORM_FN, MT_STATE_FN, C.c_void_p, ul, C.POINTER(ul),
+                                                     C.POINTER(AttemptLog), ul, C.POINTER(ul), C.c_char_p, sz]
     lib.bchmc_shim_HamiltonianMC_scripted.argtypes = [hv, _dp, ul, UNIFORM_FN, C.c_void_p, ul, C.POINTER(ul),
                                                       C.POINTER(AttemptLog), ul, C.POINTER(ul), C.c_char_p, sz]
     lib.bchmc_shim_kinetic_term.argtypes = [hv, _dp, _dp, C.c_char_p, sz]
@@ -262,6 +266,27 @@ class ShimHamil:
         self._chk(self.lib.bchmc_shim_HamiltonianMC(C.byref(self.hd), cb, None, int(seed), int(itmax),
                                                     C.byref(self.count_attempts), log, int(itmax), C.byref(n),
                                                     self._err, len(self._err)))
+        return [{k: getattr(log[i], k) for k, _ in AttemptLog._fields_} for i in range(n.value)]
+
+    def HamiltonianMC_mt19937(self, rng, itmax=2000):
+        """One sample of the C++ loop with the exact device draw from ``rng`` (a ``gsl_mt19937.GslMT19937``), which
+        supplies the uniforms too and is advanced in place.  Returns the list of attempt records."""
+        log = (AttemptLog * itmax)()
+        n = C.c_ulong(0)
+        cb = UNIFORM_FN(lambda _state: float(rng.uniform()))
+
+        def state(_rng, mt, mti, store):
+            if store:
+                rng.set_state(np.ctypeslib.as_array(mt, shape=(624,)).copy(), mti[0])
+            else:
+                key, pos = rng.get_state()
+                np.ctypeslib.as_array(mt, shape=(624,))[:] = key
+                mti[0] = pos
+
+        sf = MT_STATE_FN(state)
+        self._chk(self.lib.bchmc_shim_HamiltonianMC_mt19937(C.byref(self.hd), cb, sf, None, int(itmax),
+                                                            C.byref(self.count_attempts), log, int(itmax), C.byref(n),
+                                                            self._err, len(self._err)))
         return [{k: getattr(log[i], k) for k, _ in AttemptLog._fields_} for i in range(n.value)]
 
     def HamiltonianMC_scripted(self, script_dH, uniform, itmax=2000, log_cap=None):

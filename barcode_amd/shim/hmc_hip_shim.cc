@@ -279,6 +279,44 @@ ULONG HamiltonianMC(HamilView *hd, uniform_fn uniform, void *rng_state, uint64_t
   }
 }
 
+namespace {
+// engine of the exact-draw loop: the handle plus the caller's generator
+struct MtEngine {
+  bchmc_handle *h;
+  mt19937_state_fn state;
+  void *rng_state;
+};
+int mt_draw(void *e, uint64_t, uint64_t) {
+  MtEngine *m = static_cast<MtEngine *>(e);
+  uint32_t mt[624];
+  int32_t mti = 0;
+  m->state(m->rng_state, mt, &mti, 0);
+  const int rc = bchmc_chain_draw_momenta_mt19937(m->h, mt, &mti, nullptr);
+  if (rc == 0) m->state(m->rng_state, mt, &mti, 1);
+  return rc;
+}
+int mt_setp(void *e, const real_prec *p) { return bchmc_chain_set_momenta(static_cast<MtEngine *>(e)->h, p); }
+int mt_attempt(void *e, double eps, uint64_t neps, double *dH, double terms[6], uint64_t *done) {
+  return bchmc_chain_attempt(static_cast<MtEngine *>(e)->h, eps, neps, dH, terms, done);
+}
+int mt_accept(void *e, int a) { return bchmc_chain_accept(static_cast<MtEngine *>(e)->h, a); }
+}  // namespace
+
+ULONG HamiltonianMC_mt19937(HamilView *hd, uniform_fn uniform, mt19937_state_fn state, void *rng_state, ULONG itmax,
+                            ULONG *count_attempts, AttemptLog *log, ULONG log_cap) {
+  if (!state) throw std::runtime_error("In HamiltonianMC_mt19937: no generator state hook");
+  bchmc_handle *h = engine_for(hd);
+  MtEngine m = {h, state, rng_state};
+  const ChainOps ops = {mt_draw, mt_setp, mt_attempt, mt_accept};
+  try {
+    return HamiltonianMC_ops(hd, ops, &m, uniform, rng_state, 0, itmax, count_attempts, log, log_cap, nullptr, nullptr);
+  } catch (const std::runtime_error &e) {
+    const char *detail = bchmc_last_error(h);
+    if (detail && detail[0]) throw std::runtime_error(std::string(e.what()) + " (" + detail + ")");
+    throw;
+  }
+}
+
 ULONG HamiltonianMC_ops(HamilView *hd, const ChainOps &ops, void *engine, uniform_fn uniform, void *rng_state,
                         uint64_t seed, ULONG itmax, ULONG *count_attempts, AttemptLog *log, ULONG log_cap,
                         momenta_fn momenta, void *momenta_state) {
@@ -627,6 +665,14 @@ int bchmc_shim_HamiltonianMC_scripted(bchmc_shim::HamilView *hd, const double *s
     const bchmc_shim::ChainOps ops = {sc_draw, sc_setp, sc_attempt, sc_accept};
     *n_attempts = bchmc_shim::HamiltonianMC_ops(hd, ops, &sc, uniform, rng_state, 0, itmax, count_attempts, log, log_cap,
                                                 nullptr, nullptr);
+  });
+}
+int bchmc_shim_HamiltonianMC_mt19937(bchmc_shim::HamilView *hd, bchmc_shim::uniform_fn uniform,
+                                     bchmc_shim::mt19937_state_fn state, void *rng_state, unsigned long itmax,
+                                     unsigned long *count_attempts, bchmc_shim::AttemptLog *log, unsigned long log_cap,
+                                     unsigned long *n_attempts, char *err, size_t errlen) {
+  return guarded(err, errlen, [&] {
+    *n_attempts = bchmc_shim::HamiltonianMC_mt19937(hd, uniform, state, rng_state, itmax, count_attempts, log, log_cap);
   });
 }
 int bchmc_shim_kinetic_term(bchmc_shim::HamilView *hd, const double *momenta, double *out, char *err, size_t errlen) {

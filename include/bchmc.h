@@ -181,6 +181,16 @@ int bchmc_chain_get_momenta(bchmc_handle *h, double *p);
 /* p ~ N(0, M) on the device: counter-based Philox4x32-10, a pure function of (seed, attempt, cell).  Statistical
  * stand-in for draw_momenta (HMC_momenta.cc:42-94), whose serial GSL stream it does not reproduce. */
 int bchmc_chain_draw_momenta(bchmc_handle *h, uint64_t seed, uint64_t attempt);
+/* draw_momenta (HMC_momenta.cc:42-94) on the device from the caller's GSL mt19937 state; mt/mti in: state before the
+ * draw, out: the state GSL holds after it.  words_used may be NULL.
+ * Exactly the reference's momenta: create_GARFIELD's Gaussians in the walk of resolution_independent_random_grid_FS,
+ * then the real-space part from the same stream (polar Box-Muller, r2 without FMA contraction; log / sqrt may differ
+ * from glibc by an ulp).  The first call on a handle also precomputes the stream's jump polynomials (host, once). */
+int bchmc_chain_draw_momenta_mt19937(bchmc_handle *h, uint32_t mt[624], int32_t *mti, uint64_t *words_used);
+/* host only (tests, callers that skip ahead): the state `steps` outputs later */
+int bchmc_mt19937_jump(const uint32_t mt_in[624], int32_t mti_in, uint64_t steps, uint32_t mt_out[624], int32_t *mti_out);
+/* host only: index of cell (i, j, k) in the walk of resolution_independent_random_grid_FS (random.hpp:35-120) */
+int bchmc_garfield_walk_index(uint32_t n, uint32_t i, uint32_t j, uint32_t k, uint64_t *index);
 /* Hamiltonian_EoM + delta_Hamiltonian from the resident (q, p); terms as in bchmc_delta_hamiltonian.
  * The chain carries gradient_psi and -log L of its state from one attempt to the next: the last force evaluation of an
  * accepted trajectory (HMC.cc:349) is at the point where the next one starts, and a rejected attempt restarts from the

@@ -164,6 +164,15 @@ void chain_get_state(HamilView *hd, real_prec *x);
 ULONG HamiltonianMC(HamilView *hd, uniform_fn uniform, void *rng_state, uint64_t seed, ULONG itmax, ULONG *count_attempts,
                     AttemptLog *log, ULONG log_cap, momenta_fn momenta, void *momenta_state);
 
+// The same loop with the momenta drawn on the device from the caller's own gsl_rng (mt19937 only): every attempt reads
+// the generator's state through `state` (store = 0: fill mt / mti from the generator), draws draw_momenta's exact
+// momenta (bchmc_chain_draw_momenta_mt19937) and writes the advanced state back (store = 1) before `uniform` is called
+// for Neps -- so momenta, Neps, epsilon and the Metropolis uniform come from one stream in the reference's order
+// (HMC.cc:449, 260-261, 480).  INTEGRATION.md shows the barlib side (gsl_rng_state of a gsl_rng_mt19937).
+using mt19937_state_fn = void (*)(void *rng_state, uint32_t mt[624], int32_t *mti, int store);
+ULONG HamiltonianMC_mt19937(HamilView *hd, uniform_fn uniform, mt19937_state_fn state, void *rng_state, ULONG itmax,
+                            ULONG *count_attempts, AttemptLog *log, ULONG log_cap);
+
 // The four engine calls HamiltonianMC makes, as a table: the default binds the C ABI (bchmc_chain_*); the CPU tests
 // bind a scripted stand-in so that the loop's bookkeeping is testable without a GPU.
 struct ChainOps {
@@ -212,6 +221,10 @@ int bchmc_shim_chain_get_state(bchmc_shim::HamilView *hd, double *x, char *err, 
 int bchmc_shim_HamiltonianMC(bchmc_shim::HamilView *hd, bchmc_shim::uniform_fn uniform, void *rng_state, uint64_t seed,
                              unsigned long itmax, unsigned long *count_attempts, bchmc_shim::AttemptLog *log,
                              unsigned long log_cap, unsigned long *n_attempts, char *err, size_t errlen);
+int bchmc_shim_HamiltonianMC_mt19937(bchmc_shim::HamilView *hd, bchmc_shim::uniform_fn uniform,
+                                     bchmc_shim::mt19937_state_fn state, void *rng_state, unsigned long itmax,
+                                     unsigned long *count_attempts, bchmc_shim::AttemptLog *log, unsigned long log_cap,
+                                     unsigned long *n_attempts, char *err, size_t errlen);
 /* the same loop on a scripted engine: attempt k returns dH = script_dH[k] (CPU tests of the bookkeeping) */
 int bchmc_shim_HamiltonianMC_scripted(bchmc_shim::HamilView *hd, const double *script_dH, unsigned long n_script,
                                       bchmc_shim::uniform_fn uniform, void *rng_state, unsigned long itmax,
