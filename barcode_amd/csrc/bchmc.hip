@@ -9,6 +9,7 @@
 // float: BASELINE config 5, "fp32 field arrays"); the C ABI always exchanges double arrays.
 #include "../../include/bchmc.h"
 #include "kernels.hpp"
+#include "fft_host.hpp"
 
 #include <rocfft/rocfft.h>
 #include <rocprofiler-sdk-roctx/roctx.h>
@@ -2279,15 +2280,7 @@ int bchmc_create(const bchmc_config *cfg, bchmc_handle **out) {
   g.nh = g.n / 2 + 1;
   g.N = (long long)g.n * g.n * g.n;
   g.Nh = (long long)g.n * g.n * g.nh;
-  // Row stride: whole 128-byte lines per row for n >= 128 (measured with scripts/fft_layout_bench.hip: batch-3 3-D
-  // transforms run 15-22 % faster in fp64 and ~30 % faster in fp32 than on contiguous n/2+1 rows; no gain below).
-  {
-    // BCHMC_FFT_PAD=0 / 1 forces the padding off / on at every n (tests run the small parity cases both ways).
-    const int per_line = 128 / (int)(2 * h->esz);
-    const char *ev = getenv("BCHMC_FFT_PAD");
-    const bool pad = ev ? (ev[0] == '1') : (g.n >= 128);
-    g.nhp = pad ? (g.nh + per_line - 1) / per_line * per_line : g.nh;
-  }
+  g.nhp = fft_row_stride(g.n, (int)h->esz);  // whole 128-byte lines per row for n >= 128 (fft_host.hpp)
   g.Nhp = (long long)g.n * g.n * g.nhp;
   g.L = cfg->L;
   g.d = cfg->L / (double)cfg->Nx;
@@ -2350,19 +2343,14 @@ int bchmc_create(const bchmc_config *cfg, bchmc_handle **out) {
       if ((1 << l2) == g.n && g.n >= 32 && g.n <= 512 && g.nhp % KB == 0) {
         h->log2n = l2;
         const bool ok2 = make_plans_2d(h, 3 * (size_t)g.n, &h->r2c2d, &h->c2r2d) == BCHMC_OK;
-        // twiddles exp(-2 pi i r / n), r < n / 2, from the host's libm
-        std::vector<double> tw(g.n);
-        for (int r = 0; r < g.n / 2; r++) {
-          const double ang = -2. * M_PI * (double)r / (double)g.n;
-          tw[2 * r] = std::cos(ang);
-          tw[2 * r + 1] = std::sin(ang);
-        }
+        // twiddles exp(-2 pi i r / n), r < n / 2, from the host's libm (fft_host.hpp)
         CHK(dev_alloc_bytes(h, &h->xtw, (size_t)g.n * h->esz));
         if (h->f32) {
-          std::vector<float> twf(tw.begin(), tw.end());
+          const std::vector<float> twf = fft_twiddles<float>(g.n);
           HIPCHK(hipMemcpyAsync(h->xtw, twf.data(), twf.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));
           HIPCHK(hipStreamSynchronize(h->stream));
         } else {
+          const std::vector<double> tw = fft_twiddles<double>(g.n);
           HIPCHK(hipMemcpyAsync(h->xtw, tw.data(), tw.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
           HIPCHK(hipStreamSynchronize(h->stream));
         }
