@@ -729,6 +729,48 @@ int build_conv_table(bchmc_handle *h) {
   return BCHMC_OK;
 }
 
+// measure_spectrum's bin width |k|_max / n_bin (field_statistics.cpp:37-39)
+double spectrum_dk(const Geo &g, uint64_t n_bin) {
+  const double knyq = g.kfac * (double)(g.n / 2);
+  const double kmax = std::sqrt(knyq * knyq + knyq * knyq + knyq * knyq);
+  return kmax / (double)n_bin;
+}
+
+// measure_spectrum (field_statistics.cpp:20-90) of a half-complex transform xk in the handle's storage type: n_bin
+// bins, Hermitian mode weights (k_spectrum); kmode / power on the host, empty bins 0.  Synchronises.
+int spectrum_bins(bchmc_handle *h, const void *xk, uint64_t n_bin, double *kmode, double *power) {
+  if (h->spec_cap < 3 * (size_t)n_bin) {  // kept in the handle: barcoderunner measures a spectrum after every sample
+    if (h->spec_bins) (void)hipFree(h->spec_bins);
+    h->spec_bins = nullptr;
+    h->spec_cap = 0;
+    CHK(dev_alloc(h, &h->spec_bins, 3 * (size_t)n_bin));
+    h->spec_cap = 3 * (size_t)n_bin;
+  }
+  double *bins = h->spec_bins;
+  HIPCHK(hipMemsetAsync(bins, 0, 3 * (size_t)n_bin * sizeof(double), h->stream));
+  const Geo &g = h->g;
+  const double dk = spectrum_dk(g, n_bin);
+  const int grid = std::min(nblk_stride(g.Nhp), 512);
+  if (h->f32)
+    k_spectrum<float><<<grid, 256, 3 * n_bin * sizeof(double), h->stream>>>(
+        g, reinterpret_cast<const float2 *>(xk), (int)n_bin, dk, bins);
+  else
+    k_spectrum<double><<<grid, 256, 3 * n_bin * sizeof(double), h->stream>>>(
+        g, reinterpret_cast<const double2 *>(xk), (int)n_bin, dk, bins);
+  std::vector<double> hb(3 * n_bin);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = hipMemcpyAsync(hb.data(), bins, hb.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+  if (e != hipSuccess) return h->fail(BCHMC_ERR_HIP, "measure_spectrum: %s", hipGetErrorString(e));
+  const double N = (double)g.N, NORM = g.L * g.L * g.L / N / N;  // FOURIER_DEF_2, field_statistics.cpp:73-75
+  for (uint64_t l = 0; l < n_bin; l++) {
+    const double cnt = hb[2 * n_bin + l];
+    kmode[l] = cnt > 0. ? hb[l] / cnt : 0.;
+    power[l] = cnt > 0. ? hb[n_bin + l] / cnt * NORM : 0.;
+  }
+  return BCHMC_OK;
+}
+
 // ======================================================================================================
 // The pipeline, for storage type T
 // ======================================================================================================
@@ -2031,6 +2073,164 @@ struct Pipe {
     }
     return BCHMC_OK;
   }
+
+  // ---- Hamiltonian_mass (HMC_mass.cc:315-368) ---------------------------------------------------------------------
+  // measure_spectrum of likelihood_grad_log_like at the state in qk (likeli_force_power, 39-50): the likelihood force
+  // before grad_psi_likeli_factor, binned from its k-space form in gk (the R2C of the real force up to round-off:
+  // grad_inv_lap_FS keeps it Hermitian).  Leaves the force's forward model in the handle.
+  static int mass_force_spectrum(bchmc_handle *h, uint64_t n_bin, double *kmode, double *power) {
+    int like_mode = 2;
+    double b = 0.;
+    CHK(force_sources(h, false, &like_mode, &b));
+    double norm = -1.;  // zeldovich_norm, HMC_models.cc:458-461, without the test factor
+    norm *= h->c.deltaQ_factor;
+    if (h->c.correct_delta) norm *= h->c.D1;
+    CHK(launch_assemble<false>(h, 0., norm, like_mode, 0., nullptr));
+    return spectrum_bins(h, h->gk, n_bin, kmode, power);
+  }
+
+  // (pairs + cells) x outputs of one k_jasche_accum launch, so that no kernel holds a shared device long: measured
+  // 5.4-6.5 ms per launch at 64^3 (profiles/mass_kernel_stats_64.csv)
+  static constexpr long long kJascheWork = 1ll << 32;
+
+  // likeli_force_1st_order_diagonal_mass (230-306) at the state in qk into d_r (N doubles).  G first (its transform
+  // uses Ck / psi), then Lag2Eul(signal) as bchmc_forward runs it, the (particle, cell) pairs, the sums in slices.
+  static int mass_jasche(bchmc_handle *h, double *d_r) {
+    const Geo &g = h->g;
+    const long long N = g.N;
+    struct Scratch {  // released after the stream has drained
+      bchmc_handle *h;
+      std::vector<void *> p;
+      ~Scratch() {
+        (void)hipStreamSynchronize(h->stream);
+        for (void *q : p) (void)hipFree(q);
+      }
+    } s{h, {}};
+    auto alloc = [&](void **p, size_t bytes) -> int {
+      CHK(dev_alloc_bytes(h, p, bytes));
+      s.p.push_back(*p);
+      return BCHMC_OK;
+    };
+    double *G = nullptr, *acc = nullptr;
+    int *cnt = nullptr, *off = nullptr;
+    long long *total = nullptr;
+    JRec *rec = nullptr;
+    CHK(alloc((void **)&G, 3 * (size_t)N * sizeof(double)));
+    CHK(alloc((void **)&acc, (size_t)N * sizeof(double)));
+    CHK(alloc((void **)&cnt, (size_t)N * sizeof(int)));
+    CHK(alloc((void **)&off, ((size_t)N + 1) * sizeof(int)));
+    CHK(alloc((void **)&total, sizeof(long long)));
+    {
+      ProfScope ps(h, BCHMC_K_OTHER);
+      k_glap_impulse<T><<<nblk_stride(g.Nhp), 256, 0, h->stream>>>(g, C(h->Ck));
+      HIPCHK(hipGetLastError());
+    }
+    CHK(fft_exec(h, h->c2r3, h->Ck, h->psi, BCHMC_K_FFT_C2R));
+    {
+      ProfScope ps(h, BCHMC_K_OTHER);
+      k_convert<T, double><<<nblk_stride(3 * N), 256, 0, h->stream>>>(3 * N, R(h->psi), G);
+      HIPCHK(hipGetLastError());
+    }
+    // Lag2Eul(signal) (HMC_mass.cc:242-257): no deltaQ_factor, rsd_model as configured
+    const int rsd = h->c.rsd_model;
+    CHK(displacement(h, 1., rsd));
+    CHK(forward_rest(h, rsd));
+    const PosPar pp = make_pos(h, rsd);
+    JaschePar jp;
+    jp.h = h->c.particle_kernel_h;
+    const double h2 = jp.h * jp.h;
+    jp.norm = 1. / (M_PI * (h2 * h2 * jp.h));  // gsl_pow_5
+    jp.reach = (int)(2. * jp.h / g.d) + 1;
+    const T *window = R(h->in_arr[BCHMC_F_WINDOW]), *noise = R(h->in_arr[BCHMC_F_NOISE]);
+    {
+      ProfScope ps(h, BCHMC_K_OTHER);
+      k_jasche_pairs<T, false><<<nblk_stride(N), 256, 0, h->stream>>>(g, pp, jp, R(h->psi), window, cnt, nullptr, nullptr);
+      k_jasche_scan<<<1, 1024, 0, h->stream>>>(N, cnt, total, off);
+      HIPCHK(hipGetLastError());
+    }
+    long long npairs = 0;
+    HIPCHK(hipMemcpyAsync(&npairs, total, sizeof npairs, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (npairs >= 0x7fffffffLL)
+      return h->fail(BCHMC_ERR_UNSUPPORTED, "Jasche mass: %lld (particle, cell) pairs exceed the 32-bit offsets", npairs);
+    CHK(alloc((void **)&rec, (size_t)std::max(npairs, 1ll) * sizeof(JRec)));
+    HIPCHK(hipMemsetAsync(cnt, 0, (size_t)N * sizeof(int), h->stream));
+    {
+      ProfScope ps(h, BCHMC_K_OTHER);
+      k_jasche_pairs<T, true><<<nblk_stride(N), 256, 0, h->stream>>>(g, pp, jp, R(h->psi), window, cnt, off, rec);
+      k_jasche_sort<<<nblk_stride(N), 256, 0, h->stream>>>(N, off, rec);
+      HIPCHK(hipGetLastError());
+    }
+    std::vector<int> hoff((size_t)N + 1);
+    HIPCHK(hipMemcpyAsync(hoff.data(), off, hoff.size() * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    const long long budget = std::max(kJascheWork / N, 1ll);
+    for (long long l0 = 0; l0 < N;) {
+      long long l1 = l0 + 1;
+      while (l1 < N && (long long)(hoff[l1 + 1] - hoff[l0]) + (l1 + 1 - l0) <= budget) l1++;
+      ProfScope ps(h, BCHMC_K_OTHER);
+      k_jasche_accum<<<nblk_full(N), 256, 0, h->stream>>>(g, rec, off, l0, l1, G, acc);
+      HIPCHK(hipGetLastError());
+      l0 = l1;
+    }
+    const double m = h->c.rho_c * (g.L * g.L * g.L) / (double)N;  // rho_c vol / N
+    ProfScope ps(h, BCHMC_K_OTHER);
+    k_jasche_final<T><<<nblk_stride(N), 256, 0, h->stream>>>(N, acc, window, noise, m * m, d_r);
+    HIPCHK(hipGetLastError());
+    return BCHMC_OK;
+  }
+
+  // The whole of Hamiltonian_mass for the handle's mass_type.  The state is the R2C of dstage[0, N) (a host signal) or
+  // the resident chain state (from_chain).  mass_f goes to dstage[0, N), mass_r to dstage[N, 2N), both then taken in
+  // exactly like bchmc_upload takes an array (load_real + k_prepare_mult).
+  static int mass_build(bchmc_handle *h, bool from_chain, const bchmc_mass_opts &o, bool force, bool jasche) {
+    const int t = h->c.mass_type;
+    const long long N = h->g.N;
+    double *d_f = h->dstage, *d_r = h->dstage + N;
+    if (force || jasche) {
+      if (from_chain)
+        HIPCHK(hipMemcpyAsync(h->qk, h->cq, 2 * (size_t)h->g.Nhp * sizeof(T), hipMemcpyDeviceToDevice, h->stream));
+      else
+        CHK(r2c_state(h, h->dstage, h->ioq, h->qk));
+    }
+    double dk = 0., fbar = 0.;
+    std::vector<double> kmode, power;
+    if (force) {
+      kmode.resize(o.n_bin);
+      power.resize(o.n_bin);
+      CHK(mass_force_spectrum(h, o.n_bin, kmode.data(), power.data()));
+      dk = spectrum_dk(h->g, o.n_bin);
+      if (t == 3) {  // Hamiltonian_mass_mean_likeli_force (86-114)
+        double fm = 0., kv = 0.;
+        for (uint64_t i = 0; i < o.n_bin; i++) fm += 4. * M_PI * kmode[i] * kmode[i] * dk * power[i];
+        for (uint64_t i = 0; i < o.n_bin; i++) kv += 4. * M_PI * kmode[i] * kmode[i] * dk;
+        fbar = fm / kv;
+      } else {  // the binned force power, read by k_mass_elementwise (spectrum_bins left room for 3 n_bin doubles)
+        HIPCHK(hipMemcpyAsync(h->spec_bins, power.data(), o.n_bin * sizeof(double), hipMemcpyHostToDevice, h->stream));
+      }
+    }
+    if (h->mass_fs) {
+      const int mode = (t == 1 || t == 5) ? MASS_INVP : t == 2 ? MASS_FORCE : t == 3 ? MASS_MEAN : MASS_PS;
+      ProfScope ps(h, BCHMC_K_OTHER);
+      k_mass_elementwise<T><<<nblk_stride(N), 256, 0, h->stream>>>(h->g, mode, R(h->in_arr[BCHMC_F_SIGNAL_PS]),
+                                                                   h->spec_bins, (int)o.n_bin, dk, fbar, o.mass_factor,
+                                                                   d_f);
+      HIPCHK(hipGetLastError());
+    }
+    if (h->mass_rs) {
+      if (jasche) {
+        CHK(mass_jasche(h, d_r));
+      } else {  // fill_one: type 0, type 60 before its switch
+        ProfScope ps(h, BCHMC_K_OTHER);
+        k_mass_elementwise<T><<<nblk_stride(N), 256, 0, h->stream>>>(h->g, MASS_ONE, nullptr, nullptr, 0, 0., 0., 1., d_r);
+        HIPCHK(hipGetLastError());
+      }
+    }
+    if (h->mass_fs) CHK(upload(h, BCHMC_F_MASS_F, d_f));
+    if (h->mass_rs) CHK(upload(h, BCHMC_F_MASS_R, d_r));
+    HIPCHK(hipStreamSynchronize(h->stream));  // `power` is a local vector
+    return BCHMC_OK;
+  }
 };
 
 #define DISPATCH(h, call) ((h)->f32 ? Pipe<float>::call : Pipe<double>::call)
@@ -2931,38 +3131,43 @@ int bchmc_measure_spectrum(bchmc_handle *h, const double *signal, uint64_t n_bin
     if (!h->have_cq) return h->fail(BCHMC_ERR_STATE, "no chain state: call bchmc_chain_set_state first");
     xk = h->cq;
   }
-  if (h->spec_cap < 3 * (size_t)n_bin) {  // kept in the handle: barcoderunner measures a spectrum after every sample
-    if (h->spec_bins) (void)hipFree(h->spec_bins);
-    h->spec_bins = nullptr;
-    h->spec_cap = 0;
-    CHK(dev_alloc(h, &h->spec_bins, 3 * (size_t)n_bin));
-    h->spec_cap = 3 * (size_t)n_bin;
+  return spectrum_bins(h, xk, n_bin, kmode, power);
+}
+
+int bchmc_hamiltonian_mass(bchmc_handle *h, const double *signal, const bchmc_mass_opts *opts, double *mass_f,
+                           double *mass_r) {
+  if (!h || !opts) return BCHMC_ERR_ARG;
+  ENTER(h);
+  const int t = h->c.mass_type;
+  const bool force = (t == 2 || t == 3);
+  const bool jasche = (t == 5 || t == 6 || (t == 60 && !(opts->iGibbs < opts->s_eps_total)));
+  if (force && h->c.likelihood == 3)
+    return h->fail(BCHMC_ERR_UNSUPPORTED, "mass_type %d needs likelihood_grad_log_like, which is an empty function for "
+                                          "the GRF likelihood (gaussian_random_field.cpp:21-23)", t);
+  if (force && (opts->n_bin == 0 || opts->n_bin > 2048))
+    return h->fail(BCHMC_ERR_ARG, "n_bin = %llu outside 1..2048", (unsigned long long)opts->n_bin);
+  if (jasche && h->g.n > 1024) return h->fail(BCHMC_ERR_UNSUPPORTED, "Jasche mass: n = %d > 1024", h->g.n);
+  if (h->mass_fs) CHK(need_input(h, BCHMC_F_SIGNAL_PS, "signal_PS"));
+  if (force) {
+    CHK(need_input(h, BCHMC_F_NOBS, "nobs"));
+    CHK(need_input(h, BCHMC_F_WINDOW, "window"));
+    if (h->c.likelihood != 0) CHK(need_input(h, BCHMC_F_NOISE, "noise"));
   }
-  double *bins = h->spec_bins;
-  HIPCHK(hipMemsetAsync(bins, 0, 3 * (size_t)n_bin * sizeof(double), h->stream));
-  const Geo &g = h->g;
-  const double knyq = g.kfac * (double)(g.n / 2);
-  const double kmax = std::sqrt(knyq * knyq + knyq * knyq + knyq * knyq);
-  const double dk = kmax / (double)n_bin;
-  const int grid = std::min(nblk_stride(g.Nhp), 512);
-  if (h->f32)
-    k_spectrum<float><<<grid, 256, 3 * n_bin * sizeof(double), h->stream>>>(
-        g, reinterpret_cast<const float2 *>(xk), (int)n_bin, dk, bins);
-  else
-    k_spectrum<double><<<grid, 256, 3 * n_bin * sizeof(double), h->stream>>>(
-        g, reinterpret_cast<const double2 *>(xk), (int)n_bin, dk, bins);
-  std::vector<double> hb(3 * n_bin);
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess) e = hipMemcpyAsync(hb.data(), bins, hb.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-  if (e != hipSuccess) return h->fail(BCHMC_ERR_HIP, "measure_spectrum: %s", hipGetErrorString(e));
-  const double N = (double)g.N, NORM = g.L * g.L * g.L / N / N;  // FOURIER_DEF_2, field_statistics.cpp:73-75
-  for (uint64_t l = 0; l < n_bin; l++) {
-    const double cnt = hb[2 * n_bin + l];
-    kmode[l] = cnt > 0. ? hb[l] / cnt : 0.;
-    power[l] = cnt > 0. ? hb[n_bin + l] / cnt * NORM : 0.;
+  if (jasche) {
+    CHK(need_input(h, BCHMC_F_WINDOW, "window"));
+    CHK(need_input(h, BCHMC_F_NOISE, "noise"));
   }
-  return BCHMC_OK;
+  const bool state = force || jasche;
+  if (state && !signal && !h->have_cq) return h->fail(BCHMC_ERR_STATE, "no chain state: call bchmc_chain_set_state first");
+  clobber_proposal(h);
+  const size_t N = (size_t)h->g.N, bytes = N * sizeof(double);
+  if (state && signal) CHK(h2d(h, h->dstage, signal, bytes));
+  CHK(DISPATCH(h, mass_build(h, state && !signal, *opts, force, jasche)));
+  if (h->mass_fs) h->have[BCHMC_F_MASS_F] = true;
+  if (h->mass_rs) h->have[BCHMC_F_MASS_R] = true;
+  if (mass_f && h->mass_fs) CHK(d2h(h, mass_f, h->dstage, bytes));
+  if (mass_r && h->mass_rs) CHK(d2h(h, mass_r, h->dstage + N, bytes));
+  return read_ctl(h, nullptr);  // synchronises; adapts the binning's record slots to the forward model just run
 }
 
 int bchmc_philox_kat(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]) {

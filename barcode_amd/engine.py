@@ -45,6 +45,16 @@ class EpsRecord(C.Structure):
     _fields_ = [("epsilon", C.c_double), ("accepted", C.c_int32), ("neps", C.c_int32)]
 
 
+class MassOpts(C.Structure):
+    """bchmc_mass_opts: the HAMIL_NUMERICAL scalars Hamiltonian_mass reads."""
+    _fields_ = [("n_bin", C.c_uint64), ("mass_factor", C.c_double), ("iGibbs", C.c_uint64), ("s_eps_total", C.c_uint64)]
+
+
+# which mass arrays a mass_type has (struct_hamil.h:272-313)
+MASS_F_TYPES = (1, 2, 3, 4, 5)
+MASS_R_TYPES = (0, 5, 6, 60)
+
+
 EPS_BATCH = 32            # BCHMC_EPS_BATCH
 UNIQUE_ID_BYTES = 128     # BCHMC_UNIQUE_ID_BYTES
 PACKET_BYTES = 8 + 16 * EPS_BATCH
@@ -72,7 +82,7 @@ EXPORTS = ("bchmc_create", "bchmc_destroy", "bchmc_strerror", "bchmc_last_error"
            "bchmc_measure_spectrum", "bchmc_philox_kat", "bchmc_kinetic_term", "bchmc_psi",
            "bchmc_comm_unique_id", "bchmc_comm_create", "bchmc_comm_create_custom", "bchmc_comm_destroy",
            "bchmc_comm_last_error", "bchmc_eps_exchange", "bchmc_comm_pending", "bchmc_comm_world", "bchmc_comm_rank",
-           "bchmc_comm_transport", "bchmc_garfield_walk_index")
+           "bchmc_comm_transport", "bchmc_garfield_walk_index", "bchmc_hamiltonian_mass")
 # declared as well, listed apart: the header scan of the ABI test matches names of letters and underscores only
 EXPORTS_MT19937 = ("bchmc_chain_draw_momenta_mt19937", "bchmc_mt19937_jump")
 
@@ -122,6 +132,7 @@ def load():
     lib.bchmc_chain_get_proposal.argtypes = [vp, dp, dp]
     lib.bchmc_chain_accept.argtypes = [vp, C.c_int]
     lib.bchmc_measure_spectrum.argtypes = [vp, dp, C.c_uint64, dp, dp]
+    lib.bchmc_hamiltonian_mass.argtypes = [vp, dp, C.POINTER(MassOpts), dp, dp]
     lib.bchmc_philox_kat.argtypes = [C.POINTER(C.c_uint32)] * 3
     lib.bchmc_kinetic_term.argtypes = [vp, dp, dp]
     lib.bchmc_psi.argtypes = [vp, dp, dp]
@@ -386,6 +397,19 @@ class Engine:
         sig = None if signal is None else _p(self._in(signal))
         self._chk(self.lib.bchmc_measure_spectrum(self.h, sig, int(n_bin), _p(kmode), _p(power)))
         return kmode, power
+
+    def hamiltonian_mass(self, signal=None, n_bin=200, mass_factor=1.0, iGibbs=1, s_eps_total=0):
+        """Hamiltonian_mass (HMC_mass.cc:315-368) on the device at a host field, or at the resident chain state when
+        ``signal`` is None; the engine then uses the new mass as if it had been uploaded.  Defaults: N_bin and
+        mass_factor of data/input.par:129,150.  Returns (mass_f, mass_r), None where the mass_type has none."""
+        t = int(self.params.mass_type)
+        mf = np.empty(self.N) if t in MASS_F_TYPES else None
+        mr = np.empty(self.N) if t in MASS_R_TYPES else None
+        o = MassOpts(int(n_bin), float(mass_factor), int(iGibbs), int(s_eps_total))
+        sig = None if signal is None else _p(self._in(signal))
+        self._chk(self.lib.bchmc_hamiltonian_mass(self.h, sig, C.byref(o), None if mf is None else _p(mf),
+                                                  None if mr is None else _p(mr)))
+        return mf, mr
 
     def tile_info(self):
         out = (C.c_int32 * 8)()

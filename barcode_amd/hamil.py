@@ -38,6 +38,10 @@ class HamilNumerical:
     count_attempts: int = 0
     iGibbs: int = 1        # sample number (struct_hamil.h:106): scheme 3's fast initial phase runs while it is 1
     rejections: int = 0    # rejected attempts of the current sample (HMC.cc:500-501)
+    # read by Hamiltonian_mass (struct_hamil.h:81-119; defaults data/input.par:129,150)
+    N_bin: int = 200
+    mass_factor: float = 1.0
+    s_eps_total: int = 0   # mass_type 60: ones while iGibbs < s_eps_total, the Jasche mass afterwards
 
 
 class HamilData:
@@ -123,7 +127,25 @@ def measure_spectrum(hd, signal=None, N_bin=200):
     return hd.engine.measure_spectrum(signal, N_bin)
 
 
-def HamiltonianMC(hd, uniform, seed=1, itmax=2000, ring=None, group=None, momenta=None, eps_cfg=None):
+def Hamiltonian_mass(hd, signal=None):
+    """HMC_mass.cc:315-368 on the device at ``signal`` (None: the resident chain state); the engine takes the new mass
+    as if it had been uploaded.  Returns (mass_f, mass_r), None where the mass_type has none."""
+    n = hd.numerical
+    return hd.engine.hamiltonian_mass(signal, n_bin=n.N_bin, mass_factor=n.mass_factor, iGibbs=n.iGibbs,
+                                      s_eps_total=n.s_eps_total)
+
+
+def massnum_due(iGibbs, massnum_init, massnum_burn):
+    """HMC.cc:387-400: whether HamiltonianMC recomputes the mass at the top of sample ``iGibbs``.  massnum == 0 means
+    never (upstream divides by it; data/input.par:104-105 ships 0)."""
+    massnum = massnum_burn if iGibbs > massnum_burn else massnum_init
+    if massnum == 0:
+        return False
+    return iGibbs % massnum == 0 or iGibbs == 1
+
+
+def HamiltonianMC(hd, uniform, seed=1, itmax=2000, ring=None, group=None, momenta=None, eps_cfg=None,
+                  massnum_init=0, massnum_burn=0):
     """One sample of the reference's HamiltonianMC loop (HMC.cc:431-511) on the device-resident chain:
     repeat { draw momenta; draw (Neps, epsilon); trajectory; dH; Metropolis test } until accepted.
 
@@ -139,10 +161,18 @@ def HamiltonianMC(hd, uniform, seed=1, itmax=2000, ring=None, group=None, moment
     ``eps_cfg``, a ``time_step.EpsConfig``), ``rejections`` += 1 on a reject (500-501), the attempt into the ring
     (``update_epsilon_acc_rate_tables``, 506-507).  With a ``group``, ONE exchange after the loop -- the fixed point
     every chain reaches once per sample -- pools the other chains' records into the ring.
+
+    Mass: at the top of the sample, when ``massnum_due(iGibbs, massnum_init, massnum_burn)`` (HMC.cc:387-400), the
+    mass is rebuilt on the device from the resident state (``Hamiltonian_mass``); a mass_r holding a NaN raises like
+    HMC.cc:404-406.  The defaults (0) never rebuild it.
     """
     from . import time_step
     n = hd.numerical
     e = hd.engine
+    if massnum_due(n.iGibbs, massnum_init, massnum_burn):
+        _, mass_r = Hamiltonian_mass(hd)
+        if mass_r is not None and np.isnan(mass_r).any():
+            raise RuntimeError("auxmass_r contains a NaN! aborting.")
     exact = isinstance(momenta, str)
     if exact:
         from .gsl_mt19937 import GslMT19937

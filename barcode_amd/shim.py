@@ -24,7 +24,7 @@ SHIM_EXPORTS = ("bchmc_shim_Hamiltonian_EoM", "bchmc_shim_delta_Hamiltonian", "b
                 "bchmc_shim_eps_acceptance_rate", "bchmc_shim_update_eps_fac", "bchmc_shim_update_tables",
                 "bchmc_shim_comm_bootstrap_file", "bchmc_shim_comm_attach", "bchmc_shim_comm_release",
                 "bchmc_shim_inputs_changed", "bchmc_shim_mass_changed", "bchmc_shim_bootstrap_exchange_id",
-                "bchmc_shim_bootstrap_cleanup")
+                "bchmc_shim_bootstrap_cleanup", "bchmc_shim_Hamiltonian_mass")
 
 _dp = C.POINTER(C.c_double)
 
@@ -46,6 +46,8 @@ class HamilNumericalView(C.Structure):
         ("psi_prior_i", C.c_double), ("psi_prior_f", C.c_double), ("psi_likeli_i", C.c_double),
         ("psi_likeli_f", C.c_double), ("H_kin_i", C.c_double), ("H_kin_f", C.c_double),
         ("iGibbs", C.c_ulong), ("rejections", C.c_ulong), ("accepted", C.c_bool),
+        ("N_bin", C.c_ulong), ("massnum_init", C.c_ulong), ("massnum_burn", C.c_ulong), ("s_eps_total", C.c_ulong),
+        ("mass_factor", C.c_double),
     ]
 
 
@@ -106,6 +108,7 @@ def load():
     lib.bchmc_shim_delta_Hamiltonian.argtypes = [hv, _dp, _dp, _dp, _dp, _dp, C.c_char_p, sz]
     lib.bchmc_shim_gradient_psi.argtypes = [hv, _dp, C.c_char_p, sz]
     lib.bchmc_shim_measure_spectrum.argtypes = [hv, _dp, _dp, _dp, ul, C.c_char_p, sz]
+    lib.bchmc_shim_Hamiltonian_mass.argtypes = [hv, _dp, _dp, _dp, C.c_char_p, sz]
     lib.bchmc_shim_chain_set_state.argtypes = [hv, _dp, C.c_char_p, sz]
     lib.bchmc_shim_chain_get_state.argtypes = [hv, _dp, C.c_char_p, sz]
     lib.bchmc_shim_HamiltonianMC.argtypes = [hv, UNIFORM_FN, C.c_void_p, C.c_uint64, ul, C.POINTER(ul),
@@ -192,6 +195,7 @@ class ShimHamil:
         n.planepar, n.periodic = bool(p.planepar), bool(p.periodic)
         n.correct_delta, n.div_dH_by_N = bool(p.correct_delta), bool(p.div_dH_by_N)
         n.N_eps_fac = N_eps_fac
+        n.N_bin, n.mass_factor = 200, 1.0  # data/input.par:129,150; massnum_* = 0: the mass is never rebuilt
         n.eps_fac = p.eps_heuristic() if eps_fac is None else eps_fac
         self.numerical = n
         hd = HamilView()
@@ -249,6 +253,17 @@ class ShimHamil:
         self._chk(self.lib.bchmc_shim_measure_spectrum(C.byref(self.hd), _p(self._in(signal)), _p(km), _p(pw), N_bin,
                                                        self._err, len(self._err)))
         return km, pw
+
+    def Hamiltonian_mass(self, signal=None):
+        """bchmc_shim::Hamiltonian_mass at ``signal`` (None: the resident state) -> (mass_f, mass_r), None where the
+        mass_type has none."""
+        t = self.numerical.mass_type
+        mf = np.empty(self.N) if t in (1, 2, 3, 4, 5) else None
+        mr = np.empty(self.N) if t in (0, 5, 6, 60) else None
+        sig = None if signal is None else _p(self._in(signal))
+        self._chk(self.lib.bchmc_shim_Hamiltonian_mass(C.byref(self.hd), sig, None if mf is None else _p(mf),
+                                                       None if mr is None else _p(mr), self._err, len(self._err)))
+        return mf, mr
 
     def chain_set_state(self, x):
         self._chk(self.lib.bchmc_shim_chain_set_state(C.byref(self.hd), _p(self._in(x)), self._err, len(self._err)))

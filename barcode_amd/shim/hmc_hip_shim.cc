@@ -244,6 +244,47 @@ void measure_spectrum(HamilView *hd, const real_prec *signal, real_prec *kmode, 
   if (rc) fail(h, rc, "measure_spectrum");
 }
 
+void Hamiltonian_mass(HamilView *hd, const real_prec *signal, real_prec *mass_f_out, real_prec *mass_r_out) {
+  bchmc_handle *h = engine_for(hd);
+  const HamilNumericalView *n = hd->numerical;
+  bchmc_mass_opts o;
+  o.n_bin = n->N_bin;
+  o.mass_factor = n->mass_factor;
+  o.iGibbs = n->iGibbs;
+  o.s_eps_total = n->s_eps_total;
+  const int rc = bchmc_hamiltonian_mass(h, signal, &o, mass_f_out, mass_r_out);
+  if (rc) fail(h, rc, "Hamiltonian_mass");
+  // the engine holds the new mass: a new generation, already in place (engine_for must not upload older host arrays)
+  hd->mass_generation++;
+  hd->mass_uploaded_generation = hd->mass_generation;
+  hd->eom.valid = false;
+}
+
+bool massnum_due(ULONG iGibbs, ULONG massnum_init, ULONG massnum_burn) {
+  const ULONG massnum = iGibbs > massnum_burn ? massnum_burn : massnum_init;  // HMC.cc:387-391
+  return massnum != 0 && (iGibbs % massnum == 0 || iGibbs == 1);             // HMC.cc:400, 0 = never
+}
+
+// HamiltonianMC's mass step (HMC.cc:387-413) on the resident state.  The built arrays go where upstream's
+// Hamiltonian_mass writes them, the caller-owned hd->mass_f / hd->mass_r (when the view has them), so that a later
+// inputs_changed() uploads the same values again.
+void mass_schedule(HamilView *hd) {
+  const HamilNumericalView *n = hd->numerical;
+  if (!massnum_due(n->iGibbs, n->massnum_init, n->massnum_burn)) return;
+  const bool fs = n->mass_type >= 1 && n->mass_type <= 5;
+  const bool rs = n->mass_type == 0 || n->mass_type == 5 || n->mass_type == 6 || n->mass_type == 60;
+  std::vector<real_prec> tmp_r;
+  real_prec *mr = const_cast<real_prec *>(hd->mass_r);
+  if (rs && !mr) {
+    tmp_r.resize(n->N);
+    mr = tmp_r.data();
+  }
+  Hamiltonian_mass(hd, nullptr, fs ? const_cast<real_prec *>(hd->mass_f) : nullptr, rs ? mr : nullptr);
+  if (rs)
+    for (ULONG i = 0; i < n->N; i++)
+      if (std::isnan(mr[i])) throw std::runtime_error("auxmass_r contains a NaN! aborting.");  // HMC.cc:404-406
+}
+
 void chain_set_state(HamilView *hd, const real_prec *x) {
   bchmc_handle *h = engine_for(hd);
   const int rc = bchmc_chain_set_state(h, x);
@@ -270,6 +311,7 @@ ULONG HamiltonianMC(HamilView *hd, uniform_fn uniform, void *rng_state, uint64_t
   bchmc_handle *h = engine_for(hd);
   const ChainOps ops = {op_draw, op_setp, op_attempt, op_accept};
   try {
+    mass_schedule(hd);
     return HamiltonianMC_ops(hd, ops, h, uniform, rng_state, seed, itmax, count_attempts, log, log_cap, momenta,
                              momenta_state);
   } catch (const std::runtime_error &e) {
@@ -309,6 +351,7 @@ ULONG HamiltonianMC_mt19937(HamilView *hd, uniform_fn uniform, mt19937_state_fn 
   MtEngine m = {h, state, rng_state};
   const ChainOps ops = {mt_draw, mt_setp, mt_attempt, mt_accept};
   try {
+    mass_schedule(hd);
     return HamiltonianMC_ops(hd, ops, &m, uniform, rng_state, 0, itmax, count_attempts, log, log_cap, nullptr, nullptr);
   } catch (const std::runtime_error &e) {
     const char *detail = bchmc_last_error(h);
@@ -620,6 +663,10 @@ int bchmc_shim_gradient_psi(bchmc_shim::HamilView *hd, const double *signal, cha
 int bchmc_shim_measure_spectrum(bchmc_shim::HamilView *hd, const double *signal, double *kmode, double *power,
                                 unsigned long N_bin, char *err, size_t errlen) {
   return guarded(err, errlen, [&] { bchmc_shim::measure_spectrum(hd, signal, kmode, power, N_bin); });
+}
+int bchmc_shim_Hamiltonian_mass(bchmc_shim::HamilView *hd, const double *signal, double *mass_f, double *mass_r, char *err,
+                                size_t errlen) {
+  return guarded(err, errlen, [&] { bchmc_shim::Hamiltonian_mass(hd, signal, mass_f, mass_r); });
 }
 int bchmc_shim_chain_set_state(bchmc_shim::HamilView *hd, const double *x, char *err, size_t errlen) {
   return guarded(err, errlen, [&] { bchmc_shim::chain_set_state(hd, x); });

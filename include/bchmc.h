@@ -204,6 +204,20 @@ int bchmc_chain_accept(bchmc_handle *h, int accepted);         /* accepted: q :=
  * resident chain state (no transform and no field transfer: its R2C is what the chain keeps).  kmode / power:
  * n_bin doubles each; empty bins stay 0 like upstream. */
 int bchmc_measure_spectrum(bchmc_handle *h, const double *signal, uint64_t n_bin, double *kmode, double *power);
+/* Hamiltonian_mass (HMC_mass.cc:315-368; HamiltonianMC calls it at HMC.cc:387-423) for the handle's mass_type. */
+typedef struct bchmc_mass_opts {
+  uint64_t n_bin;               /* HAMIL_NUMERICAL::N_bin (types 2, 3); 1..2048 like bchmc_measure_spectrum */
+  double mass_factor;           /* HAMIL_NUMERICAL::mass_factor */
+  uint64_t iGibbs, s_eps_total; /* type 60's switch */
+} bchmc_mass_opts;
+/* Hamiltonian_mass at `signal` (N host doubles, or NULL = resident chain state).  The handle then uses the new mass
+ * exactly as if it had been uploaded; mass_f / mass_r (may be NULL) receive host copies of what was built (an array the
+ * type has none of is left untouched).  Does not touch the chain's q, momenta, carried gradient or -log L; drops a
+ * pending proposal like bchmc_forward.  deltaX / pos* afterwards: the likelihood force's forward model (types 2, 3),
+ * Lag2Eul(signal) (5, 6, 60 after its switch), unchanged otherwise.  Types 2 and 3 with the GRF likelihood:
+ * BCHMC_ERR_UNSUPPORTED (upstream's likelihood_grad_log_like is an empty function there). */
+int bchmc_hamiltonian_mass(bchmc_handle *h, const double *signal, const bchmc_mass_opts *opts, double *mass_f,
+                           double *mass_r);
 int bchmc_philox_kat(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]); /* known-answer hook for tests */
 
 /* Diagnostic (tests, logs): how the particle-mesh path is currently set up.  out = { tile-sorted path in use, one-pass

@@ -47,6 +47,10 @@ struct HamilNumericalView {
   ULONG iGibbs = 1;      // sample number; scheme 3's fast initial phase runs while iGibbs == 1 (time_step.cpp:141)
   ULONG rejections = 0;  // rejected attempts of the current sample (HMC.cc:500-501)
   bool accepted = false; // outcome of the last attempt (HMC.cc:503-504)
+  // read by Hamiltonian_mass (HMC_mass.cc:315-368) and HamiltonianMC's mass schedule (HMC.cc:387-400),
+  // struct_hamil.h:81-119; massnum 0 means never (upstream divides by it; data/input.par:104-105 ships 0)
+  ULONG N_bin = 200, massnum_init = 0, massnum_burn = 0, s_eps_total = 0;
+  real_prec mass_factor = 1;
 };
 
 // HAMIL_DATA members used by the path (struct_hamil.h:146-222), reference names.
@@ -114,6 +118,12 @@ real_prec kinetic_term(HamilView *hd, const real_prec *momenta);  // HMC.cc:64-1
 real_prec psi(HamilView *hd, const real_prec *signal);            // HMC.cc:124-143 (stores psi_prior, psi_likeli)
 // field_statistics.cpp:20-90
 void measure_spectrum(HamilView *hd, const real_prec *signal, real_prec *kmode, real_prec *power, ULONG N_bin);
+// HMC_mass.cc:315-368 on the device at `signal` (null: the resident chain state).  The engine keeps the built mass (the
+// mass generation is bumped and marked uploaded, so nothing re-uploads a host array over it, and the EoM energies are
+// dropped); mass_f_out / mass_r_out (may be null) receive host copies where the mass_type has the array.
+void Hamiltonian_mass(HamilView *hd, const real_prec *signal, real_prec *mass_f_out, real_prec *mass_r_out);
+// HMC.cc:387-400: whether HamiltonianMC rebuilds the mass at the top of sample iGibbs (massnum 0: never).
+bool massnum_due(ULONG iGibbs, ULONG massnum_init, ULONG massnum_burn);
 // ---- step-size adaptation (barlib/src/hmc/leapfrog/time_step.cpp, include/hmc/leapfrog/time_step.hpp) ------------
 // The keys of data/input.par:59-87 and the two tables they act on.  Host-only, O(N_a) work per call.
 struct EpsAdapt;
@@ -216,6 +226,8 @@ int bchmc_shim_delta_Hamiltonian(bchmc_shim::HamilView *hd, const double *signal
 int bchmc_shim_gradient_psi(bchmc_shim::HamilView *hd, const double *signal, char *err, size_t errlen);
 int bchmc_shim_measure_spectrum(bchmc_shim::HamilView *hd, const double *signal, double *kmode, double *power,
                                 unsigned long N_bin, char *err, size_t errlen);
+int bchmc_shim_Hamiltonian_mass(bchmc_shim::HamilView *hd, const double *signal, double *mass_f, double *mass_r, char *err,
+                                size_t errlen);
 int bchmc_shim_chain_set_state(bchmc_shim::HamilView *hd, const double *x, char *err, size_t errlen);
 int bchmc_shim_chain_get_state(bchmc_shim::HamilView *hd, double *x, char *err, size_t errlen);
 int bchmc_shim_HamiltonianMC(bchmc_shim::HamilView *hd, bchmc_shim::uniform_fn uniform, void *rng_state, uint64_t seed,
