@@ -136,20 +136,11 @@ struct bchmc_handle {
   void *xtw = nullptr;                           // n / 2 twiddles exp(-2 pi i r / n), C2<T>
   int log2n = 0;
   bool planes_ok = false;                        // plans + kernel available for this grid
-  bool planes_c2r = false, planes_r2c = false;   // per force evaluation: which transform the next FFT call uses
   bool sort_direct = false;  // one-pass tile binning into fixed slots (two-pass sort as overflow fallback)
   rocfft_plan r2c2d_2 = nullptr, c2r2d_2 = nullptr;  // 2-D plans over 2 n planes: delta(1) | Phi and A | B of the ALPT model
   bool alpt_plans_failed = false;
-  bool planes_c2r_once = false;  // Ck holds a displacement in planes space (launch_alpt): the next C2R is the 2-D one
-  bool alpt_pending = false;     // Ck[0], Ck[1] hold delta(1)^ | Phi^ planes left by k_step_boundary_x<ALPT>
   double alpt_wtot = 0.;     // kernelcomp's normalisation (sum of the real-space kernel), computed on first use
   bool std81 = false;  // standard 81-cell hull on 8 x 8 x 16 tiles with halo 2: fully unrolled scatter/gather kernels
-  unsigned short *stage_inv = nullptr;  // staged position -> cell of the scatter's LDS image (owner-blocked order)
-  unsigned *stage_tab = nullptr;  // k_stage_combine81's (neighbour, own cell, image cell) table, kStageCells entries
-  double *stage = nullptr;  // staging area of the scatter's LDS images, one 12 x 12 x 20 image per (tile, chunk) work item
-  bool rho_unread = false;  // set around an interior step's force evaluation: the combine pass need not store rho
-  bool psi_unread = false;  // ... and nobody reads its displacements / positions: the z pass may end in the binning
-  bool staged = false;      // the images of the last scatter have not been summed into rho yet (k_stage_combine81)
   TilePar tp{};
   int *t_cnt = nullptr, *t_woff = nullptr;   // 9 ntiles + 2 (one-pass counts per (tile, octant), fallback counts per tile,
                                              // overflow flags), ntiles + 1
@@ -228,6 +219,22 @@ inline bool env_on(const char *name) {
 
 inline int nblk_stride(long long n) { return (int)std::min<long long>((n + 255) / 256, 2048); }
 inline int nblk_full(long long n) { return (int)((n + 255) / 256); }
+
+struct EvalMode {             // how ONE force evaluation runs; decided by the caller
+  bool planes_c2r = false;    // Psi^ in Ck is in planes space: only the (y, z) passes remain
+  bool planes_r2c = false;    // V^ is wanted in planes space
+  bool alpt_pending = false;  // Ck[0], Ck[1] hold delta(1)^ | Phi^ planes left by k_step_boundary_x<ALPT>
+  bool psi_unread = false;    // interior step: nobody reads Psi / positions, the z pass may end in the binning
+};
+
+// Launch with `lds` bytes of dynamic LDS: above the 48 KiB every kernel may use, the kernel's own limit is raised first.
+template <typename... P, typename... A>
+int launch_lds(bchmc_handle *h, void (*kern)(P...), int grid, int threads, size_t lds, A... args) {
+  if (lds > 48 * 1024)
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  kern<<<grid, threads, lds, h->stream>>>(args...);
+  return BCHMC_OK;
+}
 
 // ---- profiling ------------------------------------------------------------------------------------
 // roctx range names: the kernel ids of SURVEY.md 2.1 that each launch group replaces, so that a
@@ -827,9 +834,12 @@ struct Pipe {
   // Zel'dovich whatever sfmodel says, HMC_models.cc:395-405).
   static bool uses_alpt(const bchmc_handle *h, int rsd) { return !rsd && h->c.sfmodel != 1; }
 
-  // Psi^ of the forward model selected by (sfmodel, rsd) from the current q^
-  static int displacement(bchmc_handle *h, double dq_factor, int rsd) {
-    return uses_alpt(h, rsd) ? launch_alpt(h, dq_factor) : launch_za(h, dq_factor);
+  // Psi^ of the forward model selected by (sfmodel, rsd) from the current q^; *psi_planes: it is left in planes space
+  // (EvalMode::planes_c2r of the forward_rest that follows)
+  static int displacement(bchmc_handle *h, double dq_factor, int rsd, bool *psi_planes) {
+    const bool alpt = uses_alpt(h, rsd);
+    *psi_planes = alpt && alpt_planes(h);
+    return alpt ? launch_alpt(h, dq_factor, *psi_planes) : launch_za(h, dq_factor);
   }
 
   // kernelcomp: wtot = sum over the box of the inverse transform of the kernel table (= K(0) up to round-off)
@@ -857,8 +867,8 @@ struct Pipe {
   }
 
   // ALPT displacement (Lag2Eul_non_zeldovich, Lag2Eul.cc:160-267), second part: from delta(1)^ and Phi^ in Ck[0], Ck[1]
-  // (full k-space, or planes space when `planes`) to Psi^ of the three components in Ck, cell-boundary average
-  // included.  Scratch: V, psi (planes) / plike, rho, V (3-D).
+  // (full k-space, or planes space when `planes`) to Psi^ of the three components in Ck, in the same space, cell-boundary
+  // average included.  Scratch: V, psi (planes) / plike, rho, V (3-D).
   static int alpt_middle(bchmc_handle *h, bool planes) {
     const long long N = h->g.N, Nhp = h->g.Nhp;
     CT *Ck = C(h->Ck);
@@ -883,7 +893,6 @@ struct Pipe {
       CHK(fft_exec(h, h->r2c2d_2, h->V, Ck, BCHMC_K_FFT_R2C));         // A^, B^ of every (y, z) plane
       ProfScope ps(h, BCHMC_K_KSPACE_DRIFT_ZA);
       CHK(launch_alpt_mix_x(h));
-      h->planes_c2r_once = true;  // forward_rest: Psi^ needs only the (y, z) passes
     } else {
       CHK(fft_exec(h, h->r2c1, a_out, Ck, BCHMC_K_FFT_R2C));           // A^ = FFT[D1 delta(1) - D2 delta(2)]
       CHK(fft_exec(h, h->r2c1, b_out, Ck + Nhp, BCHMC_K_FFT_R2C));     // B^ = FFT[spherical-collapse source]
@@ -894,10 +903,10 @@ struct Pipe {
     return BCHMC_OK;
   }
 
-  // ALPT displacement from the current q^.
-  static int launch_alpt(bchmc_handle *h, double dq_factor) {
+  // ALPT displacement from the current q^, on the 2-D plans (`planes` = alpt_planes(h)) or the 3-D ones.
+  static int launch_alpt(bchmc_handle *h, double dq_factor, bool planes) {
     const double scale = dq_factor / (double)h->g.N;
-    if (alpt_planes(h)) {
+    if (planes) {
       {
         ProfScope ps(h, BCHMC_K_KSPACE_DRIFT_ZA);
         StepCtl nc{h->stop, h->steps_done, nullptr, 0., 0};
@@ -920,15 +929,9 @@ struct Pipe {
     const int n = h->g.n, grid = n * (h->g.nhp / KB);
     const size_t lds = ((size_t)n * KB + n / 2) * sizeof(CT);
     const CT *tw = reinterpret_cast<const CT *>(h->xtw);
-#define BCHMC_LAUNCH_AX(NT, PER)                                                                                   \
-  do {                                                                                                             \
-    auto kern = k_alpt_mix_x<T, NT, PER>;                                                                          \
-    if (lds > 48 * 1024)                                                                                           \
-      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                 (int)lds));                                                                       \
-    kern<<<grid, NT, lds, h->stream>>>(h->g, h->log2n, tw, C(h->Ck), h->c.kth, 1. / h->alpt_wtot,                 \
-                                       1. / (double)h->g.N);                                                       \
-  } while (0)
+#define BCHMC_LAUNCH_AX(NT, PER)                                                                                 \
+  CHK(launch_lds(h, k_alpt_mix_x<T, NT, PER>, grid, NT, lds, h->g, h->log2n, tw, C(h->Ck), h->c.kth, 1. / h->alpt_wtot, \
+                 1. / (double)h->g.N))
     switch (n) {
       case 32: BCHMC_LAUNCH_AX(NT_SMALL, 4); break;
       case 64: BCHMC_LAUNCH_AX(NT_SMALL, 8); break;
@@ -955,20 +958,16 @@ struct Pipe {
   static bool yfwd_ok(const bchmc_handle *h) {
     // fp32 fields: R2C class 2.59 -> 1.85 ms per step (17.96 -> 17.35 ms, +3.5 %); fp64: rocFFT's double-precision
     // column kernel is as fast as the pair (3.14 against 3.16 ms) and stays unless BCHMC_YFWD_F64=1
-    return h->g.n == 512 && (sizeof(T) == 4 || env_on("BCHMC_YFWD_F64")) && h->planes_ok && h->xtw &&
-           !env_on("BCHMC_NO_YFWD");
+    return h->g.n == 512 && (sizeof(T) == 4 || env_on("BCHMC_YFWD_F64")) && h->planes_ok && h->xtw;
   }
 
   // C2R of the three displacement components, mass assignment, sum of rho.  Lag2Eul.cc:90-131 / 363-423.
-  // defer_combine: the caller (like_force) sums the staged density images itself, fused with the likelihood partial
-  static int forward_rest(bchmc_handle *h, int rsd, bool defer_combine = false) {
-    const bool stage = h->stage && h->std81 && !h->fix && h->c.mk == 3 && h->tiled;
-    h->staged = false;
+  // Reads m.planes_c2r (where the caller or `displacement` left Psi^) and m.psi_unread.
+  static int forward_rest(bchmc_handle *h, int rsd, EvalMode m) {
     if (rsd && !h->c.planepar) return h->fail(BCHMC_ERR_RSD_NOT_PLANEPAR, "non-plane-parallel RSD is not implemented");
     bool zbin = false;
     {
-      const bool planes = h->planes_c2r || h->planes_c2r_once;
-      h->planes_c2r_once = false;
+      const bool planes = m.planes_c2r;
       // Interior steps of a trajectory at 128^3 / 256^3 / 512^3 (nobody reads Psi or the positions of such a step): the engine's own y
       // pass, and the z pass inside the binning kernel below -- Psi does not go through HBM (zpass.hpp).
       // The other planes-space evaluations (the one before the first step, the last step) use the same kernels and
@@ -980,14 +979,8 @@ struct Pipe {
         const int n = h->g.n, ygrid = 3 * n * (h->g.nhp / KB);
         const size_t lds = ((size_t)n * KB + n / 2) * sizeof(CT);
         const CT *tw = reinterpret_cast<const CT *>(h->xtw);
-#define BCHMC_LAUNCH_Y(NT, NN)                                                                                     \
-  do {                                                                                                             \
-    auto kern = k_ypass<T, NT, NN * KB / NT, BCHMC_YPASS_NT>;                                                 \
-    if (lds > 48 * 1024)                                                                                           \
-      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                 (int)lds));                                                                       \
-    kern<<<ygrid, NT, lds, h->stream>>>(h->g, h->log2n, tw, C(h->Ck));                                             \
-  } while (0)
+#define BCHMC_LAUNCH_Y(NT, NN) \
+  CHK(launch_lds(h, k_ypass<T, NT, NN * KB / NT, BCHMC_YPASS_NT>, ygrid, NT, lds, h->g, h->log2n, tw, C(h->Ck)))
         if (n == 128) BCHMC_LAUNCH_Y(256, 128);
         else if (n == 256) BCHMC_LAUNCH_Y(512, 256);
         else BCHMC_LAUNCH_Y(512, 512);
@@ -1021,20 +1014,12 @@ struct Pipe {
         // below needs Psi after all (returns at once otherwise)
 #define BCHMC_LAUNCH_Z(NZ)                                                                                          \
   do {                                                                                                              \
-    auto kern = k_zbin_direct<T, NZ>;                                                                               \
-    auto kpsi = k_zbin_direct<T, NZ, true>;                                                                         \
-    if (zlds > 48 * 1024) {                                                                                         \
-      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,  \
-                                 (int)zlds));                                                                       \
-      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(kpsi), hipFuncAttributeMaxDynamicSharedMemorySize,  \
-                                 (int)zlds));                                                                       \
-    }                                                                                                               \
-    kern<<<zgrid, NZ, zlds, h->stream>>>(h->g, pp, sp, h->tp, h->log2n, tw, C(h->Ck), cnt1, ovf, (RecQuad *)h->srec, \
-                                         R(h->V), h->rho_part, (h->fix || stage) ? nullptr : R(h->rho),             \
-                                         h->fix ? h->rho_fix : nullptr, h->psi_unread ? nullptr : R(h->psi));       \
-    if (h->psi_unread)                                                                                              \
-      kpsi<<<zgrid, NZ, zlds, h->stream>>>(h->g, pp, sp, h->tp, h->log2n, tw, C(h->Ck), cnt1, ovf, nullptr, nullptr, \
-                                           nullptr, nullptr, nullptr, R(h->psi));                                   \
+    CHK(launch_lds(h, k_zbin_direct<T, NZ>, zgrid, NZ, zlds, h->g, pp, sp, h->tp, h->log2n, tw, C(h->Ck), cnt1, ovf, \
+                   (RecQuad *)h->srec, R(h->V), h->rho_part, h->fix ? nullptr : R(h->rho),                          \
+                   h->fix ? h->rho_fix : nullptr, m.psi_unread ? nullptr : R(h->psi)));                             \
+    if (m.psi_unread)                                                                                               \
+      CHK(launch_lds(h, k_zbin_direct<T, NZ, true>, zgrid, NZ, zlds, h->g, pp, sp, h->tp, h->log2n, tw, C(h->Ck),   \
+                     cnt1, ovf, nullptr, nullptr, nullptr, nullptr, nullptr, R(h->psi)));                           \
   } while (0)
         if (n == 128) BCHMC_LAUNCH_Z(128);
         else if (n == 256) BCHMC_LAUNCH_Z(256);
@@ -1045,7 +1030,7 @@ struct Pipe {
         const int nsuper = (nbricks + kBinPer - 1) / kBinPer;
         k_bin_direct<T><<<nsuper, BCHMC_BIN_THREADS, 0, h->stream>>>(h->g, pp, sp, h->tp, nsuper, R(h->psi), cnt1, ovf,
                                                        (RecQuad *)h->srec, R(h->V), h->rho_part,
-                                                       (h->fix || stage) ? nullptr : R(h->rho),
+                                                       h->fix ? nullptr : R(h->rho),
                                                        h->fix ? h->rho_fix : nullptr);
         rho_cleared = true;
       } else {
@@ -1065,7 +1050,7 @@ struct Pipe {
       // fixed point (deterministic mode): scale = 2^46 / largest single contribution (W(0) = 1/(pi h^3) for the SPH
       // kernel, 1 for NGP / CIC / TSC weights)
       const double fix_scale = h->c.mk == 3 ? 70368744177664. / sp.w_norm : 70368744177664.;
-      if (rho_cleared || stage) {  // staged images: every cell of rho is written by the combine pass
+      if (rho_cleared) {
       } else if (h->fix) {
         HIPCHK(hipMemsetAsync(h->rho_fix, 0, h->g.N * sizeof(long long), h->stream));
       } else {
@@ -1077,9 +1062,8 @@ struct Pipe {
         if (!h->sort_direct && !h->fix) HIPCHK(hipMemsetAsync(h->rho_part, 0, kRedBlocks * sizeof(double), h->stream));
         const int grid = h->tp.ntiles + (int)(h->g.N / h->tp.chunk) + 1;  // upper bound on (tile, chunk) work items
         const int ncol = h->hull_exact ? h->hull_n : 0;
-        // sub-cell ordering inside each work item: binary digits per axis (BCHMC_SUBSORT_BITS = 0 / 1 / 2)
-        const char *sb = std::getenv("BCHMC_SUBSORT_BITS");
-        const int reorder = (h->tp.chunk > 2048) ? 0 : (sb ? std::min(std::max(atoi(sb), 0), 2) : 2);
+        // sub-cell ordering inside each work item: two binary digits per axis
+        const int reorder = (h->tp.chunk > 2048) ? 0 : 2;
         if (reorder) {  // orders the records only after a fallback sort; returns at once otherwise
           k_subsort<T><<<std::min(grid, 8192), 256, 0, h->stream>>>(h->g, h->tp, reorder, (RecQuad *)h->srec, h->t_off, h->t_end, h->t_woff,
                                                    h->t_oct, h->t_seg);
@@ -1091,18 +1075,12 @@ struct Pipe {
                 h->g, sp, h->tp, (const RecQuad *)h->srec, h->t_off, h->t_end, h->t_woff,
                 h->t_oct, h->t_seg, h->rho_fix, h->rho_part, h->t_cnt,
                 (kOct + 1) * h->tp.ntiles + 1, fix_scale);
-          else if (stage)
-            k_scatter_tile81<T, 12, 20, false, true><<<grid, 256, tile_lds(h, 0, sizeof(double)), h->stream>>>(
-                h->g, sp, h->tp, (const RecQuad *)h->srec, h->t_off, h->t_end, h->t_woff,
-                h->t_oct, h->t_seg, R(h->rho), h->rho_part, h->t_cnt,
-                (kOct + 1) * h->tp.ntiles + 1, fix_scale, h->stage, h->stage_inv);
           else
             k_scatter_tile81<T, 12, 20, false><<<grid, 256, tile_lds(h, 0, sizeof(double)), h->stream>>>(
                 h->g, sp, h->tp, (const RecQuad *)h->srec, h->t_off, h->t_end, h->t_woff,
                 h->t_oct, h->t_seg, R(h->rho), h->rho_part, h->t_cnt,
                 (kOct + 1) * h->tp.ntiles + 1, fix_scale);
           h->cnt_clean = true;
-          h->staged = stage;
         } else if (h->fix) {
           k_scatter_tile<T, true><<<grid, 256, tile_lds(h, ncol, sizeof(double)), h->stream>>>(
               h->g, sp, h->tp, h->hull, ncol, (const RecQuad *)h->srec, h->t_off, h->t_end,
@@ -1154,33 +1132,8 @@ struct Pipe {
       k_sum<T><<<kRedBlocks, 256, 0, h->stream>>>(R(h->rho), h->g.N, h->rho_part);
       HIPCHK(hipGetLastError());
     }
-    if (h->staged && !defer_combine) CHK(combine_staged(h, false));
     h->have_eval = true;
     h->last_rsd = rsd;
-    return BCHMC_OK;
-  }
-
-  // rho (and, with `like`, the likelihood partial) from the staged images of the last scatter.  Interior steps of a
-  // trajectory (h->rho_unread) skip the store of rho itself: nothing reads it before the next scatter.
-  static int combine_staged(bchmc_handle *h, bool like) {
-    ProfScope ps(h, BCHMC_K_MEAN_PARTIAL);
-    const int grid = std::min(h->tp.ntiles, 4096);
-    const T *nobs = R(h->in_arr[BCHMC_F_NOBS]), *noise = R(h->in_arr[BCHMC_F_NOISE]), *window = R(h->in_arr[BCHMC_F_WINDOW]);
-    if (like && h->rho_unread)
-      k_stage_combine81<T, true, false><<<grid, 256, 0, h->stream>>>(h->g, h->tp, make_like(h), h->stage, h->stage_tab,
-                                                                     h->t_woff, R(h->rho), h->rho_part, nobs, noise,
-                                                                     window, R(h->plike));
-    else if (like)
-      k_stage_combine81<T, true, true><<<grid, 256, 0, h->stream>>>(h->g, h->tp, make_like(h), h->stage, h->stage_tab,
-                                                                    h->t_woff, R(h->rho), h->rho_part, nobs, noise,
-                                                                    window, R(h->plike));
-    else
-      k_stage_combine81<T, false, true><<<grid, 256, 0, h->stream>>>(h->g, h->tp, make_like(h), h->stage, h->stage_tab,
-                                                                     h->t_woff, R(h->rho), h->rho_part, nullptr, nullptr,
-                                                                     nullptr, nullptr);
-    HIPCHK(hipGetLastError());
-    h->staged = false;
-    h->have_eval = !(like && h->rho_unread);  // without rho there is no deltaX to fetch
     return BCHMC_OK;
   }
 
@@ -1190,7 +1143,7 @@ struct Pipe {
   }
 
   // After forward_rest: leaves the k-space likelihood source in Ck and returns the assemble mode.
-  static int like_force(bchmc_handle *h, int *like_mode) {
+  static int like_force(bchmc_handle *h, EvalMode m, int *like_mode) {
     if (h->c.calc_h == 2 || h->c.calc_h == 3) {
       if (h->c.mk != 3)
         return h->fail(BCHMC_ERR_MK_NOT_SPH, "Must use SPH mass kernel (masskernel = 3) with calc_h = 2 or 3");
@@ -1198,9 +1151,7 @@ struct Pipe {
       return h->fail(BCHMC_ERR_ARG, "calc_h = %d is not a valid value (0..3)", h->c.calc_h);
     }
     const long long N = h->g.N, Nh = h->g.Nhp;
-    if (h->staged) {
-      CHK(combine_staged(h, true));  // rho and the likelihood partial in one pass over the staged images
-    } else {
+    {
       ProfScope ps(h, BCHMC_K_MEAN_PARTIAL);
       k_partial_like<T><<<nblk_stride(N), 256, 0, h->stream>>>(h->g, make_like(h), R(h->rho), h->rho_part,
                                                                R(h->in_arr[BCHMC_F_NOBS]), R(h->in_arr[BCHMC_F_NOISE]),
@@ -1275,7 +1226,7 @@ struct Pipe {
       if (h->tiled && h->sorted_valid) {
         const int grid = h->tp.ntiles + (int)(N / h->tp.chunk) + 1;
         if (h->std81)
-          k_gather_tile81<T, 12, 20><<<grid, 256, tile_lds(h, 0, sizeof(T)) * (20 + BCHMC_GATHER_LZPAD) / 20, h->stream>>>(
+          k_gather_tile81<T, 12, 20><<<grid, 256, tile_lds(h, 0, sizeof(T)), h->stream>>>(
               h->g, hp, h->tp, h->last_rsd, (RecQuad *)h->srec, h->t_off, h->t_end, h->t_woff,
               h->t_oct, h->t_seg, R(h->plike), R(h->V));
         else
@@ -1288,7 +1239,7 @@ struct Pipe {
       }
       HIPCHK(hipGetLastError());
     }
-    if (h->planes_r2c && yfwd_ok(h)) {
+    if (m.planes_r2c && yfwd_ok(h)) {
       // 512^3: the engine's own row and column passes (rocFFT's length-512 column kernel runs at 2.3 TB/s, its 1-D row
       // plan alone at half the speed of the same pass inside the 2-D plan: k_zr2c + k_ypass<forward>, zpass.hpp)
       ProfScope ps(h, BCHMC_K_FFT_R2C);
@@ -1296,17 +1247,12 @@ struct Pipe {
       const int n = h->g.n;
       const CT *tw = reinterpret_cast<const CT *>(h->xtw);
       const size_t zl = ((size_t)n * 6 + n / 2) * sizeof(CT), yl = ((size_t)n * KB + n / 2) * sizeof(CT);
-      auto kz = k_zr2c<T, 512>;
-      auto ky = k_ypass<T, 512, 512 * KB / 512, BCHMC_YPASS_NT, false>;
-      if (zl > 48 * 1024)
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(kz), hipFuncAttributeMaxDynamicSharedMemorySize, (int)zl));
-      if (yl > 48 * 1024)
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(ky), hipFuncAttributeMaxDynamicSharedMemorySize, (int)yl));
-      kz<<<(n / 2) * (n / 2), 512, zl, h->stream>>>(h->g, h->log2n, tw, R(h->V), C(h->Ck));
-      ky<<<3 * n * (h->g.nhp / KB), 512, yl, h->stream>>>(h->g, h->log2n, tw, C(h->Ck));
+      CHK(launch_lds(h, k_zr2c<T, 512>, (n / 2) * (n / 2), 512, zl, h->g, h->log2n, tw, R(h->V), C(h->Ck)));
+      CHK(launch_lds(h, k_ypass<T, 512, 512 * KB / 512, BCHMC_YPASS_NT, false>, 3 * n * (h->g.nhp / KB), 512, yl, h->g,
+                     h->log2n, tw, C(h->Ck)));
       HIPCHK(hipGetLastError());
     } else {
-      CHK(fft_exec(h, h->planes_r2c ? h->r2c2d : h->r2c3, h->V, h->Ck, BCHMC_K_FFT_R2C));
+      CHK(fft_exec(h, m.planes_r2c ? h->r2c2d : h->r2c3, h->V, h->Ck, BCHMC_K_FFT_R2C));
     }
     *like_mode = 0;
     return BCHMC_OK;
@@ -1333,8 +1279,8 @@ struct Pipe {
   }
 
   // Likelihood part of gradient_psi from the current q^: fills Ck, returns (like_mode, b).
-  // pre_za: Psi^ is already in Ck (the fused kick+drift+ZA kernel ran).
-  static int force_sources(bchmc_handle *h, bool pre_za, int *like_mode, double *b) {
+  // pre_za: Psi^ is already in Ck (the fused kick+drift+ZA kernel ran), or with m.alpt_pending the ALPT model's inputs.
+  static int force_sources(bchmc_handle *h, bool pre_za, EvalMode m, int *like_mode, double *b) {
     if (h->c.likelihood == 3) {
       CHK(grf_force(h));
       *like_mode = 1;
@@ -1342,13 +1288,13 @@ struct Pipe {
       return BCHMC_OK;
     }
     if (!pre_za) {
-      CHK(displacement(h, h->c.deltaQ_factor, h->c.rsd_model));
-    } else if (h->alpt_pending) {
-      h->alpt_pending = false;
+      CHK(displacement(h, h->c.deltaQ_factor, h->c.rsd_model, &m.planes_c2r));
+    } else if (m.alpt_pending) {
       CHK(alpt_middle(h, true));  // delta(1)^ | Phi^ planes left by k_step_boundary_x<ALPT> -> Psi^ planes
+      m.planes_c2r = true;
     }
-    CHK(forward_rest(h, h->c.rsd_model, /*defer_combine=*/true));
-    CHK(like_force(h, like_mode));
+    CHK(forward_rest(h, h->c.rsd_model, m));
+    CHK(like_force(h, m, like_mode));
     double norm = -1.;  // zeldovich_norm, HMC_models.cc:458-461
     norm *= h->c.deltaQ_factor;
     if (h->c.correct_delta) norm *= h->c.D1;
@@ -1461,11 +1407,10 @@ struct Pipe {
           CHK(launch_boundary_x<BX_FIRST>(h, C(h->qk), nullptr, nullptr, nullptr, nullptr, 0., 0., 0., 0., pl.c_za, nullptr,
                                           nc, nullptr, nullptr));
       }
-      h->alpt_pending = pl.alpt_x;
-      h->planes_c2r = h->planes_r2c = true;
-      const int rc = force_sources(h, true, &like_mode, &b);
-      h->planes_c2r = h->planes_r2c = false;
-      CHK(rc);
+      EvalMode m;
+      m.planes_c2r = m.planes_r2c = true;
+      m.alpt_pending = pl.alpt_x;
+      CHK(force_sources(h, true, m, &like_mode, &b));
       if (like_mode != 0) return h->fail(BCHMC_ERR_STATE, "planes mode without the three V components");
       if (like_i) CHK(tap_loglike(h, like_i));
       h->prop_g_valid = false;
@@ -1473,7 +1418,7 @@ struct Pipe {
       CHK(launch_boundary_x<BX_LAST>(h, C(h->qk), nullptr, nullptr, nullptr, nullptr, pl.a, b, 0., 0., 0., nullptr, nc,
                                      nullptr, C(h->gk)));
     } else {
-      CHK(force_sources(h, false, &like_mode, &b));
+      CHK(force_sources(h, false, EvalMode{}, &like_mode, &b));
       if (like_i) CHK(tap_loglike(h, like_i));
       CHK(launch_assemble<false>(h, pl.a, b, like_mode, 0., nullptr));
     }
@@ -1534,7 +1479,7 @@ struct Pipe {
                                                                              C(h->tC), C(h->Ck), 0., eps, c_za, ctl2);
         HIPCHK(hipGetLastError());
       }
-      CHK(force_sources(h, fused_za, &like_mode, &b));
+      CHK(force_sources(h, fused_za, EvalMode{}, &like_mode, &b));
       if (tap && tap->like_f && s + 1 == neps) CHK(tap_loglike(h, tap->like_f));
       CHK(launch_assemble<true>(h, a, b, like_mode, 0.5 * eps, h->guard + s));
     }
@@ -1551,15 +1496,9 @@ struct Pipe {
     const int n = h->g.n, grid = n * (h->g.nhp / KB);
     const size_t lds = ((size_t)n * KB + n / 2) * sizeof(CT);
     const CT *tw = reinterpret_cast<const CT *>(h->xtw);
-#define BCHMC_LAUNCH_X(NT, PER)                                                                                    \
-  do {                                                                                                             \
-    auto kern = k_step_boundary_x<T, NT, PER, MODE, ALPT>;                                                         \
-    if (lds > 48 * 1024)                                                                                           \
-      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                 (int)lds));                                                                       \
-    kern<<<grid, NT, lds, h->stream>>>(h->g, h->log2n, tw, C(h->Ck), qi, pi, qo, po, h->wS, wM, a, b, half_eps,  \
-                                       eps, c_za, guard_slot, ctl, g_in, g_out);                                   \
-  } while (0)
+#define BCHMC_LAUNCH_X(NT, PER)                                                                                      \
+  CHK(launch_lds(h, k_step_boundary_x<T, NT, PER, MODE, ALPT>, grid, NT, lds, h->g, h->log2n, tw, C(h->Ck), qi, pi, qo, \
+                 po, h->wS, wM, a, b, half_eps, eps, c_za, guard_slot, ctl, g_in, g_out))
     // interior Zel'dovich boundary with fp32 fields: the two-tile formulation (k_step_boundary_x2).  A 1024-thread
     // workgroup is alone on its CU there and the first formulation leaves its memory phases exposed: 0.283 -> 0.231 ms
     // at 256^3.  With fp64 fields (two 512-thread workgroups per CU) both formulations take the same 0.329 ms --
@@ -1570,14 +1509,8 @@ struct Pipe {
         (unsigned long long)h->g.Nhp * sizeof(CT) < (1ull << 32)) {  // its lane offsets are 32-bit byte offsets
       const size_t lds2 = ((size_t)2 * n * KB + n / 2) * sizeof(CT);
 #define BCHMC_LAUNCH_X2(NT, PER)                                                                                   \
-  do {                                                                                                             \
-    auto kern = k_step_boundary_x2<T, NT, PER>;                                                                    \
-    if (lds2 > 48 * 1024)                                                                                          \
-      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                 (int)lds2));                                                                      \
-    kern<<<grid, NT, lds2, h->stream>>>(h->g, h->log2n, tw, C(h->Ck), qi, pi, qo, po, h->wS, wM, a, b, half_eps, \
-                                        eps, c_za, guard_slot, ctl);                                               \
-  } while (0)
+  CHK(launch_lds(h, k_step_boundary_x2<T, NT, PER>, grid, NT, lds2, h->g, h->log2n, tw, C(h->Ck), qi, pi, qo, po, h->wS, \
+                 wM, a, b, half_eps, eps, c_za, guard_slot, ctl))
       if (n == 128) BCHMC_LAUNCH_X2(NT_BIG, 4);
       else BCHMC_LAUNCH_X2(2 * NT_BIG, 4);
 #undef BCHMC_LAUNCH_X2
@@ -1636,20 +1569,15 @@ struct Pipe {
         HIPCHK(hipEventRecord(h->ev_q, h->stream));
         h->early_q_done = true;
       }
-      if (h->slot_watch && h->tiled && h->sort_direct && s > 0 && s % kSlotPoll == 0 && !env_on("BCHMC_NO_SLOT_POLL"))
+      if (h->slot_watch && h->tiled && h->sort_direct && s > 0 && s % kSlotPoll == 0)
         CHK(poll_slots(h, s / kSlotPoll));
-      h->planes_c2r = planes && (s > 0 || ends);  // Psi^ left by k_step_boundary_x still needs only the (y, z) passes
-      h->planes_r2c = planes && (!last || ends);  // ... and V^ for it gets only those
-      h->alpt_pending = alpt_x;                    // ... or delta(1)^ | Phi^ planes for the ALPT pipeline
-      h->rho_unread = !last && h->c.calc_h != 0 && !env_on("BCHMC_KEEP_RHO");  // rho of an interior step is read by
-                                                                                   // nobody (calc_h 0: k_overdens does)
-      h->psi_unread = !last;
-      const int rc = force_sources(h, true, &like_mode, &b);
-      h->rho_unread = false;
-      h->psi_unread = false;
-      const bool xmode = h->planes_r2c && like_mode == 0;
-      h->planes_c2r = h->planes_r2c = false;
-      CHK(rc);
+      EvalMode m;
+      m.planes_c2r = planes && (s > 0 || ends);  // Psi^ left by k_step_boundary_x still needs only the (y, z) passes
+      m.planes_r2c = planes && (!last || ends);  // ... and V^ for it gets only those
+      m.alpt_pending = alpt_x;                   // ... or delta(1)^ | Phi^ planes for the ALPT pipeline
+      m.psi_unread = !last;
+      CHK(force_sources(h, true, m, &like_mode, &b));
+      const bool xmode = m.planes_r2c && like_mode == 0;
       if (tap && tap->like_f && last) CHK(tap_loglike(h, tap->like_f));
       StepCtl ctl{h->stop, h->steps_done, s > 0 ? h->guard + (s - 1) : nullptr, guard_limit, s};
       void *qi = cur ? q1 : q0, *pi = cur ? p1 : p0, *qo = cur ? q0 : q1, *po = cur ? p0 : p1;
@@ -1814,8 +1742,10 @@ struct Pipe {
           CHK(c2r_state(h, h->qk, h->ioq, h->dstage));
         }
         // runaway guard fired (HMC.cc:360-364): the tapped forward model is not the final state's; redo it
-        CHK(displacement(h, h->c.likelihood == 1 ? h->c.deltaQ_factor : 1., h->c.likelihood == 1 ? h->c.rsd_model : 0));
-        CHK(forward_rest(h, h->c.likelihood == 1 ? h->c.rsd_model : 0));
+        EvalMode m;
+        CHK(displacement(h, h->c.likelihood == 1 ? h->c.deltaQ_factor : 1., h->c.likelihood == 1 ? h->c.rsd_model : 0,
+                         &m.planes_c2r));
+        CHK(forward_rest(h, h->c.likelihood == 1 ? h->c.rsd_model : 0, m));
         CHK(tap_loglike(h, P));
         CHK(host_sum(h, P, &terms[5]));
       }
@@ -1961,8 +1891,9 @@ struct Pipe {
       // gaussian log_like applies deltaQ_factor and honours rsd_model (gaussian_independent.cpp:57-76);
       // poissonian / log-normal log_like do neither (poissonian.cpp:54-56, lognormal_independent.cpp:105-107)
       const bool gauss = (h->c.likelihood == 1);
-        CHK(displacement(h, gauss ? h->c.deltaQ_factor : 1., gauss ? h->c.rsd_model : 0));
-      CHK(forward_rest(h, gauss ? h->c.rsd_model : 0));
+      EvalMode m;
+      CHK(displacement(h, gauss ? h->c.deltaQ_factor : 1., gauss ? h->c.rsd_model : 0, &m.planes_c2r));
+      CHK(forward_rest(h, gauss ? h->c.rsd_model : 0, m));
       k_loglike<T><<<kRedBlocks, 256, 0, h->stream>>>(h->g, make_like(h), R(h->rho), h->rho_part,
                                                       R(h->in_arr[BCHMC_F_NOBS]), R(h->in_arr[BCHMC_F_NOISE]),
                                                       R(h->in_arr[BCHMC_F_WINDOW]), h->partA);
@@ -1982,8 +1913,9 @@ struct Pipe {
 
   static int forward(bchmc_handle *h, const double *d_q, int rsd) {
     CHK(r2c_state(h, d_q, h->ioq, h->qk));
-    CHK(displacement(h, 1., rsd));
-    return forward_rest(h, rsd);
+    EvalMode m;
+    CHK(displacement(h, 1., rsd, &m.planes_c2r));
+    return forward_rest(h, rsd, m);
   }
 
   static int gradient(bchmc_handle *h, const double *d_q, double *d_g) {
@@ -1995,7 +1927,7 @@ struct Pipe {
     CHK(r2c_state(h, d_q, h->ioq, h->qk));
     int like_mode = 2;
     double b = 0.;
-    CHK(force_sources(h, false, &like_mode, &b));
+    CHK(force_sources(h, false, EvalMode{}, &like_mode, &b));
     CHK(launch_assemble<false>(h, h->c.grad_psi_prior_factor, 0., 2, 0., nullptr));
     CHK(c2r_scaled(h, h->gk, h->gprior));
     CHK(launch_assemble<false>(h, 0., b, like_mode, 0., nullptr));
@@ -2081,7 +2013,7 @@ struct Pipe {
   static int mass_force_spectrum(bchmc_handle *h, uint64_t n_bin, double *kmode, double *power) {
     int like_mode = 2;
     double b = 0.;
-    CHK(force_sources(h, false, &like_mode, &b));
+    CHK(force_sources(h, false, EvalMode{}, &like_mode, &b));
     double norm = -1.;  // zeldovich_norm, HMC_models.cc:458-461, without the test factor
     norm *= h->c.deltaQ_factor;
     if (h->c.correct_delta) norm *= h->c.D1;
@@ -2133,8 +2065,9 @@ struct Pipe {
     }
     // Lag2Eul(signal) (HMC_mass.cc:242-257): no deltaQ_factor, rsd_model as configured
     const int rsd = h->c.rsd_model;
-    CHK(displacement(h, 1., rsd));
-    CHK(forward_rest(h, rsd));
+    EvalMode mode;
+    CHK(displacement(h, 1., rsd, &mode.planes_c2r));
+    CHK(forward_rest(h, rsd, mode));
     const PosPar pp = make_pos(h, rsd);
     JaschePar jp;
     jp.h = h->c.particle_kernel_h;
@@ -2662,7 +2595,7 @@ int bchmc_create(const bchmc_config *cfg, bchmc_handle **out) {
           // ... and which spline branch a candidate can take (k_scatter_tile81): the home cell must stay at q <= 1,
           // i.e. h >= (sqrt(3) / 2) d -- the 81-cell hull alone would also admit 0.83 d <= h < 0.866 d
           if (cfg->particle_kernel_h < 0.8661 * g.d) is81 = false;
-          h->std81 = is81 && cfg->mk == 3 && !env_on("BCHMC_NO_UNROLL");
+          h->std81 = is81 && cfg->mk == 3;
           // One-pass binning: the record array holds cap_alloc = 16x the mean occupancy in slots per tile (the 288 GB
           // of HBM pay for a whole pass over the particles: 8.6 GB at 256^3 fp64), all of it in use as eight octant
           // segments of cap / 8; it is reallocated for 1.5x the largest (tile, octant) population the binning reports
@@ -2695,48 +2628,6 @@ int bchmc_create(const bchmc_config *cfg, bchmc_handle **out) {
           CHK(dev_alloc(h, &h->t_woff, (size_t)tp.ntiles + 1));
           CHK(dev_alloc(h, &h->t_rank, N));
           CHK(dev_alloc_bytes(h, &h->srec, nrec * 4 * e));
-          // staging area for the density images of the unrolled scatter (k_scatter_tile81<STAGE>): one image per
-          // possible work item, 566 MB at 256^3.  Opt-in (BCHMC_STAGE=1): measured a wash against the flush through
-          // global atomics -- scatter 0.92 -> 0.83 ms, but the combine pass that replaces k_partial_like 0.13 -> 0.25 ms
-          // (profiles/r03_ab_stage.txt)
-          if (h->std81 && !h->fix && env_on("BCHMC_STAGE")) {
-            const size_t items = (size_t)tp.ntiles + N / (size_t)tp.chunk + 1;
-            CHK(dev_alloc(h, &h->stage, items * (size_t)tp.lx * tp.ly * tp.lz));
-            // which tile owns each cell of a 12 x 12 x 20 image: direction delta from the image's tile to the owner,
-            // the owner's cell; staged position = cells grouped by owner (27 blocks), z fastest inside a block
-            struct Cellinfo { int block, own, img; };
-            std::vector<Cellinfo> cells;
-            for (int lx = 0; lx < 12; lx++)
-              for (int ly = 0; ly < 12; ly++)
-                for (int lz = 0; lz < 20; lz++) {
-                  const int ex = lx < 2 ? -1 : (lx >= 10 ? 1 : 0), ey = ly < 2 ? -1 : (ly >= 10 ? 1 : 0),
-                            ez = lz < 2 ? -1 : (lz >= 18 ? 1 : 0);
-                  const int x = lx - 2 - 8 * ex, y = ly - 2 - 8 * ey, z = lz - 2 - 16 * ez;  // owner-local cell
-                  cells.push_back({(ez + 1) + 3 * ((ey + 1) + 3 * (ex + 1)), z + 16 * (y + 8 * x), lz + 20 * (ly + 12 * lx)});
-                }
-            std::stable_sort(cells.begin(), cells.end(), [](const Cellinfo &a, const Cellinfo &b) {
-              return a.block != b.block ? a.block < b.block : a.own < b.own;
-            });
-            std::vector<unsigned> tab;
-            std::vector<unsigned short> inv;
-            for (size_t pos = 0; pos < cells.size(); pos++) {
-              // the owner sees the image's tile at -delta: neighbour index 26 - block; one entry per pair of cells
-              // (every block is a whole number of z-adjacent pairs: its z extent is 16 or 2 cells from an even z)
-              if (pos % 2 == 0) {
-                if (cells[pos + 1].block != cells[pos].block || cells[pos + 1].own != cells[pos].own + 1)
-                  return h->fail(BCHMC_ERR_STATE, "stage table: position %zu does not start a pair", pos);
-                tab.push_back(stage_entry(26 - cells[pos].block, cells[pos].own, (int)pos));
-              }
-              inv.push_back((unsigned short)cells[pos].img);
-            }
-            CHK(dev_alloc(h, &h->stage_inv, inv.size()));
-            HIPCHK(hipMemcpyAsync(h->stage_inv, inv.data(), inv.size() * sizeof(unsigned short), hipMemcpyHostToDevice,
-                                  h->stream));
-            if ((int)tab.size() != kStagePairs) return h->fail(BCHMC_ERR_STATE, "stage table has %zu entries", tab.size());
-            CHK(dev_alloc(h, &h->stage_tab, tab.size()));
-            HIPCHK(hipMemcpyAsync(h->stage_tab, tab.data(), tab.size() * sizeof(unsigned), hipMemcpyHostToDevice, h->stream));
-            HIPCHK(hipStreamSynchronize(h->stream));
-          }
         }
       }
     }
@@ -2759,7 +2650,7 @@ void bchmc_destroy(bchmc_handle *h) {
   if (h->info) rocfft_execution_info_destroy(h->info);
   void *ptrs[] = {h->work,  h->wS,       h->wM,    h->qk,    h->pk,   h->gk,     h->Ck,         h->tC,   h->psi,
                   h->V,     h->rho,      h->plike, h->ioq,   h->iop,  h->gprior, h->glike,      h->conv, h->convF,
-                  h->dstage, h->rho_fix, h->fix_sat, h->stage, h->stage_tab, h->stage_inv, h->spec_bins, h->cq, h->cp, h->cg, h->qk2, h->pk2, h->xtw, h->part6, h->rho_part, h->partA, h->guard, h->stop, h->steps_done, h->hull,  h->t_cnt, h->t_off,
+                  h->dstage, h->rho_fix, h->fix_sat, h->spec_bins, h->cq, h->cp, h->cg, h->qk2, h->pk2, h->xtw, h->part6, h->rho_part, h->partA, h->guard, h->stop, h->steps_done, h->hull,  h->t_cnt, h->t_off,
                   h->t_woff, h->t_oct, h->t_seg, h->t_end, h->t_rank,  h->srec};
   for (void *p : ptrs)
     if (p) (void)hipFree(p);
@@ -3190,7 +3081,7 @@ int bchmc_tile_info(bchmc_handle *h, int32_t out[8]) {
   out[2] = h->tp.cap;
   out[3] = (int32_t)std::min<long long>(h->cap_alloc, INT32_MAX);
   out[4] = h->slot_watch ? 1 : 0;
-  out[5] = h->stage ? 1 : 0;
+  out[5] = 0;  // reserved
   out[6] = h->std81 ? 1 : 0;
   out[7] = (h->c2r2d_2 != nullptr) ? 1 : 0;
   return BCHMC_OK;

@@ -3,9 +3,6 @@
 #pragma once
 #include "common.hpp"
 
-#ifndef BCHMC_BX_SWIZZLE
-#define BCHMC_BX_SWIZZLE 1
-#endif
 #ifndef BCHMC_BX_WAVES
 #define BCHMC_BX_WAVES 4
 #endif
@@ -183,10 +180,8 @@ k_step_boundary_x(Geo g, int log2n, const C2<T> *__restrict__ twiddle, C2<T> *Ck
   for (int t = threadIdx.x; t < n / 2; t += blockDim.x) tw[t] = twiddle[t];
   const int ntk = g.nhp / KB;
   int bid = (int)blockIdx.x;
-#if BCHMC_BX_SWIZZLE
   // workgroups are dealt round-robin to the 8 XCDs: give each XCD a contiguous range of (j, k0) columns
   if ((gridDim.x & 7) == 0) bid = (bid & 7) * (int)(gridDim.x >> 3) + (bid >> 3);
-#endif
   const int j = bid / ntk, k0 = (bid % ntk) * KB;
   const int c = threadIdx.x % KB, irow = threadIdx.x / KB;
   constexpr int rows = NT / KB, per = PER;
@@ -495,9 +490,7 @@ k_step_boundary_x2(Geo g, int log2n, const C2<T> *__restrict__ twiddle, C2<T> *C
   for (int t = threadIdx.x; t < n / 2; t += blockDim.x) tw[t] = twiddle[t];
   const int ntk = g.nhp / KB;
   int bid = (int)blockIdx.x;
-#if BCHMC_BX_SWIZZLE
   if ((gridDim.x & 7) == 0) bid = (bid & 7) * (int)(gridDim.x >> 3) + (bid >> 3);
-#endif
   const int j = bid / ntk, k0 = (bid % ntk) * KB;
   const int c = threadIdx.x % KB, irow = threadIdx.x / KB;
   constexpr int rows = NT / KB;

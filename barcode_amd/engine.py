@@ -414,7 +414,7 @@ class Engine:
     def tile_info(self):
         out = (C.c_int32 * 8)()
         self._chk(self.lib.bchmc_tile_info(self.h, out))
-        keys = ("tiled", "one_pass", "cap", "cap_alloc", "watch", "stage", "unrolled81", "alpt_planes")
+        keys = ("tiled", "one_pass", "cap", "cap_alloc", "watch", "reserved", "unrolled81", "alpt_planes")
         return dict(zip(keys, [int(v) for v in out]))
 
     # ---- measurement ---------------------------------------------------------------------------

@@ -222,7 +222,7 @@ int bchmc_philox_kat(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[
 
 /* Diagnostic (tests, logs): how the particle-mesh path is currently set up.  out = { tile-sorted path in use, one-pass
  * binning in use, record slots per tile in use, record slots per tile allocated, long trajectories poll the slot words,
- * staged density flush available, unrolled 81-cell kernels in use, ALPT planes pipeline available }. */
+ * reserved (0), unrolled 81-cell kernels in use, ALPT planes pipeline available }. */
 int bchmc_tile_info(bchmc_handle *h, int32_t out[8]);
 
 /* ---- measurement hooks (bench.py): per-kernel-class HIP-event timing on the engine's stream ---- */

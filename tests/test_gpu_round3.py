@@ -1,6 +1,6 @@
-"""Round-3 paths against the oracle and against their predecessors: the staged density flush (k_scatter_tile81<STAGE> +
-k_stage_combine81), record slots sized from the measured populations (adapt_slots / poll_slots), and the ALPT model on
-the 2-D plans (k_step_boundary_x<ALPT>, k_alpt_mix_x with the cell-boundary average as a k-space phase)."""
+"""Round-3 paths against the oracle and against their predecessors: the unrolled scatter's flush with many work items
+per tile (k_scatter_tile81), record slots sized from the measured populations (adapt_slots / poll_slots), and the ALPT
+model on the 2-D plans (k_step_boundary_x<ALPT>, k_alpt_mix_x with the cell-boundary average as a k-space phase)."""
 import numpy as np
 import pytest
 
@@ -11,23 +11,21 @@ pytestmark = pytest.mark.gpu
 
 @pytest.mark.parametrize("nx,chunk", [(16, None), (32, None), (32, "64"), (48, "128")],
                          ids=["n16", "n32", "n32_many_items_per_tile", "n48_three_tiles_in_z"])
-def test_staged_flush_against_oracle_and_atomic_flush(monkeypatch, nx, chunk):
-    """The scatter writes its LDS images to the staging area, the combine pass sums the <= 8 images per cell (all work
-    items of each tile: BCHMC_CHUNK=64 makes ~16 per tile) -- same density as the oracle's and as the atomic flush."""
+def test_tile_flush_against_oracle(monkeypatch, nx, chunk):
+    """Every work item of a tile adds its LDS image (tile + halo) to the density, up to 8 images per cell and all work
+    items of each tile (BCHMC_CHUNK=64 makes ~16 per tile) -- same density as the oracle's."""
     if chunk:
         monkeypatch.setenv("BCHMC_CHUNK", chunk)
-    monkeypatch.setenv("BCHMC_STAGE", "1")                 # opt-in: measured a wash at 256^3 (DESIGN.md 5.4)
     c = Case(Nx=nx, likelihood=1, rsd_model=1)
     dX, px, py, pz = c.oracle.Lag2Eul(c.truth, rsd=1)
     rho_o = c.oracle.getDensity(3, px, py, pz)
     e = c.engine()
-    info = e.tile_info()
-    assert info["stage"] == 1 and info["unrolled81"] == 1
-    e.forward(c.truth, 1)                                  # forward_rest combines on its own (no likelihood pass)
+    assert e.tile_info()["unrolled81"] == 1
+    e.forward(c.truth, 1)
     rho = e.fetch("rho")
     assert rel_l2(rho, rho_o) < TOL_FIELD and rel_l2(e.fetch("deltaX"), dX) < TOL_FIELD
     assert abs(rho.sum() - rho_o.sum()) <= 1e-12 * rho_o.sum()
-    g, _, gl = c.oracle.gradient_psi(c.q0)                 # like_force: combine fused with the likelihood partial
+    g, _, gl = c.oracle.gradient_psi(c.q0)
     assert rel_l2(e.gradient(c.q0), g) < 10 * TOL_FIELD
     pl = c.oracle.partial_f_delta_x_log_like(c.oracle.get("deltaX"))
     assert rel_l2(e.fetch("part_like"), pl) < 10 * TOL_FIELD and rel_l2(e.fetch("deltaX"), c.oracle.get("deltaX")) < TOL_FIELD
@@ -37,23 +35,14 @@ def test_staged_flush_against_oracle_and_atomic_flush(monkeypatch, nx, chunk):
     assert done == 6 and rel_l2(q1, q1o) < TOL_TRAJ_10 and rel_l2(p1, p1o) < TOL_TRAJ_10
     assert np.all(np.abs(t - to) <= 10 * TOL_ENERGY * np.abs(to))
     e.close()
-    monkeypatch.setenv("BCHMC_STAGE", "0")
-    e2 = c.engine()
-    assert e2.tile_info()["stage"] == 0
-    e2.forward(c.truth, 1)
-    assert rel_l2(e2.fetch("rho"), rho) < 1e-14
-    q2, p2, _ = e2.leapfrog(c.q0, c.p0, c.eps, 6)
-    assert rel_l2(q2, q1) < 1e-13 and rel_l2(p2, p1) < 1e-13
-    e2.close()
 
 
-def test_staged_flush_other_likelihoods_and_fp32(monkeypatch):
-    monkeypatch.setenv("BCHMC_STAGE", "1")
+def test_tile_flush_other_likelihoods_and_fp32():
     for kw, prec, tol in ((dict(likelihood=0, rsd_model=0), 0, 10 * TOL_FIELD), (dict(likelihood=2, rsd_model=0), 0, 10 * TOL_FIELD),
                           (dict(likelihood=1, rsd_model=1), 1, 2e-5)):
         c = Case(Nx=32, **kw)
         e = c.engine(precision=prec)
-        assert e.tile_info()["stage"] == 1
+        assert e.tile_info()["unrolled81"] == 1
         g, _, _ = c.oracle.gradient_psi(c.q0)
         assert rel_l2(e.gradient(c.q0), g) < tol
         assert rel_l2(e.fetch("deltaX"), c.oracle.get("deltaX")) < (TOL_FIELD if prec == 0 else 2e-5)
