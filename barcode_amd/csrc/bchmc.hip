@@ -105,8 +105,13 @@ struct bchmc_handle {
     unsigned long long *res = nullptr;  // 8 counters + the 624-word end state
     unsigned long long *h_io = nullptr; // pinned mirror of res (the input window goes out through its state words)
     double *gauss = nullptr;
+    long long gauss_cap = 0;            // doubles allocated for gauss (grown by mt_reserve outside trajectories)
     double setup_ms = 0.;
   } mt;
+  // setup_random_test (mock.hpp): windowed cells per tile, their scan, {windowed cells, first noise == 0 index}
+  struct Mock {
+    unsigned long long *cnt = nullptr, *off = nullptr, *gsum = nullptr, *goff = nullptr, *res = nullptr;
+  } mock;
   double *spec_bins = nullptr;                       // measure_spectrum's 3 * n_bin accumulators
   size_t spec_cap = 0;
   // host-array entry points: caller arrays are pageable, so they cross PCIe through two pinned staging chunks
@@ -845,15 +850,19 @@ struct Pipe {
   // kernelcomp: wtot = sum over the box of the inverse transform of the kernel table (= K(0) up to round-off)
   static int alpt_norm(bchmc_handle *h) {
     if (h->alpt_wtot != 0.) return BCHMC_OK;
+    return kernel_norm(h, h->c.kth, h->rho, &h->alpt_wtot);
+  }
+  // the same for any scale; `scratch`: N elements of T
+  static int kernel_norm(bchmc_handle *h, double smol, void *scratch, double *wtot) {
     ProfScope ps(h, BCHMC_K_OTHER);
-    k_alpt_kernel_table<T><<<nblk_stride(h->g.Nhp), 256, 0, h->stream>>>(h->g, C(h->tC), h->c.kth);
+    k_alpt_kernel_table<T><<<nblk_stride(h->g.Nhp), 256, 0, h->stream>>>(h->g, C(h->tC), smol);
     HIPCHK(hipGetLastError());
-    CHK(fft_exec(h, h->c2r1, h->tC, h->rho, BCHMC_K_FFT_C2R));
-    k_sum<T><<<kRedBlocks, 256, 0, h->stream>>>(R(h->rho), h->g.N, h->partA);
+    CHK(fft_exec(h, h->c2r1, h->tC, scratch, BCHMC_K_FFT_C2R));
+    k_sum<T><<<kRedBlocks, 256, 0, h->stream>>>(R(scratch), h->g.N, h->partA);
     HIPCHK(hipGetLastError());
     double v;
     CHK(host_sum(h, h->partA, &v));
-    h->alpt_wtot = v / (double)h->g.N;
+    *wtot = v / (double)h->g.N;
     return BCHMC_OK;
   }
 
@@ -1995,6 +2004,89 @@ struct Pipe {
     return BCHMC_OK;
   }
 
+  // ---- setup_random_test / make_initial_guess (barcoderunner.cc:42-247; mock.hpp) ----------------------------------
+  // create_GARFIELD(signal_PS) from the 2 N unit Gaussians of the draw, placed in k-space into dst (qk or cq): the
+  // R2C of upstream's real-space field, like the momenta of mt_place.
+  static int mock_place(bchmc_handle *h, void *dst) {
+    const long long N = h->g.N;
+    const int n = h->g.n;
+    ProfScope ps(h, BCHMC_K_OTHER);
+    HIPCHK(hipMemsetAsync(dst, 0, 2 * (size_t)h->g.Nhp * sizeof(T), h->stream));
+    const long long cells = (long long)(n / 2 + 1) * (n / 2 + 1) * (n / 2 + 1);
+    const double amp = (double)N * (double)N / (h->g.L * h->g.L * h->g.L);  // random.cpp:88-90
+    k_mt_place<T><<<nblk_stride(cells), 256, 0, h->stream>>>(n, h->g.nhp, h->mt.gauss, R(h->in_arr[BCHMC_F_SIGNAL_PS]),
+                                                             amp, C(dst));
+    HIPCHK(hipGetLastError());
+    return BCHMC_OK;
+  }
+
+  static long long mock_tiles(const bchmc_handle *h) { return (h->g.N + kMockTile - 1) / kMockTile; }
+  static long long mock_groups(const bchmc_handle *h) { return (mock_tiles(h) + kMtThreads - 1) / kMtThreads; }
+
+  static int mock_alloc(bchmc_handle *h) {
+    auto &k = h->mock;
+    if (k.cnt) return BCHMC_OK;
+    CHK(dev_alloc(h, &k.cnt, (size_t)mock_tiles(h)));
+    CHK(dev_alloc(h, &k.off, (size_t)mock_tiles(h)));
+    CHK(dev_alloc(h, &k.gsum, (size_t)mock_groups(h)));
+    CHK(dev_alloc(h, &k.goff, (size_t)mock_groups(h)));
+    CHK(dev_alloc(h, &k.res, (size_t)2));
+    return BCHMC_OK;
+  }
+
+  // From the truth's k-space form in qk: delta_lag -> dstage[0, N), its forward model (left in the handle) with
+  // delta_eul -> dstage[N, 2N), the window into the handle's input array, the ranks of its cells; res[0] = their count.
+  static int mock_window(bchmc_handle *h, int rsd, int window_type) {
+    const long long N = h->g.N;
+    auto &k = h->mock;
+    CHK(c2r_state(h, h->qk, h->ioq, h->dstage));
+    EvalMode m;
+    CHK(displacement(h, 1., rsd, &m.planes_c2r));
+    CHK(forward_rest(h, rsd, m));
+    CHK(fetch(h, BCHMC_F_DELTAX, h->dstage + N));
+    ProfScope ps(h, BCHMC_K_OTHER);
+    HIPCHK(hipMemsetAsync(k.res, 0xff, 2 * sizeof(unsigned long long), h->stream));
+    k_mock_window<T><<<(int)mock_tiles(h), kMockThreads, 0, h->stream>>>(N, window_type, h->dstage + N,
+                                                                         R(h->in_arr[BCHMC_F_WINDOW]), k.cnt);
+    k_mock_scan<<<(int)mock_groups(h), kMtThreads, 0, h->stream>>>(k.cnt, mock_tiles(h), k.off, k.gsum);
+    k_mt_scan<<<1, kMtThreads, 0, h->stream>>>(k.gsum, (int)mock_groups(h), k.goff, k.res, 0, nullptr);
+    HIPCHK(hipGetLastError());
+    return BCHMC_OK;
+  }
+
+  // nobs and noise into the handle's input arrays from the split Gaussians of the second draw
+  static int mock_noise(bchmc_handle *h, const MockPar &mp) {
+    const long long N = h->g.N;
+    auto &k = h->mock;
+    ProfScope ps(h, BCHMC_K_OTHER);
+    k_mock_noise<T><<<(int)mock_tiles(h), kMockThreads, 0, h->stream>>>(
+        N, mp, h->dstage, h->dstage + N, R(h->in_arr[BCHMC_F_WINDOW]), k.off, k.goff,
+        reinterpret_cast<const double2 *>(h->mt.gauss), R(h->in_arr[BCHMC_F_NOBS]), R(h->in_arr[BCHMC_F_NOISE]), k.res);
+    HIPCHK(hipGetLastError());
+    return BCHMC_OK;
+  }
+
+  // initial_guess 3: the placed field in cq times kernelcomp's table
+  static int mock_smooth(bchmc_handle *h, double smol) {
+    double wtot = 0.;
+    CHK(kernel_norm(h, smol, h->ioq, &wtot));
+    ProfScope ps(h, BCHMC_K_OTHER);
+    k_mock_smooth<T><<<nblk_stride(h->g.Nhp), 256, 0, h->stream>>>(h->g, C(h->cq), smol, 1. / wtot);
+    HIPCHK(hipGetLastError());
+    return BCHMC_OK;
+  }
+
+  // initial_guess 4: N draws gsl_ran_gaussian(sigma) in cell order, taken in like bchmc_chain_set_state takes an array
+  static int mock_guess_noise(bchmc_handle *h, double sigma) {
+    {
+      ProfScope ps(h, BCHMC_K_OTHER);
+      k_mock_guess_noise<<<nblk_stride(h->g.N), kMockThreads, 0, h->stream>>>(
+          h->g.N, sigma, reinterpret_cast<const double2 *>(h->mt.gauss), h->dstage);
+      HIPCHK(hipGetLastError());
+    }
+    return r2c_state(h, h->dstage, h->ioq, h->cq);
+  }
+
   static int upload(bchmc_handle *h, bchmc_field field, const double *d_src) {
     CHK(load_real(h, d_src, R(h->in_arr[field])));
     const double normFS = h->g.L * h->g.L * h->g.L / (double)h->g.N;  // FOURIER_DEF_2, HMC_help.cc:25-27
@@ -2278,7 +2370,8 @@ int mt_setup(bchmc_handle *h) {
   CHK(dev_alloc(h, &m.st, (size_t)kMtN));
   for (unsigned long long **p : {&m.nz, &m.nzoff, &m.acc, &m.accoff, &m.lastend}) CHK(dev_alloc(h, p, (size_t)B));
   CHK(dev_alloc(h, &m.res, (size_t)8 + kMtN / 2));
-  CHK(dev_alloc(h, &m.gauss, (size_t)std::max(m.G, 1LL)));
+  m.gauss_cap = std::max(m.G, 1LL);
+  CHK(dev_alloc(h, &m.gauss, (size_t)m.gauss_cap));
   HIPCHK(hipHostMalloc((void **)&m.h_io, (8 + kMtN / 2) * sizeof(unsigned long long)));
   HIPCHK(hipMemcpyAsync(m.poly, polys.data(), polys.size() * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
   HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_mt_segments), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -2288,9 +2381,22 @@ int mt_setup(bchmc_handle *h) {
   return BCHMC_OK;
 }
 
+// The Gaussian buffer was sized for the momenta (m.G); a request of another size (the mock data: 2 N for the truth,
+// 2 doubles per windowed cell in split form) grows it.  Only called between trajectories.
+int mt_reserve(bchmc_handle *h, long long doubles) {
+  auto &m = h->mt;
+  if (doubles <= m.gauss_cap) return BCHMC_OK;
+  HIPCHK(hipStreamSynchronize(h->stream));
+  HIPCHK(hipFree(m.gauss));
+  m.gauss = nullptr, m.gauss_cap = 0;
+  CHK(dev_alloc(h, &m.gauss, (size_t)doubles));
+  m.gauss_cap = doubles;
+  return BCHMC_OK;
+}
+
 // One pass: C words from the window at position P (counted from mt[0] of the caller's state), Gaussians
-// gauss[done ..) up to the G - done still needed.  Leaves res on the host in m.h_io.
-int mt_pass(bchmc_handle *h, const uint32_t *win, unsigned long long P, long long done) {
+// done .. G of the request into gauss (split: two doubles each, k_mt_pairs).  Leaves res on the host in m.h_io.
+int mt_pass(bchmc_handle *h, const uint32_t *win, unsigned long long P, long long done, long long G, bool split) {
   auto &m = h->mt;
   ProfScope ps(h, BCHMC_K_OTHER);
   uint32_t *io_st = reinterpret_cast<uint32_t *>(m.h_io + 8);
@@ -2303,30 +2409,40 @@ int mt_pass(bchmc_handle *h, const uint32_t *win, unsigned long long P, long lon
   k_mt_pairs<false><<<m.B, kMtThreads, 0, h->stream>>>(m.words, m.C, m.S, m.nzoff, nullptr, m.acc, m.lastend, 0,
                                                         nullptr, m.res);
   k_mt_scan<<<1, kMtThreads, 0, h->stream>>>(m.acc, m.B, m.accoff, m.res, 0, m.lastend);
-  k_mt_pairs<true><<<m.B, kMtThreads, 0, h->stream>>>(m.words, m.C, m.S, m.nzoff, m.accoff, nullptr, nullptr,
-                                                       m.G - done, m.gauss + done, m.res);
+  if (split)
+    k_mt_pairs<true, true><<<m.B, kMtThreads, 0, h->stream>>>(m.words, m.C, m.S, m.nzoff, m.accoff, nullptr, nullptr,
+                                                               G - done, m.gauss + 2 * done, m.res);
+  else
+    k_mt_pairs<true><<<m.B, kMtThreads, 0, h->stream>>>(m.words, m.C, m.S, m.nzoff, m.accoff, nullptr, nullptr,
+                                                         G - done, m.gauss + done, m.res);
   k_mt_final<<<1, 640, 0, h->stream>>>(m.words, m.C, P, m.res, reinterpret_cast<uint32_t *>(m.res + 8));
   HIPCHK(hipGetLastError());
   return BCHMC_OK;
 }
 
-int mt_draw(bchmc_handle *h, uint32_t *mt, int32_t *mti, uint64_t *words_used) {
+int mt_place_momenta(bchmc_handle *h);
+
+// G Gaussians of the stream from the GSL state (mt, mti) into m.gauss, unit or split; `place` (may be null) is what the
+// caller makes of them, queued while the host still waits for the pass.
+int mt_draw(bchmc_handle *h, uint32_t *mt, int32_t *mti, uint64_t *words_used, long long G, bool split,
+            int (*place)(bchmc_handle *)) {
   CHK(mt_setup(h));
   auto &m = h->mt;
+  CHK(mt_reserve(h, (split ? 2 : 1) * G));
   const int32_t mti_in = *mti;
   uint32_t win[kMtN];
   mt_host::gsl_to_window(mt, mti_in, win);
   unsigned long long P = (unsigned long long)mti_in;
   long long done = 0;
   for (int pass = 0;; pass++) {
-    CHK(mt_pass(h, win, P, done));
+    CHK(mt_pass(h, win, P, done, G, split));
     // placed now, so that it runs while the host waits; a continuation pass places again
-    if (pass == 0) CHK(DISPATCH(h, mt_place(h)));
+    if (pass == 0 && place) CHK(place(h));
     HIPCHK(hipMemcpyAsync(m.h_io, m.res, (8 + kMtN / 2) * sizeof(unsigned long long), hipMemcpyDeviceToHost,
                           h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     const unsigned long long got = m.h_io[0];
-    if ((long long)got >= m.G - done) {
+    if ((long long)got >= G - done) {
       const unsigned long long used = P + m.h_io[2] - (unsigned long long)mti_in;
       if (m.h_io[3]) {
         const unsigned long long Q = P + m.h_io[2];
@@ -2340,7 +2456,7 @@ int mt_draw(bchmc_handle *h, uint32_t *mt, int32_t *mti, uint64_t *words_used) {
         *mti = mo;
       }
       if (words_used) *words_used = used;
-      if (pass > 0) CHK(DISPATCH(h, mt_place(h)));
+      if (pass > 0 && place) CHK(place(h));
       return BCHMC_OK;
     }
     // the pass ran out of words (a far statistical tail, or a capacity set small on purpose): continue the stream
@@ -2354,6 +2470,10 @@ int mt_draw(bchmc_handle *h, uint32_t *mt, int32_t *mti, uint64_t *words_used) {
     P += E;
   }
 }
+
+int mt_place_momenta(bchmc_handle *h) { return DISPATCH(h, mt_place(h)); }
+int mock_place_truth(bchmc_handle *h) { return DISPATCH(h, mock_place(h, h->qk)); }
+int mock_place_guess(bchmc_handle *h) { return DISPATCH(h, mock_place(h, h->cq)); }
 
 }  // namespace
 
@@ -2659,7 +2779,8 @@ void bchmc_destroy(bchmc_handle *h) {
   if (h->h_part) (void)hipHostFree(h->h_part);
   for (void *p : {(void *)h->mt.poly, (void *)h->mt.win, (void *)h->mt.words, (void *)h->mt.st, (void *)h->mt.nz,
                   (void *)h->mt.nzoff, (void *)h->mt.acc, (void *)h->mt.accoff, (void *)h->mt.lastend,
-                  (void *)h->mt.res, (void *)h->mt.gauss})
+                  (void *)h->mt.res, (void *)h->mt.gauss, (void *)h->mock.cnt, (void *)h->mock.off,
+                  (void *)h->mock.gsum, (void *)h->mock.goff, (void *)h->mock.res})
     if (p) (void)hipFree(p);
   if (h->mt.h_io) (void)hipHostFree(h->mt.h_io);
   if (h->copy_stream) (void)hipStreamDestroy(h->copy_stream);
@@ -2932,7 +3053,8 @@ int bchmc_chain_draw_momenta_mt19937(bchmc_handle *h, uint32_t mt[624], int32_t 
   if (h->mass_fs && !h->have[BCHMC_F_MASS_F]) return h->fail(BCHMC_ERR_STATE, "mass_f was never uploaded");
   if (h->mass_rs && !h->have[BCHMC_F_MASS_R]) return h->fail(BCHMC_ERR_STATE, "mass_r was never uploaded");
   CHK(DISPATCH(h, chain_alloc(h)));
-  CHK(mt_draw(h, mt, mti, words_used));
+  CHK(mt_setup(h));
+  CHK(mt_draw(h, mt, mti, words_used, h->mt.G, false, mt_place_momenta));
   h->have_cp = true;
   return BCHMC_OK;
 }
@@ -3059,6 +3181,103 @@ int bchmc_hamiltonian_mass(bchmc_handle *h, const double *signal, const bchmc_ma
   if (mass_f && h->mass_fs) CHK(d2h(h, mass_f, h->dstage, bytes));
   if (mass_r && h->mass_rs) CHK(d2h(h, mass_r, h->dstage + N, bytes));
   return read_ctl(h, nullptr);  // synchronises; adapts the binning's record slots to the forward model just run
+}
+
+int bchmc_setup_random_test(bchmc_handle *h, const bchmc_mock_opts *o, uint32_t mt[624], int32_t *mti,
+                            uint64_t *words_used, double *delta_lag, double *delta_eul) {
+  if (!h || !o || !mt || !mti) return BCHMC_ERR_ARG;
+  ENTER(h);
+  // everything that can be refused is refused before anything is queued or the generator is touched
+  if (*mti < 0 || *mti > 624) return h->fail(BCHMC_ERR_ARG, "mti = %d outside [0, 624]", (int)*mti);
+  if (o->window_type != 1 && o->window_type != 10 && o->window_type != 23)
+    return h->fail(BCHMC_ERR_ARG, "in barcoderunner: window_type = %d is not a valid choice!", (int)o->window_type);
+  if (o->data_model != 0 && o->data_model != 1)
+    return h->fail(BCHMC_ERR_ARG, "in barcoderunner: data_model = %d is not a valid choice!", (int)o->data_model);
+  if (o->data_model == 0 && h->c.likelihood == 0)
+    return h->fail(BCHMC_ERR_UNSUPPORTED, "Poissonian mock data: gsl_ran_poisson consumes a data-dependent number of "
+                                          "words per cell, which has no parallel form here");
+  if (o->data_model == 0 && h->c.likelihood == 2)
+    return h->fail(BCHMC_ERR_ARG, "in barcoderunner: linear data model was chosen (additive error), but incompatible "
+                                  "likelihood!");
+  if (h->g.n & 1) return h->fail(BCHMC_ERR_UNSUPPORTED, "create_GARFIELD's placement needs an even Nx (%d)", h->g.n);
+  const int rsd = o->random_test_rsd ? 1 : 0;
+  if (rsd && !h->c.planepar) return h->fail(BCHMC_ERR_RSD_NOT_PLANEPAR, "non-plane-parallel RSD is not implemented");
+  CHK(need_input(h, BCHMC_F_SIGNAL_PS, "signal_PS"));
+  CHK(mt_setup(h));
+  CHK(DISPATCH(h, mock_alloc(h)));
+  clobber_proposal(h);
+  h->cg_valid = false;
+  h->have[BCHMC_F_WINDOW] = h->have[BCHMC_F_NOBS] = h->have[BCHMC_F_NOISE] = false;
+  const long long N = h->g.N;
+  uint64_t used1 = 0, used2 = 0;
+  CHK(mt_draw(h, mt, mti, &used1, 2 * N, false, mock_place_truth));
+  CHK(DISPATCH(h, mock_window(h, rsd, o->window_type)));
+  unsigned long long res[2] = {0, 0};
+  HIPCHK(hipMemcpyAsync(res, h->mock.res, sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  const long long count = (long long)res[0];
+  if (count < 0 || count > N) return h->fail(BCHMC_ERR_STATE, "window count %lld outside [0, N]", count);
+  // the noise is a second draw from the state the first one returned: its size depends on the window
+  if (count > 0) CHK(mt_draw(h, mt, mti, &used2, count, true, nullptr));
+  MockPar mp{o->window_type, o->data_model, h->c.likelihood, o->negative_obs, o->sigma_min, o->sigma_fac,
+             h->c.rho_c,     h->c.delta_min};
+  CHK(DISPATCH(h, mock_noise(h, mp)));
+  HIPCHK(hipMemcpyAsync(res, h->mock.res, sizeof res, hipMemcpyDeviceToHost, h->stream));
+  if (delta_lag) CHK(d2h(h, delta_lag, h->dstage, (size_t)N * sizeof(double)));
+  if (delta_eul) CHK(d2h(h, delta_eul, h->dstage + N, (size_t)N * sizeof(double)));
+  if (words_used) *words_used = used1 + used2;
+  CHK(read_ctl(h, nullptr));  // synchronises; adapts the binning's record slots to the forward model just run
+  if (res[1] != ~0ull)
+    return h->fail(BCHMC_ERR_STATE, "in barcoderunner(): noise = 0 found! Index %llu", res[1]);
+  h->have[BCHMC_F_WINDOW] = h->have[BCHMC_F_NOBS] = h->have[BCHMC_F_NOISE] = true;
+  return BCHMC_OK;
+}
+
+int bchmc_make_initial_guess(bchmc_handle *h, int32_t initial_guess, const double *file_field, int32_t smoothing_type,
+                             double smoothing_scale, uint32_t mt[624], int32_t *mti, uint64_t *words_used) {
+  if (!h) return BCHMC_ERR_ARG;
+  ENTER(h);
+  if (initial_guess < 0 || initial_guess > 4)
+    return h->fail(BCHMC_ERR_ARG, "In barcoderunner: invalid choice of initial_guess (%d)!", (int)initial_guess);
+  const bool draws = initial_guess >= 2;
+  if (initial_guess == 1 && !file_field) return h->fail(BCHMC_ERR_ARG, "initial_guess 1 needs the field read from file");
+  if (draws && (!mt || !mti)) return h->fail(BCHMC_ERR_ARG, "initial_guess %d needs the generator state", (int)initial_guess);
+  if (draws && (*mti < 0 || *mti > 624)) return h->fail(BCHMC_ERR_ARG, "mti = %d outside [0, 624]", (int)*mti);
+  if (initial_guess == 3 && (smoothing_type != 1 || !(smoothing_scale > 0.)))
+    return h->fail(BCHMC_ERR_ARG, "initial_guess 3: only the Gaussian kernel (initial_guess_smoothing_type 1) with a "
+                                  "positive scale is built (type %d, scale %g)", (int)smoothing_type, smoothing_scale);
+  if (initial_guess == 2 || initial_guess == 3) {
+    if (h->g.n & 1) return h->fail(BCHMC_ERR_UNSUPPORTED, "create_GARFIELD's placement needs an even Nx (%d)", h->g.n);
+    CHK(need_input(h, BCHMC_F_SIGNAL_PS, "signal_PS"));
+  }
+  CHK(DISPATCH(h, chain_alloc(h)));
+  const long long N = h->g.N;
+  uint64_t used = 0;
+  switch (initial_guess) {
+    case 0:
+      HIPCHK(hipMemsetAsync(h->cq, 0, 2 * (size_t)h->g.Nhp * h->esz, h->stream));
+      break;
+    case 1:
+      CHK(h2d(h, h->dstage, file_field, (size_t)N * sizeof(double)));
+      CHK(DISPATCH(h, r2c_state(h, h->dstage, h->ioq, h->cq)));
+      break;
+    case 2:
+    case 3:
+      CHK(mt_draw(h, mt, mti, &used, 2 * N, false, mock_place_guess));
+      if (initial_guess == 3) CHK(DISPATCH(h, mock_smooth(h, smoothing_scale)));
+      break;
+    default:
+      clobber_proposal(h);  // the R2C staging below is the trajectory's too
+      CHK(mt_draw(h, mt, mti, &used, N, true, nullptr));
+      CHK(DISPATCH(h, mock_guess_noise(h, 1.e-1)));
+      break;
+  }
+  HIPCHK(hipStreamSynchronize(h->stream));
+  h->have_cq = true;
+  h->have_prop = false;
+  h->cg_valid = h->prop_g_valid = false;
+  if (words_used) *words_used = used;
+  return BCHMC_OK;
 }
 
 int bchmc_philox_kat(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]) {

@@ -226,7 +226,9 @@ __global__ void __launch_bounds__(kMtThreads) k_mt_scan(const unsigned long long
 // pair of an earlier segment.  Count pass (EMIT = false): acc[b] = accepted pairs, lastend[b] = 1 + position of the
 // second word of the segment's last complete pair.  Emit pass: Gaussian accoff[b] + r goes to gauss[..] while below
 // G; the one numbered G - 1 records 1 + the position of its second word in res[2] (= words used by this pass).
-template <bool EMIT>
+// SPLIT: gauss[2 g], gauss[2 g + 1] = y and sqrt(-2 log r2 / r2) apart, for callers that form gsl_ran_gaussian's
+// sigma * y * root in GSL's product order (mock.hpp); the unit Gaussian y * root otherwise.
+template <bool EMIT, bool SPLIT = false>
 __global__ void __launch_bounds__(kMtThreads) k_mt_pairs(const uint32_t *__restrict__ words, long long C, long long S,
                                                           const unsigned long long *__restrict__ nzoff,
                                                           const unsigned long long *__restrict__ accoff,
@@ -242,7 +244,12 @@ __global__ void __launch_bounds__(kMtThreads) k_mt_pairs(const uint32_t *__restr
   const unsigned long long g0 = EMIT ? accoff[b] : 0;
   auto emit = [&](double y, double r2, unsigned long long gi, uint32_t p2) {
     if (gi < (unsigned long long)G) {
-      gauss[gi] = y * sqrt(-2.0 * log(r2) / r2);
+      if (SPLIT) {
+        gauss[2 * gi] = y;
+        gauss[2 * gi + 1] = sqrt(-2.0 * log(r2) / r2);
+      } else {
+        gauss[gi] = y * sqrt(-2.0 * log(r2) / r2);
+      }
       if (gi == (unsigned long long)G - 1) res[2] = (unsigned long long)p2 + 1;
     }
   };

@@ -50,6 +50,12 @@ class MassOpts(C.Structure):
     _fields_ = [("n_bin", C.c_uint64), ("mass_factor", C.c_double), ("iGibbs", C.c_uint64), ("s_eps_total", C.c_uint64)]
 
 
+class MockOpts(C.Structure):
+    """bchmc_mock_opts: the NUMERICAL / OBSERVATIONAL scalars setup_random_test reads (barcoderunner.cc:42-205)."""
+    _fields_ = [("window_type", C.c_int32), ("data_model", C.c_int32), ("negative_obs", C.c_int32),
+                ("random_test_rsd", C.c_int32), ("sigma_min", C.c_double), ("sigma_fac", C.c_double)]
+
+
 # which mass arrays a mass_type has (struct_hamil.h:272-313)
 MASS_F_TYPES = (1, 2, 3, 4, 5)
 MASS_R_TYPES = (0, 5, 6, 60)
@@ -82,7 +88,8 @@ EXPORTS = ("bchmc_create", "bchmc_destroy", "bchmc_strerror", "bchmc_last_error"
            "bchmc_measure_spectrum", "bchmc_philox_kat", "bchmc_kinetic_term", "bchmc_psi",
            "bchmc_comm_unique_id", "bchmc_comm_create", "bchmc_comm_create_custom", "bchmc_comm_destroy",
            "bchmc_comm_last_error", "bchmc_eps_exchange", "bchmc_comm_pending", "bchmc_comm_world", "bchmc_comm_rank",
-           "bchmc_comm_transport", "bchmc_garfield_walk_index", "bchmc_hamiltonian_mass")
+           "bchmc_comm_transport", "bchmc_garfield_walk_index", "bchmc_hamiltonian_mass",
+           "bchmc_setup_random_test", "bchmc_make_initial_guess")
 # declared as well, listed apart: the header scan of the ABI test matches names of letters and underscores only
 EXPORTS_MT19937 = ("bchmc_chain_draw_momenta_mt19937", "bchmc_mt19937_jump")
 
@@ -154,6 +161,8 @@ def load():
     lib.bchmc_chain_draw_momenta_mt19937.argtypes = [vp, u32p, i32p, C.POINTER(u64)]
     lib.bchmc_mt19937_jump.argtypes = [u32p, C.c_int32, u64, u32p, i32p]
     lib.bchmc_garfield_walk_index.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(u64)]
+    lib.bchmc_setup_random_test.argtypes = [vp, C.POINTER(MockOpts), u32p, i32p, C.POINTER(u64), dp, dp]
+    lib.bchmc_make_initial_guess.argtypes = [vp, C.c_int32, dp, C.c_int32, C.c_double, u32p, i32p, C.POINTER(u64)]
     _lib = lib
     return lib
 
@@ -375,6 +384,42 @@ class Engine:
         self._chk(self.lib.bchmc_chain_draw_momenta_mt19937(self.h, _u32p(mt), C.byref(m), C.byref(used)))
         rng.set_state(mt, m.value)
         return used.value
+
+    def _with_rng(self, rng, call):
+        """Run ``call(mt, mti, used)`` on the state of ``rng`` (a ``GslMT19937``); the generator is advanced in place
+        when the call succeeds, and left as it was when it raises.  Returns the words consumed."""
+        mt, mti = rng.get_state()
+        mt = np.ascontiguousarray(mt, dtype=np.uint32).copy()
+        m = C.c_int32(int(mti))
+        used = C.c_uint64()
+        self._chk(call(_u32p(mt), C.byref(m), C.byref(used)))
+        rng.set_state(mt, m.value)
+        return used.value
+
+    def setup_random_test(self, rng, window_type=1, data_model=0, negative_obs=False, random_test_rsd=False,
+                          sigma_min=None, sigma_fac=0.0, deltas=True):
+        """setup_random_test (barcoderunner.cc:42-205) on the device from ``rng``: the truth field from ``signal_PS``,
+        its forward model, the window, nobs and noise, which the engine then holds as if they had been uploaded
+        (``fetch("window")`` ...).  Defaults: data/input.par.  Returns (words used, delta_lag, delta_eul); the two
+        arrays are None with ``deltas=False``."""
+        o = MockOpts(int(window_type), int(data_model), int(bool(negative_obs)), int(bool(random_test_rsd)),
+                     float(self.params.sigma_min if sigma_min is None else sigma_min), float(sigma_fac))
+        dl, de = (np.empty(self.N), np.empty(self.N)) if deltas else (None, None)
+        used = self._with_rng(rng, lambda mt, m, u: self.lib.bchmc_setup_random_test(
+            self.h, C.byref(o), mt, m, u, None if dl is None else _p(dl), None if de is None else _p(de)))
+        return used, dl, de
+
+    def make_initial_guess(self, rng, initial_guess=0, file_field=None, smoothing_type=1, smoothing_scale=0.0):
+        """make_initial_guess (barcoderunner.cc:207-247): sets the resident chain state; 2, 3 and 4 draw from ``rng``
+        (0 and 1 leave it alone, and ``rng`` may be None).  Returns the words used."""
+        ff = None if file_field is None else _p(self._in(file_field))
+        if rng is None:
+            used = C.c_uint64()
+            self._chk(self.lib.bchmc_make_initial_guess(self.h, int(initial_guess), ff, int(smoothing_type),
+                                                        float(smoothing_scale), None, None, C.byref(used)))
+            return used.value
+        return self._with_rng(rng, lambda mt, m, u: self.lib.bchmc_make_initial_guess(
+            self.h, int(initial_guess), ff, int(smoothing_type), float(smoothing_scale), mt, m, u))
 
     def chain_attempt(self, eps, neps):
         dH, done = C.c_double(), C.c_uint64()

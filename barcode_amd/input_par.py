@@ -90,3 +90,28 @@ def hamil_params(filename, **overrides):
     )
     kw.update(overrides)
     return HamilParams(**kw)
+
+
+def mock_params(filename, **overrides):
+    """The keys of ``load_initial_fields`` (barcoderunner.cc:284-344) as ``INIT_PARAMS`` reads them (init_par.cc:61-67,
+    99-102, 134, 149-150): a dict with ``seed``, ``random_test``, ``random_test_rsd``, ``window_type``, ``data_model``,
+    ``negative_obs``, ``sigma_min``, ``sigma_fac``, ``initial_guess``, ``initial_guess_file``,
+    ``initial_guess_smoothing_type``, ``initial_guess_smoothing_scale``, ``N_bin``, ``likelihood``.  Raises like
+    init_par.cc:75-77 when ``data_model`` and ``likelihood`` do not go together."""
+    p = parameter_inifile(filename)
+    kw = dict(
+        seed=p.find(int, "seed"),
+        random_test=p.find(bool, "random_test"), random_test_rsd=p.find(bool, "random_test_rsd"),
+        window_type=p.find(int, "window_type"), data_model=p.find(int, "data_model"),
+        negative_obs=p.find(bool, "negative_obs"),
+        sigma_min=p.find(float, "sigma_min"), sigma_fac=p.find(float, "sigma_fac"),
+        initial_guess=p.find(int, "initial_guess"), initial_guess_file=p.find(str, "initial_guess_file"),
+        initial_guess_smoothing_type=p.find(int, "initial_guess_smoothing_type"),
+        initial_guess_smoothing_scale=p.find(float, "initial_guess_smoothing_scale"),
+        N_bin=p.find(int, "N_bin"), likelihood=p.find(int, "likelihood"),
+    )
+    kw.update(overrides)
+    if (kw["data_model"] == 1) != (kw["likelihood"] == 2):
+        raise RuntimeError("Error: incompatible data_model and likelihood in input.par! Logarithmic and log-normal "
+                           "must go together, or you must choose other models.")
+    return kw

@@ -24,7 +24,8 @@ SHIM_EXPORTS = ("bchmc_shim_Hamiltonian_EoM", "bchmc_shim_delta_Hamiltonian", "b
                 "bchmc_shim_eps_acceptance_rate", "bchmc_shim_update_eps_fac", "bchmc_shim_update_tables",
                 "bchmc_shim_comm_bootstrap_file", "bchmc_shim_comm_attach", "bchmc_shim_comm_release",
                 "bchmc_shim_inputs_changed", "bchmc_shim_mass_changed", "bchmc_shim_bootstrap_exchange_id",
-                "bchmc_shim_bootstrap_cleanup", "bchmc_shim_Hamiltonian_mass")
+                "bchmc_shim_bootstrap_cleanup", "bchmc_shim_Hamiltonian_mass",
+                "bchmc_shim_setup_random_test", "bchmc_shim_make_initial_guess", "bchmc_shim_sizeof_mock")
 
 _dp = C.POINTER(C.c_double)
 
@@ -84,6 +85,14 @@ class AttemptLog(C.Structure):
 
 
 UNIFORM_FN = C.CFUNCTYPE(C.c_double, C.c_void_p)
+class MockView(C.Structure):
+    """bchmc_shim::MockView (include/bchmc_shim.hpp): the scalars of setup_random_test / make_initial_guess."""
+    _fields_ = [("window_type", C.c_int), ("data_model", C.c_int), ("negative_obs", C.c_int),
+                ("random_test_rsd", C.c_int), ("sigma_min", C.c_double), ("sigma_fac", C.c_double),
+                ("initial_guess", C.c_int), ("initial_guess_smoothing_type", C.c_int),
+                ("initial_guess_smoothing_scale", C.c_double), ("initial_guess_field", C.POINTER(C.c_double))]
+
+
 # bchmc_shim::mt19937_state_fn: void (*)(void *rng_state, uint32_t mt[624], int32_t *mti, int store)
 MT_STATE_FN = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_int32), C.c_int)
 
@@ -115,6 +124,10 @@ def load():
                                              C.POINTER(AttemptLog), ul, C.POINTER(ul), C.c_char_p, sz]
     lib.bchmc_shim_HamiltonianMC_mt19937.argtypes = [hv, UNIFORM_FN, MT_STATE_FN, C.c_void_p, ul, C.POINTER(ul),
                                                      C.POINTER(AttemptLog), ul, C.POINTER(ul), C.c_char_p, sz]
+    lib.bchmc_shim_sizeof_mock.restype = sz
+    lib.bchmc_shim_setup_random_test.argtypes = [hv, C.POINTER(MockView), MT_STATE_FN, C.c_void_p, _dp, _dp,
+                                                 C.c_char_p, sz]
+    lib.bchmc_shim_make_initial_guess.argtypes = [hv, C.POINTER(MockView), MT_STATE_FN, C.c_void_p, C.c_char_p, sz]
     lib.bchmc_shim_HamiltonianMC_scripted.argtypes = [hv, _dp, ul, UNIFORM_FN, C.c_void_p, ul, C.POINTER(ul),
                                                       C.POINTER(AttemptLog), ul, C.POINTER(ul), C.c_char_p, sz]
     lib.bchmc_shim_kinetic_term.argtypes = [hv, _dp, _dp, C.c_char_p, sz]
@@ -149,7 +162,8 @@ def load():
     lib.bchmc_shim_release.restype = None
     if lib.bchmc_shim_sizeof_view() != C.sizeof(HamilView) or \
             lib.bchmc_shim_sizeof_numerical() != C.sizeof(HamilNumericalView) or \
-            lib.bchmc_shim_sizeof_attempt_log() != C.sizeof(AttemptLog):
+            lib.bchmc_shim_sizeof_attempt_log() != C.sizeof(AttemptLog) or \
+            lib.bchmc_shim_sizeof_mock() != C.sizeof(MockView):
         raise ImportError("bchmc_shim.hpp and barcode_amd/shim.py disagree on the struct layouts")
     _lib = lib
     return lib
@@ -283,13 +297,8 @@ class ShimHamil:
                                                     self._err, len(self._err)))
         return [{k: getattr(log[i], k) for k, _ in AttemptLog._fields_} for i in range(n.value)]
 
-    def HamiltonianMC_mt19937(self, rng, itmax=2000):
-        """One sample of the C++ loop with the exact device draw from ``rng`` (a ``gsl_mt19937.GslMT19937``), which
-        supplies the uniforms too and is advanced in place.  Returns the list of attempt records."""
-        log = (AttemptLog * itmax)()
-        n = C.c_ulong(0)
-        cb = UNIFORM_FN(lambda _state: float(rng.uniform()))
-
+    @staticmethod
+    def _state_fn(rng):
         def state(_rng, mt, mti, store):
             if store:
                 rng.set_state(np.ctypeslib.as_array(mt, shape=(624,)).copy(), mti[0])
@@ -298,7 +307,33 @@ class ShimHamil:
                 np.ctypeslib.as_array(mt, shape=(624,))[:] = key
                 mti[0] = pos
 
-        sf = MT_STATE_FN(state)
+        return MT_STATE_FN(state)
+
+    def setup_random_test(self, rng, window_type=1, data_model=0, negative_obs=False, random_test_rsd=False,
+                          sigma_min=1.0, sigma_fac=0.0):
+        """bchmc_shim::setup_random_test from ``rng`` (a ``GslMT19937``, advanced in place): (delta_lag, delta_eul)."""
+        m = MockView(int(window_type), int(data_model), int(bool(negative_obs)), int(bool(random_test_rsd)),
+                     float(sigma_min), float(sigma_fac), 0, 1, 0.0, None)
+        dl, de = np.empty(self.N), np.empty(self.N)
+        self._chk(self.lib.bchmc_shim_setup_random_test(C.byref(self.hd), C.byref(m), self._state_fn(rng), None, _p(dl),
+                                                        _p(de), self._err, len(self._err)))
+        return dl, de
+
+    def make_initial_guess(self, rng, initial_guess=0, file_field=None, smoothing_type=1, smoothing_scale=0.0):
+        """bchmc_shim::make_initial_guess from ``rng``: sets the resident chain state."""
+        ff = None if file_field is None else np.ascontiguousarray(file_field, dtype=np.float64).reshape(-1)
+        m = MockView(1, 0, 0, 0, 1.0, 0.0, int(initial_guess), int(smoothing_type), float(smoothing_scale),
+                     None if ff is None else _p(ff))
+        self._chk(self.lib.bchmc_shim_make_initial_guess(C.byref(self.hd), C.byref(m), self._state_fn(rng), None,
+                                                         self._err, len(self._err)))
+
+    def HamiltonianMC_mt19937(self, rng, itmax=2000):
+        """One sample of the C++ loop with the exact device draw from ``rng`` (a ``gsl_mt19937.GslMT19937``), which
+        supplies the uniforms too and is advanced in place.  Returns the list of attempt records."""
+        log = (AttemptLog * itmax)()
+        n = C.c_ulong(0)
+        cb = UNIFORM_FN(lambda _state: float(rng.uniform()))
+        sf = self._state_fn(rng)
         self._chk(self.lib.bchmc_shim_HamiltonianMC_mt19937(C.byref(self.hd), cb, sf, None, int(itmax),
                                                             C.byref(self.count_attempts), log, int(itmax), C.byref(n),
                                                             self._err, len(self._err)))

@@ -297,6 +297,48 @@ void chain_get_state(HamilView *hd, real_prec *x) {
   if (rc) fail(h, rc, "chain_get_state");
 }
 
+void setup_random_test(HamilView *hd, const MockView *m, mt19937_state_fn state, void *rng_state, real_prec *delta_lag,
+                       real_prec *delta_eul) {
+  if (!m || !state) throw std::runtime_error("In setup_random_test: no parameters or no generator state hook");
+  bchmc_handle *h = engine_for(hd);
+  bchmc_mock_opts o;
+  o.window_type = m->window_type;
+  o.data_model = m->data_model;
+  o.negative_obs = m->negative_obs;
+  o.random_test_rsd = m->random_test_rsd;
+  o.sigma_min = m->sigma_min;
+  o.sigma_fac = m->sigma_fac;
+  uint32_t mt[624];
+  int32_t mti = 0;
+  state(rng_state, mt, &mti, 0);
+  int rc = bchmc_setup_random_test(h, &o, mt, &mti, nullptr, delta_lag, delta_eul);
+  if (rc) fail(h, rc, "setup_random_test");
+  state(rng_state, mt, &mti, 1);
+  // upstream writes o->window / nobs / noise_sf, which call_hamil.cc hands to HAMIL_DATA: keep the caller's copies equal
+  struct { bchmc_field f; const real_prec *p; } arr[] = {
+      {BCHMC_F_WINDOW, hd->window}, {BCHMC_F_NOBS, hd->nobs}, {BCHMC_F_NOISE, hd->noise}};
+  for (auto &a : arr)
+    if (a.p) {
+      rc = bchmc_fetch(h, a.f, const_cast<real_prec *>(a.p), hd->numerical->N);
+      if (rc) fail(h, rc, "bchmc_fetch");
+    }
+}
+
+void make_initial_guess(HamilView *hd, const MockView *m, mt19937_state_fn state, void *rng_state) {
+  if (!m) throw std::runtime_error("In make_initial_guess: no parameters");
+  bchmc_handle *h = engine_for(hd);
+  const bool draws = m->initial_guess >= 2 && m->initial_guess <= 4;
+  if (draws && !state) throw std::runtime_error("In make_initial_guess: no generator state hook");
+  uint32_t mt[624];
+  int32_t mti = 0;
+  if (draws) state(rng_state, mt, &mti, 0);
+  const int rc = bchmc_make_initial_guess(h, m->initial_guess, m->initial_guess_field, m->initial_guess_smoothing_type,
+                                          m->initial_guess_smoothing_scale, draws ? mt : nullptr, draws ? &mti : nullptr,
+                                          nullptr);
+  if (rc) fail(h, rc, "make_initial_guess");
+  if (draws) state(rng_state, mt, &mti, 1);
+}
+
 namespace {
 int op_draw(void *e, uint64_t seed, uint64_t attempt) { return bchmc_chain_draw_momenta(static_cast<bchmc_handle *>(e), seed, attempt); }
 int op_setp(void *e, const real_prec *p) { return bchmc_chain_set_momenta(static_cast<bchmc_handle *>(e), p); }
@@ -722,6 +764,16 @@ int bchmc_shim_HamiltonianMC_mt19937(bchmc_shim::HamilView *hd, bchmc_shim::unif
     *n_attempts = bchmc_shim::HamiltonianMC_mt19937(hd, uniform, state, rng_state, itmax, count_attempts, log, log_cap);
   });
 }
+int bchmc_shim_setup_random_test(bchmc_shim::HamilView *hd, const bchmc_shim::MockView *m,
+                                 bchmc_shim::mt19937_state_fn state, void *rng_state, double *delta_lag,
+                                 double *delta_eul, char *err, size_t errlen) {
+  return guarded(err, errlen, [&] { bchmc_shim::setup_random_test(hd, m, state, rng_state, delta_lag, delta_eul); });
+}
+int bchmc_shim_make_initial_guess(bchmc_shim::HamilView *hd, const bchmc_shim::MockView *m,
+                                  bchmc_shim::mt19937_state_fn state, void *rng_state, char *err, size_t errlen) {
+  return guarded(err, errlen, [&] { bchmc_shim::make_initial_guess(hd, m, state, rng_state); });
+}
+size_t bchmc_shim_sizeof_mock(void) { return sizeof(bchmc_shim::MockView); }
 int bchmc_shim_kinetic_term(bchmc_shim::HamilView *hd, const double *momenta, double *out, char *err, size_t errlen) {
   return guarded(err, errlen, [&] { *out = bchmc_shim::kinetic_term(hd, momenta); });
 }

@@ -218,6 +218,44 @@ typedef struct bchmc_mass_opts {
  * BCHMC_ERR_UNSUPPORTED (upstream's likelihood_grad_log_like is an empty function there). */
 int bchmc_hamiltonian_mass(bchmc_handle *h, const double *signal, const bchmc_mass_opts *opts, double *mass_f,
                            double *mass_r);
+/* ---- the start of a run: load_initial_fields (barcoderunner.cc:284-344) with random_test = true --------------------
+ * setup_random_test (:42-205) and make_initial_guess (:207-247) on the device, from the SAME GSL mt19937 state the chain
+ * later draws its momenta from: mt / mti in: the state before the call, out: what GSL holds after it (the convention of
+ * bchmc_chain_draw_momenta_mt19937, so the three calls chain).  words_used may be NULL. */
+typedef struct bchmc_mock_opts {
+  int32_t window_type;      /* 1 ones, 10 zeros in the first N/2 cells, 23 one where delta_eul > 3 (:91-113, upstream's
+                             * code, not its comment); anything else BCHMC_ERR_ARG */
+  int32_t data_model;       /* 0 linear, 1 log-normal (:117-188); anything else BCHMC_ERR_ARG */
+  int32_t negative_obs;     /* 0: nobs of the Gaussian likelihood is clamped at 0 (:140-142) */
+  int32_t random_test_rsd;  /* 1: Lag2Eul_rsd_zeldovich whatever sfmodel says, 0: Lag2Eul(sfmodel), never RSD (:67-82) */
+  double sigma_min, sigma_fac;
+} bchmc_mock_opts;
+/* Needs signal_PS uploaded (it is upstream's o->Power).  Stream order: 2 N Gaussians for create_GARFIELD in the walk of
+ * resolution_independent_random_grid_FS, then ONE gsl_ran_gaussian(sigma_i) per cell with window > 0 in cell order and
+ * none for the others (with window_type 23 that count depends on the forward model, so the noise is a second stream
+ * draw sized after an 8-byte read-back).  Per cell, Lambda as upstream: Gaussian likelihood sigma = sigma_min +
+ * sigma_fac Lambda, nobs = Lambda + g, clamped at 0 unless negative_obs; GRF likelihood sigma = sigma_min + sigma_fac
+ * delta_lag^2, nobs = delta_lag + g; data_model 1: Lambda = lognormal_likelihood_f_delta_x_i_calc, sigma = sigma_fac,
+ * nobs of an unwindowed cell = log((rho_c (1 + delta_min))^2).  g = sigma * y * sqrt(-2 log r2 / r2), products in GSL's
+ * order, no FMA contraction.  noise of an unwindowed cell is 0 (upstream leaves it unwritten).
+ * Afterwards window, nobs and noise are in the handle exactly as if they had been uploaded (bchmc_fetch reads them);
+ * the carried gradient / -log L and a pending proposal are dropped; deltaX / pos* are those of the truth; delta_lag /
+ * delta_eul (may be NULL) receive the truth and its forward model (dump_deltas' arrays).  The chain state is untouched.
+ * Refused before anything is queued or the generator is touched: data_model 0 with the log-normal likelihood
+ * (BCHMC_ERR_ARG, upstream's text, :156), and data_model 0 with the Poissonian likelihood (BCHMC_ERR_UNSUPPORTED):
+ * gsl_ran_poisson consumes a data-dependent number of words per cell through the rejection loops of gsl_ran_gamma_int /
+ * gsl_ran_binomial, so where cell i starts in the stream depends on every earlier cell's draw -- not a scan with
+ * bounded state.  After the draw: a windowed cell with noise == 0 under likelihood 1 or 3 -> BCHMC_ERR_STATE naming the
+ * first such index (:190-198); the generator has then advanced like upstream's, the three arrays count as not uploaded. */
+int bchmc_setup_random_test(bchmc_handle *h, const bchmc_mock_opts *o, uint32_t mt[624], int32_t *mti,
+                            uint64_t *words_used, double *delta_lag, double *delta_eul);
+/* make_initial_guess: sets the resident chain state like bchmc_chain_set_state.  initial_guess 0: zero; 1: file_field (N
+ * host doubles); 2: create_GARFIELD(signal_PS) from the stream, placed in k-space directly; 3: the same, then
+ * kernelcomp(smoothing_scale, smoothing_type) o convcomp as one k-space multiply (type 1, the Gaussian kernel, only;
+ * others BCHMC_ERR_ARG); 4: N draws gsl_ran_gaussian(r, 0.1) in cell order.  Cases 0 and 1 leave the generator as it is
+ * (mt / mti may be NULL) and report 0 words. */
+int bchmc_make_initial_guess(bchmc_handle *h, int32_t initial_guess, const double *file_field, int32_t smoothing_type,
+                             double smoothing_scale, uint32_t mt[624], int32_t *mti, uint64_t *words_used);
 int bchmc_philox_kat(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]); /* known-answer hook for tests */
 
 /* Diagnostic (tests, logs): how the particle-mesh path is currently set up.  out = { tile-sorted path in use, one-pass

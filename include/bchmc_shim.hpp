@@ -183,6 +183,25 @@ using mt19937_state_fn = void (*)(void *rng_state, uint32_t mt[624], int32_t *mt
 ULONG HamiltonianMC_mt19937(HamilView *hd, uniform_fn uniform, mt19937_state_fn state, void *rng_state, ULONG itmax,
                             ULONG *count_attempts, AttemptLog *log, ULONG log_cap);
 
+// The start of a run (load_initial_fields, barcoderunner.cc:284-344, with random_test): the scalars setup_random_test
+// and make_initial_guess read.  They live in upstream's NUMERICAL / OBSERVATIONAL, not in HAMIL_DATA, hence a struct of
+// their own beside the views.
+struct MockView {
+  int window_type = 1, data_model = 0, negative_obs = 0, random_test_rsd = 0;  // init_par.cc:61-67
+  real_prec sigma_min = 1., sigma_fac = 0.;                                    // init_par.cc:149-150
+  int initial_guess = 0, initial_guess_smoothing_type = 1;                     // init_par.cc:99-102
+  real_prec initial_guess_smoothing_scale = 0.;
+  const real_prec *initial_guess_field = nullptr;  // initial_guess 1: what get_scalar read from initial_guess_file
+};
+// setup_random_test (barcoderunner.cc:42-205) on the device from the caller's gsl_rng (mt19937; `state` as in
+// HamiltonianMC_mt19937: read before, written back after).  The engine then holds window / nobs / noise as if they had
+// been uploaded; where the view has caller-owned arrays for them they receive the built values (so that a later
+// inputs_changed() uploads the same numbers).  delta_lag / delta_eul may be null.  Throws like the reference.
+void setup_random_test(HamilView *hd, const MockView *m, mt19937_state_fn state, void *rng_state, real_prec *delta_lag,
+                       real_prec *delta_eul);
+// make_initial_guess (barcoderunner.cc:207-247): sets the resident chain state (read it with chain_get_state)
+void make_initial_guess(HamilView *hd, const MockView *m, mt19937_state_fn state, void *rng_state);
+
 // The four engine calls HamiltonianMC makes, as a table: the default binds the C ABI (bchmc_chain_*); the CPU tests
 // bind a scripted stand-in so that the loop's bookkeeping is testable without a GPU.
 struct ChainOps {
@@ -242,6 +261,12 @@ int bchmc_shim_HamiltonianMC_scripted(bchmc_shim::HamilView *hd, const double *s
                                       bchmc_shim::uniform_fn uniform, void *rng_state, unsigned long itmax,
                                       unsigned long *count_attempts, bchmc_shim::AttemptLog *log, unsigned long log_cap,
                                       unsigned long *n_attempts, char *err, size_t errlen);
+int bchmc_shim_setup_random_test(bchmc_shim::HamilView *hd, const bchmc_shim::MockView *m,
+                                 bchmc_shim::mt19937_state_fn state, void *rng_state, double *delta_lag,
+                                 double *delta_eul, char *err, size_t errlen);
+int bchmc_shim_make_initial_guess(bchmc_shim::HamilView *hd, const bchmc_shim::MockView *m,
+                                  bchmc_shim::mt19937_state_fn state, void *rng_state, char *err, size_t errlen);
+size_t bchmc_shim_sizeof_mock(void);
 int bchmc_shim_kinetic_term(bchmc_shim::HamilView *hd, const double *momenta, double *out, char *err, size_t errlen);
 int bchmc_shim_psi(bchmc_shim::HamilView *hd, const double *signal, double *out, char *err, size_t errlen);
 bchmc_shim::EpsAdapt *bchmc_shim_eps_create(int update_type, unsigned N_a, double acc_min, double acc_max, int down_smooth,
