@@ -114,6 +114,26 @@ struct bchmc_handle {
   } mock;
   double *spec_bins = nullptr;                       // measure_spectrum's 3 * n_bin accumulators
   size_t spec_cap = 0;
+  // measure_corr / measure_corr2d (corr.hpp): accumulators and the geometry of the last n_bin of each function, kept in
+  // the handle like spec_bins (the driver measures after every sample with the same n_bin)
+  struct Corr1 {
+    uint64_t n_bin = 0;                // the geometry below is this bin count's (0: none yet)
+    unsigned long long *acc = nullptr; // 5 n_bin + 1: { A limbs [2][n_bin], scale, rtot limbs [2][n_bin], counts }
+    size_t cap = 0;
+    std::vector<double> rmode;
+    std::vector<uint64_t> nmode;
+  } corr1;
+  struct Corr2 {
+    uint64_t n_bin = 0;
+    int *idx = nullptr;        // rows sorted by perp bin | par_start [npb + 1] | perp_slice [n_bin + 1]
+    int2 *slices = nullptr;    // nsl: { first row, rows }
+    double *part = nullptr;    // nsl * npb
+    double *out = nullptr;     // [2][n_bin * npb]: rtot sums, A sums
+    int nrows = 0, nsl = 0, npb = 0, max_rows = 0;
+    std::vector<uint64_t> row_cnt, par_cnt;  // rows of a perp bin, cells along z of a populated par bin
+    std::vector<int> par_bin;                // nbin_par of populated par bin c
+    std::vector<double> rsum;                // n_bin * npb sums of rtot
+  } corr2;
   // host-array entry points: caller arrays are pageable, so they cross PCIe through two pinned staging chunks
   // (N-thread memcpy into one chunk while the DMA of the other is in flight)
   void *stg[2] = {nullptr, nullptr};
@@ -780,6 +800,93 @@ int spectrum_bins(bchmc_handle *h, const void *xk, uint64_t n_bin, double *kmode
     kmode[l] = cnt > 0. ? hb[l] / cnt : 0.;
     power[l] = cnt > 0. ? hb[n_bin + l] / cnt * NORM : 0.;
   }
+  return BCHMC_OK;
+}
+
+// The correlation tools' bin width rmax / n_bin, rmax = L/2 sqrt(3) (2D_corr_fct.cc:35-39), in this order on the host
+double corr_dr(const Geo &g, uint64_t n_bin) {
+  const double rmax = g.L / 2 * std::sqrt(3.);
+  return rmax / (double)n_bin;
+}
+
+// measure_corr2D's geometry for n_bin, built when n_bin changes: the rows (i, j) sorted by nbin_perp and cut into slices,
+// the runs of |z| that make up the populated par bins, the counts (products of the two), and on the device the sums of
+// rtot.  The bin indices are computed here exactly as the tool does (IEEE sqrt and divide, no FMA contraction).
+// Synchronises (the tables are uploaded from local vectors).
+int corr2d_setup(bchmc_handle *h, uint64_t n_bin) {
+#pragma clang fp contract(off)
+  auto &c = h->corr2;
+  if (c.n_bin == n_bin) return BCHMC_OK;
+  const Geo &g = h->g;
+  const int n = g.n;
+  const double dr = corr_dr(g, n_bin);
+  HIPCHK(hipStreamSynchronize(h->stream));
+  c.n_bin = 0;
+  for (void **p : {(void **)&c.idx, (void **)&c.slices, (void **)&c.part, (void **)&c.out}) {
+    if (*p) (void)hipFree(*p);
+    *p = nullptr;
+  }
+  // rows by perp bin: a counting sort that keeps the row order inside a bin
+  std::vector<int> perp((size_t)n * n);
+  c.row_cnt.assign(n_bin, 0);
+  for (int i = 0; i < n; i++)
+    for (int j = 0; j < n; j++) {
+      const double x = corr_pos(i, n, g.d), y = corr_pos(j, n, g.d);
+      const double rperp = std::sqrt(x * x + y * y);
+      const unsigned long long b = (unsigned long long)(rperp / dr);
+      perp[(size_t)i * n + j] = b < n_bin ? (int)b : -1;
+      if (b < n_bin) c.row_cnt[b]++;
+    }
+  std::vector<int> first(n_bin + 1, 0);
+  for (uint64_t p = 0; p < n_bin; p++) first[p + 1] = first[p] + (int)c.row_cnt[p];
+  c.nrows = first[n_bin];
+  std::vector<int> rows((size_t)std::max(c.nrows, 1)), fill(first.begin(), first.end() - 1);
+  for (int r = 0; r < n * n; r++)
+    if (perp[r] >= 0) rows[fill[perp[r]]++] = r;
+  // slices of one perp bin: enough of them to fill the device, few enough that a slice amortises its combine step
+  const int per = std::max(8, std::min(64, n * n / 2048));
+  std::vector<int2> slices;
+  std::vector<int> perp_slice(n_bin + 1, 0);
+  c.max_rows = 0;
+  for (uint64_t p = 0; p < n_bin; p++) {
+    perp_slice[p] = (int)slices.size();
+    for (int o = 0; o < (int)c.row_cnt[p]; o += per) slices.push_back(make_int2(first[p] + o, std::min(per, (int)c.row_cnt[p] - o)));
+    c.max_rows = std::max(c.max_rows, (int)c.row_cnt[p]);
+  }
+  perp_slice[n_bin] = (int)slices.size();
+  c.nsl = (int)slices.size();
+  // populated par bins: nbin_par is monotone in kk = min(k, n - k), so every bin is one run of kk
+  std::vector<int> par_start;
+  c.par_bin.clear();
+  c.par_cnt.clear();
+  int kk = 0;
+  for (; kk <= n / 2; kk++) {
+    const double z = corr_pos(kk, n, g.d);
+    const double rpar = std::sqrt(z * z);
+    const unsigned long long b = (unsigned long long)(rpar / dr);
+    if (b >= n_bin) break;
+    if (c.par_bin.empty() || c.par_bin.back() != (int)b) {
+      par_start.push_back(kk);
+      c.par_bin.push_back((int)b);
+      c.par_cnt.push_back(0);
+    }
+    c.par_cnt.back() += (kk == 0 || kk == n - kk) ? 1 : 2;
+  }
+  par_start.push_back(kk);
+  c.npb = (int)c.par_bin.size();
+  if (c.nsl == 0 || c.npb == 0) return h->fail(BCHMC_ERR_STATE, "measure_corr2d: no populated bin");
+  std::vector<int> idx(rows.begin(), rows.begin() + c.nrows);
+  idx.insert(idx.end(), par_start.begin(), par_start.end());
+  idx.insert(idx.end(), perp_slice.begin(), perp_slice.end());
+  CHK(dev_alloc(h, &c.idx, idx.size()));
+  CHK(dev_alloc(h, &c.slices, slices.size()));
+  CHK(dev_alloc(h, &c.part, (size_t)c.nsl * c.npb));
+  CHK(dev_alloc(h, &c.out, 2 * (size_t)n_bin * c.npb));
+  HIPCHK(hipMemcpyAsync(c.idx, idx.data(), idx.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(c.slices, slices.data(), slices.size() * sizeof(int2), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));  // idx and slices are local vectors
+  c.rsum.clear();  // filled by the first measurement
+  c.n_bin = n_bin;
   return BCHMC_OK;
 }
 
@@ -1927,6 +2034,155 @@ struct Pipe {
     return forward_rest(h, rsd, m);
   }
 
+  // Lag2Eul of the resident chain state, from its q^ directly (no transform pair through real space)
+  static int chain_forward(bchmc_handle *h, int rsd) {
+    HIPCHK(hipMemcpyAsync(h->qk, h->cq, 2 * (size_t)h->g.Nhp * sizeof(T), hipMemcpyDeviceToDevice, h->stream));
+    EvalMode m;
+    CHK(displacement(h, 1., rsd, &m.planes_c2r));
+    return forward_rest(h, rsd, m);
+  }
+
+  // ---- measure_corr_grid / measure_corr2D (corr.hpp) ----------------------------------------------------------------
+  // A(r) = C2R[|x^|^2] / N of the source into ioq.  Scratch: tC, ioq (and dstage for a host signal, already there);
+  // qk / pk / gk, the chain's arrays, the inputs and rho / psi are not touched.  C2R destroys its input, so |x^|^2
+  // always goes to tC, never back into cq.
+  static int corr_field(bchmc_handle *h, int src) {
+    const void *xk = h->tC;
+    if (src == BCHMC_CORR_HOST) {
+      CHK(r2c_state(h, h->dstage, h->ioq, h->tC));
+    } else if (src == BCHMC_CORR_CHAIN_STATE) {
+      xk = h->cq;
+    } else {  // deltaX exactly as bchmc_fetch makes it
+      k_overdens<T><<<nblk_stride(h->g.N), 256, 0, h->stream>>>(h->g, R(h->rho), h->rho_part, R(h->ioq));
+      HIPCHK(hipGetLastError());
+      CHK(fft_exec(h, h->r2c1, h->ioq, h->tC, BCHMC_K_FFT_R2C));
+    }
+    {
+      ProfScope ps(h, BCHMC_K_OTHER);
+      k_corr_abs2<T><<<nblk_stride(h->g.Nhp), 256, 0, h->stream>>>(h->g.Nhp, C(xk), C(h->tC), 1. / (double)h->g.N);
+      HIPCHK(hipGetLastError());
+    }
+    return fft_exec(h, h->c2r1, h->tC, h->ioq, BCHMC_K_FFT_C2R);
+  }
+
+  // The 1-D bin sums of A in ioq; the first call for an n_bin also builds rmode / nmode.  One synchronise.
+  static int corr1d_bins(bchmc_handle *h, uint64_t n_bin, double *rmode, uint64_t *nmode, double *corr) {
+    auto &c = h->corr1;
+    const Geo &g = h->g;
+    const size_t nb = (size_t)n_bin, words = 5 * nb + 1;
+    if (c.cap < words) {
+      if (c.acc) (void)hipFree(c.acc);
+      c.acc = nullptr;
+      c.cap = 0;
+      c.n_bin = 0;
+      CHK(dev_alloc(h, &c.acc, words));
+      c.cap = words;
+    }
+    const bool geom = c.n_bin != n_bin;
+    const double dr = corr_dr(g, n_bin);
+    const int grid = std::min(nblk_full(g.N), 1024);
+    unsigned long long *d_geo = c.acc + 2 * nb + 1;
+    std::vector<unsigned long long> hb(words);
+    {
+      ProfScope ps(h, BCHMC_K_OTHER);
+      HIPCHK(hipMemsetAsync(c.acc, 0, (geom ? words : 2 * nb + 1) * sizeof(unsigned long long), h->stream));
+      if (geom) {
+        // rtot < 2 rmax < 2^(e + 1) and a multiple of ulp(d) >= 2^(e - 62) for n <= 1024: rtot 2^(62 - e) is an integer
+        const double rscale = std::ldexp(1., 62 - std::ilogb(g.L / 2 * std::sqrt(3.)));
+        k_corr1d<T, true><<<grid, 256, 3 * nb * sizeof(unsigned long long), h->stream>>>(g, nullptr, (int)n_bin, dr,
+                                                                                      rscale, d_geo);
+      }
+      k_corr1d<T, false><<<grid, 256, 2 * nb * sizeof(unsigned long long), h->stream>>>(g, R(h->ioq), (int)n_bin, dr, 0.,
+                                                                                     c.acc);
+      HIPCHK(hipGetLastError());
+      HIPCHK(hipMemcpyAsync(hb.data(), c.acc, (geom ? words : 2 * nb + 1) * sizeof(unsigned long long),
+                            hipMemcpyDeviceToHost, h->stream));
+    }
+    HIPCHK(hipStreamSynchronize(h->stream));
+    const long double limb = (long double)(1ull << kCorrLimb);
+    if (geom) {
+      const long double rscale = std::ldexp(1.L, 62 - std::ilogb(g.L / 2 * std::sqrt(3.)));
+      const unsigned long long *hg = hb.data() + 2 * nb + 1;
+      c.rmode.assign(nb, 0.);
+      c.nmode.assign(nb, 0);
+      for (size_t l = 0; l < nb; l++) {
+        c.nmode[l] = hg[2 * nb + l];
+        if (c.nmode[l]) {
+          const double rsum = (double)(((long double)hg[l] * limb + (long double)hg[nb + l]) / rscale);
+          c.rmode[l] = rsum / (double)c.nmode[l];
+        }
+      }
+      c.n_bin = n_bin;
+    }
+    double sc;
+    std::memcpy(&sc, &hb[2 * nb], sizeof sc);
+    const double N = (double)g.N;
+    for (size_t l = 0; l < nb; l++) {
+      rmode[l] = c.rmode[l];
+      nmode[l] = c.nmode[l];
+      corr[l] = 0.;
+      if (c.nmode[l] && sc != sc) corr[l] = sc;  // a non-finite field: NaN, like the host tool's sums
+      if (c.nmode[l] && sc > 0.) {
+        const double asum = (double)(((long double)(long long)hb[l] * limb + (long double)hb[nb + l]) / (long double)sc);
+        corr[l] = asum / ((double)c.nmode[l] * N);
+      }
+    }
+    return BCHMC_OK;
+  }
+
+  template <bool GEOM>
+  static int launch_corr2d_slices(bchmc_handle *h) {
+    auto &c = h->corr2;
+    const int n = h->g.n, bd = std::min(256, (n + 63) / 64 * 64), kpt = (n + bd - 1) / bd;
+    const size_t lds = ((size_t)n + n / 2 + 1) * sizeof(double);
+    const int *par_start = c.idx + c.nrows;
+#define BCHMC_LAUNCH_C2(KPT) \
+  k_corr2d_slices<T, KPT, GEOM><<<c.nsl, bd, lds, h->stream>>>(h->g, R(h->ioq), c.idx, c.slices, par_start, c.npb, c.part)
+    if (kpt == 1) BCHMC_LAUNCH_C2(1);
+    else if (kpt == 2) BCHMC_LAUNCH_C2(2);
+    else BCHMC_LAUNCH_C2(4);
+#undef BCHMC_LAUNCH_C2
+    const int *perp_slice = par_start + c.npb + 1;
+    k_corr2d_reduce<<<nblk_stride((long long)c.n_bin * c.npb), 256, 0, h->stream>>>(
+        c.part, perp_slice, (int)c.n_bin, c.npb, c.out + (GEOM ? 0 : (size_t)c.n_bin * c.npb));
+    HIPCHK(hipGetLastError());
+    return BCHMC_OK;
+  }
+
+  // The 2-D bin sums of A in ioq (corr2d_setup has run).  One synchronise.
+  static int corr2d_bins(bchmc_handle *h, uint64_t n_bin, double *rmode, uint64_t *nmode, double *corr) {
+    auto &c = h->corr2;
+    const size_t nb = (size_t)n_bin, cells = nb * c.npb;
+    const bool geom = c.rsum.empty();
+    std::vector<double> hb(cells), hr(geom ? cells : 0);
+    {
+      ProfScope ps(h, BCHMC_K_OTHER);
+      if (geom) {
+        CHK(launch_corr2d_slices<true>(h));
+        HIPCHK(hipMemcpyAsync(hr.data(), c.out, cells * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+      }
+      CHK(launch_corr2d_slices<false>(h));
+      HIPCHK(hipMemcpyAsync(hb.data(), c.out + cells, cells * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    }
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (geom) c.rsum.swap(hr);
+    std::memset(rmode, 0, nb * nb * sizeof(double));
+    std::memset(corr, 0, nb * nb * sizeof(double));
+    std::memset(nmode, 0, nb * nb * sizeof(uint64_t));
+    const double N = (double)h->g.N;
+    for (size_t p = 0; p < nb; p++) {
+      if (!c.row_cnt[p]) continue;
+      for (int q = 0; q < c.npb; q++) {
+        const uint64_t nm = c.row_cnt[p] * c.par_cnt[q];
+        const size_t ii = (size_t)c.par_bin[q] + nb * p;  // 2D_corr_fct.cc:87
+        nmode[ii] = nm;
+        rmode[ii] = c.rsum[p * c.npb + q] / (double)nm;
+        corr[ii] = hb[p * c.npb + q] / ((double)nm * N);
+      }
+    }
+    return BCHMC_OK;
+  }
+
   static int gradient(bchmc_handle *h, const double *d_q, double *d_g) {
     const size_t N = (size_t)h->g.N;
     if (!h->gprior) {
@@ -2780,7 +3036,8 @@ void bchmc_destroy(bchmc_handle *h) {
   for (void *p : {(void *)h->mt.poly, (void *)h->mt.win, (void *)h->mt.words, (void *)h->mt.st, (void *)h->mt.nz,
                   (void *)h->mt.nzoff, (void *)h->mt.acc, (void *)h->mt.accoff, (void *)h->mt.lastend,
                   (void *)h->mt.res, (void *)h->mt.gauss, (void *)h->mock.cnt, (void *)h->mock.off,
-                  (void *)h->mock.gsum, (void *)h->mock.goff, (void *)h->mock.res})
+                  (void *)h->mock.gsum, (void *)h->mock.goff, (void *)h->mock.res, (void *)h->corr1.acc,
+                  (void *)h->corr2.idx, (void *)h->corr2.slices, (void *)h->corr2.part, (void *)h->corr2.out})
     if (p) (void)hipFree(p);
   if (h->mt.h_io) (void)hipHostFree(h->mt.h_io);
   if (h->copy_stream) (void)hipStreamDestroy(h->copy_stream);
@@ -3145,6 +3402,46 @@ int bchmc_measure_spectrum(bchmc_handle *h, const double *signal, uint64_t n_bin
     xk = h->cq;
   }
   return spectrum_bins(h, xk, n_bin, kmode, power);
+}
+
+static int corr_measure(bchmc_handle *h, bool two_d, bchmc_corr_source src, const double *signal, uint64_t n_bin,
+                        double *rmode, uint64_t *nmode, double *corr) {
+  if (!h || !rmode || !nmode || !corr) return BCHMC_ERR_ARG;
+  const char *name = two_d ? "measure_corr2d" : "measure_corr";
+  if (n_bin == 0 || n_bin > 2048) return h->fail(BCHMC_ERR_ARG, "%s: n_bin = %llu outside 1..2048", name, (unsigned long long)n_bin);
+  if (src != BCHMC_CORR_HOST && src != BCHMC_CORR_CHAIN_STATE && src != BCHMC_CORR_DELTAX)
+    return h->fail(BCHMC_ERR_ARG, "%s: unknown source %d", name, (int)src);
+  if ((src == BCHMC_CORR_HOST) != (signal != nullptr))
+    return h->fail(BCHMC_ERR_ARG, "%s: signal must be given for BCHMC_CORR_HOST and NULL otherwise", name);
+  ENTER(h);
+  if (src == BCHMC_CORR_CHAIN_STATE && !h->have_cq)
+    return h->fail(BCHMC_ERR_STATE, "no chain state: call bchmc_chain_set_state first");
+  if (src == BCHMC_CORR_DELTAX && !h->have_eval) return h->fail(BCHMC_ERR_STATE, "no forward evaluation to take deltaX from");
+  // both kernels are laid out for n <= 1024: the 1-D limb sums hold N <= 2^30 cells, the 2-D slices 4 k per thread of 256
+  if (h->g.n > 1024) return h->fail(BCHMC_ERR_UNSUPPORTED, "%s: n = %d > 1024", name, h->g.n);
+  if (two_d) CHK(corr2d_setup(h, n_bin));
+  if (signal) CHK(h2d(h, h->dstage, signal, h->g.N * sizeof(double)));
+  CHK(DISPATCH(h, corr_field(h, (int)src)));
+  return two_d ? DISPATCH(h, corr2d_bins(h, n_bin, rmode, nmode, corr)) : DISPATCH(h, corr1d_bins(h, n_bin, rmode, nmode, corr));
+}
+
+int bchmc_measure_corr(bchmc_handle *h, bchmc_corr_source src, const double *signal, uint64_t n_bin, double *rmode,
+                       uint64_t *nmode, double *corr) {
+  return corr_measure(h, false, src, signal, n_bin, rmode, nmode, corr);
+}
+
+int bchmc_measure_corr2d(bchmc_handle *h, bchmc_corr_source src, const double *signal, uint64_t n_bin, double *rmode,
+                         uint64_t *nmode, double *corr) {
+  return corr_measure(h, true, src, signal, n_bin, rmode, nmode, corr);
+}
+
+int bchmc_chain_forward(bchmc_handle *h, int use_rsd) {
+  if (!h) return BCHMC_ERR_ARG;
+  ENTER(h);
+  if (!h->have_cq) return h->fail(BCHMC_ERR_STATE, "no chain state: call bchmc_chain_set_state first");
+  clobber_proposal(h);
+  CHK(DISPATCH(h, chain_forward(h, use_rsd < 0 ? h->c.rsd_model : (use_rsd ? 1 : 0))));
+  return read_ctl(h, nullptr);  // synchronises; adapts the binning's record slots like bchmc_forward
 }
 
 int bchmc_hamiltonian_mass(bchmc_handle *h, const double *signal, const bchmc_mass_opts *opts, double *mass_f,

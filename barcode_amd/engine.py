@@ -89,9 +89,13 @@ EXPORTS = ("bchmc_create", "bchmc_destroy", "bchmc_strerror", "bchmc_last_error"
            "bchmc_comm_unique_id", "bchmc_comm_create", "bchmc_comm_create_custom", "bchmc_comm_destroy",
            "bchmc_comm_last_error", "bchmc_eps_exchange", "bchmc_comm_pending", "bchmc_comm_world", "bchmc_comm_rank",
            "bchmc_comm_transport", "bchmc_garfield_walk_index", "bchmc_hamiltonian_mass",
-           "bchmc_setup_random_test", "bchmc_make_initial_guess")
+           "bchmc_setup_random_test", "bchmc_make_initial_guess", "bchmc_measure_corr", "bchmc_chain_forward")
 # declared as well, listed apart: the header scan of the ABI test matches names of letters and underscores only
 EXPORTS_MT19937 = ("bchmc_chain_draw_momenta_mt19937", "bchmc_mt19937_jump")
+EXPORTS_CORR2D = ("bchmc_measure_corr2d",)  # a digit in the name, like the two above
+
+# bchmc_corr_source
+CORR_SOURCES = dict(host=0, chain=1, deltaX=2)
 
 
 def load():
@@ -140,6 +144,9 @@ def load():
     lib.bchmc_chain_accept.argtypes = [vp, C.c_int]
     lib.bchmc_measure_spectrum.argtypes = [vp, dp, C.c_uint64, dp, dp]
     lib.bchmc_hamiltonian_mass.argtypes = [vp, dp, C.POINTER(MassOpts), dp, dp]
+    lib.bchmc_measure_corr.argtypes = [vp, C.c_int, dp, C.c_uint64, dp, C.POINTER(u64), dp]
+    lib.bchmc_measure_corr2d.argtypes = [vp, C.c_int, dp, C.c_uint64, dp, C.POINTER(u64), dp]
+    lib.bchmc_chain_forward.argtypes = [vp, C.c_int]
     lib.bchmc_philox_kat.argtypes = [C.POINTER(C.c_uint32)] * 3
     lib.bchmc_kinetic_term.argtypes = [vp, dp, dp]
     lib.bchmc_psi.argtypes = [vp, dp, dp]
@@ -204,6 +211,12 @@ def garfield_walk_index(n, i, j, k):
     if rc:
         raise BchmcError(rc, lib.bchmc_strerror(rc).decode())
     return idx.value
+
+
+def corr_auto_nbin(n, L):
+    """The correlation tools' "N_bin = 0" rule (2D_corr_fct.cc:277-286): ceil(rmax / d), rmax = L/2 sqrt(3), d = L/n."""
+    rmax = float(L) / 2 * np.sqrt(3)
+    return int(np.ceil(rmax / (float(L) / float(n))))
 
 
 def make_config(params, device=0, precision=0, deterministic=0):
@@ -442,6 +455,34 @@ class Engine:
         sig = None if signal is None else _p(self._in(signal))
         self._chk(self.lib.bchmc_measure_spectrum(self.h, sig, int(n_bin), _p(kmode), _p(power)))
         return kmode, power
+
+    def _measure_corr(self, fn, cells, signal, n_bin, source):
+        if source is None:
+            source = "chain" if signal is None else "host"
+        n_bin = int(n_bin) if n_bin else corr_auto_nbin(self.Nx, self.params.L)
+        size = n_bin ** cells if 1 <= n_bin <= 2048 else 1  # out of range: the library refuses before it writes
+        rmode, corr, nmode = np.empty(size), np.empty(size), np.empty(size, dtype=np.uint64)
+        sig = None if signal is None else _p(self._in(signal))
+        self._chk(fn(self.h, CORR_SOURCES[source], sig, n_bin, _p(rmode), nmode.ctypes.data_as(C.POINTER(C.c_uint64)),
+                     _p(corr)))
+        shape = (n_bin,) * cells
+        return rmode.reshape(shape), nmode.reshape(shape), corr.reshape(shape)
+
+    def measure_corr(self, signal=None, n_bin=0, source=None):
+        """measure_corr_grid (tools/corr_fct.cc:20-80) of a host field (``source="host"``), of the resident chain state
+        (``"chain"``, the default without a signal) or of the handle's deltaX (``"deltaX"``).  ``n_bin=0``: the tools'
+        automatic bin count.  Returns (rmode, nmode, corr), n_bin each."""
+        return self._measure_corr(self.lib.bchmc_measure_corr, 1, signal, n_bin, source)
+
+    def measure_corr2d(self, signal=None, n_bin=0, source=None):
+        """measure_corr2D (tools/2D_corr_fct.cc:23-124), plane-parallel along z.  Returns (rmode, nmode, corr) shaped
+        (n_bin, n_bin) with r_perp as the first axis (the tool's element ``par + n_bin * perp``)."""
+        return self._measure_corr(self.lib.bchmc_measure_corr2d, 2, signal, n_bin, source)
+
+    def chain_forward(self, rsd=-1):
+        """Lag2Eul of the resident chain state: ``forward(chain_get_state(), rsd)`` without the field leaving the
+        device.  ``fetch("deltaX")`` etc. afterwards."""
+        self._chk(self.lib.bchmc_chain_forward(self.h, int(rsd)))
 
     def hamiltonian_mass(self, signal=None, n_bin=200, mass_factor=1.0, iGibbs=1, s_eps_total=0):
         """Hamiltonian_mass (HMC_mass.cc:315-368) on the device at a host field, or at the resident chain state when

@@ -127,6 +127,19 @@ def measure_spectrum(hd, signal=None, N_bin=200):
     return hd.engine.measure_spectrum(signal, N_bin)
 
 
+def measure_corr_grid(hd, signal=None, N_bin=0, source=None):
+    """tools/corr_fct.cc:20-80 -> (rmode, nmode, corr).  ``signal`` None = the resident chain state, or with
+    ``source="deltaX"`` the density of the last forward model; ``N_bin`` 0 = the tools' automatic bin count."""
+    return hd.engine.measure_corr(signal, N_bin, source)
+
+
+def measure_corr2D(hd, signal=None, N_bin=0, source=None, planepar=True):
+    """tools/2D_corr_fct.cc:23-124 -> (rmode, nmode, corr) shaped (N_bin, N_bin), r_perp first."""
+    if not planepar:
+        raise RuntimeError("non-plane-parallel option not yet implemented")  # 2D_corr_fct.cc:75
+    return hd.engine.measure_corr2d(signal, N_bin, source)
+
+
 def Hamiltonian_mass(hd, signal=None):
     """HMC_mass.cc:315-368 on the device at ``signal`` (None: the resident chain state); the engine takes the new mass
     as if it had been uploaded.  Returns (mass_f, mass_r), None where the mass_type has none."""

@@ -2,6 +2,8 @@
 
 * Field dumps: raw native-endian ``real_prec`` (double) arrays, no header -- ``write_array`` / ``read_array``
   (``barlib/src/IOfunctionsGen.cc:185-229``), including the ``.dat`` extension rule (`add_extension_if_missing`).
+* Correlation-function tools: ``<name>_r`` / ``<name>_eta`` as such arrays (``tools/2D_corr_fct.cc:283-303``), and
+  ``dump_deltas``' deltaLAG / deltaRSS / deltaEUL fields (``IOfunctionsGen.cc:136-171``).
 * ``performance_log.txt``: one tab-separated row of 14 columns per attempt (``HMC.cc:40-60``) under the header
   written by ``barcoderunner.cc:357-358``.
 """
@@ -65,3 +67,44 @@ def dump_measured_spec(kmode, power, fname):
 
 def power_spectrum_filename(directory, iGibbs):
     return os.path.join(directory, "powSpecit%d.dat" % int(iGibbs)) if directory else "powSpecit%d.dat" % int(iGibbs)
+
+
+def corr_filenames(fname_out, n_bin, auto_nbin=False):
+    """The two files of ``tools/2D_corr_fct.cc:301-303`` (before ``write_array``'s extension rule); the ``_Nbin<N>``
+    suffix is added when the tool chose the bin count itself (:278-286)."""
+    base = fname_out + ("_Nbin%d" % int(n_bin) if auto_nbin else "")
+    return base + "_r", base + "_eta"
+
+
+def dump_corr(fname_out, rmode, corr, auto_nbin=False, n_bin=None):
+    """``dump_scalar(rmode, ...)``, ``dump_scalar(corr, ...)`` of the correlation tools: raw ``real_prec`` arrays of
+    N_bin (1-D) or N_bin^2 values (2-D, element ``par + N_bin * perp``).  ``n_bin`` names the bin count for the
+    ``_Nbin`` suffix; without it the first axis of ``rmode`` is taken, which is right for 1-D arrays and for 2-D arrays
+    shaped (N_bin, N_bin), not for a flat N_bin^2 one.  Returns the two paths written."""
+    rmode, corr = np.asarray(rmode), np.asarray(corr)
+    names = corr_filenames(fname_out, rmode.shape[0] if n_bin is None else n_bin, auto_nbin)
+    for name, a in zip(names, (rmode, corr)):
+        write_array(name, a)
+    return tuple(add_extension_if_missing(n) for n in names)
+
+
+def dump_deltas(engine, directory, suffix=""):
+    """``dump_deltas`` (IOfunctionsGen.cc:136-171) of the resident chain state: deltaLAG, then deltaEUL without
+    ``rsd_model``, or deltaRSS (the configured forward model) and deltaEUL (a second Lag2Eul without RSD) with it.
+    The forward models run on the device from the resident state (``chain_forward``); only the dumped fields cross to
+    the host.  Returns the paths in the order written."""
+    def put(name, a):
+        path = os.path.join(directory, name + suffix) if directory else name + suffix
+        write_array(path, a)
+        return add_extension_if_missing(path)
+
+    out = [put("deltaLAG", engine.chain_get_state())]
+    if not engine.params.rsd_model:
+        engine.chain_forward(0)
+        out.append(put("deltaEUL", engine.fetch("deltaX")))
+    else:
+        engine.chain_forward(1)
+        out.append(put("deltaRSS", engine.fetch("deltaX")))
+        engine.chain_forward(0)
+        out.append(put("deltaEUL", engine.fetch("deltaX")))
+    return out

@@ -25,7 +25,8 @@ SHIM_EXPORTS = ("bchmc_shim_Hamiltonian_EoM", "bchmc_shim_delta_Hamiltonian", "b
                 "bchmc_shim_comm_bootstrap_file", "bchmc_shim_comm_attach", "bchmc_shim_comm_release",
                 "bchmc_shim_inputs_changed", "bchmc_shim_mass_changed", "bchmc_shim_bootstrap_exchange_id",
                 "bchmc_shim_bootstrap_cleanup", "bchmc_shim_Hamiltonian_mass",
-                "bchmc_shim_setup_random_test", "bchmc_shim_make_initial_guess", "bchmc_shim_sizeof_mock")
+                "bchmc_shim_setup_random_test", "bchmc_shim_make_initial_guess", "bchmc_shim_sizeof_mock",
+                "bchmc_shim_measure_corr_grid", "bchmc_shim_measure_corr2D", "bchmc_shim_chain_forward")
 
 _dp = C.POINTER(C.c_double)
 
@@ -118,6 +119,9 @@ def load():
     lib.bchmc_shim_gradient_psi.argtypes = [hv, _dp, C.c_char_p, sz]
     lib.bchmc_shim_measure_spectrum.argtypes = [hv, _dp, _dp, _dp, ul, C.c_char_p, sz]
     lib.bchmc_shim_Hamiltonian_mass.argtypes = [hv, _dp, _dp, _dp, C.c_char_p, sz]
+    lib.bchmc_shim_measure_corr_grid.argtypes = [hv, _dp, ul, _dp, C.POINTER(ul), _dp, C.c_int, C.c_char_p, sz]
+    lib.bchmc_shim_measure_corr2D.argtypes = [hv, _dp, ul, _dp, C.POINTER(ul), _dp, C.c_int, C.c_int, C.c_char_p, sz]
+    lib.bchmc_shim_chain_forward.argtypes = [hv, C.c_int, C.c_char_p, sz]
     lib.bchmc_shim_chain_set_state.argtypes = [hv, _dp, C.c_char_p, sz]
     lib.bchmc_shim_chain_get_state.argtypes = [hv, _dp, C.c_char_p, sz]
     lib.bchmc_shim_HamiltonianMC.argtypes = [hv, UNIFORM_FN, C.c_void_p, C.c_uint64, ul, C.POINTER(ul),
@@ -278,6 +282,33 @@ class ShimHamil:
         self._chk(self.lib.bchmc_shim_Hamiltonian_mass(C.byref(self.hd), sig, None if mf is None else _p(mf),
                                                        None if mr is None else _p(mr), self._err, len(self._err)))
         return mf, mr
+
+    def _corr(self, cells, signal, N_bin, of_deltaX, planepar=None):
+        size = int(N_bin) ** cells if 1 <= int(N_bin) <= 2048 else 1  # out of range: refused before anything is written
+        rm, co, nm = np.empty(size), np.empty(size), np.empty(size, dtype=np.uint64)
+        sig = None if signal is None else _p(self._in(signal))
+        nmp = nm.ctypes.data_as(C.POINTER(C.c_ulong))
+        tail = (int(bool(of_deltaX)), self._err, len(self._err))
+        if cells == 1:
+            rc = self.lib.bchmc_shim_measure_corr_grid(C.byref(self.hd), sig, int(N_bin), _p(rm), nmp, _p(co), *tail)
+        else:
+            rc = self.lib.bchmc_shim_measure_corr2D(C.byref(self.hd), sig, int(N_bin), _p(rm), nmp, _p(co),
+                                                    int(bool(planepar)), *tail)
+        self._chk(rc)
+        shape = (int(N_bin),) * cells
+        return rm.reshape(shape), nm.reshape(shape), co.reshape(shape)
+
+    def measure_corr_grid(self, signal, N_bin, of_deltaX=False):
+        """bchmc_shim::measure_corr_grid at ``signal`` (None: the resident state, or deltaX) -> (rmode, nmode, corr)."""
+        return self._corr(1, signal, N_bin, of_deltaX)
+
+    def measure_corr2D(self, signal, N_bin, planepar=True, of_deltaX=False):
+        return self._corr(2, signal, N_bin, of_deltaX, planepar)
+
+    def chain_forward(self, use_rsd=-1):
+        """bchmc_shim::chain_forward: Lag2Eul of the resident state; returns the view's deltaX array."""
+        self._chk(self.lib.bchmc_shim_chain_forward(C.byref(self.hd), int(use_rsd), self._err, len(self._err)))
+        return self._keep["deltaX"]
 
     def chain_set_state(self, x):
         self._chk(self.lib.bchmc_shim_chain_set_state(C.byref(self.hd), _p(self._in(x)), self._err, len(self._err)))

@@ -244,6 +244,37 @@ void measure_spectrum(HamilView *hd, const real_prec *signal, real_prec *kmode, 
   if (rc) fail(h, rc, "measure_spectrum");
 }
 
+namespace {
+bchmc_corr_source corr_source(const real_prec *signal, bool of_deltaX) {
+  return signal ? BCHMC_CORR_HOST : (of_deltaX ? BCHMC_CORR_DELTAX : BCHMC_CORR_CHAIN_STATE);
+}
+static_assert(sizeof(ULONG) == sizeof(uint64_t), "nmode is passed through as uint64_t");
+}  // namespace
+
+void measure_corr_grid(HamilView *hd, const real_prec *signal, ULONG N_bin, real_prec *rmode, ULONG *nmode,
+                       real_prec *corr, bool of_deltaX) {
+  bchmc_handle *h = engine_for(hd);
+  const int rc = bchmc_measure_corr(h, corr_source(signal, of_deltaX), signal, N_bin, rmode,
+                                    reinterpret_cast<uint64_t *>(nmode), corr);
+  if (rc) fail(h, rc, "measure_corr_grid");
+}
+
+void measure_corr2D(HamilView *hd, const real_prec *signal, ULONG N_bin, real_prec *rmode, ULONG *nmode, real_prec *corr,
+                    bool planepar, bool of_deltaX) {
+  if (!planepar) throw std::runtime_error("non-plane-parallel option not yet implemented");  // 2D_corr_fct.cc:75
+  bchmc_handle *h = engine_for(hd);
+  const int rc = bchmc_measure_corr2d(h, corr_source(signal, of_deltaX), signal, N_bin, rmode,
+                                      reinterpret_cast<uint64_t *>(nmode), corr);
+  if (rc) fail(h, rc, "measure_corr2D");
+}
+
+void chain_forward(HamilView *hd, int use_rsd) {
+  bchmc_handle *h = engine_for(hd);
+  const int rc = bchmc_chain_forward(h, use_rsd);
+  if (rc) fail(h, rc, "chain_forward");
+  fetch_eval_state(hd, h);
+}
+
 void Hamiltonian_mass(HamilView *hd, const real_prec *signal, real_prec *mass_f_out, real_prec *mass_r_out) {
   bchmc_handle *h = engine_for(hd);
   const HamilNumericalView *n = hd->numerical;
@@ -709,6 +740,20 @@ int bchmc_shim_measure_spectrum(bchmc_shim::HamilView *hd, const double *signal,
 int bchmc_shim_Hamiltonian_mass(bchmc_shim::HamilView *hd, const double *signal, double *mass_f, double *mass_r, char *err,
                                 size_t errlen) {
   return guarded(err, errlen, [&] { bchmc_shim::Hamiltonian_mass(hd, signal, mass_f, mass_r); });
+}
+int bchmc_shim_measure_corr_grid(bchmc_shim::HamilView *hd, const double *signal, unsigned long N_bin, double *rmode,
+                                 unsigned long *nmode, double *corr, int of_deltaX, char *err, size_t errlen) {
+  return guarded(err, errlen, [&] { bchmc_shim::measure_corr_grid(hd, signal, N_bin, rmode, nmode, corr, of_deltaX != 0); });
+}
+int bchmc_shim_measure_corr2D(bchmc_shim::HamilView *hd, const double *signal, unsigned long N_bin, double *rmode,
+                                   unsigned long *nmode, double *corr, int planepar, int of_deltaX, char *err,
+                                   size_t errlen) {
+  return guarded(err, errlen, [&] {
+    bchmc_shim::measure_corr2D(hd, signal, N_bin, rmode, nmode, corr, planepar != 0, of_deltaX != 0);
+  });
+}
+int bchmc_shim_chain_forward(bchmc_shim::HamilView *hd, int use_rsd, char *err, size_t errlen) {
+  return guarded(err, errlen, [&] { bchmc_shim::chain_forward(hd, use_rsd); });
 }
 int bchmc_shim_chain_set_state(bchmc_shim::HamilView *hd, const double *x, char *err, size_t errlen) {
   return guarded(err, errlen, [&] { bchmc_shim::chain_set_state(hd, x); });

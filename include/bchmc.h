@@ -204,6 +204,47 @@ int bchmc_chain_accept(bchmc_handle *h, int accepted);         /* accepted: q :=
  * resident chain state (no transform and no field transfer: its R2C is what the chain keeps).  kmode / power:
  * n_bin doubles each; empty bins stay 0 like upstream. */
 int bchmc_measure_spectrum(bchmc_handle *h, const double *signal, uint64_t n_bin, double *kmode, double *power);
+/* ---- correlation functions of a sample (upstream: tools/corr_fct.cc, tools/2D_corr_fct.cc on dumped fields) ----------
+ * xi(r) and xi(r_perp, r_par) of a host field, of the resident chain state (no forward transform: its R2C is what the
+ * chain keeps) or of the handle's deltaX (the Eulerian or redshift-space density of the last forward model), binned on
+ * the device: A(r) = C2R[|R2C delta|^2] / N, rmax = L/2 sqrt(3), dr = rmax / n_bin, cell positions by
+ * pacman_center_on_origin, bin indices (ULONG)(r / dr) with IEEE sqrt and divide and no FMA contraction, so that every
+ * cell lands in the bin the host tool puts it in.  Per bin: rmode = mean 3-D distance, nmode = cells, corr = sum of A /
+ * (nmode N); empty bins are 0.  n_bin: 1..2048.  Nx <= 1024 (BCHMC_ERR_UNSUPPORTED above).  rmode / nmode depend on the
+ * grid and n_bin only and are kept in the handle per function, so repeated calls with one n_bin sum corr only.
+ * Results are bitwise repeatable on every handle: the 2-D sums use no atomics and a fixed order, the 1-D sums are
+ * exact-integer accumulations.  fp32 handles: transforms and A in float, bin sums as above.  A field that is not finite
+ * gives NaN in every populated bin of corr (the host tool's sums would be NaN too); a zero field gives 0.
+ * A measurement leaves the chain state, the momenta, the carried gradient and -log L, the uploaded inputs, deltaX / pos*
+ * AND a pending proposal as they were (it uses the transfer staging and scratch arrays only).
+ * Errors, checked before anything is queued: signal given with a source other than BCHMC_CORR_HOST, or missing with it,
+ * n_bin out of range: BCHMC_ERR_ARG; no chain state, or no forward evaluation in the handle (where
+ * bchmc_fetch(BCHMC_F_DELTAX) fails): BCHMC_ERR_STATE.
+ * Two properties of the upstream tools:
+ *  C1 (deviation) measure_corr_grid does not bound the bin index (its guard is commented out, corr_fct.cc:60-67).  The
+ *     corner cell (n/2, n/2, n/2) has rtot == rmax and lands in bin n_bin exactly: upstream writes one element past
+ *     rmode, corr and nmode.  The engine drops that cell, as measure_corr2D and measure_spectrum do with theirs.
+ *  C2 (immaterial) absolute_squared_array(Signal, Signal) sets the real part only, so upstream's inverse transform sees
+ *     |delta^|^2 + i Im delta^ and its A(r) carries the odd part (delta(r) - delta(-r)) / 2 of the field as well.  Every
+ *     bin is symmetric under r -> -r, so the term cancels inside each bin; the engine transforms |delta^|^2 alone. */
+typedef enum bchmc_corr_source {
+  BCHMC_CORR_HOST = 0,        /* `signal`: N host doubles */
+  BCHMC_CORR_CHAIN_STATE = 1, /* the resident chain state (deltaLAG); signal must be NULL */
+  BCHMC_CORR_DELTAX = 2       /* the handle's deltaX (what bchmc_fetch(BCHMC_F_DELTAX) would return); signal must be NULL */
+} bchmc_corr_source;
+/* measure_corr_grid (tools/corr_fct.cc:20-80): rmode, corr: n_bin doubles; nmode: n_bin counts */
+int bchmc_measure_corr(bchmc_handle *h, bchmc_corr_source src, const double *signal, uint64_t n_bin, double *rmode,
+                       uint64_t *nmode, double *corr);
+/* measure_corr2D (tools/2D_corr_fct.cc:23-124), plane-parallel, line of sight = z (the axis rsd.cc:52-58 displaces):
+ * arrays of n_bin * n_bin, element nbin_par + n_bin * nbin_perp */
+int bchmc_measure_corr2d(bchmc_handle *h, bchmc_corr_source src, const double *signal, uint64_t n_bin, double *rmode,
+                         uint64_t *nmode, double *corr);
+/* Lag2Eul of the resident chain state: bchmc_forward without the host array (it starts from the chain's q^, so no field
+ * crosses PCIe and no transform pair is spent).  use_rsd as there.  Leaves deltaX / pos* in the handle, synchronises and
+ * adapts the binning's record slots like bchmc_forward; drops a pending proposal like it.  The chain state, the momenta
+ * and the carried gradient / -log L are untouched.  With bchmc_fetch this gives dump_deltas' arrays
+ * (IOfunctionsGen.cc:136-171): deltaRSS from use_rsd = 1, deltaEUL from use_rsd = 0. */
+int bchmc_chain_forward(bchmc_handle *h, int use_rsd);
 /* Hamiltonian_mass (HMC_mass.cc:315-368; HamiltonianMC calls it at HMC.cc:387-423) for the handle's mass_type. */
 typedef struct bchmc_mass_opts {
   uint64_t n_bin;               /* HAMIL_NUMERICAL::N_bin (types 2, 3); 1..2048 like bchmc_measure_spectrum */

@@ -118,6 +118,16 @@ real_prec kinetic_term(HamilView *hd, const real_prec *momenta);  // HMC.cc:64-1
 real_prec psi(HamilView *hd, const real_prec *signal);            // HMC.cc:124-143 (stores psi_prior, psi_likeli)
 // field_statistics.cpp:20-90
 void measure_spectrum(HamilView *hd, const real_prec *signal, real_prec *kmode, real_prec *power, ULONG N_bin);
+// tools/corr_fct.cc:20-80 and tools/2D_corr_fct.cc:23-124 on the device.  `signal` null: the resident chain state, or
+// with of_deltaX the engine's deltaX (the density of the last forward model, e.g. of chain_forward).  rmode / corr:
+// N_bin (N_bin * N_bin) values, element nbin_par + N_bin * nbin_perp.  planepar == false throws like upstream.
+void measure_corr_grid(HamilView *hd, const real_prec *signal, ULONG N_bin, real_prec *rmode, ULONG *nmode,
+                       real_prec *corr, bool of_deltaX = false);
+void measure_corr2D(HamilView *hd, const real_prec *signal, ULONG N_bin, real_prec *rmode, ULONG *nmode, real_prec *corr,
+                    bool planepar = true, bool of_deltaX = false);
+// Lag2Eul of the resident chain state (dump_deltas' second forward model, IOfunctionsGen.cc:158-169, with use_rsd = 0);
+// hd->deltaX / pos* <- this evaluation's.  use_rsd < 0: as configured.
+void chain_forward(HamilView *hd, int use_rsd);
 // HMC_mass.cc:315-368 on the device at `signal` (null: the resident chain state).  The engine keeps the built mass (the
 // mass generation is bumped and marked uploaded, so nothing re-uploads a host array over it, and the EoM energies are
 // dropped); mass_f_out / mass_r_out (may be null) receive host copies where the mass_type has the array.
@@ -247,6 +257,12 @@ int bchmc_shim_measure_spectrum(bchmc_shim::HamilView *hd, const double *signal,
                                 unsigned long N_bin, char *err, size_t errlen);
 int bchmc_shim_Hamiltonian_mass(bchmc_shim::HamilView *hd, const double *signal, double *mass_f, double *mass_r, char *err,
                                 size_t errlen);
+int bchmc_shim_measure_corr_grid(bchmc_shim::HamilView *hd, const double *signal, unsigned long N_bin, double *rmode,
+                                 unsigned long *nmode, double *corr, int of_deltaX, char *err, size_t errlen);
+int bchmc_shim_measure_corr2D(bchmc_shim::HamilView *hd, const double *signal, unsigned long N_bin, double *rmode,
+                                   unsigned long *nmode, double *corr, int planepar, int of_deltaX, char *err,
+                                   size_t errlen);
+int bchmc_shim_chain_forward(bchmc_shim::HamilView *hd, int use_rsd, char *err, size_t errlen);
 int bchmc_shim_chain_set_state(bchmc_shim::HamilView *hd, const double *x, char *err, size_t errlen);
 int bchmc_shim_chain_get_state(bchmc_shim::HamilView *hd, double *x, char *err, size_t errlen);
 int bchmc_shim_HamiltonianMC(bchmc_shim::HamilView *hd, bchmc_shim::uniform_fn uniform, void *rng_state, uint64_t seed,
