@@ -1106,6 +1106,14 @@ struct Pipe {
         CHK(fft_exec(h, planes ? h->c2r2d : h->c2r3, h->Ck, h->psi, BCHMC_K_FFT_C2R));
       }
     }
+    return particle_stage(h, rsd, m, zbin);
+  }
+
+  // Everything of the forward model after the C2R of Psi: binning (one-pass, or the two-pass sort + subsort after an
+  // overflow), mass assignment, fixed-point conversion, sum of rho.  Reads Psi from h->psi -- unless `zbin`, where
+  // k_zbin_direct takes the z pass of Psi^ (Ck) on its way (forward_rest only: bchmc_probe_displacement, the other
+  // caller, has no Psi^ to give it).
+  static int particle_stage(bchmc_handle *h, int rsd, EvalMode m, bool zbin) {
     h->sorted_valid = false;
     bool rho_cleared = false;  // by k_bin_direct, on its way through the lattice
     const PosPar pp = make_pos(h, rsd);
@@ -1259,7 +1267,8 @@ struct Pipe {
   }
 
   // After forward_rest: leaves the k-space likelihood source in Ck and returns the assemble mode.
-  static int like_force(bchmc_handle *h, EvalMode m, int *like_mode) {
+  // transform = false (bchmc_probe_displacement): stops before the R2C that ends each branch; part_like and V stay.
+  static int like_force(bchmc_handle *h, EvalMode m, int *like_mode, bool transform = true) {
     if (h->c.calc_h == 2 || h->c.calc_h == 3) {
       if (h->c.mk != 3)
         return h->fail(BCHMC_ERR_MK_NOT_SPH, "Must use SPH mass kernel (masskernel = 3) with calc_h = 2 or 3");
@@ -1275,7 +1284,7 @@ struct Pipe {
       HIPCHK(hipGetLastError());
     }
     if (h->c.calc_h == 1) {
-      CHK(fft_exec(h, h->r2c1, h->plike, h->Ck, BCHMC_K_FFT_R2C));
+      if (transform) CHK(fft_exec(h, h->r2c1, h->plike, h->Ck, BCHMC_K_FFT_R2C));
       *like_mode = 1;
       return BCHMC_OK;
     }
@@ -1303,7 +1312,7 @@ struct Pipe {
         k_findif_mul<T><<<nblk_stride(N), 256, 0, h->stream>>>(h->g, make_like(h), R(h->ioq), R(h->plike), R(h->V));
         HIPCHK(hipGetLastError());
       }
-      CHK(fft_exec(h, h->r2c3, h->V, h->Ck, BCHMC_K_FFT_R2C));
+      if (transform) CHK(fft_exec(h, h->r2c3, h->V, h->Ck, BCHMC_K_FFT_R2C));
       *like_mode = 0;
       return BCHMC_OK;
     }
@@ -1355,7 +1364,8 @@ struct Pipe {
       }
       HIPCHK(hipGetLastError());
     }
-    if (m.planes_r2c && yfwd_ok(h)) {
+    if (!transform) {
+    } else if (m.planes_r2c && yfwd_ok(h)) {
       // 512^3: the engine's own row and column passes (rocFFT's length-512 column kernel runs at 2.3 TB/s, its 1-D row
       // plan alone at half the speed of the same pass inside the 2-D plan: k_zr2c + k_ypass<forward>, zpass.hpp)
       ProfScope ps(h, BCHMC_K_FFT_R2C);
@@ -2040,6 +2050,17 @@ struct Pipe {
     EvalMode m;
     CHK(displacement(h, 1., rsd, &m.planes_c2r));
     return forward_rest(h, rsd, m);
+  }
+
+  // bchmc_probe_displacement: the particle stage (and the likelihood force up to V) of a displacement given in real
+  // space; component c of it is staged in dstage
+  static int probe_load(bchmc_handle *h, int c) { return load_real(h, h->dstage, R(h->psi) + (size_t)c * h->g.N); }
+  static int probe(bchmc_handle *h, int rsd, bool with_force) {
+    EvalMode m;
+    CHK(particle_stage(h, rsd, m, false));
+    int like_mode = 0;
+    if (with_force) CHK(like_force(h, m, &like_mode, false));
+    return BCHMC_OK;
   }
 
   // ---- measure_corr_grid / measure_corr2D (corr.hpp) ----------------------------------------------------------------
@@ -3242,6 +3263,27 @@ int bchmc_forward(bchmc_handle *h, const double *q, int use_rsd) {
   CHK(h2d(h, h->dstage, q, h->g.N * sizeof(double)));
   CHK(DISPATCH(h, forward(h, h->dstage, use_rsd < 0 ? h->c.rsd_model : (use_rsd ? 1 : 0))));
   return read_ctl(h, nullptr);  // synchronises; enlarges the binning's record slots if this field overflowed them
+}
+
+int bchmc_probe_displacement(bchmc_handle *h, const double *psi, int use_rsd, int with_force) {
+  if (!h || !psi) return BCHMC_ERR_ARG;
+  ENTER(h);
+  const int rsd = use_rsd < 0 ? h->c.rsd_model : (use_rsd ? 1 : 0);
+  if (rsd && !h->c.planepar) return h->fail(BCHMC_ERR_RSD_NOT_PLANEPAR, "non-plane-parallel RSD is not implemented");
+  if (with_force) {
+    if (h->c.likelihood == 3)
+      return h->fail(BCHMC_ERR_UNSUPPORTED, "the GRF likelihood's force has no particle stage to probe");
+    CHK(check_inputs(h));
+  }
+  clobber_proposal(h);
+  h->cg_valid = false;
+  const size_t N = (size_t)h->g.N;
+  for (int c = 0; c < 3; c++) {
+    CHK(h2d(h, h->dstage, psi + c * N, N * sizeof(double)));
+    CHK(DISPATCH(h, probe_load(h, c)));
+  }
+  CHK(DISPATCH(h, probe(h, rsd, with_force != 0)));
+  return read_ctl(h, nullptr);  // synchronises; adapts the binning's record slots like bchmc_forward
 }
 
 int bchmc_gradient(bchmc_handle *h, const double *q, double *gout) {

@@ -89,7 +89,8 @@ EXPORTS = ("bchmc_create", "bchmc_destroy", "bchmc_strerror", "bchmc_last_error"
            "bchmc_comm_unique_id", "bchmc_comm_create", "bchmc_comm_create_custom", "bchmc_comm_destroy",
            "bchmc_comm_last_error", "bchmc_eps_exchange", "bchmc_comm_pending", "bchmc_comm_world", "bchmc_comm_rank",
            "bchmc_comm_transport", "bchmc_garfield_walk_index", "bchmc_hamiltonian_mass",
-           "bchmc_setup_random_test", "bchmc_make_initial_guess", "bchmc_measure_corr", "bchmc_chain_forward")
+           "bchmc_setup_random_test", "bchmc_make_initial_guess", "bchmc_measure_corr", "bchmc_chain_forward",
+           "bchmc_probe_displacement")
 # declared as well, listed apart: the header scan of the ABI test matches names of letters and underscores only
 EXPORTS_MT19937 = ("bchmc_chain_draw_momenta_mt19937", "bchmc_mt19937_jump")
 EXPORTS_CORR2D = ("bchmc_measure_corr2d",)  # a digit in the name, like the two above
@@ -147,6 +148,7 @@ def load():
     lib.bchmc_measure_corr.argtypes = [vp, C.c_int, dp, C.c_uint64, dp, C.POINTER(u64), dp]
     lib.bchmc_measure_corr2d.argtypes = [vp, C.c_int, dp, C.c_uint64, dp, C.POINTER(u64), dp]
     lib.bchmc_chain_forward.argtypes = [vp, C.c_int]
+    lib.bchmc_probe_displacement.argtypes = [vp, dp, C.c_int, C.c_int]
     lib.bchmc_philox_kat.argtypes = [C.POINTER(C.c_uint32)] * 3
     lib.bchmc_kinetic_term.argtypes = [vp, dp, dp]
     lib.bchmc_psi.argtypes = [vp, dp, dp]
@@ -339,6 +341,16 @@ class Engine:
 
     def forward(self, q, rsd=-1):
         self._chk(self.lib.bchmc_forward(self.h, _p(self._in(q)), int(rsd)))
+
+    def probe_displacement(self, psi, rsd, with_force=False):
+        """Tests, diagnostics: the particle stage of the forward model (binning, mass assignment, sum of rho) from a
+        displacement given in real space, ``psi[3, N]`` = (x, y, z), instead of from a field; with ``with_force`` also
+        the likelihood force up to V (needs the inputs uploaded).  ``fetch("posx" / "rho" / "deltaX" / "part_like" /
+        "Vx" ...)`` afterwards, like after ``forward``."""
+        psi = np.ascontiguousarray(psi, dtype=np.float64).reshape(-1)
+        if psi.size != 3 * self.N:
+            raise ValueError("psi must hold 3 N = %d values, got %d" % (3 * self.N, psi.size))
+        self._chk(self.lib.bchmc_probe_displacement(self.h, _p(psi), int(rsd), int(bool(with_force))))
 
     # ---- device-resident entry points (torch tensors on the engine's device, float64, contiguous) ----
     @staticmethod

@@ -304,6 +304,24 @@ int bchmc_philox_kat(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[
  * reserved (0), unrolled 81-cell kernels in use, ALPT planes pipeline available }. */
 int bchmc_tile_info(bchmc_handle *h, int32_t out[8]);
 
+/* Diagnostic (tests, diagnostics): the particle stage of the forward model from a displacement given in real space
+ * instead of from a field.  psi: 3 N host doubles, the x, y and z components one after the other; particle i starts at
+ * the centre of lattice cell i and is displaced by (psi[i], psi[N + i], psi[2 N + i]) (particle_pos, Lag2Eul.cc), so a
+ * test can put every particle at a place of its choice.  psi is converted to the handle's field type and then takes
+ * exactly the path a forward model takes after the C2R of its displacement, with the handle's state as it is: tile
+ * binning into the record slots, the two-pass sort and the sub-cell ordering after an overflow, mass assignment (every
+ * masskernel, tiles or not, deterministic or not), sum of rho.  use_rsd as in bchmc_forward.
+ * with_force != 0: then the likelihood force of that density from the uploaded nobs / noise / window (all inputs must
+ * have been uploaded as for bchmc_gradient: BCHMC_ERR_STATE otherwise; GRF likelihood: BCHMC_ERR_UNSUPPORTED) up to,
+ * and excluding, the transform to k-space that ends it: partial_f_delta_x_log_like and, for calc_h 0 / 2 / 3, V.
+ * Ends like bchmc_forward: synchronises and adapts the binning's record slots; a pending proposal and the chain's
+ * carried gradient / -log L are dropped; the chain state and the momenta are untouched.  Afterwards bchmc_fetch gives
+ * POS*, PSI*, RHO, DELTAX and, after with_force, PART_LIKE and V* of this evaluation.
+ * Not reachable through it: the fused z pass + binning of interior trajectory steps at 128^3 and above (k_zbin_direct),
+ * which takes Psi^ from k-space; its binning half is the code of k_bin_direct, which this entry does reach.
+ * (Added within ABI version 4: no struct or existing entry point changed.) */
+int bchmc_probe_displacement(bchmc_handle *h, const double *psi, int use_rsd, int with_force);
+
 /* ---- measurement hooks (bench.py): per-kernel-class HIP-event timing on the engine's stream ---- */
 enum {
   BCHMC_K_FFT_C2R = 0, BCHMC_K_FFT_R2C, BCHMC_K_KSPACE_DRIFT_ZA, BCHMC_K_SCATTER, BCHMC_K_MEAN_PARTIAL,
