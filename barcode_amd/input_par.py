@@ -6,6 +6,8 @@ white-space character is removed from a line first, lines that are empty or star
 ``std::stringstream >> std::boolalpha >> value``.  ``hamil_params`` reads the keys of the leapfrog path as
 ``INIT_PARAMS`` does (``barlib/src/init_par.cc:52-186, 293-334``).
 """
+import numpy as np
+
 from .params import HamilParams
 
 
@@ -68,8 +70,32 @@ def _leading_float(text):
     return best
 
 
+def growth_integral(a, OM, OL, nodes=64):
+    """``I(z) = int_z^inf (1 + z') / E(z')^3 dz'`` at ``z = 1/a - 1`` (``growth_var``, cosmo.cc:68-82, integrated by
+    ``D_growth``, cosmo.cc:124-176).  With ``z' = 1/a' - 1`` the integral is ``int_0^a da' / (a' E(a'))^3`` and
+    ``(a' E)^2 = OM / a' + OK + OL a'^2``; ``a' = t^2`` removes the square root at the origin and leaves the smooth
+    ``int_0^sqrt(a) 2 t^4 / (OM + OK t^2 + OL t^6)^(3/2) dt``, done with one Gauss-Legendre rule."""
+    OK = 1.0 - OM - OL
+    x, w = np.polynomial.legendre.leggauss(nodes)
+    top = np.sqrt(a)
+    t = 0.5 * top * (x + 1.0)
+    f = 2.0 * t ** 4 / (OM + OK * t ** 2 + OL * t ** 6) ** 1.5
+    return float(0.5 * top * np.dot(w, f))
+
+
+def growth_factor(a, OM, OL):
+    """``D1 = D_growth(ascale)`` of init_par.cc:519-528: ``E(a) I(z) / I(0)`` (cosmo.cc:124-176), 1 at ``a = 1`` for
+    any cosmology and ``a`` for Einstein-de Sitter.  Pinned to the integral, not to a GSL build: the reference
+    integrates with ``gsl_integration_qagiu`` at ``epsrel = 1e-8``, so the ``D1`` a reference run prints can differ
+    from this one at the 1e-8 level."""
+    E = np.sqrt(OM / a ** 3 + (1.0 - OM - OL) / a ** 2 + OL)
+    return float(E * growth_integral(a, OM, OL) / growth_integral(1.0, OM, OL))
+
+
 def hamil_params(filename, **overrides):
-    """HamilParams from an ``input.par`` (keys and meaning: init_par.cc:52-186, 293-334; cubic grid: Nx, Lx only)."""
+    """HamilParams from an ``input.par`` (keys and meaning: init_par.cc:52-186, 293-334; cubic grid: Nx, Lx only).
+    ``ascale = 1 / (1 + z)`` (init_par.cc:143) and, unless overridden, ``D1 = D_growth(ascale, OM, OL)``
+    (``growth_factor``); ``D2 = -3/7 D1^2 Omega(a)^(-1/143)`` is then derived from that ``D1`` by ``HamilParams``."""
     p = parameter_inifile(filename)
     kw = dict(
         Nx=p.find(int, "Nx"), L=p.find(float, "Lx"),
@@ -89,6 +115,9 @@ def hamil_params(filename, **overrides):
         ascale=1.0 / (1.0 + p.find(float, "z")),
     )
     kw.update(overrides)
+    if "D1" not in kw:
+        defaults = HamilParams.__dataclass_fields__
+        kw["D1"] = growth_factor(kw["ascale"], kw.get("OM", defaults["OM"].default), kw.get("OL", defaults["OL"].default))
     return HamilParams(**kw)
 
 

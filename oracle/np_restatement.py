@@ -145,16 +145,17 @@ class NpHamil:
         p = self.p
         w, nobs, s = self.window, self.nobs, self.noise
         if p.likelihood == 1:
-            lam = w * p.rho_c * (1 + p.biasP * dX) ** p.biasE
+            with np.errstate(invalid="ignore"):  # negative base, fractional biasE: NaN fails lam > 0, as in C
+                lam = w * p.rho_c * (1 + p.biasP * dX) ** p.biasE
             return np.where((w > 0) & (lam > 0), (nobs - lam) / (s * s), 0.0)
         if p.likelihood == 0:
             dens = 1 + p.biasP * dX
-            lam = w * p.rho_c * dens ** p.biasE
             with np.errstate(divide="ignore", invalid="ignore"):
+                lam = w * p.rho_c * dens ** p.biasE
                 v = (1 - nobs / lam) * p.rho_c * p.biasE * p.biasP * dens ** (p.biasE - 1)
             return np.where((w > 0) & (dens > 0), v, 0.0)
         if p.likelihood == 2:
-            with np.errstate(divide="ignore"):
+            with np.errstate(divide="ignore", invalid="ignore"):
                 lam = np.log(p.rho_c * (1 + p.biasP * dX) ** p.biasE)
             return np.where(w > 0, (nobs - lam) / (s * s), 0.0)
         raise ValueError
@@ -193,6 +194,41 @@ class NpHamil:
             V[2] = V[2] + (p.OM / (E * E * p.ascale ** 3)) ** (5.0 / 9.0) * V[2]
         return [v.reshape(self.shape) for v in V]
 
+    # interpolate_grid.cpp:134-191 -- bug-for-bug: the "+1" weights of x and y are built from dz (lines 166-168)
+    def interpolate_tsc(self, pos, field):
+        n, d = self.n, self.d
+        xk, yk, zk = (a.ravel() / d for a in pos)
+        c = [a.astype(np.int64) for a in (xk, yk, zk)]
+        dx, dy, dz = (a - (ci + 0.5) for a, ci in zip((xk, yk, zk), c))
+        up = 0.5 * (1.5 - np.abs(dz - 1)) ** 2
+        w = [[0.5 * (1.5 - np.abs(dd + 1)) ** 2, 0.75 - dd * dd, up] for dd in (dx, dy, dz)]
+        idx = [[(ci - 1 + n) % n, ci, (ci + 1) % n] for ci in c]
+        out = np.zeros(self.N)
+        f = field.ravel()
+        for i in range(3):
+            for j in range(3):
+                for k in range(3):
+                    out += w[0][i] * w[1][j] * w[2][k] * f[(idx[0][i] * n + idx[1][j]) * n + idx[2][k]]
+        return out
+
+    # HMC_models_testing.cpp:54-188 (calc_h = 3): V from the Fourier transform of the SPH kernel (its argument is k,
+    # not k h, as upstream), interpolated to the particles with the TSC weights above
+    def calc_V_fourier_tsc(self, part_like, pos, rsd):
+        p = self.p
+        h = p.particle_kernel_h
+        norm = 24.0 / h ** 3 * (p.rho_c * self.L ** 3 / self.N)
+        ksq = self.ksq
+        kk = np.sqrt(ksq)
+        ksink = kk * np.sin(kk)
+        K = np.full(ksq.shape, 1.0 / h ** 3)
+        np.divide(norm * (3 + np.cos(2 * kk) - ksink + np.cos(kk) * (ksink - 4)), ksq ** 3, out=K, where=ksq != 0)
+        base = 1j * h * self.r2c(part_like) * K
+        V = [self.interpolate_tsc(pos, self.c2r(base * k)) for k in (self.kx, self.ky, self.kz)]
+        if rsd:
+            E = np.sqrt(p.OM / p.ascale ** 3 + (1 - p.OM - p.OL) / p.ascale ** 2 + p.OL)
+            V[2] = V[2] + (p.OM / (E * E * p.ascale ** 3)) ** (5.0 / 9.0) * V[2]
+        return [v.reshape(self.shape) for v in V]
+
     # HMC_models.cc:312-372 + gradient.cpp:157-211
     def calc_h(self, V):
         inv = np.zeros_like(self.ksq)
@@ -223,8 +259,13 @@ class NpHamil:
         self.deltaX, self.pos = dX, pos
         if p.calc_h == 0:
             hfield = self.calc_h_legacy(dX)
-        else:
+        elif p.calc_h == 2:
             hfield = self.calc_h(self.calc_V(self.partial_f(dX), pos, rsd))
+        elif p.calc_h == 3:
+            hfield = self.calc_h(self.calc_V_fourier_tsc(self.partial_f(dX), pos, rsd))
+        else:
+            # calc_h = 1 (h = partial_f, HMC_models.cc:413-415) and other mass kernels exist in the C oracle only
+            raise NotImplementedError("NpHamil restates calc_h 0, 2 and 3 only (got %d)" % p.calc_h)
         norm = -1.0 * p.deltaQ_factor * (p.D1 if p.correct_delta else 1.0)
         return norm * hfield
 
@@ -257,11 +298,13 @@ class NpHamil:
         w, nobs, s = self.window, self.nobs, self.noise
         if p.likelihood == 1:
             dX, _ = self.lag2eul(p.deltaQ_factor * q, bool(p.rsd_model))
-            lam = w * p.rho_c * (1 + p.biasP * dX) ** p.biasE
+            with np.errstate(invalid="ignore"):
+                lam = w * p.rho_c * (1 + p.biasP * dX) ** p.biasE
             return float(np.sum(np.where((w > 0) & (lam > 0), 0.5 * ((lam - nobs) / s) ** 2, 0.0)))
         if p.likelihood == 0:
             dX, _ = self.lag2eul(q, False)
-            lam = w * p.rho_c * (1 + p.biasP * dX) ** p.biasE
+            with np.errstate(invalid="ignore"):
+                lam = w * p.rho_c * (1 + p.biasP * dX) ** p.biasE
             with np.errstate(divide="ignore", invalid="ignore"):
                 return float(np.sum(np.where((w > 0) & (lam > 0), lam - nobs * np.log(lam), 0.0)))
         if p.likelihood == 2:

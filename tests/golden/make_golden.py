@@ -20,6 +20,7 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
 
+from tests.offdefault import OFF, OFF_LN  # noqa: E402
 from tests.util import Case  # noqa: E402
 
 CASES = {
@@ -35,6 +36,12 @@ CASES = {
     "poisson_calch3_8": dict(Nx=8, likelihood=0, rsd_model=0, calc_h=3),
     "poisson_ngp_calch1_8": dict(Nx=8, likelihood=0, rsd_model=0, calc_h=1, mk=0),
     "gauss_tsc_calch1_rsd_8": dict(Nx=8, likelihood=1, rsd_model=1, calc_h=1, mk=2),
+    # every cosmology and observational scalar off its default (tests/offdefault.py).  Step sizes probed at 8^3 for the
+    # ten steps as tests/util.Case describes: amplification 29, 26 (1.2e10 at the default 0.03), 0.25 and 10.
+    "gauss_rsd_off_8": dict(Nx=8, likelihood=1, rsd_model=1, **OFF),
+    "poisson_off_8": dict(Nx=8, likelihood=0, rsd_model=0, eps_scale=0.01, **OFF),
+    "lognormal_off_8": dict(Nx=8, likelihood=2, rsd_model=0, **OFF_LN),
+    "gauss_alpt_off_8": dict(Nx=8, likelihood=1, rsd_model=0, sfmodel=2, **OFF),
 }
 NEPS = 10
 

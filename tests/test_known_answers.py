@@ -30,6 +30,13 @@ K3  SPH-kernel gradient gather for a single excited cell (``likelihood_calc_V_SP
     The engine is driven to this state through its data arrays: Gaussian likelihood, window = sigma = 1, rho_c = 1,
     undisplaced lattice (q = 0 => delta_x = 0 => Lambda = 1), so part_like = (nobs - Lambda) / sigma^2 = nobs - 1
     (gaussian_independent.cpp:24-42): nobs = 1 everywhere, 2 in c0.
+
+The same three with the scalars in them (tests/offdefault.OFF: nothing at 0, 1 or its default), at the end of the file:
+K2 at D1 != 1 keeps its form, Psi_x = -(D1 A / k0) sin(k0 x); for a wave along z with RSD the particle of cell k sits at
+    z = pacman(pacman(z0 + Psi_z) + (c_pecvel Psi_z) / (Hub a)),   c_pecvel = f 100 E a,  Hub = 100 E,  f = Omega^(5/9),
+    E^2 = OM / a^3 + (1 - OM - OL) / a^2 + OL,  Omega = OM / (E^2 a^3)   (cosmo.cc:26-31, 182-235, rsd.cc:26-68);
+K3 at rho_c != 1 has m = rho_c d^3: V = rho_c f(q) (i, j, k) / (pi d), and V_z (1 + f1) under RSD (HMC_models.cc:289-296).
+    The engine reaches part_like = 1 in c0 with Lambda = rho_c (delta_x = 0: the bias drops out): nobs = rho_c, rho_c + 1 in c0.
 """
 import itertools
 
@@ -195,5 +202,118 @@ def test_k3_engine_gradient_gather_of_one_excited_cell():
     scale = 0.75 / (np.pi * D)
     for name, want in zip(("Vx", "Vy", "Vz"), exp):
         # part_like is 1 + O(1e-16) in c0 and O(1e-16) elsewhere (delta_x = 0 to rounding): same bound
+        assert np.max(np.abs(e.fetch(name).reshape(N, N, N) - want)) < 1e-13 * scale
+    e.close()
+
+
+# ---- K2 and K3 with the scalars off their defaults ----------------------------------------------------------------
+from tests.offdefault import OFF  # noqa: E402
+
+
+def rsd_factors(s):
+    a, OM, OL = s["ascale"], s["OM"], s["OL"]
+    E = np.sqrt(OM / a ** 3 + (1 - OM - OL) / a ** 2 + OL)
+    f = (OM / (E * E * a ** 3)) ** (5.0 / 9.0)
+    return f, f * 100.0 * E * a, 100.0 * E          # f1, c_pecvel, Hub
+
+
+def fold(x):
+    return np.where(x < 0, x + L, np.where(x >= L, x - L, x))
+
+
+def plane_wave_along(axis, m, A, D1):
+    k0 = 2 * np.pi * m / L
+    x = np.arange(N) * D
+    shape = [1, 1, 1]
+    shape[axis] = N
+    delta = np.broadcast_to((A * np.cos(k0 * x)).reshape(shape), (N, N, N)).copy()
+    psi = np.broadcast_to((-(D1 * A / k0) * np.sin(k0 * x)).reshape(shape), (N, N, N)).copy()
+    return delta, psi
+
+
+def k2_off_expected(m, rsd):
+    """(delta, axis, Psi along the axis, position along the axis) for a wave along x (no RSD) or along z (RSD)."""
+    axis = 2 if rsd else 0
+    delta, psi = plane_wave_along(axis, m, 0.3, OFF["D1"])
+    shape = [1, 1, 1]
+    shape[axis] = N
+    pos = fold(((np.arange(N) + 0.5) * D).reshape(shape) + psi)
+    if rsd:
+        f1, cpec, hub = rsd_factors(OFF)
+        pos = fold(pos + (cpec * psi) * (1.0 / hub / OFF["ascale"]))
+    return delta, axis, psi, pos
+
+
+@pytest.mark.parametrize("rsd", [0, 1], ids=["x", "z_rsd"])
+@pytest.mark.parametrize("m", [1, 3, 7])
+def test_k2_oracle_plane_wave_displacement_off_default(m, rsd):
+    p = params(**OFF)
+    o = Oracle(p)
+    delta, axis, psi, pos = k2_off_expected(m, rsd)
+    v = o.theta2vel(-p.D1 * delta)
+    scale = np.abs(psi).max()
+    assert scale == pytest.approx(OFF["D1"] * 0.3 * L / (2 * np.pi * m), rel=0.05)   # D1 is in it
+    for a in range(3):
+        want = psi if a == axis else 0.0
+        assert np.max(np.abs(v[a].reshape(N, N, N) - want)) < 1e-13 * scale
+    got = o.Lag2Eul(delta, rsd=rsd)[1 + axis]
+    assert np.max(np.abs(got.reshape(N, N, N) - pos)) < 1e-12
+    o.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("rsd", [0, 1], ids=["x", "z_rsd"])
+@pytest.mark.parametrize("m", [1, 3, 7])
+def test_k2_engine_plane_wave_displacement_off_default(m, rsd):
+    from barcode_amd.engine import Engine
+    e = Engine(params(**OFF))
+    one = np.ones(N ** 3)
+    e.upload(signal_PS=one, mass_f=one, nobs=one, noise=one, window=one)
+    delta, axis, psi, pos = k2_off_expected(m, rsd)
+    e.forward(delta, rsd)
+    scale = np.abs(psi).max()
+    for a, name in enumerate(("psix", "psiy", "psiz")):
+        want = psi if a == axis else 0.0
+        assert np.max(np.abs(e.fetch(name).reshape(N, N, N) - want)) < 1e-13 * scale
+    assert np.max(np.abs(e.fetch(("posx", "posy", "posz")[axis]).reshape(N, N, N) - pos)) < 1e-12
+    e.close()
+
+
+@pytest.mark.parametrize("rsd", [0, 1], ids=["real", "rsd"])
+def test_k3_oracle_gradient_gather_off_default(rsd):
+    o = Oracle(HamilParams(Nx=N, L=L, likelihood=1, rsd_model=rsd, sfmodel=1, **OFF))
+    c0 = (0, 7, 15)
+    plike = np.zeros((N, N, N))
+    plike[c0] = 1.0
+    V = o.likelihood_calc_V_SPH(plike, *lattice())
+    exp = OFF["rho_c"] * k3_expected(c0)
+    exp[2] *= 1 + rsd * rsd_factors(OFF)[0]
+    scale = OFF["rho_c"] * 0.75 / (np.pi * D)
+    for got, want in zip(V, exp):
+        assert np.max(np.abs(got.reshape(N, N, N) - want)) < 1e-14 * scale
+    assert V[0].reshape(N, N, N)[1, 7, 15] == pytest.approx(-scale, rel=1e-15)
+    assert V[2].reshape(N, N, N)[0, 7, 0] == pytest.approx(-scale * (1 + rsd * rsd_factors(OFF)[0]), rel=1e-15)
+    o.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("rsd", [0, 1], ids=["real", "rsd"])
+def test_k3_engine_gradient_gather_off_default(rsd):
+    from barcode_amd.engine import Engine
+    e = Engine(HamilParams(Nx=N, L=L, likelihood=1, rsd_model=rsd, sfmodel=1, **OFF))
+    one = np.ones(N ** 3)
+    c0 = (0, 7, 15)
+    nobs = np.full((N, N, N), OFF["rho_c"])
+    nobs[c0] = OFF["rho_c"] + 1.0
+    e.upload(signal_PS=one, mass_f=one, nobs=nobs, noise=one, window=one)
+    e.gradient(np.zeros(N ** 3))
+    plike = e.fetch("part_like").reshape(N, N, N)
+    exp_pl = np.zeros((N, N, N))
+    exp_pl[c0] = 1.0
+    assert np.max(np.abs(plike - exp_pl)) < 1e-14
+    exp = OFF["rho_c"] * k3_expected(c0)
+    exp[2] *= 1 + rsd * rsd_factors(OFF)[0]
+    scale = OFF["rho_c"] * 0.75 / (np.pi * D)
+    for name, want in zip(("Vx", "Vy", "Vz"), exp):
         assert np.max(np.abs(e.fetch(name).reshape(N, N, N) - want)) < 1e-13 * scale
     e.close()
