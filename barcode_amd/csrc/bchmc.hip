@@ -10,6 +10,7 @@
 #include "../../include/bchmc.h"
 #include "kernels.hpp"
 #include "fft_host.hpp"
+#include "owned.hpp"
 
 #include <rocfft/rocfft.h>
 #include <rocprofiler-sdk-roctx/roctx.h>
@@ -29,15 +30,13 @@
 #include <vector>
 
 using namespace bchmc;
+using namespace owned;
 
 namespace {
 
-std::mutex g_rocfft_mu;
-int g_rocfft_users = 0;
-
 struct ProfRec {
   int cls;
-  hipEvent_t a, b;
+  Event a, b;
 };
 
 }  // namespace
@@ -48,87 +47,87 @@ struct bchmc_handle {
   bool f32 = false;   // storage type of the field arrays
   size_t esz = 8;     // sizeof(T)
   int mass_fs = 0, mass_rs = 0;
-  hipStream_t stream = nullptr;
   std::string err;
+  // Every resource below is an owner of owned.hpp, and bchmc_destroy only deletes the handle: members are destroyed
+  // in reverse declaration order, and three things depend on that order.  The stream is declared before every buffer
+  // and event, so it outlives them; the rocFFT user before the stream, so rocfft_cleanup runs after the stream is
+  // gone; the work buffer before the execution info and the plans that point at it, so they go first.
+  RocfftUser fft_user;
+  Stream stream;
 
   // rocFFT
-  rocfft_plan r2c1 = nullptr, c2r1 = nullptr, r2c3 = nullptr, c2r3 = nullptr;
-  rocfft_execution_info info = nullptr;
-  void *work = nullptr;
-  size_t work_bytes = 0;
+  DevBytes work;  // shared by all plans; its capacity is what info was told
+  FftInfo info;
+  FftPlan r2c1, c2r1, r2c3, c2r3;
 
   // inputs (N elements of T each) + derived half-layout multipliers (always double)
-  void *in_arr[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  DevBytes in_arr[6];
   bool have[6] = {false, false, false, false, false, false};
-  double *wS = nullptr, *wM = nullptr;  // normFS / signal_PS, normFS / mass_f on the half-complex layout
+  DevBuf<double> wS, wM;  // normFS / signal_PS, normFS / mass_f on the half-complex layout
 
   // state and scratch (T / C2<T>)
-  void *qk = nullptr, *pk = nullptr, *gk = nullptr;  // Nhp complex each
-  void *qk2 = nullptr, *pk2 = nullptr;               // ping-pong partners of (qk, pk) for the fused step boundary
-  void *Ck = nullptr;                                // 3 Nhp: Psi^ / V^
-  void *tC = nullptr;                                // Nhp scratch
-  void *psi = nullptr;                               // 3 N: displacement components
-  void *V = nullptr;                                 // 3 N: V components
-  void *rho = nullptr, *plike = nullptr;             // N each
-  long long *rho_fix = nullptr;                      // N: fixed-point density (deterministic mode only)
-  int *fix_sat = nullptr;                            // 1: set by k_fix_to_rho when a fixed-point cell came near wrapping
+  DevBytes qk, pk, gk;                               // Nhp complex each
+  DevBytes qk2, pk2;                                 // ping-pong partners of (qk, pk) for the fused step boundary
+  DevBytes Ck;                                       // 3 Nhp: Psi^ / V^
+  DevBytes tC;                                       // Nhp scratch
+  DevBytes psi;                                      // 3 N: displacement components
+  DevBytes V;                                        // 3 N: V components
+  DevBytes rho, plike;                               // N each
+  DevBuf<long long> rho_fix;                         // N: fixed-point density (deterministic mode only)
+  DevBuf<int> fix_sat;                               // 1: set by k_fix_to_rho when a fixed-point cell came near wrapping
   long long fix_sat_limit = 1ll << 62;               // (BCHMC_FIX_SAT_LOG2 lowers it: test hook for the error path)
   bool fix = false;                                  // deterministic mode
-  void *ioq = nullptr, *iop = nullptr;               // N each: staging / scratch
-  void *gprior = nullptr, *glike = nullptr;          // N each, lazily allocated by bchmc_gradient
-  void *conv = nullptr;                              // 3 N, lazily allocated for calc_h 0 / 3
-  double *convF = nullptr;                           // Nhp: SPH kernel transform table for calc_h = 3
-  double *dstage = nullptr;                          // 2 N doubles: ABI <-> T conversion staging
+  DevBytes ioq, iop;                                 // N each: staging / scratch
+  DevBytes gprior, glike;                            // N each, lazily allocated by bchmc_gradient
+  DevBytes conv;                                     // 3 N, lazily allocated for calc_h 0 / 3
+  DevBuf<double> convF;                              // Nhp: SPH kernel transform table for calc_h = 3
+  DevBuf<double> dstage;                             // 2 N doubles: ABI <-> T conversion staging
   // device-resident chain: current sample and momenta in k-space, energy partials
-  void *cq = nullptr, *cp = nullptr;                 // Nhp complex each
-  double *part6 = nullptr;                           // 6 * kRedBlocks doubles
+  DevBytes cq, cp;                                   // Nhp complex each
+  DevBuf<double> part6;                              // 6 * kRedBlocks doubles
   bool have_cq = false, have_cp = false, have_prop = false;
   // Force carried along the chain: g^ = FFT-space gradient_psi at the chain state cq, with its -log L.  The end of an
   // accepted trajectory (or the start of a rejected one) IS the next trajectory's start, so the gradient HMC.cc:279
   // evaluates there is already known; only the fast attempt mode uses it.  Any new input or state invalidates it.
-  void *cg = nullptr;
+  DevBytes cg;
   bool cg_valid = false, prop_g_valid = false;
   double c_like = 0., prop_like = 0.;
-  double *rho_part = nullptr, *partA = nullptr;      // kRedBlocks doubles each
-  double *guard = nullptr;                           // guard slots, one per step
-  size_t guard_cap = 0;
-  int *stop = nullptr;
-  unsigned long long *steps_done = nullptr;
-  double *h_part = nullptr;                          // pinned host staging for partials
+  DevBuf<double> rho_part, partA;                    // kRedBlocks doubles each
+  DevBuf<double> guard;                              // guard slots, one per step
+  DevBuf<int> stop;
+  DevBuf<unsigned long long> steps_done;
+  PinnedBuf<double> h_part;                          // pinned host staging for partials
   // draw_momenta from a GSL mt19937 state (mt_draw.hpp), set up on the first such draw: S words per segment, B
   // segments, C = B S words per pass, G Gaussians per draw
   struct MtDraw {
     long long S = 0, C = 0, G = 0;
     int B = 0;
-    uint32_t *poly = nullptr, *win = nullptr, *words = nullptr, *st = nullptr;
-    unsigned long long *nz = nullptr, *nzoff = nullptr, *acc = nullptr, *accoff = nullptr, *lastend = nullptr;
-    unsigned long long *res = nullptr;  // 8 counters + the 624-word end state
-    unsigned long long *h_io = nullptr; // pinned mirror of res (the input window goes out through its state words)
-    double *gauss = nullptr;
-    long long gauss_cap = 0;            // doubles allocated for gauss (grown by mt_reserve outside trajectories)
+    DevBuf<uint32_t> poly, win, words, st;
+    DevBuf<unsigned long long> nz, nzoff, acc, accoff, lastend;
+    DevBuf<unsigned long long> res;      // 8 counters + the 624-word end state
+    PinnedBuf<unsigned long long> h_io;  // pinned mirror of res (the input window goes out through its state words)
+    DevBuf<double> gauss;                // grown by mt_reserve outside trajectories
     double setup_ms = 0.;
   } mt;
   // setup_random_test (mock.hpp): windowed cells per tile, their scan, {windowed cells, first noise == 0 index}
   struct Mock {
-    unsigned long long *cnt = nullptr, *off = nullptr, *gsum = nullptr, *goff = nullptr, *res = nullptr;
+    DevBuf<unsigned long long> cnt, off, gsum, goff, res;
   } mock;
-  double *spec_bins = nullptr;                       // measure_spectrum's 3 * n_bin accumulators
-  size_t spec_cap = 0;
+  DevBuf<double> spec_bins;                          // measure_spectrum's 3 * n_bin accumulators
   // measure_corr / measure_corr2d (corr.hpp): accumulators and the geometry of the last n_bin of each function, kept in
   // the handle like spec_bins (the driver measures after every sample with the same n_bin)
   struct Corr1 {
     uint64_t n_bin = 0;                // the geometry below is this bin count's (0: none yet)
-    unsigned long long *acc = nullptr; // 5 n_bin + 1: { A limbs [2][n_bin], scale, rtot limbs [2][n_bin], counts }
-    size_t cap = 0;
+    DevBuf<unsigned long long> acc;    // 5 n_bin + 1: { A limbs [2][n_bin], scale, rtot limbs [2][n_bin], counts }
     std::vector<double> rmode;
     std::vector<uint64_t> nmode;
   } corr1;
   struct Corr2 {
     uint64_t n_bin = 0;
-    int *idx = nullptr;        // rows sorted by perp bin | par_start [npb + 1] | perp_slice [n_bin + 1]
-    int2 *slices = nullptr;    // nsl: { first row, rows }
-    double *part = nullptr;    // nsl * npb
-    double *out = nullptr;     // [2][n_bin * npb]: rtot sums, A sums
+    DevBuf<int> idx;           // rows sorted by perp bin | par_start [npb + 1] | perp_slice [n_bin + 1]
+    DevBuf<int2> slices;       // nsl: { first row, rows }
+    DevBuf<double> part;       // nsl * npb
+    DevBuf<double> out;        // [2][n_bin * npb]: rtot sums, A sums
     int nrows = 0, nsl = 0, npb = 0, max_rows = 0;
     std::vector<uint64_t> row_cnt, par_cnt;  // rows of a perp bin, cells along z of a populated par bin
     std::vector<int> par_bin;                // nbin_par of populated par bin c
@@ -136,20 +135,20 @@ struct bchmc_handle {
   } corr2;
   // host-array entry points: caller arrays are pageable, so they cross PCIe through two pinned staging chunks
   // (N-thread memcpy into one chunk while the DMA of the other is in flight)
-  void *stg[2] = {nullptr, nullptr};
-  hipEvent_t stg_ev[2] = {nullptr, nullptr};
+  PinnedBuf<void> stg[2];
+  Event stg_ev[2];
   size_t stg_chunk = 0;
   int stg_threads = 1;
-  hipStream_t copy_stream = nullptr;  // transfers that run beside compute (host-array trajectories: the momenta on their
+  Stream copy_stream;                 // transfers that run beside compute (host-array trajectories: the momenta on their
                                       // way in beside the start-state force, the final q on its way out beside the last one)
   // Early download of a host-array trajectory's q1: the last step only kicks p, so the final q exists one force
   // evaluation before the trajectory ends.  Armed by the host entry points (early_q_dev = where its real-space copy
   // goes); trajectory_fused transforms it there before the last force evaluation and records ev_q; early_q_done says so.
   double *early_q_dev = nullptr;
   bool early_q_done = false;
-  hipEvent_t ev_q = nullptr;
+  Event ev_q;
 
-  int4 *hull = nullptr;
+  DevBuf<int4> hull;
   int hull_n = 0;
   int reach = 0;
   int hull_maxlen = 0;      // longest k-range of a hull column
@@ -157,23 +156,23 @@ struct bchmc_handle {
   // tile-sorted particle-mesh path
   bool tiled = false;
   // "planes" mode of the interior step boundary: 2-D (y, z) transforms by rocFFT, x passes inside k_step_boundary_x
-  rocfft_plan r2c2d = nullptr, c2r2d = nullptr;  // batch 3 n planes
-  void *xtw = nullptr;                           // n / 2 twiddles exp(-2 pi i r / n), C2<T>
+  FftPlan r2c2d, c2r2d;                          // batch 3 n planes
+  DevBytes xtw;                                  // n / 2 twiddles exp(-2 pi i r / n), C2<T>
   int log2n = 0;
   bool planes_ok = false;                        // plans + kernel available for this grid
   bool sort_direct = false;  // one-pass tile binning into fixed slots (two-pass sort as overflow fallback)
-  rocfft_plan r2c2d_2 = nullptr, c2r2d_2 = nullptr;  // 2-D plans over 2 n planes: delta(1) | Phi and A | B of the ALPT model
+  FftPlan r2c2d_2, c2r2d_2;  // 2-D plans over 2 n planes: delta(1) | Phi and A | B of the ALPT model
   bool alpt_plans_failed = false;
   double alpt_wtot = 0.;     // kernelcomp's normalisation (sum of the real-space kernel), computed on first use
   bool std81 = false;  // standard 81-cell hull on 8 x 8 x 16 tiles with halo 2: fully unrolled scatter/gather kernels
   TilePar tp{};
-  int *t_cnt = nullptr, *t_woff = nullptr;   // 9 ntiles + 2 (one-pass counts per (tile, octant), fallback counts per tile,
+  DevBuf<int> t_cnt, t_woff;                 // 9 ntiles + 2 (one-pass counts per (tile, octant), fallback counts per tile,
                                              // overflow flags), ntiles + 1
-  int4 *t_oct = nullptr;                     // 2 ntiles: octant segment starts of every tile (k_scan_tiles)
-  int *t_seg = nullptr;                      // 1: slots per octant segment of the current sort, 0 = contiguous records
-  long long *t_off = nullptr, *t_end = nullptr;  // ntiles each: record range of every tile (ntiles * cap can pass 2^31)
-  int2 *t_rank = nullptr;                                      // N
-  void *srec = nullptr;  // tile-sorted particle records { x, y, z, original index | flags }: 4 * sizeof(T) bytes each
+  DevBuf<int4> t_oct;                        // 2 ntiles: octant segment starts of every tile (k_scan_tiles)
+  DevBuf<int> t_seg;                         // 1: slots per octant segment of the current sort, 0 = contiguous records
+  DevBuf<long long> t_off, t_end;                // ntiles each: record range of every tile (ntiles * cap can pass 2^31)
+  DevBuf<int2> t_rank;                                         // N
+  DevBytes srec;         // tile-sorted particle records { x, y, z, original index | flags }: 4 * sizeof(T) bytes each
   bool sorted_valid = false;
   long long cap_alloc = 0;  // record slots per tile the array srec was allocated for; tp.cap <= cap_alloc is the part in use
   long long cap_wanted = 0; // > cap_alloc: what the next synchronising call should reallocate to (0 = nothing pending)
@@ -181,8 +180,8 @@ struct bchmc_handle {
   long long cap_budget = 0; // most record slots per tile the array may ever be reallocated for (a quarter of the device)
   bool slot_watch = true;   // the populations seen last were close to the segment size (or unknown yet): a long
                             // trajectory polls the binning's flag every few steps instead of only at its end
-  int *h_slots = nullptr;   // pinned: two snapshots of {sticky overflow stamp, largest population} for those polls
-  hipEvent_t slot_ev[2] = {nullptr, nullptr};
+  PinnedBuf<int> h_slots;   // pinned: two snapshots of {sticky overflow stamp, largest population} for those polls
+  Event slot_ev[2];
   bool cnt_clean = false;   // t_cnt[0 .. 2 ntiles] was cleared by the last k_scatter_tile81 (no fill launch needed)
   bool have_eval = false;  // rho / psi hold a forward evaluation
   int last_rsd = 0;
@@ -190,7 +189,7 @@ struct bchmc_handle {
   // profiling
   bool prof_on = false;
   std::vector<ProfRec> prof_recs;
-  std::vector<hipEvent_t> ev_pool;
+  std::vector<Event> ev_pool;
   double prof_ms[BCHMC_K_COUNT] = {0};
   uint64_t prof_n[BCHMC_K_COUNT] = {0};
 
@@ -223,17 +222,20 @@ struct bchmc_handle {
 
 namespace {
 
-int dev_alloc_bytes(bchmc_handle *h, void **p, size_t bytes) {
-  hipError_t e = hipMalloc(p, bytes);
-  if (e != hipSuccess) return h->fail(BCHMC_ERR_NOMEM, "hipMalloc(%zu bytes): %s", bytes, hipGetErrorString(e));
-  // zero-fill ON THE HANDLE'S STREAM (it is non-blocking: a null-stream memset could land after the first kernels
-  // that use the buffer); row padding of the half-complex arrays must hold finite values
-  HIPCHK(hipMemsetAsync(*p, 0, bytes, h->stream));
-  return BCHMC_OK;
+// DevBuf::alloc / reserve on the handle's stream, zero-filled there (row padding of the half-complex arrays must hold
+// finite values); count is in bytes for a DevBytes
+int alloc_rc(bchmc_handle *h, hipError_t e, size_t bytes) {
+  if (e == hipSuccess) return BCHMC_OK;
+  return h->fail(e == hipErrorOutOfMemory ? BCHMC_ERR_NOMEM : BCHMC_ERR_HIP, "device buffer of %zu bytes: %s", bytes,
+                 hipGetErrorString(e));
 }
 template <typename U>
-int dev_alloc(bchmc_handle *h, U **p, size_t count) {
-  return dev_alloc_bytes(h, (void **)p, count * sizeof(U));
+int dev_alloc(bchmc_handle *h, DevBuf<U> &b, size_t count) {
+  return alloc_rc(h, b.alloc(count, h->stream), count * b.kElem);
+}
+template <typename U>
+int dev_reserve(bchmc_handle *h, DevBuf<U> &b, size_t count) {
+  return alloc_rc(h, b.reserve(count, h->stream), count * b.kElem);
 }
 
 // Debug/A-B switches: set to 1 to enable (unset or 0 = off).
@@ -254,7 +256,7 @@ struct EvalMode {             // how ONE force evaluation runs; decided by the c
 
 // Launch with `lds` bytes of dynamic LDS: above the 48 KiB every kernel may use, the kernel's own limit is raised first.
 template <typename... P, typename... A>
-int launch_lds(bchmc_handle *h, void (*kern)(P...), int grid, int threads, size_t lds, A... args) {
+int launch_lds(bchmc_handle *h, void (*kern)(P...), int grid, int threads, size_t lds, const A &...args) {
   if (lds > 48 * 1024)
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   kern<<<grid, threads, lds, h->stream>>>(args...);
@@ -287,16 +289,16 @@ struct ProfScope {
     if (!h->prof_on) return;
     ProfRec r;
     r.cls = cls;
-    for (hipEvent_t *e : {&r.a, &r.b}) {
+    for (Event *e : {&r.a, &r.b}) {
       if (!h->ev_pool.empty()) {
-        *e = h->ev_pool.back();
+        *e = std::move(h->ev_pool.back());
         h->ev_pool.pop_back();
       } else {
-        (void)hipEventCreate(e);
+        (void)e->create();
       }
     }
     (void)hipEventRecord(r.a, h->stream);
-    h->prof_recs.push_back(r);
+    h->prof_recs.push_back(std::move(r));
     idx = (int)h->prof_recs.size() - 1;
   }
   ~ProfScope() {
@@ -312,8 +314,8 @@ void prof_collect(bchmc_handle *h) {
     (void)hipEventElapsedTime(&ms, r.a, r.b);
     h->prof_ms[r.cls] += ms;
     h->prof_n[r.cls] += 1;
-    h->ev_pool.push_back(r.a);
-    h->ev_pool.push_back(r.b);
+    h->ev_pool.push_back(std::move(r.a));
+    h->ev_pool.push_back(std::move(r.b));
   }
   h->prof_recs.clear();
 }
@@ -443,6 +445,7 @@ int check_inputs(bchmc_handle *h) {
 // 1100-step trajectory whose populations doubled on the way (profiles/r03_sustained_ab.txt: 311 against 336 steps/s).
 // A partition smaller than the allocation (BCHMC_SORT_CAP) is also extended inside a trajectory, by a lagging poll
 // every few steps (poll_slots).
+RecQuad *recs(const bchmc_handle *h) { return static_cast<RecQuad *>(h->srec.get()); }  // the records, as the kernels take them
 int *slot_words(bchmc_handle *h) { return h->t_cnt + (kOct + 1) * (size_t)h->tp.ntiles + 1; }  // {sticky stamp, max}
 
 int realloc_slots(bchmc_handle *h, long long cap) {
@@ -461,12 +464,11 @@ int realloc_slots(bchmc_handle *h, long long cap) {
   }
   // The old array goes first (its contents are rebuilt by the next binning anyway): at 512^3 fp64 it is 69 GB, and the
   // new one next to it would not fit.  Never fewer than N records: the two-pass sort packs all particles.
-  (void)hipFree(h->srec);
-  h->srec = nullptr;
+  (void)h->srec.release();
   h->sorted_valid = false;
   for (long long c : {cap, h->cap_alloc, 0ll}) {
     const size_t nrec = std::max<size_t>((size_t)h->g.N, (size_t)c * h->tp.ntiles);
-    if (hipMalloc(&h->srec, nrec * 4 * h->esz) == hipSuccess) {
+    if (h->srec.alloc(nrec * 4 * h->esz) == hipSuccess) {
       if (c == cap) {
         h->cap_alloc = cap;
         if (verbose) fprintf(stderr, "bchmc: record array reallocated for %lld slots per tile\n", cap);
@@ -478,7 +480,6 @@ int realloc_slots(bchmc_handle *h, long long cap) {
       return BCHMC_OK;
     }
     (void)hipGetLastError();
-    h->srec = nullptr;
   }
   return h->fail(BCHMC_ERR_NOMEM, "no device memory for the particle records");
 }
@@ -556,8 +557,8 @@ int read_ctl(bchmc_handle *h, unsigned long long *steps_done) {
 constexpr uint64_t kSlotPoll = 4;
 int poll_slots(bchmc_handle *h, uint64_t k) {
   if (!h->h_slots) {
-    HIPCHK(hipHostMalloc((void **)&h->h_slots, 4 * sizeof(int)));
-    for (auto &e : h->slot_ev) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    HIPCHK(h->h_slots.alloc(4));
+    for (Event &e : h->slot_ev) HIPCHK(e.create(hipEventDisableTiming));
   }
   if (k >= 2) {
     const int b = (int)((k - 1) & 1);
@@ -573,7 +574,7 @@ int poll_slots(bchmc_handle *h, uint64_t k) {
 
 // Batched 2-D (y, z) real transforms over `batch` consecutive planes of the padded half-complex layout (planes mode).
 // Optional fast path: on failure both plans are left null and the batched 3-D plans carry the work.
-int make_plans_2d(bchmc_handle *h, size_t batch, rocfft_plan *r2c, rocfft_plan *c2r) {
+int make_plans_2d(bchmc_handle *h, size_t batch, FftPlan &r2c, FftPlan &c2r) {
   const Geo &g = h->g;
   const rocfft_precision prec = h->f32 ? rocfft_precision_single : rocfft_precision_double;
   const size_t len2[2] = {(size_t)g.n, (size_t)g.n};
@@ -587,41 +588,36 @@ int make_plans_2d(bchmc_handle *h, size_t batch, rocfft_plan *r2c, rocfft_plan *
   ok2 = ok2 && rocfft_plan_description_set_data_layout(i2, rocfft_array_type_hermitian_interleaved, rocfft_array_type_real,
                                                        nullptr, nullptr, 2, cs2, (size_t)g.n * g.nhp, 2, rs2,
                                                        (size_t)g.n * g.n) == rocfft_status_success;
-  ok2 = ok2 && rocfft_plan_create(r2c, rocfft_placement_notinplace, rocfft_transform_type_real_forward, prec, 2, len2,
-                                  batch, f2) == rocfft_status_success;
-  ok2 = ok2 && rocfft_plan_create(c2r, rocfft_placement_notinplace, rocfft_transform_type_real_inverse, prec, 2, len2,
-                                  batch, i2) == rocfft_status_success;
+  ok2 = ok2 && r2c.create(rocfft_plan_create, rocfft_placement_notinplace, rocfft_transform_type_real_forward, prec, 2,
+                          len2, batch, f2) == rocfft_status_success;
+  ok2 = ok2 && c2r.create(rocfft_plan_create, rocfft_placement_notinplace, rocfft_transform_type_real_inverse, prec, 2,
+                          len2, batch, i2) == rocfft_status_success;
   if (f2) rocfft_plan_description_destroy(f2);
   if (i2) rocfft_plan_description_destroy(i2);
   if (ok2 && h->info) {
     // plans made after bchmc_create: the shared work buffer may have to grow
     size_t need = 0;
-    for (rocfft_plan p : {*r2c, *c2r}) {
+    for (const FftPlan *p : {&r2c, &c2r}) {
       size_t wb = 0;
-      if (rocfft_plan_get_work_buffer_size(p, &wb) != rocfft_status_success) ok2 = false;
+      if (rocfft_plan_get_work_buffer_size(*p, &wb) != rocfft_status_success) ok2 = false;
       need = std::max(need, wb);
     }
-    if (ok2 && need > h->work_bytes) {
-      void *nw = nullptr;
+    if (ok2 && need > h->work.capacity()) {
+      // not DevBuf::reserve: the execution info points at the old buffer until it has been given the new one
+      DevBytes nw;
       (void)hipStreamSynchronize(h->stream);
-      if (hipMalloc(&nw, need) == hipSuccess &&
+      if (nw.alloc(need) == hipSuccess &&
           rocfft_execution_info_set_work_buffer(h->info, nw, need) == rocfft_status_success) {
-        if (h->work) (void)hipFree(h->work);
-        h->work = nw;
-        h->work_bytes = need;
+        h->work = std::move(nw);
       } else {
-        if (nw) (void)hipFree(nw);
         (void)hipGetLastError();
         ok2 = false;
       }
     }
   }
   if (!ok2) {
-    for (rocfft_plan *pp : {r2c, c2r})
-      if (*pp) {
-        rocfft_plan_destroy(*pp);
-        *pp = nullptr;
-      }
+    r2c.reset();
+    c2r.reset();
     return BCHMC_ERR_ROCFFT;
   }
   return BCHMC_OK;
@@ -665,8 +661,8 @@ int stg_init(bchmc_handle *h) {
   int nt = (int)std::min(8u, std::max(1u, std::thread::hardware_concurrency() / 2));
   if (const char *ev = std::getenv("BCHMC_STAGE_THREADS")) nt = std::max(1, atoi(ev));
   for (int b = 0; b < 2; b++) {
-    HIPCHK(hipHostMalloc(&h->stg[b], chunk));
-    HIPCHK(hipEventCreateWithFlags(&h->stg_ev[b], hipEventDisableTiming));
+    HIPCHK(h->stg[b].alloc(chunk));
+    HIPCHK(h->stg_ev[b].create(hipEventDisableTiming));
   }
   h->stg_chunk = chunk;
   h->stg_threads = nt;
@@ -755,7 +751,7 @@ int build_conv_table(bchmc_handle *h) {
       }
     }
   }
-  CHK(dev_alloc(h, &h->convF, (size_t)g.Nhp));
+  CHK(dev_alloc(h, h->convF, (size_t)g.Nhp));
   HIPCHK(hipMemcpyAsync(h->convF, F.data(), F.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));  // F is a local vector
   return BCHMC_OK;
@@ -771,13 +767,7 @@ double spectrum_dk(const Geo &g, uint64_t n_bin) {
 // measure_spectrum (field_statistics.cpp:20-90) of a half-complex transform xk in the handle's storage type: n_bin
 // bins, Hermitian mode weights (k_spectrum); kmode / power on the host, empty bins 0.  Synchronises.
 int spectrum_bins(bchmc_handle *h, const void *xk, uint64_t n_bin, double *kmode, double *power) {
-  if (h->spec_cap < 3 * (size_t)n_bin) {  // kept in the handle: barcoderunner measures a spectrum after every sample
-    if (h->spec_bins) (void)hipFree(h->spec_bins);
-    h->spec_bins = nullptr;
-    h->spec_cap = 0;
-    CHK(dev_alloc(h, &h->spec_bins, 3 * (size_t)n_bin));
-    h->spec_cap = 3 * (size_t)n_bin;
-  }
+  CHK(dev_reserve(h, h->spec_bins, 3 * (size_t)n_bin));  // kept in the handle: barcoderunner measures after every sample
   double *bins = h->spec_bins;
   HIPCHK(hipMemsetAsync(bins, 0, 3 * (size_t)n_bin * sizeof(double), h->stream));
   const Geo &g = h->g;
@@ -822,10 +812,6 @@ int corr2d_setup(bchmc_handle *h, uint64_t n_bin) {
   const double dr = corr_dr(g, n_bin);
   HIPCHK(hipStreamSynchronize(h->stream));
   c.n_bin = 0;
-  for (void **p : {(void **)&c.idx, (void **)&c.slices, (void **)&c.part, (void **)&c.out}) {
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-  }
   // rows by perp bin: a counting sort that keeps the row order inside a bin
   std::vector<int> perp((size_t)n * n);
   c.row_cnt.assign(n_bin, 0);
@@ -878,10 +864,10 @@ int corr2d_setup(bchmc_handle *h, uint64_t n_bin) {
   std::vector<int> idx(rows.begin(), rows.begin() + c.nrows);
   idx.insert(idx.end(), par_start.begin(), par_start.end());
   idx.insert(idx.end(), perp_slice.begin(), perp_slice.end());
-  CHK(dev_alloc(h, &c.idx, idx.size()));
-  CHK(dev_alloc(h, &c.slices, slices.size()));
-  CHK(dev_alloc(h, &c.part, (size_t)c.nsl * c.npb));
-  CHK(dev_alloc(h, &c.out, 2 * (size_t)n_bin * c.npb));
+  CHK(dev_alloc(h, c.idx, idx.size()));
+  CHK(dev_alloc(h, c.slices, slices.size()));
+  CHK(dev_alloc(h, c.part, (size_t)c.nsl * c.npb));
+  CHK(dev_alloc(h, c.out, 2 * (size_t)n_bin * c.npb));
   HIPCHK(hipMemcpyAsync(c.idx, idx.data(), idx.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
   HIPCHK(hipMemcpyAsync(c.slices, slices.data(), slices.size() * sizeof(int2), hipMemcpyHostToDevice, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));  // idx and slices are local vectors
@@ -977,7 +963,7 @@ struct Pipe {
   static bool alpt_planes(bchmc_handle *h) {
     if (!planes_everywhere(h) || env_on("BCHMC_NO_ALPT_PLANES")) return false;
     if (!h->c2r2d_2 && !h->alpt_plans_failed) {
-      if (make_plans_2d(h, 2 * (size_t)h->g.n, &h->r2c2d_2, &h->c2r2d_2) != BCHMC_OK) h->alpt_plans_failed = true;
+      if (make_plans_2d(h, 2 * (size_t)h->g.n, h->r2c2d_2, h->c2r2d_2) != BCHMC_OK) h->alpt_plans_failed = true;
     }
     return h->c2r2d_2 != nullptr;
   }
@@ -1044,7 +1030,7 @@ struct Pipe {
     constexpr int NT_BIG = sizeof(T) == 8 ? 256 : 512, NT_SMALL = NT_BIG / 4;
     const int n = h->g.n, grid = n * (h->g.nhp / KB);
     const size_t lds = ((size_t)n * KB + n / 2) * sizeof(CT);
-    const CT *tw = reinterpret_cast<const CT *>(h->xtw);
+    const CT *tw = C(h->xtw);
 #define BCHMC_LAUNCH_AX(NT, PER)                                                                                 \
   CHK(launch_lds(h, k_alpt_mix_x<T, NT, PER>, grid, NT, lds, h->g, h->log2n, tw, C(h->Ck), h->c.kth, 1. / h->alpt_wtot, \
                  1. / (double)h->g.N))
@@ -1094,7 +1080,7 @@ struct Pipe {
         constexpr int KB = 128 / (int)sizeof(CT);
         const int n = h->g.n, ygrid = 3 * n * (h->g.nhp / KB);
         const size_t lds = ((size_t)n * KB + n / 2) * sizeof(CT);
-        const CT *tw = reinterpret_cast<const CT *>(h->xtw);
+        const CT *tw = C(h->xtw);
 #define BCHMC_LAUNCH_Y(NT, NN) \
   CHK(launch_lds(h, k_ypass<T, NT, NN * KB / NT, BCHMC_YPASS_NT>, ygrid, NT, lds, h->g, h->log2n, tw, C(h->Ck)))
         if (n == 128) BCHMC_LAUNCH_Y(256, 128);
@@ -1133,13 +1119,13 @@ struct Pipe {
       if (zbin) {
         const int n = h->g.n, zgrid = (n / 2) * (n / 2);
         const size_t zlds = zbin_lds<T>(n);
-        const CT *tw = reinterpret_cast<const CT *>(h->xtw);
+        const CT *tw = C(h->xtw);
         // second launch (interior steps, where Psi is not stored on the way): a segment overflowed -> the two-pass sort
         // below needs Psi after all (returns at once otherwise)
 #define BCHMC_LAUNCH_Z(NZ)                                                                                          \
   do {                                                                                                              \
     CHK(launch_lds(h, k_zbin_direct<T, NZ>, zgrid, NZ, zlds, h->g, pp, sp, h->tp, h->log2n, tw, C(h->Ck), cnt1, ovf, \
-                   (RecQuad *)h->srec, R(h->V), h->rho_part, h->fix ? nullptr : R(h->rho),                          \
+                   recs(h), R(h->V), h->rho_part, h->fix ? nullptr : R(h->rho),                          \
                    h->fix ? h->rho_fix : nullptr, m.psi_unread ? nullptr : R(h->psi)));                             \
     if (m.psi_unread)                                                                                               \
       CHK(launch_lds(h, k_zbin_direct<T, NZ, true>, zgrid, NZ, zlds, h->g, pp, sp, h->tp, h->log2n, tw, C(h->Ck),   \
@@ -1153,7 +1139,7 @@ struct Pipe {
       } else if (h->sort_direct) {
         const int nsuper = (nbricks + kBinPer - 1) / kBinPer;
         k_bin_direct<T><<<nsuper, BCHMC_BIN_THREADS, 0, h->stream>>>(h->g, pp, sp, h->tp, nsuper, R(h->psi), cnt1, ovf,
-                                                       (RecQuad *)h->srec, R(h->V), h->rho_part,
+                                                       recs(h), R(h->V), h->rho_part,
                                                        h->fix ? nullptr : R(h->rho),
                                                        h->fix ? h->rho_fix : nullptr);
         rho_cleared = true;
@@ -1164,7 +1150,7 @@ struct Pipe {
       k_scan_tiles<<<(nt + 1023) / 1024, 1024, 0, h->stream>>>(h->tp, cnt1, cnt2, ovf, h->t_off, h->t_end, h->t_woff,
                                                                h->t_oct, h->t_seg, ovf + 2);
       k_reorder<T><<<fb_grid, 256, 0, h->stream>>>(h->g, pp, nbricks, R(h->psi), h->t_rank, h->t_off, ovf,
-                                                   (RecQuad *)h->srec);
+                                                   recs(h));
       HIPCHK(hipGetLastError());
       h->sorted_valid = true;
     }
@@ -1189,29 +1175,29 @@ struct Pipe {
         // sub-cell ordering inside each work item: two binary digits per axis
         const int reorder = (h->tp.chunk > 2048) ? 0 : 2;
         if (reorder) {  // orders the records only after a fallback sort; returns at once otherwise
-          k_subsort<T><<<std::min(grid, 8192), 256, 0, h->stream>>>(h->g, h->tp, reorder, (RecQuad *)h->srec, h->t_off, h->t_end, h->t_woff,
+          k_subsort<T><<<std::min(grid, 8192), 256, 0, h->stream>>>(h->g, h->tp, reorder, recs(h), h->t_off, h->t_end, h->t_woff,
                                                    h->t_oct, h->t_seg);
           HIPCHK(hipGetLastError());
         }
         if (h->std81) {
           if (h->fix)
             k_scatter_tile81<T, 12, 20, true><<<grid, 256, tile_lds(h, 0, sizeof(double)), h->stream>>>(
-                h->g, sp, h->tp, (const RecQuad *)h->srec, h->t_off, h->t_end, h->t_woff,
+                h->g, sp, h->tp, recs(h), h->t_off, h->t_end, h->t_woff,
                 h->t_oct, h->t_seg, h->rho_fix, h->rho_part, h->t_cnt,
                 (kOct + 1) * h->tp.ntiles + 1, fix_scale);
           else
             k_scatter_tile81<T, 12, 20, false><<<grid, 256, tile_lds(h, 0, sizeof(double)), h->stream>>>(
-                h->g, sp, h->tp, (const RecQuad *)h->srec, h->t_off, h->t_end, h->t_woff,
+                h->g, sp, h->tp, recs(h), h->t_off, h->t_end, h->t_woff,
                 h->t_oct, h->t_seg, R(h->rho), h->rho_part, h->t_cnt,
                 (kOct + 1) * h->tp.ntiles + 1, fix_scale);
           h->cnt_clean = true;
         } else if (h->fix) {
           k_scatter_tile<T, true><<<grid, 256, tile_lds(h, ncol, sizeof(double)), h->stream>>>(
-              h->g, sp, h->tp, h->hull, ncol, (const RecQuad *)h->srec, h->t_off, h->t_end,
+              h->g, sp, h->tp, h->hull, ncol, recs(h), h->t_off, h->t_end,
               h->t_woff, h->t_oct, h->t_seg, h->rho_fix, h->rho_part, fix_scale);
         } else {
           k_scatter_tile<T, false><<<grid, 256, tile_lds(h, ncol, sizeof(double)), h->stream>>>(
-              h->g, sp, h->tp, h->hull, ncol, (const RecQuad *)h->srec, h->t_off, h->t_end,
+              h->g, sp, h->tp, h->hull, ncol, recs(h), h->t_off, h->t_end,
               h->t_woff, h->t_oct, h->t_seg, R(h->rho), h->rho_part, fix_scale);
         }
       } else if (tile_low) {
@@ -1221,11 +1207,11 @@ struct Pipe {
         const size_t lds = (size_t)(h->tp.tx + 2) * (h->tp.ty + 2) * (h->tp.tz + 2) * sizeof(double);
         const int ncnt = (kOct + 1) * h->tp.ntiles + 1;
         if (h->fix)
-          k_scatter_tile_low<T, true><<<grid, 256, lds, h->stream>>>(h->g, h->tp, h->c.mk, (const RecQuad *)h->srec, h->t_off,
+          k_scatter_tile_low<T, true><<<grid, 256, lds, h->stream>>>(h->g, h->tp, h->c.mk, recs(h), h->t_off,
                                                                      h->t_end, h->t_woff, h->t_oct, h->t_seg, h->rho_fix,
                                                                      h->rho_part, h->t_cnt, ncnt, fix_scale);
         else
-          k_scatter_tile_low<T, false><<<grid, 256, lds, h->stream>>>(h->g, h->tp, h->c.mk, (const RecQuad *)h->srec, h->t_off,
+          k_scatter_tile_low<T, false><<<grid, 256, lds, h->stream>>>(h->g, h->tp, h->c.mk, recs(h), h->t_off,
                                                                       h->t_end, h->t_woff, h->t_oct, h->t_seg, R(h->rho),
                                                                       h->rho_part, h->t_cnt, ncnt, fix_scale);
         h->cnt_clean = true;
@@ -1262,7 +1248,7 @@ struct Pipe {
   }
 
   static int ensure_conv(bchmc_handle *h) {
-    if (!h->conv) CHK(dev_alloc_bytes(h, &h->conv, 3 * (size_t)h->g.N * sizeof(T)));
+    if (!h->conv) CHK(dev_alloc(h, h->conv, 3 * (size_t)h->g.N * sizeof(T)));
     return BCHMC_OK;
   }
 
@@ -1336,7 +1322,7 @@ struct Pipe {
           const int grid = h->tp.ntiles + (int)(N / h->tp.chunk) + 1;
           const size_t lds = 3 * (size_t)(h->tp.tx + 2) * (h->tp.ty + 2) * (h->tp.tz + 2) * sizeof(T);
           k_interp_tsc_tile<T><<<grid, 256, lds, h->stream>>>(h->g, h->tp, h->last_rsd, fgrow1(h->c.ascale, h->c.OM, h->c.OL),
-                                                              (const RecQuad *)h->srec, h->t_off, h->t_end, h->t_woff,
+                                                              recs(h), h->t_off, h->t_end, h->t_woff,
                                                               h->t_oct, h->t_seg, R(h->conv), R(h->V));
         } else {
           k_interp_tsc<T><<<nblk_full(N), 256, 0, h->stream>>>(h->g, make_pos(h, h->last_rsd),
@@ -1352,11 +1338,11 @@ struct Pipe {
         const int grid = h->tp.ntiles + (int)(N / h->tp.chunk) + 1;
         if (h->std81)
           k_gather_tile81<T, 12, 20><<<grid, 256, tile_lds(h, 0, sizeof(T)), h->stream>>>(
-              h->g, hp, h->tp, h->last_rsd, (RecQuad *)h->srec, h->t_off, h->t_end, h->t_woff,
+              h->g, hp, h->tp, h->last_rsd, recs(h), h->t_off, h->t_end, h->t_woff,
               h->t_oct, h->t_seg, R(h->plike), R(h->V));
         else
           k_gather_tile<T><<<grid, 256, tile_lds(h, hp.ncol, sizeof(T)), h->stream>>>(
-              h->g, hp, h->tp, h->last_rsd, (RecQuad *)h->srec, h->t_off, h->t_end, h->t_woff,
+              h->g, hp, h->tp, h->last_rsd, recs(h), h->t_off, h->t_end, h->t_woff,
               h->t_oct, h->t_seg, R(h->plike), R(h->V));
       } else {
         k_gather_sph<T><<<nblk_full(N), 256, hp.ncol * sizeof(int4), h->stream>>>(h->g, make_pos(h, h->last_rsd), hp,
@@ -1371,7 +1357,7 @@ struct Pipe {
       ProfScope ps(h, BCHMC_K_FFT_R2C);
       constexpr int KB = 128 / (int)sizeof(CT);
       const int n = h->g.n;
-      const CT *tw = reinterpret_cast<const CT *>(h->xtw);
+      const CT *tw = C(h->xtw);
       const size_t zl = ((size_t)n * 6 + n / 2) * sizeof(CT), yl = ((size_t)n * KB + n / 2) * sizeof(CT);
       CHK(launch_lds(h, k_zr2c<T, 512>, (n / 2) * (n / 2), 512, zl, h->g, h->log2n, tw, R(h->V), C(h->Ck)));
       CHK(launch_lds(h, k_ypass<T, 512, 512 * KB / 512, BCHMC_YPASS_NT, false>, 3 * n * (h->g.nhp / KB), 512, yl, h->g,
@@ -1559,12 +1545,8 @@ struct Pipe {
   static int trajectory(bchmc_handle *h, double eps, uint64_t neps, const Tap *tap, const void *g0_in = nullptr,
                         void *g0_out = nullptr) {
     h->prop_g_valid = false;
-    if (neps + 1 > h->guard_cap) {
-      if (h->guard) (void)hipFree(h->guard);
-      h->guard = nullptr;
-      h->guard_cap = std::max<size_t>(4096, 2 * (neps + 1));  // generous: a reallocation synchronises the device
-      CHK(dev_alloc(h, &h->guard, h->guard_cap));
-    }
+    if (neps + 1 > h->guard.capacity())  // generous: a reallocation synchronises the device
+      CHK(dev_reserve(h, h->guard, std::max<size_t>(4096, 2 * (neps + 1))));
     HIPCHK(hipMemsetAsync(h->guard, 0, (neps + 1) * sizeof(double), h->stream));
     k_init_ctl<<<1, 1, 0, h->stream>>>(h->stop, h->steps_done, (unsigned long long)neps);
     HIPCHK(hipGetLastError());
@@ -1621,7 +1603,7 @@ struct Pipe {
     constexpr int NT_BIG = sizeof(T) == 8 ? 256 : 512, NT_SMALL = NT_BIG / 4;  // small: n = 32, 64 (tests)
     const int n = h->g.n, grid = n * (h->g.nhp / KB);
     const size_t lds = ((size_t)n * KB + n / 2) * sizeof(CT);
-    const CT *tw = reinterpret_cast<const CT *>(h->xtw);
+    const CT *tw = C(h->xtw);
 #define BCHMC_LAUNCH_X(NT, PER)                                                                                      \
   CHK(launch_lds(h, k_step_boundary_x<T, NT, PER, MODE, ALPT>, grid, NT, lds, h->g, h->log2n, tw, C(h->Ck), qi, pi, qo, \
                  po, h->wS, wM, a, b, half_eps, eps, c_za, guard_slot, ctl, g_in, g_out))
@@ -1662,8 +1644,8 @@ struct Pipe {
                               double c_za, const void *g_first, bool alpt_x = false) {
     const double guard_limit = 1e50 * (double)h->g.N;
     if (!h->qk2) {
-      CHK(dev_alloc_bytes(h, &h->qk2, 2 * (size_t)h->g.Nhp * sizeof(T)));
-      CHK(dev_alloc_bytes(h, &h->pk2, 2 * (size_t)h->g.Nhp * sizeof(T)));
+      CHK(dev_alloc(h, h->qk2, 2 * (size_t)h->g.Nhp * sizeof(T)));
+      CHK(dev_alloc(h, h->pk2, 2 * (size_t)h->g.Nhp * sizeof(T)));
     }
     void *const q0 = h->qk, *const p0 = h->pk, *const q1 = h->qk2, *const p1 = h->pk2;
     int like_mode = 2;
@@ -1761,9 +1743,9 @@ struct Pipe {
   // ---- device-resident chain --------------------------------------------------------------------------------
   static int chain_alloc(bchmc_handle *h) {
     if (!h->cq) {
-      CHK(dev_alloc_bytes(h, &h->cq, 2 * (size_t)h->g.Nhp * sizeof(T)));
-      CHK(dev_alloc_bytes(h, &h->cp, 2 * (size_t)h->g.Nhp * sizeof(T)));
-      CHK(dev_alloc(h, &h->part6, (size_t)6 * kRedBlocks));
+      CHK(dev_alloc(h, h->cq, 2 * (size_t)h->g.Nhp * sizeof(T)));
+      CHK(dev_alloc(h, h->cp, 2 * (size_t)h->g.Nhp * sizeof(T)));
+      CHK(dev_alloc(h, h->part6, (size_t)6 * kRedBlocks));
     }
     return BCHMC_OK;
   }
@@ -1820,7 +1802,7 @@ struct Pipe {
     const size_t cbytes = 2 * (size_t)h->g.Nhp * sizeof(T);
     const double N = (double)h->g.N;
     const bool fast = attempt_is_fast(h, neps);
-    if (!h->part6) CHK(dev_alloc(h, &h->part6, (size_t)6 * kRedBlocks));
+    if (!h->part6) CHK(dev_alloc(h, h->part6, (size_t)6 * kRedBlocks));
     double *P = h->part6;
     if (!fast) {
       CHK(energies_core(h, d_q0, d_p0, terms));  // leaves FFT[q0], FFT[p0] in (qk, pk)
@@ -1895,7 +1877,7 @@ struct Pipe {
       HIPCHK(hipMemcpyAsync(h->qk, h->cq, cbytes, hipMemcpyDeviceToDevice, h->stream));
       HIPCHK(hipMemcpyAsync(h->pk, h->cp, cbytes, hipMemcpyDeviceToDevice, h->stream));
       const bool use = !env_on("BCHMC_NO_FORCE_CARRY"), carry = use && h->cg_valid;
-      if (use && !h->cg) CHK(dev_alloc_bytes(h, &h->cg, cbytes));
+      if (use && !h->cg) CHK(dev_alloc(h, h->cg, cbytes));
       uint64_t done = 0;
       CHK(attempt_core(h, eps, neps, nullptr, nullptr, nullptr, nullptr, terms, &done, carry ? h->cg : nullptr,
                        h->c_like, (use && !carry) ? h->cg : nullptr));
@@ -1943,7 +1925,7 @@ struct Pipe {
   // enqueued before the momenta are uploaded, so that their PCIe transfer (3 ms per 134 MB array) runs beside it.
   static int host_prologue(bchmc_handle *h) {
     CHK(check_inputs(h));
-    if (!h->part6) CHK(dev_alloc(h, &h->part6, (size_t)6 * kRedBlocks));
+    if (!h->part6) CHK(dev_alloc(h, h->part6, (size_t)6 * kRedBlocks));
     k_init_ctl<<<1, 1, 0, h->stream>>>(h->stop, h->steps_done, 0ull);  // a stop flag left by an earlier trajectory
     HIPCHK(hipGetLastError());
     CHK(r2c_state(h, h->dstage, h->ioq, h->qk));
@@ -2091,13 +2073,9 @@ struct Pipe {
     auto &c = h->corr1;
     const Geo &g = h->g;
     const size_t nb = (size_t)n_bin, words = 5 * nb + 1;
-    if (c.cap < words) {
-      if (c.acc) (void)hipFree(c.acc);
-      c.acc = nullptr;
-      c.cap = 0;
+    if (c.acc.capacity() < words) {
       c.n_bin = 0;
-      CHK(dev_alloc(h, &c.acc, words));
-      c.cap = words;
+      CHK(dev_reserve(h, c.acc, words));
     }
     const bool geom = c.n_bin != n_bin;
     const double dr = corr_dr(g, n_bin);
@@ -2207,8 +2185,8 @@ struct Pipe {
   static int gradient(bchmc_handle *h, const double *d_q, double *d_g) {
     const size_t N = (size_t)h->g.N;
     if (!h->gprior) {
-      CHK(dev_alloc_bytes(h, &h->gprior, N * sizeof(T)));
-      CHK(dev_alloc_bytes(h, &h->glike, N * sizeof(T)));
+      CHK(dev_alloc(h, h->gprior, N * sizeof(T)));
+      CHK(dev_alloc(h, h->glike, N * sizeof(T)));
     }
     CHK(r2c_state(h, d_q, h->ioq, h->qk));
     int like_mode = 2;
@@ -2303,11 +2281,11 @@ struct Pipe {
   static int mock_alloc(bchmc_handle *h) {
     auto &k = h->mock;
     if (k.cnt) return BCHMC_OK;
-    CHK(dev_alloc(h, &k.cnt, (size_t)mock_tiles(h)));
-    CHK(dev_alloc(h, &k.off, (size_t)mock_tiles(h)));
-    CHK(dev_alloc(h, &k.gsum, (size_t)mock_groups(h)));
-    CHK(dev_alloc(h, &k.goff, (size_t)mock_groups(h)));
-    CHK(dev_alloc(h, &k.res, (size_t)2));
+    CHK(dev_alloc(h, k.cnt, (size_t)mock_tiles(h)));
+    CHK(dev_alloc(h, k.off, (size_t)mock_tiles(h)));
+    CHK(dev_alloc(h, k.gsum, (size_t)mock_groups(h)));
+    CHK(dev_alloc(h, k.goff, (size_t)mock_groups(h)));
+    CHK(dev_alloc(h, k.res, (size_t)2));
     return BCHMC_OK;
   }
 
@@ -2338,7 +2316,7 @@ struct Pipe {
     ProfScope ps(h, BCHMC_K_OTHER);
     k_mock_noise<T><<<(int)mock_tiles(h), kMockThreads, 0, h->stream>>>(
         N, mp, h->dstage, h->dstage + N, R(h->in_arr[BCHMC_F_WINDOW]), k.off, k.goff,
-        reinterpret_cast<const double2 *>(h->mt.gauss), R(h->in_arr[BCHMC_F_NOBS]), R(h->in_arr[BCHMC_F_NOISE]), k.res);
+        reinterpret_cast<const double2 *>(h->mt.gauss.get()), R(h->in_arr[BCHMC_F_NOBS]), R(h->in_arr[BCHMC_F_NOISE]), k.res);
     HIPCHK(hipGetLastError());
     return BCHMC_OK;
   }
@@ -2358,7 +2336,7 @@ struct Pipe {
     {
       ProfScope ps(h, BCHMC_K_OTHER);
       k_mock_guess_noise<<<nblk_stride(h->g.N), kMockThreads, 0, h->stream>>>(
-          h->g.N, sigma, reinterpret_cast<const double2 *>(h->mt.gauss), h->dstage);
+          h->g.N, sigma, reinterpret_cast<const double2 *>(h->mt.gauss.get()), h->dstage);
       HIPCHK(hipGetLastError());
     }
     return r2c_state(h, h->dstage, h->ioq, h->cq);
@@ -2399,28 +2377,19 @@ struct Pipe {
   static int mass_jasche(bchmc_handle *h, double *d_r) {
     const Geo &g = h->g;
     const long long N = g.N;
-    struct Scratch {  // released after the stream has drained
-      bchmc_handle *h;
-      std::vector<void *> p;
-      ~Scratch() {
-        (void)hipStreamSynchronize(h->stream);
-        for (void *q : p) (void)hipFree(q);
-      }
-    } s{h, {}};
-    auto alloc = [&](void **p, size_t bytes) -> int {
-      CHK(dev_alloc_bytes(h, p, bytes));
-      s.p.push_back(*p);
-      return BCHMC_OK;
-    };
-    double *G = nullptr, *acc = nullptr;
-    int *cnt = nullptr, *off = nullptr;
-    long long *total = nullptr;
-    JRec *rec = nullptr;
-    CHK(alloc((void **)&G, 3 * (size_t)N * sizeof(double)));
-    CHK(alloc((void **)&acc, (size_t)N * sizeof(double)));
-    CHK(alloc((void **)&cnt, (size_t)N * sizeof(int)));
-    CHK(alloc((void **)&off, ((size_t)N + 1) * sizeof(int)));
-    CHK(alloc((void **)&total, sizeof(long long)));
+    DevBuf<double> G, acc;
+    DevBuf<int> cnt, off;
+    DevBuf<long long> total;
+    DevBuf<JRec> rec;
+    struct Drain {  // declared after the scratch buffers: they are released after the stream has drained
+      hipStream_t stream;
+      ~Drain() { (void)hipStreamSynchronize(stream); }
+    } drain{h->stream};
+    CHK(dev_alloc(h, G, 3 * (size_t)N));
+    CHK(dev_alloc(h, acc, (size_t)N));
+    CHK(dev_alloc(h, cnt, (size_t)N));
+    CHK(dev_alloc(h, off, (size_t)N + 1));
+    CHK(dev_alloc(h, total, (size_t)1));
     {
       ProfScope ps(h, BCHMC_K_OTHER);
       k_glap_impulse<T><<<nblk_stride(g.Nhp), 256, 0, h->stream>>>(g, C(h->Ck));
@@ -2455,7 +2424,7 @@ struct Pipe {
     HIPCHK(hipStreamSynchronize(h->stream));
     if (npairs >= 0x7fffffffLL)
       return h->fail(BCHMC_ERR_UNSUPPORTED, "Jasche mass: %lld (particle, cell) pairs exceed the 32-bit offsets", npairs);
-    CHK(alloc((void **)&rec, (size_t)std::max(npairs, 1ll) * sizeof(JRec)));
+    CHK(dev_alloc(h, rec, (size_t)std::max(npairs, 1ll)));
     HIPCHK(hipMemsetAsync(cnt, 0, (size_t)N * sizeof(int), h->stream));
     {
       ProfScope ps(h, BCHMC_K_OTHER);
@@ -2641,15 +2610,14 @@ int mt_setup(bchmc_handle *h) {
       if (b + 1 < B) p = mt_host::mulmod(phi, p, J);
     }
   }
-  CHK(dev_alloc(h, &m.poly, polys.size()));
-  CHK(dev_alloc(h, &m.win, (size_t)34 * kMtN));
-  CHK(dev_alloc(h, &m.words, (size_t)m.C));
-  CHK(dev_alloc(h, &m.st, (size_t)kMtN));
-  for (unsigned long long **p : {&m.nz, &m.nzoff, &m.acc, &m.accoff, &m.lastend}) CHK(dev_alloc(h, p, (size_t)B));
-  CHK(dev_alloc(h, &m.res, (size_t)8 + kMtN / 2));
-  m.gauss_cap = std::max(m.G, 1LL);
-  CHK(dev_alloc(h, &m.gauss, (size_t)m.gauss_cap));
-  HIPCHK(hipHostMalloc((void **)&m.h_io, (8 + kMtN / 2) * sizeof(unsigned long long)));
+  CHK(dev_alloc(h, m.poly, polys.size()));
+  CHK(dev_alloc(h, m.win, (size_t)34 * kMtN));
+  CHK(dev_alloc(h, m.words, (size_t)m.C));
+  CHK(dev_alloc(h, m.st, (size_t)kMtN));
+  for (DevBuf<unsigned long long> *p : {&m.nz, &m.nzoff, &m.acc, &m.accoff, &m.lastend}) CHK(dev_alloc(h, *p, (size_t)B));
+  CHK(dev_alloc(h, m.res, (size_t)8 + kMtN / 2));
+  CHK(dev_alloc(h, m.gauss, (size_t)std::max(m.G, 1LL)));
+  HIPCHK(m.h_io.alloc(8 + kMtN / 2));
   HIPCHK(hipMemcpyAsync(m.poly, polys.data(), polys.size() * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
   HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_mt_segments), hipFuncAttributeMaxDynamicSharedMemorySize,
                              (int)kMtSegLds));
@@ -2662,13 +2630,9 @@ int mt_setup(bchmc_handle *h) {
 // 2 doubles per windowed cell in split form) grows it.  Only called between trajectories.
 int mt_reserve(bchmc_handle *h, long long doubles) {
   auto &m = h->mt;
-  if (doubles <= m.gauss_cap) return BCHMC_OK;
+  if (doubles <= (long long)m.gauss.capacity()) return BCHMC_OK;
   HIPCHK(hipStreamSynchronize(h->stream));
-  HIPCHK(hipFree(m.gauss));
-  m.gauss = nullptr, m.gauss_cap = 0;
-  CHK(dev_alloc(h, &m.gauss, (size_t)doubles));
-  m.gauss_cap = doubles;
-  return BCHMC_OK;
+  return dev_reserve(h, m.gauss, (size_t)doubles);
 }
 
 // One pass: C words from the window at position P (counted from mt[0] of the caller's state), Gaussians
@@ -2836,14 +2800,13 @@ int bchmc_create(const bchmc_config *cfg, bchmc_handle **out) {
         else if (mode == "oddcu") on = (cu & 1) == 1;
         if (on) mask[cu / 32] |= 1u << (cu % 32);
       }
-      HIPCHK(hipExtStreamCreateWithCUMask(&h->stream, (uint32_t)words, mask.data()));
+      hipStream_t masked = nullptr;
+      HIPCHK(hipExtStreamCreateWithCUMask(&masked, (uint32_t)words, mask.data()));
+      h->stream.reset(masked);
     } else {
-      HIPCHK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+      HIPCHK(h->stream.create(hipStreamNonBlocking));
     }
-    {
-      std::lock_guard<std::mutex> lk(g_rocfft_mu);
-      if (g_rocfft_users++ == 0) FFTCHK(rocfft_setup());
-    }
+    FFTCHK(h->fft_user.acquire());
     const size_t len[3] = {(size_t)g.n, (size_t)g.n, (size_t)g.n};  // fastest first; cubic
     const rocfft_precision prec = h->f32 ? rocfft_precision_single : rocfft_precision_double;
     // real side contiguous (n, n^2), half-complex side with row stride nhp
@@ -2855,14 +2818,14 @@ int bchmc_create(const bchmc_config *cfg, bchmc_handle **out) {
                                                    nullptr, nullptr, 3, rs, (size_t)g.N, 3, cs, (size_t)g.Nhp));
     FFTCHK(rocfft_plan_description_set_data_layout(inv, rocfft_array_type_hermitian_interleaved, rocfft_array_type_real,
                                                    nullptr, nullptr, 3, cs, (size_t)g.Nhp, 3, rs, (size_t)g.N));
-    FFTCHK(rocfft_plan_create(&h->r2c1, rocfft_placement_notinplace, rocfft_transform_type_real_forward, prec, 3, len, 1,
-                              fwd));
-    FFTCHK(rocfft_plan_create(&h->c2r1, rocfft_placement_notinplace, rocfft_transform_type_real_inverse, prec, 3, len, 1,
-                              inv));
-    FFTCHK(rocfft_plan_create(&h->r2c3, rocfft_placement_notinplace, rocfft_transform_type_real_forward, prec, 3, len, 3,
-                              fwd));
-    FFTCHK(rocfft_plan_create(&h->c2r3, rocfft_placement_notinplace, rocfft_transform_type_real_inverse, prec, 3, len, 3,
-                              inv));
+    FFTCHK(h->r2c1.create(rocfft_plan_create, rocfft_placement_notinplace, rocfft_transform_type_real_forward, prec, 3, len,
+                          1, fwd));
+    FFTCHK(h->c2r1.create(rocfft_plan_create, rocfft_placement_notinplace, rocfft_transform_type_real_inverse, prec, 3, len,
+                          1, inv));
+    FFTCHK(h->r2c3.create(rocfft_plan_create, rocfft_placement_notinplace, rocfft_transform_type_real_forward, prec, 3, len,
+                          3, fwd));
+    FFTCHK(h->c2r3.create(rocfft_plan_create, rocfft_placement_notinplace, rocfft_transform_type_real_inverse, prec, 3, len,
+                          3, inv));
     rocfft_plan_description_destroy(fwd);
     rocfft_plan_description_destroy(inv);
     {
@@ -2872,9 +2835,9 @@ int bchmc_create(const bchmc_config *cfg, bchmc_handle **out) {
       while ((1 << l2) < g.n) l2++;
       if ((1 << l2) == g.n && g.n >= 32 && g.n <= 512 && g.nhp % KB == 0) {
         h->log2n = l2;
-        const bool ok2 = make_plans_2d(h, 3 * (size_t)g.n, &h->r2c2d, &h->c2r2d) == BCHMC_OK;
+        const bool ok2 = make_plans_2d(h, 3 * (size_t)g.n, h->r2c2d, h->c2r2d) == BCHMC_OK;
         // twiddles exp(-2 pi i r / n), r < n / 2, from the host's libm (fft_host.hpp)
-        CHK(dev_alloc_bytes(h, &h->xtw, (size_t)g.n * h->esz));
+        CHK(dev_alloc(h, h->xtw, (size_t)g.n * h->esz));
         if (h->f32) {
           const std::vector<float> twf = fft_twiddles<float>(g.n);
           HIPCHK(hipMemcpyAsync(h->xtw, twf.data(), twf.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));
@@ -2888,47 +2851,48 @@ int bchmc_create(const bchmc_config *cfg, bchmc_handle **out) {
         // the ALPT model's planes pipeline transforms two fields at a time (alpt_x.hpp): plans made here, not inside
         // the first trajectory
         if (ok2 && !cfg->rsd_model && cfg->sfmodel != 1 && cfg->calc_h == 2 && cfg->mk == 3 &&
-            make_plans_2d(h, 2 * (size_t)g.n, &h->r2c2d_2, &h->c2r2d_2) != BCHMC_OK)
+            make_plans_2d(h, 2 * (size_t)g.n, h->r2c2d_2, h->c2r2d_2) != BCHMC_OK)
           h->alpt_plans_failed = true;
       }
     }
-    for (rocfft_plan p : {h->r2c1, h->c2r1, h->r2c3, h->c2r3, h->r2c2d, h->c2r2d, h->r2c2d_2, h->c2r2d_2}) {
-      if (!p) continue;
+    size_t work_bytes = 0;
+    for (const FftPlan *p : {&h->r2c1, &h->c2r1, &h->r2c3, &h->c2r3, &h->r2c2d, &h->c2r2d, &h->r2c2d_2, &h->c2r2d_2}) {
+      if (!*p) continue;
       size_t wb = 0;
-      FFTCHK(rocfft_plan_get_work_buffer_size(p, &wb));
-      h->work_bytes = std::max(h->work_bytes, wb);
+      FFTCHK(rocfft_plan_get_work_buffer_size(*p, &wb));
+      work_bytes = std::max(work_bytes, wb);
     }
-    FFTCHK(rocfft_execution_info_create(&h->info));
+    FFTCHK(h->info.create(rocfft_execution_info_create));
     FFTCHK(rocfft_execution_info_set_stream(h->info, h->stream));
-    if (h->work_bytes) {
-      HIPCHK(hipMalloc(&h->work, h->work_bytes));
-      FFTCHK(rocfft_execution_info_set_work_buffer(h->info, h->work, h->work_bytes));
+    if (work_bytes) {
+      HIPCHK(h->work.alloc(work_bytes));
+      FFTCHK(rocfft_execution_info_set_work_buffer(h->info, h->work, work_bytes));
     }
     const size_t N = (size_t)g.N, Nh = (size_t)g.Nhp, e = h->esz;
-    for (int f = 0; f < 6; f++) CHK(dev_alloc_bytes(h, &h->in_arr[f], N * e));
-    CHK(dev_alloc(h, &h->wS, Nh));
-    CHK(dev_alloc(h, &h->wM, Nh));
-    CHK(dev_alloc_bytes(h, &h->qk, 2 * Nh * e));
-    CHK(dev_alloc_bytes(h, &h->pk, 2 * Nh * e));
-    CHK(dev_alloc_bytes(h, &h->gk, 2 * Nh * e));
-    CHK(dev_alloc_bytes(h, &h->Ck, 3 * 2 * (size_t)g.Nhp * e));
-    CHK(dev_alloc_bytes(h, &h->tC, 2 * Nh * e));
-    CHK(dev_alloc_bytes(h, &h->psi, 3 * N * e));
-    CHK(dev_alloc_bytes(h, &h->V, 3 * N * e));
-    CHK(dev_alloc_bytes(h, &h->rho, N * e));
-    CHK(dev_alloc_bytes(h, &h->plike, N * e));
-    if (h->fix) CHK(dev_alloc(h, &h->rho_fix, N));
-    if (h->fix) CHK(dev_alloc(h, &h->fix_sat, (size_t)1));
+    for (int f = 0; f < 6; f++) CHK(dev_alloc(h, h->in_arr[f], N * e));
+    CHK(dev_alloc(h, h->wS, Nh));
+    CHK(dev_alloc(h, h->wM, Nh));
+    CHK(dev_alloc(h, h->qk, 2 * Nh * e));
+    CHK(dev_alloc(h, h->pk, 2 * Nh * e));
+    CHK(dev_alloc(h, h->gk, 2 * Nh * e));
+    CHK(dev_alloc(h, h->Ck, 3 * 2 * (size_t)g.Nhp * e));
+    CHK(dev_alloc(h, h->tC, 2 * Nh * e));
+    CHK(dev_alloc(h, h->psi, 3 * N * e));
+    CHK(dev_alloc(h, h->V, 3 * N * e));
+    CHK(dev_alloc(h, h->rho, N * e));
+    CHK(dev_alloc(h, h->plike, N * e));
+    if (h->fix) CHK(dev_alloc(h, h->rho_fix, N));
+    if (h->fix) CHK(dev_alloc(h, h->fix_sat, (size_t)1));
     if (const char *ev = std::getenv("BCHMC_FIX_SAT_LOG2")) h->fix_sat_limit = 1ll << std::min(std::max(atoi(ev), 1), 62);
-    CHK(dev_alloc_bytes(h, &h->ioq, N * e));
-    CHK(dev_alloc_bytes(h, &h->iop, N * e));
-    CHK(dev_alloc(h, &h->dstage, 2 * N));
-    CHK(dev_alloc(h, &h->rho_part, (size_t)kRedBlocks));
-    CHK(dev_alloc(h, &h->partA, (size_t)kRedBlocks));
-    CHK(dev_alloc(h, &h->stop, (size_t)1));
-    CHK(dev_alloc(h, &h->steps_done, (size_t)1));
+    CHK(dev_alloc(h, h->ioq, N * e));
+    CHK(dev_alloc(h, h->iop, N * e));
+    CHK(dev_alloc(h, h->dstage, 2 * N));
+    CHK(dev_alloc(h, h->rho_part, (size_t)kRedBlocks));
+    CHK(dev_alloc(h, h->partA, (size_t)kRedBlocks));
+    CHK(dev_alloc(h, h->stop, (size_t)1));
+    CHK(dev_alloc(h, h->steps_done, (size_t)1));
     HIPCHK(hipMemsetAsync(h->stop, 0, sizeof(int), h->stream));
-    HIPCHK(hipHostMalloc((void **)&h->h_part, kRedBlocks * sizeof(double)));
+    HIPCHK(h->h_part.alloc(kRedBlocks));
     std::vector<int4> cols;
     build_hull(cfg->particle_kernel_h, g.d, cols, h->reach);
     h->hull_n = (int)cols.size();
@@ -2951,7 +2915,7 @@ int bchmc_create(const bchmc_config *cfg, bchmc_handle **out) {
           }
       h->hull_exact = exact;
     }
-    CHK(dev_alloc(h, &h->hull, cols.size()));
+    CHK(dev_alloc(h, h->hull, cols.size()));
     HIPCHK(hipMemcpyAsync(h->hull, cols.data(), cols.size() * sizeof(int4), hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     // tile-sorted particle-mesh path: tiles of 8 x 8 x 16 cells (z fastest) when they divide the grid
@@ -3017,14 +2981,14 @@ int bchmc_create(const bchmc_config *cfg, bchmc_handle **out) {
               h->cap_budget = std::max<long long>(h->cap_alloc, (long long)(total_b / 4 / ((size_t)tp.ntiles * 4 * e)));
             }
           }
-          CHK(dev_alloc(h, &h->t_cnt, (kOct + 1) * (size_t)tp.ntiles + 3));
-          CHK(dev_alloc(h, &h->t_oct, 2 * (size_t)tp.ntiles));
-          CHK(dev_alloc(h, &h->t_seg, (size_t)1));
-          CHK(dev_alloc(h, &h->t_off, (size_t)tp.ntiles));
-          CHK(dev_alloc(h, &h->t_end, (size_t)tp.ntiles));
-          CHK(dev_alloc(h, &h->t_woff, (size_t)tp.ntiles + 1));
-          CHK(dev_alloc(h, &h->t_rank, N));
-          CHK(dev_alloc_bytes(h, &h->srec, nrec * 4 * e));
+          CHK(dev_alloc(h, h->t_cnt, (kOct + 1) * (size_t)tp.ntiles + 3));
+          CHK(dev_alloc(h, h->t_oct, 2 * (size_t)tp.ntiles));
+          CHK(dev_alloc(h, h->t_seg, (size_t)1));
+          CHK(dev_alloc(h, h->t_off, (size_t)tp.ntiles));
+          CHK(dev_alloc(h, h->t_end, (size_t)tp.ntiles));
+          CHK(dev_alloc(h, h->t_woff, (size_t)tp.ntiles + 1));
+          CHK(dev_alloc(h, h->t_rank, N));
+          CHK(dev_alloc(h, h->srec, nrec * 4 * e));
         }
       }
     }
@@ -3041,41 +3005,7 @@ void bchmc_destroy(bchmc_handle *h) {
   (void)hipSetDevice(h->c.device);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   prof_collect(h);
-  for (hipEvent_t e : h->ev_pool) (void)hipEventDestroy(e);
-  for (rocfft_plan p : {h->r2c1, h->c2r1, h->r2c3, h->c2r3, h->r2c2d, h->c2r2d, h->r2c2d_2, h->c2r2d_2})
-    if (p) rocfft_plan_destroy(p);
-  if (h->info) rocfft_execution_info_destroy(h->info);
-  void *ptrs[] = {h->work,  h->wS,       h->wM,    h->qk,    h->pk,   h->gk,     h->Ck,         h->tC,   h->psi,
-                  h->V,     h->rho,      h->plike, h->ioq,   h->iop,  h->gprior, h->glike,      h->conv, h->convF,
-                  h->dstage, h->rho_fix, h->fix_sat, h->spec_bins, h->cq, h->cp, h->cg, h->qk2, h->pk2, h->xtw, h->part6, h->rho_part, h->partA, h->guard, h->stop, h->steps_done, h->hull,  h->t_cnt, h->t_off,
-                  h->t_woff, h->t_oct, h->t_seg, h->t_end, h->t_rank,  h->srec};
-  for (void *p : ptrs)
-    if (p) (void)hipFree(p);
-  for (int f = 0; f < 6; f++)
-    if (h->in_arr[f]) (void)hipFree(h->in_arr[f]);
-  if (h->h_part) (void)hipHostFree(h->h_part);
-  for (void *p : {(void *)h->mt.poly, (void *)h->mt.win, (void *)h->mt.words, (void *)h->mt.st, (void *)h->mt.nz,
-                  (void *)h->mt.nzoff, (void *)h->mt.acc, (void *)h->mt.accoff, (void *)h->mt.lastend,
-                  (void *)h->mt.res, (void *)h->mt.gauss, (void *)h->mock.cnt, (void *)h->mock.off,
-                  (void *)h->mock.gsum, (void *)h->mock.goff, (void *)h->mock.res, (void *)h->corr1.acc,
-                  (void *)h->corr2.idx, (void *)h->corr2.slices, (void *)h->corr2.part, (void *)h->corr2.out})
-    if (p) (void)hipFree(p);
-  if (h->mt.h_io) (void)hipHostFree(h->mt.h_io);
-  if (h->copy_stream) (void)hipStreamDestroy(h->copy_stream);
-  if (h->ev_q) (void)hipEventDestroy(h->ev_q);
-  if (h->h_slots) (void)hipHostFree(h->h_slots);
-  for (hipEvent_t e : h->slot_ev)
-    if (e) (void)hipEventDestroy(e);
-  for (int b = 0; b < 2; b++) {
-    if (h->stg[b]) (void)hipHostFree(h->stg[b]);
-    if (h->stg_ev[b]) (void)hipEventDestroy(h->stg_ev[b]);
-  }
-  if (h->stream) {
-    (void)hipStreamDestroy(h->stream);
-    std::lock_guard<std::mutex> lk(g_rocfft_mu);
-    if (--g_rocfft_users == 0) rocfft_cleanup();
-  }
-  delete h;
+  delete h;  // the owners release everything, in the order the handle declares
 }
 
 int bchmc_upload(bchmc_handle *h, bchmc_field field, const double *host, size_t n) {
@@ -3124,10 +3054,7 @@ struct EarlyQ {
     h->early_q_done = false;
     h->early_q_dev = nullptr;
     if (!dev || !h->copy_stream || env_on("BCHMC_NO_DOWNLOAD_OVERLAP")) return;
-    if (!h->ev_q && hipEventCreateWithFlags(&h->ev_q, hipEventDisableTiming) != hipSuccess) {
-      h->ev_q = nullptr;
-      return;
-    }
+    if (!h->ev_q && h->ev_q.create(hipEventDisableTiming) != hipSuccess) return;
     h->early_q_dev = dev;
   }
   ~EarlyQ() {
@@ -3149,7 +3076,7 @@ int bchmc_leapfrog(bchmc_handle *h, const double *q0, const double *p0, double *
   const bool prologue = !env_on("BCHMC_NO_UPLOAD_OVERLAP");
   if (prologue) {
     CHK(DISPATCH(h, plain_prologue(h)));
-    if (!h->copy_stream) HIPCHK(hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking));
+    if (!h->copy_stream) HIPCHK(h->copy_stream.create(hipStreamNonBlocking));
     CHK(h2d(h, dp, p0, bytes, h->copy_stream));
   } else {
     CHK(h2d(h, dp, p0, bytes));
@@ -3182,9 +3109,7 @@ int bchmc_leapfrog_dh(bchmc_handle *h, const double *q0, const double *p0, doubl
   const bool prologue = DISPATCH(h, host_prologue_applies(h, neps));
   if (prologue) {
     CHK(DISPATCH(h, host_prologue(h)));
-    if (!h->copy_stream) {
-      HIPCHK(hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking));
-    }
+    if (!h->copy_stream) HIPCHK(h->copy_stream.create(hipStreamNonBlocking));
     CHK(h2d(h, dp, p0, bytes, h->copy_stream));
   } else {
     CHK(h2d(h, dp, p0, bytes));
@@ -3621,12 +3546,11 @@ int bchmc_make_initial_guess(bchmc_handle *h, int32_t initial_guess, const doubl
 
 int bchmc_philox_kat(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]) {
   if (!ctr || !key || !out) return BCHMC_ERR_ARG;
-  uint4 *d = nullptr;
-  if (hipMalloc((void **)&d, sizeof(uint4)) != hipSuccess) return BCHMC_ERR_NOMEM;
+  DevBuf<uint4> d;
+  if (d.alloc(1) != hipSuccess) return BCHMC_ERR_NOMEM;
   k_philox_kat<<<1, 1>>>(make_uint4(ctr[0], ctr[1], ctr[2], ctr[3]), make_uint2(key[0], key[1]), d);
   uint4 r;
   const hipError_t e = hipMemcpy(&r, d, sizeof r, hipMemcpyDeviceToHost);
-  (void)hipFree(d);
   if (e != hipSuccess) return BCHMC_ERR_HIP;
   out[0] = r.x; out[1] = r.y; out[2] = r.z; out[3] = r.w;
   return BCHMC_OK;
@@ -3642,6 +3566,12 @@ int bchmc_tile_info(bchmc_handle *h, int32_t out[8]) {
   out[5] = 0;  // reserved
   out[6] = h->std81 ? 1 : 0;
   out[7] = (h->c2r2d_2 != nullptr) ? 1 : 0;
+  return BCHMC_OK;
+}
+
+int bchmc_live_resources(uint64_t out[4]) {
+  if (!out) return BCHMC_ERR_ARG;
+  out[0] = live.dev_bufs, out[1] = live.dev_bytes, out[2] = live.pinned, out[3] = live.other;
   return BCHMC_OK;
 }
 

@@ -8,6 +8,7 @@
 // The collective is latency-bound (tens of microseconds once per SAMPLE, i.e. per 1..itmax trajectories of several
 // milliseconds each); nothing here is on the timed leapfrog path.
 #include "../../include/bchmc.h"
+#include "owned.hpp"
 
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
@@ -77,11 +78,11 @@ struct bchmc_comm {
   // custom transport
   bchmc_allgather_fn fn = nullptr;
   void *ctx = nullptr;
-  // RCCL transport
+  // RCCL transport (owners of owned.hpp: the stream is declared first and so outlives the staging buffers)
   ncclComm_t comm = nullptr;
-  hipStream_t stream = nullptr;
-  Packet *d_send = nullptr, *d_recv = nullptr;  // device staging
-  Packet *h_pin = nullptr;                      // pinned host staging: 1 + world packets
+  owned::Stream stream;
+  owned::DevBuf<Packet> d_send, d_recv;  // device staging
+  owned::PinnedBuf<Packet> h_pin;        // pinned host staging: 1 + world packets
 
   int fail(int code, const std::string &m) {
     err = m;
@@ -131,10 +132,10 @@ int bchmc_comm_create(const unsigned char id[BCHMC_UNIQUE_ID_BYTES], int rank, i
   Rccl *r = rccl();
   if (!r->err.empty()) return c->fail(BCHMC_ERR_UNSUPPORTED, r->err);
   hipError_t e = hipSetDevice(device);
-  if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
-  if (e == hipSuccess) e = hipMalloc((void **)&c->d_send, sizeof(Packet));
-  if (e == hipSuccess) e = hipMalloc((void **)&c->d_recv, sizeof(Packet) * (size_t)world);
-  if (e == hipSuccess) e = hipHostMalloc((void **)&c->h_pin, sizeof(Packet) * (size_t)(world + 1));
+  if (e == hipSuccess) e = c->stream.create(hipStreamNonBlocking);
+  if (e == hipSuccess) e = c->d_send.alloc(1);
+  if (e == hipSuccess) e = c->d_recv.alloc((size_t)world);
+  if (e == hipSuccess) e = c->h_pin.alloc((size_t)world + 1);
   if (e != hipSuccess) return c->fail(BCHMC_ERR_HIP, std::string("bchmc_comm_create: ") + hipGetErrorString(e));
   ncclUniqueId u;
   std::memcpy(&u, id, BCHMC_UNIQUE_ID_BYTES);
@@ -151,10 +152,6 @@ void bchmc_comm_destroy(bchmc_comm *c) {
   if (c->stream || c->comm) (void)hipSetDevice(c->device);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   if (c->comm) (void)rccl()->CommDestroy(c->comm);
-  if (c->d_send) (void)hipFree(c->d_send);
-  if (c->d_recv) (void)hipFree(c->d_recv);
-  if (c->h_pin) (void)hipHostFree(c->h_pin);
-  if (c->stream) (void)hipStreamDestroy(c->stream);
   delete c;
 }
 

@@ -82,7 +82,7 @@ _lib = None
 EXPORTS = ("bchmc_create", "bchmc_destroy", "bchmc_strerror", "bchmc_last_error", "bchmc_upload", "bchmc_fetch",
            "bchmc_leapfrog", "bchmc_leapfrog_dh", "bchmc_energies", "bchmc_delta_hamiltonian", "bchmc_gradient", "bchmc_forward",
            "bchmc_leapfrog_device", "bchmc_steps_done", "bchmc_energies_device", "bchmc_sync", "bchmc_stream",
-           "bchmc_profile", "bchmc_profile_read", "bchmc_kernel_name", "bchmc_tile_info",
+           "bchmc_profile", "bchmc_profile_read", "bchmc_kernel_name", "bchmc_tile_info", "bchmc_live_resources",
            "bchmc_chain_set_state", "bchmc_chain_get_state", "bchmc_chain_set_momenta", "bchmc_chain_get_momenta",
            "bchmc_chain_draw_momenta", "bchmc_chain_attempt", "bchmc_chain_get_proposal", "bchmc_chain_accept",
            "bchmc_measure_spectrum", "bchmc_philox_kat", "bchmc_kinetic_term", "bchmc_psi",
@@ -131,6 +131,7 @@ def load():
     lib.bchmc_stream.argtypes = [vp]
     lib.bchmc_stream.restype = vp
     lib.bchmc_tile_info.argtypes = [vp, C.POINTER(C.c_int32)]
+    lib.bchmc_live_resources.argtypes = [C.POINTER(u64)]
     lib.bchmc_profile.argtypes = [vp, C.c_int]
     lib.bchmc_profile_read.argtypes = [vp, dp, C.POINTER(u64)]
     lib.bchmc_kernel_name.argtypes = [C.c_int]
@@ -186,6 +187,16 @@ def philox_kat(ctr, key):
     if rc:
         raise BchmcError(rc, lib.bchmc_strerror(rc).decode())
     return [int(x) for x in o]
+
+
+def live_resources():
+    """(device buffers, their bytes, pinned host buffers, other objects) the library holds in this process right now."""
+    lib = load()
+    out = (C.c_uint64 * 4)()
+    rc = lib.bchmc_live_resources(out)
+    if rc:
+        raise BchmcError(rc, lib.bchmc_strerror(rc).decode())
+    return tuple(int(x) for x in out)
 
 
 def _u32p(a):

@@ -304,6 +304,11 @@ int bchmc_philox_kat(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[
  * reserved (0), unrolled 81-cell kernels in use, ALPT planes pipeline available }. */
 int bchmc_tile_info(bchmc_handle *h, int32_t out[8]);
 
+/* Diagnostic (tests): what all handles and communicators of this process hold on the device right now.  out = { device
+ * buffers, their bytes, pinned host buffers, other objects (events, streams, rocFFT plans and execution infos) }; every
+ * count returns to its earlier value when what was created in between has been destroyed. */
+int bchmc_live_resources(uint64_t out[4]);
+
 /* Diagnostic (tests, diagnostics): the particle stage of the forward model from a displacement given in real space
  * instead of from a field.  psi: 3 N host doubles, the x, y and z components one after the other; particle i starts at
  * the centre of lattice cell i and is displaced by (psi[i], psi[N + i], psi[2 N + i]) (particle_pos, Lag2Eul.cc), so a
