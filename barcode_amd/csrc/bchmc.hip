@@ -1181,12 +1181,12 @@ struct Pipe {
         }
         if (h->std81) {
           if (h->fix)
-            k_scatter_tile81<T, 12, 20, true><<<grid, 256, tile_lds(h, 0, sizeof(double)), h->stream>>>(
+            k_scatter_tile81<T, 12, 20, true><<<grid, kTile81Threads, tile_lds(h, 0, sizeof(double)), h->stream>>>(
                 h->g, sp, h->tp, recs(h), h->t_off, h->t_end, h->t_woff,
                 h->t_oct, h->t_seg, h->rho_fix, h->rho_part, h->t_cnt,
                 (kOct + 1) * h->tp.ntiles + 1, fix_scale);
           else
-            k_scatter_tile81<T, 12, 20, false><<<grid, 256, tile_lds(h, 0, sizeof(double)), h->stream>>>(
+            k_scatter_tile81<T, 12, 20, false><<<grid, kTile81Threads, tile_lds(h, 0, sizeof(double)), h->stream>>>(
                 h->g, sp, h->tp, recs(h), h->t_off, h->t_end, h->t_woff,
                 h->t_oct, h->t_seg, R(h->rho), h->rho_part, h->t_cnt,
                 (kOct + 1) * h->tp.ntiles + 1, fix_scale);
@@ -1337,7 +1337,7 @@ struct Pipe {
       if (h->tiled && h->sorted_valid) {
         const int grid = h->tp.ntiles + (int)(N / h->tp.chunk) + 1;
         if (h->std81)
-          k_gather_tile81<T, 12, 20><<<grid, 256, tile_lds(h, 0, sizeof(T)), h->stream>>>(
+          k_gather_tile81<T, 12, 20><<<grid, kTile81Threads, tile_lds(h, 0, sizeof(T)), h->stream>>>(
               h->g, hp, h->tp, h->last_rsd, recs(h), h->t_off, h->t_end, h->t_woff,
               h->t_oct, h->t_seg, R(h->plike), R(h->V));
         else
@@ -2945,7 +2945,8 @@ int bchmc_create(const bchmc_config *cfg, bchmc_handle **out) {
         tp.chunk = g.N >= (1ll << 23) ? 2048 : (g.N >= (1ll << 20) ? 1024 : 256);
         if (const char *ev = std::getenv("BCHMC_CHUNK")) tp.chunk = std::min(std::max(atoi(ev), 64), 2048);
         const size_t lds = (size_t)tp.lx * tp.ly * tp.lz * sizeof(double) + cols.size() * sizeof(int4) + 128;
-        if (lds <= 64 * 1024 && g.N < (1ll << 30)) {
+        // N < 2^30 and halo <= n also keep the 32-bit cell indices of the image walk in range (tile_walk.hpp)
+        if (lds <= 64 * 1024 && g.N < (1ll << 30) && tp.R <= n) {
           h->tiled = true;
           // the unrolled kernels hard-code this stencil and tile shape
           bool is81 = h->hull_exact && cols.size() == 21 && tp.tx == 8 && tp.ty == 8 && tp.tz == 16 && tp.R == 2;

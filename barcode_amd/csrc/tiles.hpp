@@ -2,6 +2,7 @@
 // Part of the bchmc engine's kernel set; include through kernels.hpp (definition order matters).
 #pragma once
 #include "common.hpp"
+#include "tile_walk.hpp"
 
 namespace bchmc {
 
@@ -713,14 +714,10 @@ k_scatter_tile(Geo g, SphPar sp, TilePar tp, const int4 *__restrict__ cols, int 
   }
   __syncthreads();
   double flushed = 0.;  // sum of everything this work item adds to rho: the mean density needs no pass over rho
-  for (int c = threadIdx.x; c < ncell; c += blockDim.x) {
+  tile_walk(tp.lx, tp.ly, tp.lz, ox, oy, oz, n, (int)threadIdx.x, (int)blockDim.x, [&](int c, int cell) {
     const Acc v = s_tile_acc[c];
-    if (v != Acc(0)) {
-      const int cz = c % tp.lz, cy = (c / tp.lz) % tp.ly, cx = c / (tp.lz * tp.ly);
-      const int gx = (ox + cx + n) % n, gy = (oy + cy + n) % n, gz = (oz + cz + n) % n;
-      flushed += flush_cell(rho + gz + (long long)n * (gy + (long long)n * gx), v);
-    }
-  }
+    if (v != Acc(0)) flushed += flush_cell(rho + cell, v);
+  });
   if (!FIX) {  // deterministic mode: k_fix_to_rho sums the converted field in a fixed order instead
     __shared__ double s_red_flush[4];
     flushed = block_sum(flushed, s_red_flush);
@@ -748,11 +745,8 @@ k_gather_tile(Geo g, HullPar hp, TilePar tp, int rsd, const RecQuad *__restrict_
   const int n = g.n;
   const int tzi = tile % tp.ntz, tyi = (tile / tp.ntz) % tp.nty, txi = tile / (tp.ntz * tp.nty);
   const int ox = txi * tp.tx - tp.R, oy = tyi * tp.ty - tp.R, oz = tzi * tp.tz - tp.R;
-  for (int c = threadIdx.x; c < ncell; c += blockDim.x) {
-    const int cz = c % tp.lz, cy = (c / tp.lz) % tp.ly, cx = c / (tp.lz * tp.ly);
-    const int gx = (ox + cx + n) % n, gy = (oy + cy + n) % n, gz = (oz + cz + n) % n;
-    s_tile_pl[c] = plike[gz + (long long)n * (gy + (long long)n * gx)];
-  }
+  tile_walk(tp.lx, tp.ly, tp.lz, ox, oy, oz, n, (int)threadIdx.x, (int)blockDim.x,
+            [&](int c, int cell) { s_tile_pl[c] = plike[cell]; });
   __syncthreads();
   const T d_h = (T)hp.d_h, h_inv = (T)hp.h_inv, norm = (T)hp.norm;
   const HomeCell<T> hc = make_home<T>(g);
@@ -823,8 +817,11 @@ __host__ __device__ constexpr int hull81_zw(int a, int b) {
 #ifndef BCHMC_GATHER_WAVES
 #define BCHMC_GATHER_WAVES 5
 #endif
+// Workgroup size of the two 81-cell kernels, a compile-time value for their image walk (tile_walk.hpp): 256 threads
+// on the 12 x 12 x 20 image are 12 rows per pass, one x-slab, so a thread's (cy, cz) never changes.
+constexpr int kTile81Threads = 256;
 template <typename T, int LY, int LZ, bool FIX>
-__global__ void __launch_bounds__(256, BCHMC_SCATTER_WAVES)
+__global__ void __launch_bounds__(kTile81Threads, BCHMC_SCATTER_WAVES)
 k_scatter_tile81(Geo g, SphPar sp, TilePar tp, const RecQuad *__restrict__ srec,
                  const long long *__restrict__ off, const long long *__restrict__ tend, const int *__restrict__ woff,
                  const int4 *__restrict__ oct, const int *__restrict__ seg_in,
@@ -845,8 +842,10 @@ k_scatter_tile81(Geo g, SphPar sp, TilePar tp, const RecQuad *__restrict__ srec,
   OctMap om;
   if (!tile_work((int)blockIdx.x, tp, off, tend, woff, oct, seg_in, tile, rec0, pb, pe, om)) return;
   srec += rec0 * rec_quads<T>();  // this tile's record slots; pb, pe are relative to them
-  const int ncell = tp.lx * LY * LZ;
-  for (int c = threadIdx.x; c < ncell; c += blockDim.x) s_tile_acc[c] = Acc(0);
+  // all-zero bits are Acc(0) for the double and for the fixed-point image; LY * LZ is even: 16 bytes per lane
+  static_assert(sizeof(Acc) == 8 && (LY * LZ) % 2 == 0, "the image is zeroed two cells at a time");
+  const int ncell2 = tp.lx * (LY * LZ / 2);
+  for (int c = threadIdx.x; c < ncell2; c += blockDim.x) reinterpret_cast<int4 *>(s_raw_scatter81)[c] = make_int4(0, 0, 0, 0);
   const T d = (T)g.d;
   const HomeCell<T> hc = make_home<T>(g);
   __syncthreads();
@@ -918,14 +917,10 @@ k_scatter_tile81(Geo g, SphPar sp, TilePar tp, const RecQuad *__restrict__ srec,
   }
   __syncthreads();
   double flushed = 0.;  // sum of everything this work item adds to rho: the mean density needs no pass over rho
-  for (int c = threadIdx.x; c < ncell; c += blockDim.x) {
+  tile_walk<LY, LZ, kTile81Threads>(tp.lx, LY, LZ, ox, oy, oz, n, (int)threadIdx.x, kTile81Threads, [&](int c, int cell) {
     const Acc v = s_tile_acc[c];
-    if (v != Acc(0)) {
-      const int cz = c % LZ, cy = (c / LZ) % LY, cx = c / (LZ * LY);
-      const int gx = (ox + cx + n) % n, gy = (oy + cy + n) % n, gz = (oz + cz + n) % n;
-      flushed += flush_cell(rho + gz + (long long)n * (gy + (long long)n * gx), v);
-    }
-  }
+    if (v != Acc(0)) flushed += flush_cell(rho + cell, v);
+  });
   if (!FIX) {  // deterministic mode: k_fix_to_rho sums the converted field in a fixed order instead
     __shared__ double s_red_flush[4];
     flushed = block_sum(flushed, s_red_flush);
@@ -938,7 +933,7 @@ k_scatter_tile81(Geo g, SphPar sp, TilePar tp, const RecQuad *__restrict__ srec,
 // share of the LDS-active cycles (r02 SQ counters) is the birthday statistics of 16 random addresses per cycle on 32
 // banks, not a stride effect -- measured with a row stride of LZ + 1 (profiles/r03_ab_levers.txt): no change.
 template <typename T, int LY, int LZ>
-__global__ void __launch_bounds__(256, BCHMC_GATHER_WAVES)
+__global__ void __launch_bounds__(kTile81Threads, BCHMC_GATHER_WAVES)
 k_gather_tile81(Geo g, HullPar hp, TilePar tp, int rsd, const RecQuad *__restrict__ srec,
                 const long long *__restrict__ off,
                 const long long *__restrict__ tend, const int *__restrict__ woff, const int4 *__restrict__ oct,
@@ -950,15 +945,11 @@ k_gather_tile81(Geo g, HullPar hp, TilePar tp, int rsd, const RecQuad *__restric
   OctMap om;
   if (!tile_work((int)blockIdx.x, tp, off, tend, woff, oct, seg_in, tile, rec0, pb, pe, om)) return;
   srec += rec0 * rec_quads<T>();  // this tile's record slots; pb, pe are relative to them
-  const int ncell = tp.lx * LY * LZ;
   const int n = g.n;
   const int tzi = tile % tp.ntz, tyi = (tile / tp.ntz) % tp.nty, txi = tile / (tp.ntz * tp.nty);
   const int ox = txi * tp.tx - 2, oy = tyi * tp.ty - 2, oz = tzi * tp.tz - 2;
-  for (int c = threadIdx.x; c < ncell; c += blockDim.x) {
-    const int cz = c % LZ, cy = (c / LZ) % LY, cx = c / (LZ * LY);
-    const int gx = (ox + cx + n) % n, gy = (oy + cy + n) % n, gz = (oz + cz + n) % n;
-    s_tile_pl[cz + LZ * (cy + LY * cx)] = plike[gz + (long long)n * (gy + (long long)n * gx)];
-  }
+  tile_walk<LY, LZ, kTile81Threads>(tp.lx, LY, LZ, ox, oy, oz, n, (int)threadIdx.x, kTile81Threads,
+                                    [&](int c, int cell) { s_tile_pl[c] = plike[cell]; });
   __syncthreads();
   const T d_h = (T)hp.d_h, h_inv = (T)hp.h_inv, norm = (T)hp.norm;
   const HomeCell<T> hc = make_home<T>(g);

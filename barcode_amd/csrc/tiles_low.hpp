@@ -119,14 +119,10 @@ k_scatter_tile_low(Geo g, TilePar tp, int mk, const RecQuad *__restrict__ srec, 
   }
   __syncthreads();
   double flushed = 0.;  // what this work item adds to rho: the mean density needs no pass over rho
-  for (int c = threadIdx.x; c < ncell; c += blockDim.x) {
+  tile_walk(lx, ly, lz, ox, oy, oz, n, (int)threadIdx.x, (int)blockDim.x, [&](int c, int cell) {
     const Acc v = img[c];
-    if (v != Acc(0)) {
-      const int cz = c % lz, cy = (c / lz) % ly, cx = c / (lz * ly);
-      const int gx = (ox + cx + n) % n, gy = (oy + cy + n) % n, gz = (oz + cz + n) % n;
-      flushed += flush_cell(rho + gz + (long long)n * (gy + (long long)n * gx), v);
-    }
-  }
+    if (v != Acc(0)) flushed += flush_cell(rho + cell, v);
+  });
   if (!FIX) {
     __shared__ double s_red_low[4];
     flushed = block_sum(flushed, s_red_low);
@@ -154,14 +150,12 @@ k_interp_tsc_tile(Geo g, TilePar tp, int rsd, double f1, const RecQuad *__restri
   const int n = g.n;
   const int tzi = tile % tp.ntz, tyi = (tile / tp.ntz) % tp.nty, txi = tile / (tp.ntz * tp.nty);
   const int ox = txi * tp.tx - kLowHalo, oy = tyi * tp.ty - kLowHalo, oz = tzi * tp.tz - kLowHalo;
-  for (int c = threadIdx.x; c < ncell; c += blockDim.x) {
-    const int cz = c % lz, cy = (c / lz) % ly, cx = c / (lz * ly);
-    const int gx = (ox + cx + n) % n, gy = (oy + cy + n) % n, gz = (oz + cz + n) % n;
-    const long long f = gz + (long long)n * (gy + (long long)n * gx);
+  tile_walk(lx, ly, lz, ox, oy, oz, n, (int)threadIdx.x, (int)blockDim.x, [&](int c, int cell) {
+    const long long f = cell;
     img[c] = conv[f];
     img[c + ncell] = conv[f + g.N];
     img[c + 2 * ncell] = conv[f + 2 * g.N];
-  }
+  });
   __syncthreads();
   for (int s = pb + threadIdx.x; s < pe; s += blockDim.x) {
     T xt, yt, zt;

@@ -17,6 +17,7 @@ __global__ void __launch_bounds__(1024) k_rate(double *out, unsigned long long *
   double a0 = seed + threadIdx.x, a1 = a0 + 1., a2 = a0 + 2., a3 = a0 + 3., a4 = a0 + 4., a5 = a0 + 5., a6 = a0 + 6.,
          a7 = a0 + 7.;
   float f0 = (float)a0;
+  unsigned u0 = threadIdx.x | 1u;
   lds[threadIdx.x] = 0.;
   lds[threadIdx.x + 1024] = 0.;
   __syncthreads();
@@ -82,11 +83,16 @@ __global__ void __launch_bounds__(1024) k_rate(double *out, unsigned long long *
       REP8(asm volatile("v_sqrt_f64 %0, %0\n v_sqrt_f64 %1, %1\n v_sqrt_f64 %2, %2\n v_sqrt_f64 %3, %3\n"
                         "v_sqrt_f64 %4, %4\n v_sqrt_f64 %5, %5\n v_sqrt_f64 %6, %6\n v_sqrt_f64 %7, %7\n"
                         : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(a5), "+v"(a6), "+v"(a7));)
+    } else if (OP == 12) {  // v_mul_lo_u32 (what a run-time division or modulo expands into, several per quotient)
+      REP64(asm volatile("v_mul_lo_u32 %0, %0, %1\n" : "+v"(u0) : "v"(u0));)
+    } else if (OP == 13) {  // v_mul_u32_u24 (reference point for the integer multiplier)
+      REP64(asm volatile("v_mul_u32_u24 %0, %0, %1\n" : "+v"(u0) : "v"(u0));)
     }
   }
   const unsigned long long t1 = __builtin_amdgcn_s_memtime();
   if ((threadIdx.x & 63) == 0) cyc[blockIdx.x * (blockDim.x / 64) + threadIdx.x / 64] = t1 - t0;
-  out[blockIdx.x * blockDim.x + threadIdx.x] = a0 + a1 + a2 + a3 + a4 + a5 + a6 + a7 + (double)f0 + lds[threadIdx.x];
+  out[blockIdx.x * blockDim.x + threadIdx.x] =
+      a0 + a1 + a2 + a3 + a4 + a5 + a6 + a7 + (double)f0 + (double)u0 + lds[threadIdx.x];
 }
 
 template <int OP>
@@ -127,5 +133,7 @@ int main() {
   run<5>("v_rsq_f32", 64);
   run<6>("cvt_f32_f64 + rsq_f32 + cvt_f64_f32 (triple)", 64);
   run<7>("ds_add_f64 (scattered cells)", 64);
+  run<12>("v_mul_lo_u32", 64);
+  run<13>("v_mul_u32_u24", 64);
   return 0;
 }
