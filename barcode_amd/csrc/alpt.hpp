@@ -148,12 +148,12 @@ __global__ void __launch_bounds__(256) k_alpt_mix(Geo g, C2<T> *Ck, double smol,
     const double ksq = kx * kx + ky * ky + kz * kz;
     const double2 A = ld2<T>(Ck, idx), B = ld2<T>(Ck, idx + g.Nhp);
     double2 ox = make_double2(0., 0.), oy = ox, oz = ox;
-    const bool nyq = (i == g.n / 2) || (j == g.n / 2) || (k == g.n / 2);
-    if (ksq > 1.e-14 && !nyq) {
+    const double keep = nyq_keep(g.n, i, j, k);
+    if (ksq > 1.e-14 && keep != 0.) {
       const double K = exp(-ksq * smol * smol / 2.) * inv_wtot;
       // K o Psi^2LPT + Psi^SC - K o Psi^SC, in the reference's order of operations (Lag2Eul.cc:240-250)
       const double mr = (K * A.x + B.x) - K * B.x, mi = (K * A.y + B.y) - K * B.y;
-      const double fac = inv_n / ksq;
+      const double fac = keep * inv_n / ksq;
       double sn, cs;
       sincospi(-2. * (double)((i + j + k) % g.n) / (double)g.n, &sn, &cs);
       const double pr = 0.5 * (1. + cs), pi = 0.5 * sn;

@@ -3275,6 +3275,10 @@ int bchmc_chain_draw_momenta_mt19937(bchmc_handle *h, uint32_t mt[624], int32_t 
   if (!h || !mt || !mti) return BCHMC_ERR_ARG;
   if (*mti < 0 || *mti > 624) return h->fail(BCHMC_ERR_ARG, "mti = %d outside [0, 624]", (int)*mti);
   ENTER(h);
+  // the Fourier-space part is placed by create_GARFIELD's walk (mt_walk_index), which pairs i with n - i around i = n / 2;
+  // the real-space part (mass_type 0, 6, 60) is white noise per cell and has no such condition
+  if (h->mass_fs && (h->g.n & 1))
+    return h->fail(BCHMC_ERR_UNSUPPORTED, "create_GARFIELD's placement needs an even Nx (%d)", h->g.n);
   if (h->mass_fs && !h->have[BCHMC_F_MASS_F]) return h->fail(BCHMC_ERR_STATE, "mass_f was never uploaded");
   if (h->mass_rs && !h->have[BCHMC_F_MASS_R]) return h->fail(BCHMC_ERR_STATE, "mass_r was never uploaded");
   CHK(DISPATCH(h, chain_alloc(h)));

@@ -47,6 +47,23 @@ __device__ __forceinline__ double kval(int i, int n, double kfac) {
   return (i <= n / 2) ? kfac * (double)i : -kfac * (double)(n - i);
 }
 
+// The reference zeroes the displacement and the force on (i == N1/2) || (j == N2/2) || (k == N3/2), dividing as integers
+// (EqSolvers.cc:254-265, gradient.cpp:167-210).  At even n these are the Nyquist planes and each is its own conjugate
+// partner.  At odd n the rule hits the ordinary mode n / 2 and leaves its partner n - n / 2 alone.  In the plane k = 0,
+// where both partners are stored, the masked array is then not Hermitian, and the reference's complex-to-real transform
+// (complex along x and y, then half-complex along z, which reads the real part of its k = 0 element only) returns the
+// transform of the Hermitian part: the mask m(i, j) acts as (m(i, j) + m(-i, -j)) / 2.  nyq_keep is that weight -- 1, 1/2 or
+// 0; 1 or 0 at even n and for k > 0, whose partners are not stored -- so every half-complex array the engine keeps or
+// transforms is the transform of a real field (the Parseval sums of the energies, the resident p^ and q^ and the force
+// spectrum of the mass need that, and no C2R is handed a non-Hermitian plane) and the fields are the reference's.
+__device__ __forceinline__ double nyq_keep(int n, int i, int j, int k) {
+  const int h = n / 2;
+  const double own = ((i == h) || (j == h) || (k == h)) ? 0. : 1.;
+  if ((n & 1) == 0 || k != 0) return own;
+  const int ic = i ? n - i : 0, jc = j ? n - j : 0;
+  return 0.5 * (own + (((ic == h) || (jc == h)) ? 0. : 1.));
+}
+
 __device__ __forceinline__ double r_fmod(double a, double b) { return fmod(a, b); }
 __device__ __forceinline__ float r_fmod(float a, float b) { return fmodf(a, b); }
 __device__ __forceinline__ double r_floor(double a) { return floor(a); }

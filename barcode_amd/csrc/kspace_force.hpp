@@ -22,11 +22,11 @@ __device__ __forceinline__ double2 assemble_g(const Geo &g, const C2<T> *__restr
   if (like_mode == 0) {
     const long long ij = idx / g.nhp;
     const int j = (int)(ij % g.n), i = (int)(ij / g.n);
-    const bool nyq = (i == g.n / 2) || (j == g.n / 2) || (k == g.n / 2);
+    const double keep = nyq_keep(g.n, i, j, k);
     const double kx = kval(i, g.n, g.kfac), ky = kval(j, g.n, g.kfac), kz = kval(k, g.n, g.kfac);
     const double kmod = kx * kx + ky * ky + kz * kz;
-    if (kmod > 0 && !nyq) {
-      const double f = 1 / kmod;
+    if (kmod > 0 && keep != 0.) {
+      const double f = keep / kmod;
       const double2 vx = ld2<T>(Ck, idx), vy = ld2<T>(Ck, idx + g.Nhp), vz = ld2<T>(Ck, idx + 2 * g.Nhp);
       const double fx = kx * f, fy = ky * f, fz = kz * f;
       hk.x = fx * vx.y + fy * vy.y + fz * vz.y;
@@ -134,9 +134,9 @@ k_step_boundary(Geo g, C2<T> *Ck, const C2<T> *q_in, const C2<T> *p_in, C2<T> *q
     const double kx = kval(i, g.n, g.kfac), ky = kval(j, g.n, g.kfac), kz = kval(k, g.n, g.kfac);
     const double ksq = kx * kx + ky * ky + kz * kz;
     double2 ox = make_double2(0., 0.), oy = ox, oz = ox;
-    const bool nyq = (i == g.n / 2) || (j == g.n / 2) || (k == g.n / 2);
-    if (ksq > 1.e-14 && !nyq) {
-      const double fac = 1. / ksq;
+    const double keep = nyq_keep(g.n, i, j, k);
+    if (ksq > 1.e-14 && keep != 0.) {
+      const double fac = keep / ksq;
       const double pr = c_za * q.x, pi = c_za * q.y;
       const double fx = fac * kx, fy = fac * ky, fz = fac * kz;
       ox = make_double2(fx * pi, fx * -pr);

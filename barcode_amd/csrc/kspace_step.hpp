@@ -98,9 +98,9 @@ k_kick_drift_za(Geo g, C2<T> *__restrict__ qk, C2<T> *__restrict__ pk, const C2<
     const double kx = kval(i, g.n, g.kfac), ky = kval(j, g.n, g.kfac), kz = kval(k, g.n, g.kfac);
     const double ksq = kx * kx + ky * ky + kz * kz;
     double2 ox = make_double2(0., 0.), oy = ox, oz = ox;
-    const bool nyq = (i == g.n / 2) || (j == g.n / 2) || (k == g.n / 2);
-    if (ksq > 1.e-14 && !nyq) {
-      const double fac = 1. / ksq;
+    const double keep = nyq_keep(g.n, i, j, k);
+    if (ksq > 1.e-14 && keep != 0.) {
+      const double fac = keep / ksq;
       const double pr = c_za * q.x, pi = c_za * q.y;
       const double fx = fac * kx, fy = fac * ky, fz = fac * kz;
       ox = make_double2(fx * pi, fx * -pr);

@@ -179,15 +179,15 @@ k_gradfft_mult(Geo g, const C2<T> *__restrict__ fk, C2<T> *__restrict__ Ck, doub
     const int k = (int)(idx % g.nhp);
     const long long ij = idx / g.nhp;
     const int j = (int)(ij % g.n), i = (int)(ij / g.n);
-    const bool nyq = (i == g.n / 2) || (j == g.n / 2) || (k == g.n / 2);
+    const double keep = nyq_keep(g.n, i, j, k) * inv_n;
     const double2 v = ld2<T>(fk, idx);
     const double kk[3] = {kval(i, g.n, g.kfac), kval(j, g.n, g.kfac), kval(k, g.n, g.kfac)};
 #pragma unroll
     for (int c = 0; c < 3; c++) {
-      if (nyq)
+      if (keep == 0.)
         st2<T>(Ck, idx + c * g.Nhp, 0., 0.);
       else
-        st2<T>(Ck, idx + c * g.Nhp, -kk[c] * v.y * inv_n, kk[c] * v.x * inv_n);
+        st2<T>(Ck, idx + c * g.Nhp, -kk[c] * v.y * keep, kk[c] * v.x * keep);
     }
   }
 }

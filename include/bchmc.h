@@ -27,7 +27,15 @@ extern "C" {
  * reference (init_par.cc:116-118). */
 typedef struct bchmc_config {
   uint32_t abi_version;      /* must be BCHMC_ABI_VERSION */
-  uint32_t Nx;               /* N1 = N2 = N3 */
+  uint32_t Nx;               /* N1 = N2 = N3.  Any Nx >= 4 with particle_kernel_h <= L / 4 is accepted, odd ones included:
+                              * 4 runs the tile kernels on one 4^3 tile, 5, 6, 7 and every other size no tile shape divides
+                              * the direct ones.  At odd Nx the reference's "Nyquist" rule i == Nx / 2 (integer division)
+                              * zeroes an ordinary mode; it is kept as it is.  Entry points that need an even Nx (they
+                              * return BCHMC_ERR_UNSUPPORTED naming Nx before anything is queued, the generator state and
+                              * the handle untouched): bchmc_chain_draw_momenta_mt19937 with a Fourier-space mass,
+                              * bchmc_setup_random_test, bchmc_make_initial_guess 2 and 3 -- all through create_GARFIELD's
+                              * walk, which pairs i with Nx - i around Nx / 2 -- and bchmc_garfield_walk_index itself
+                              * (BCHMC_ERR_ARG, it has no handle) */
   double L;                  /* L1 = L2 = L3 [Mpc/h] */
   double min1, min2, min3;   /* xllc, yllc, zllc */
   double xobs, yobs, zobs;
@@ -185,7 +193,9 @@ int bchmc_chain_draw_momenta(bchmc_handle *h, uint64_t seed, uint64_t attempt);
  * draw, out: the state GSL holds after it.  words_used may be NULL.
  * Exactly the reference's momenta: create_GARFIELD's Gaussians in the walk of resolution_independent_random_grid_FS,
  * then the real-space part from the same stream (polar Box-Muller, r2 without FMA contraction; log / sqrt may differ
- * from glibc by an ulp).  The first call on a handle also precomputes the stream's jump polynomials (host, once). */
+ * from glibc by an ulp).  The first call on a handle also precomputes the stream's jump polynomials (host, once).
+ * Odd Nx with a Fourier-space mass (mass_type 1 .. 5): BCHMC_ERR_UNSUPPORTED before anything is queued, mt / mti and the
+ * resident momenta untouched (the walk is defined for even Nx); the real-space types 0, 6 and 60 draw at any Nx. */
 int bchmc_chain_draw_momenta_mt19937(bchmc_handle *h, uint32_t mt[624], int32_t *mti, uint64_t *words_used);
 /* host only (tests, callers that skip ahead): the state `steps` outputs later */
 int bchmc_mt19937_jump(const uint32_t mt_in[624], int32_t mti_in, uint64_t steps, uint32_t mt_out[624], int32_t *mti_out);
@@ -287,14 +297,16 @@ typedef struct bchmc_mock_opts {
  * gsl_ran_poisson consumes a data-dependent number of words per cell through the rejection loops of gsl_ran_gamma_int /
  * gsl_ran_binomial, so where cell i starts in the stream depends on every earlier cell's draw -- not a scan with
  * bounded state.  After the draw: a windowed cell with noise == 0 under likelihood 1 or 3 -> BCHMC_ERR_STATE naming the
- * first such index (:190-198); the generator has then advanced like upstream's, the three arrays count as not uploaded. */
+ * first such index (:190-198); the generator has then advanced like upstream's, the three arrays count as not uploaded.
+ * Odd Nx: BCHMC_ERR_UNSUPPORTED, refused like the two cases above (create_GARFIELD's walk is defined for even Nx). */
 int bchmc_setup_random_test(bchmc_handle *h, const bchmc_mock_opts *o, uint32_t mt[624], int32_t *mti,
                             uint64_t *words_used, double *delta_lag, double *delta_eul);
 /* make_initial_guess: sets the resident chain state like bchmc_chain_set_state.  initial_guess 0: zero; 1: file_field (N
  * host doubles); 2: create_GARFIELD(signal_PS) from the stream, placed in k-space directly; 3: the same, then
  * kernelcomp(smoothing_scale, smoothing_type) o convcomp as one k-space multiply (type 1, the Gaussian kernel, only;
  * others BCHMC_ERR_ARG); 4: N draws gsl_ran_gaussian(r, 0.1) in cell order.  Cases 0 and 1 leave the generator as it is
- * (mt / mti may be NULL) and report 0 words. */
+ * (mt / mti may be NULL) and report 0 words.  Odd Nx: 2 and 3 return BCHMC_ERR_UNSUPPORTED before anything is queued
+ * (create_GARFIELD's walk), generator and chain state untouched; 0, 1 and 4 work at any Nx. */
 int bchmc_make_initial_guess(bchmc_handle *h, int32_t initial_guess, const double *file_field, int32_t smoothing_type,
                              double smoothing_scale, uint32_t mt[624], int32_t *mti, uint64_t *words_used);
 int bchmc_philox_kat(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]); /* known-answer hook for tests */

@@ -42,6 +42,12 @@ CASES = {
     "poisson_off_8": dict(Nx=8, likelihood=0, rsd_model=0, eps_scale=0.01, **OFF),
     "lognormal_off_8": dict(Nx=8, likelihood=2, rsd_model=0, **OFF_LN),
     "gauss_alpt_off_8": dict(Nx=8, likelihood=1, rsd_model=0, sfmodel=2, **OFF),
+    # odd grids and the smallest one ("Grid sizes").  Step sizes probed for the ten steps in the same way:
+    # amplification 27, 4.9, 0.66 (881 at the default 0.03) and 1.3 (103 at the default 0.1).
+    "gauss_rsd_9": dict(Nx=9, likelihood=1, rsd_model=1),
+    "gauss_alpt_5": dict(Nx=5, likelihood=1, rsd_model=0, sfmodel=2),
+    "poisson_7": dict(Nx=7, likelihood=0, rsd_model=0, eps_scale=0.01),
+    "gauss_rsd_4": dict(Nx=4, likelihood=1, rsd_model=1, eps_scale=0.03),
 }
 NEPS = 10
 

@@ -86,13 +86,17 @@ long long check_case(const Case &k, int nt) {
 
 int main() {
   const Case cases[] = {{16, 8, 8, 16, 2}, {32, 8, 8, 16, 2}, {48, 8, 8, 16, 2}, {256, 8, 8, 16, 2},
-                        {24, 8, 8, 8, 2},  {12, 4, 4, 4, 2},  {16, 8, 8, 16, 1}, {32, 8, 8, 16, 1}};
+                        {24, 8, 8, 8, 2},  {12, 4, 4, 4, 2},  {16, 8, 8, 16, 1}, {32, 8, 8, 16, 1},
+                        // n = 4: ONE tile whose halo wraps onto the tile on every axis (halo 2: the image is (2 n)^3 and
+                        // holds every cell 8 times); halo 1 (low-order kernels), 3 (the cube loop of h = 1.3 d), 4 = n
+                        {4, 4, 4, 4, 2},   {4, 4, 4, 4, 1},   {4, 4, 4, 4, 3},   {4, 4, 4, 4, 4}};
   long long tiles = 0;
   for (const Case &k : cases) tiles += check_case(k, 256);
   // not what the kernels launch, but what the walker promises: other block sizes -- a row longer than the block
   // (several cells per lane), a block one row wide, one that is no multiple of anything, more rows per pass than ly --
   // and a halo as wide as the tile
-  const Case extra[] = {{16, 8, 8, 16, 2}, {12, 4, 4, 4, 2}, {16, 8, 8, 16, 1}, {8, 4, 4, 4, 4}, {24, 8, 8, 8, 3}};
+  const Case extra[] = {{16, 8, 8, 16, 2}, {12, 4, 4, 4, 2}, {16, 8, 8, 16, 1}, {8, 4, 4, 4, 4}, {24, 8, 8, 8, 3},
+                        {4, 4, 4, 4, 2},   {4, 4, 4, 4, 4}};
   const int blocks[] = {1, 7, 16, 20, 64, 100, 1024};
   for (const Case &k : extra)
     for (int nt : blocks) tiles += check_case(k, nt);

@@ -217,6 +217,43 @@ def test_grid_and_tile_shapes(n, expect, names):
         run_sph(n, 1.0, 1, ("mixed", "collapse_corner") if n == 32 else ("mixed", "corners"), expect=expect)
 
 
+# collapse_inside puts every particle around (3.6, 3.3, 5.4) d: outside the box at n = 4 and 5, where it would only be a
+# second collapse_corner-like set after folding.  It is the one set left out, at those two sizes.
+SMALL_BOX_SETS = tuple(s for s in ref.ALL_SETS if s != "collapse_inside")
+
+
+@pytest.mark.parametrize("precision", (0, 1), ids=("fp64", "fp32"))
+@pytest.mark.parametrize("n,h_rel,no_tiles,expect", ((4, 1.0, False, "tile"), (4, 0.87, False, "tile"), (4, 1.0, True, "sph"),
+                                                     (5, 1.0, False, "sph"), (7, 1.0, False, "sph")),
+                         ids=("n4_tile", "n4_tile_h0.87", "n4_direct", "n5_direct", "n7_direct"))
+def test_smallest_and_odd_grids(n, h_rel, no_tiles, expect, precision, monkeypatch):
+    """4^3: one 4 x 4 x 4 tile whose halo wraps onto the tile on every axis (every cell is in the image 8 times), at h = d
+    and at h = 0.87 d; the direct kernels there (BCHMC_NO_TILES=1: stencil offsets -2 and +2 are one cell); 5^3 (the stencil
+    is as wide as the box) and 7^3 on the direct kernels.  Every set but collapse_inside at 4 and 5 (SMALL_BOX_SETS), every
+    set at 7; RSD on a second pass."""
+    if no_tiles:
+        monkeypatch.setenv("BCHMC_NO_TILES", "1")
+    names = ref.ALL_SETS if n == 7 else SMALL_BOX_SETS
+    run_sph(n, h_rel, precision, names, expect=expect, impulse_on=("uniform", "corners"))
+    run_sph(n, h_rel, precision, ("mixed", "faces", "far_out"), rsd=1, expect=expect)
+
+
+@pytest.mark.parametrize("precision", (0, 1), ids=("fp64", "fp32"))
+@pytest.mark.parametrize("mk", (0, 1, 2), ids=("ngp", "cic", "tsc"))
+def test_low_order_kernels_on_an_odd_grid(mk, precision):
+    """NGP / CIC / TSC at 9^3: no tile shape divides it, the direct form runs."""
+    dtype = DTYPE[precision]
+    p = params(9, mk=mk, calc_h=1)
+    geo = ref.Geometry(9, p.L)
+    e = engine(p, precision)
+    assert family(e.tile_info(), mk, 9) == "scatter_low_order"
+    for name, psi in ref.position_sets(geo, dtype, names=ref.ALL_SETS).items():
+        e.probe_displacement(psi, 0, False)
+        pos = check_positions(e, p, psi, 0, dtype)
+        check_density(e, p, pos, dtype, "mk=%d %s" % (mk, name))
+    e.close()
+
+
 def test_one_case_at_64():
     run_sph(64, 1.0, 0, ("mixed",), expect="tile81")
 
@@ -365,7 +402,16 @@ def test_adjoint_identity_against_a_finite_difference():
     along e.  The derivative is a longdouble central difference of pm_reference's density functional with step s =
     2^-20 d; its truncation error is estimated from the pair (s, s / 2): for an O(s^2) error the two differ by three
     times the error of the finer one, so |D(s) - D(s / 2)| bounds it with room.  On top comes the summed gather bound."""
-    n, dtype = 16, np.float64
+    adjoint_identity(16)
+
+
+def test_adjoint_identity_against_a_finite_difference_at_5():
+    """The same identity where the stencil is as wide as the box (direct kernels)."""
+    adjoint_identity(5)
+
+
+def adjoint_identity(n):
+    dtype = np.float64
     p = params(n)
     geo = ref.Geometry(n, p.L)
     psi = ref.position_sets(geo, dtype, names=("mixed",))["mixed"]

@@ -10,6 +10,9 @@ tests/pm_bound.py (their derivation is there; nothing is added to them here):
     16^3, 32^3, 48^3    k_scatter_tile81 / k_gather_tile81, float64 and float32 (16^3: the halo wraps onto the tile)
     24^3                k_scatter_tile / k_gather_tile (8 x 8 x 8 tiles)
     32^3 with mk = 1    k_scatter_tile_low (CIC; the 10 x 10 x 18 image)
+    12^3                k_scatter_tile / k_gather_tile (4 x 4 x 4 tiles, 27 of them)
+    4^3                 the same with ONE 4 x 4 x 4 tile, float64 and float32: the halo (R = 2) wraps onto the tile on all
+                        three axes, the 8 x 8 x 8 image is (2 n)^3 and holds every global cell 8 times; and with mk = 1
 
 rho cell by cell and V particle by particle must be under the bound, what the reference leaves empty must be exactly 0,
 and with deterministic=1 two fresh handles must give identical rho and V.  The reference density of a case is computed
@@ -30,7 +33,8 @@ pytestmark = pytest.mark.gpu
 DTYPE = {0: np.float64, 1: np.float32}
 # (n, mk, precision, kernel family)
 CASES = [(16, 3, 0, "tile81"), (16, 3, 1, "tile81"), (32, 3, 0, "tile81"), (32, 3, 1, "tile81"), (48, 3, 0, "tile81"),
-         (48, 3, 1, "tile81"), (24, 3, 0, "tile"), (32, 1, 0, "tile_low")]
+         (48, 3, 1, "tile81"), (24, 3, 0, "tile"), (32, 1, 0, "tile_low"),
+         (4, 3, 0, "tile"), (4, 3, 1, "tile"), (12, 3, 0, "tile"), (4, 1, 0, "tile_low")]
 IDS = ["n%d-mk%d-%s" % (n, mk, ("fp64", "fp32")[pr]) for n, mk, pr, _ in CASES]
 
 

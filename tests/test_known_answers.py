@@ -1,4 +1,4 @@
-"""Hand-derived known answers for three pieces of the path, checked by BOTH the oracle (CPU tests) and the engine
+"""Hand-derived known answers for three pieces of the path (K2 also on an odd grid, K2o), checked by BOTH the oracle (CPU tests) and the engine
 (``-m gpu`` tests).  They do not lift "parity unpinned" (the reference holds no vectors for this path and cannot be
 built here) but they anchor the oracle -- and the engine -- to closed forms derived from the reference's formulas
 instead of to each other.
@@ -18,6 +18,20 @@ K2  Zel'dovich displacement of one plane wave (``theta2vel``, EqSolvers.cc:168-2
     inverse-Laplacian phi = -phi / k0^2 = D1 A cos(k0 x) / k0^2, so
         Psi_x(x_i) = -(D1 A / k0) sin(k0 x_i),   Psi_y = Psi_z = 0,
     and the particle of cell i sits at (i + 1/2) d + Psi_x(x_i) (``disp_part``, disp_part.cc:55-107), wrapped to [0, L).
+
+K2o K2 on an odd grid, n = 9: the reference's "Nyquist" rule (i == N1/2) || (j == N2/2) || (k == N3/2) (EqSolvers.cc:254-265)
+    divides as integers, so at n = 9 it zeroes index 4, the ordinary mode m = 4, and leaves its conjugate partner,
+    index n - 4 = 5 (m = -4), alone.  The arrays are half-complex along z (k = 0 .. 4) and full along x and y.
+      m = 3 along any axis: untouched by the rule, the K2 closed form.
+      m = 4 along z: the pair (k, n - k) = (4, 5) is stored once, as k = 4, and that element is zeroed: Psi == 0.
+      m = 4 along x (or y): the wave is A/2 at i = 4 plus A/2 at i = 5, both in the plane k = 0.  i = 4 is zeroed, i = 5
+        keeps its -i k_x / k^2 factor, and the plane is no longer Hermitian.  The complex-to-real transform (FFTW's, and
+        the oracle's: complex transforms along x and y, then the half-complex one along z, which reads the real part
+        of its k = 0 element and nothing of the imaginary part) returns the real part of the surviving exponential,
+        Re[(i D1 A / (2 k0)) e^{-i k0 x}] -- exactly half of the wave:
+            Psi_x(x_i) = -(D1 A / (2 k0)) sin(k0 x_i),   k0 = 2 pi 4 / L,   Psi_y = Psi_z = 0.
+    A true Nyquist rule ((n & 1) == 0 && i == n / 2) would leave both untouched and give the full K2 form for m = 4, so
+    either answer separates the two rules; every odd-n trajectory of the suite carries this half of the i = 4 planes.
 
 K3  SPH-kernel gradient gather for a single excited cell (``likelihood_calc_V_SPH``, HMC_models.cc:200-303, with
     ``grad_SPH_kernel_3D_h_units``, SPH_kernel.cpp:148-208).  On the undisplaced lattice with part_like = 1 in one cell
@@ -165,6 +179,62 @@ def test_k2_engine_plane_wave_displacement(m):
     exp = ((np.arange(N) + 0.5) * D)[:, None, None] + psi_x
     exp = np.where(exp < 0, exp + L, np.where(exp >= L, exp - L, exp))
     assert np.max(np.abs(e.fetch("posx").reshape(N, N, N) - exp)) < 1e-12
+    e.close()
+
+
+# ---- K2o: K2 at n = 9 ----------------------------------------------------------------------------------------
+N9 = 9
+L9 = D * N9                    # the same cell size
+# (axis, m, the fraction of the K2 closed form that survives the integer-division rule)
+K2_ODD = [(0, 3, 1.0), (1, 3, 1.0), (2, 3, 1.0), (0, 4, 0.5), (1, 4, 0.5), (2, 4, 0.0)]
+K2_ODD_IDS = ["%s-m%d" % ("xyz"[a], m) for a, m, _ in K2_ODD]
+
+
+def k2_odd_expected(axis, m, part, A=0.3):
+    """(delta, Psi along the axis, the K2 amplitude A / k0, position along the axis) at n = 9, D1 = 1."""
+    k0 = 2 * np.pi * m / L9
+    x = np.arange(N9) * D
+    shape = [1, 1, 1]
+    shape[axis] = N9
+    full = (N9,) * 3
+    delta = np.broadcast_to((A * np.cos(k0 * x)).reshape(shape), full).copy()
+    psi = np.broadcast_to((-part * (A / k0) * np.sin(k0 * x)).reshape(shape), full).copy()
+    pos = ((np.arange(N9) + 0.5) * D).reshape(shape) + psi
+    pos = np.where(pos < 0, pos + L9, np.where(pos >= L9, pos - L9, pos))
+    return delta, psi, A / k0, pos
+
+
+def params9():
+    return HamilParams(Nx=N9, L=L9, likelihood=1, rsd_model=0, sfmodel=1)
+
+
+@pytest.mark.parametrize("axis,m,part", K2_ODD, ids=K2_ODD_IDS)
+def test_k2_oracle_plane_wave_on_an_odd_grid(axis, m, part):
+    p = params9()
+    o = Oracle(p)
+    delta, psi, scale, pos = k2_odd_expected(axis, m, part)
+    v = o.theta2vel(-p.D1 * delta)
+    for a in range(3):
+        want = psi if a == axis else 0.0
+        assert np.max(np.abs(v[a].reshape(psi.shape) - want)) < 1e-13 * scale
+    got = o.Lag2Eul(delta, rsd=0)[1 + axis]
+    assert np.max(np.abs(got.reshape(psi.shape) - pos)) < 1e-12
+    o.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("axis,m,part", K2_ODD, ids=K2_ODD_IDS)
+def test_k2_engine_plane_wave_on_an_odd_grid(axis, m, part):
+    from barcode_amd.engine import Engine
+    e = Engine(params9())
+    one = np.ones(N9 ** 3)
+    e.upload(signal_PS=one, mass_f=one, nobs=one, noise=one, window=one)
+    delta, psi, scale, pos = k2_odd_expected(axis, m, part)
+    e.forward(delta)
+    for a, name in enumerate(("psix", "psiy", "psiz")):
+        want = psi if a == axis else 0.0
+        assert np.max(np.abs(e.fetch(name).reshape(psi.shape) - want)) < 1e-13 * scale
+    assert np.max(np.abs(e.fetch(("posx", "posy", "posz")[axis]).reshape(psi.shape) - pos)) < 1e-12
     e.close()
 
 

@@ -5,6 +5,7 @@ flush), compiled as plain C++ into a stand-alone program (tests/host/tile_walk_c
     n = 16, 32, 48, 256 with 8 x 8 x 16 tiles and halo 2 (the 12 x 12 x 20 image; n = 16: the halo wraps onto the tile),
     n = 24 with 8 x 8 x 8 and n = 12 with 4 x 4 x 4 tiles, halo 2,
     n = 16, 32 with 8 x 8 x 16 tiles and halo 1 (the 10 x 10 x 18 image of the low-order kernels),
+    n = 4 with its one 4 x 4 x 4 tile and halo 1, 2, 3 and 4 (halo 2: the image is (2 n)^3 and holds every cell 8 times),
 
 every tile for n <= 48 and the 27 corner / edge-midpoint / face-centre / centre tiles of the lattice at n = 256, through
 the run-time walker and, for the 12 x 12 x 20 image, through the compile-time instantiation of the 81-cell kernels as
