@@ -124,6 +124,8 @@ struct bchmc_handle {
   } corr1;
   struct Corr2 {
     uint64_t n_bin = 0;
+    int n = 0;                 // the grid and the cut rpar, rperp < l_max (infinity: none) the tables were built for
+    double l_max = 0.;
     DevBuf<int> idx;           // rows sorted by perp bin | par_start [npb + 1] | perp_slice [n_bin + 1]
     DevBuf<int2> slices;       // nsl: { first row, rows }
     DevBuf<double> part;       // nsl * npb
@@ -133,6 +135,20 @@ struct bchmc_handle {
     std::vector<int> par_bin;                // nbin_par of populated par bin c
     std::vector<double> rsum;                // n_bin * npb sums of rtot
   } corr2;
+  // bchmc_interp_upres / bchmc_measure_corr2d_interp (upres.hpp): the fine grid of the last n_out, built on first use,
+  // kept for the next call with the same n_out, replaced for another one, freed by bchmc_upres_release.  The work buffer
+  // is declared before the execution info and the plans that point at it, like the handle's own.
+  struct Upres {
+    int n_out = 0;             // the grid everything below is for (0: nothing held)
+    Geo g{};
+    DevBytes real, half;       // N_out elements of T, Nhp_out of C2<T>
+    DevBytes work;
+    FftInfo info;
+    FftPlan r2c, c2r;
+    DevBuf<int> cell;          // interp_field's table: i0 [n_out] | i1 [n_out]
+    DevBuf<double> dx;         // n_out
+    Corr2 bins;                // the 2-D bin tables on the fine grid, keyed by (n_out, n_bin, l_max)
+  } up;
   // host-array entry points: caller arrays are pageable, so they cross PCIe through two pinned staging chunks
   // (N-thread memcpy into one chunk while the DMA of the other is in flight)
   PinnedBuf<void> stg[2];
@@ -321,10 +337,10 @@ void prof_collect(bchmc_handle *h) {
 }
 
 // ---- FFT wrapper (unnormalised both ways; callers fold 1/N into the preceding k-space kernel) -------
-int fft_exec(bchmc_handle *h, rocfft_plan plan, void *in, void *out, int cls) {
+int fft_exec(bchmc_handle *h, rocfft_plan plan, void *in, void *out, int cls, rocfft_execution_info info = nullptr) {
   ProfScope ps(h, cls);
   void *ib[1] = {in}, *ob[1] = {out};
-  FFTCHK(rocfft_execute(plan, ib, ob, h->info));
+  FFTCHK(rocfft_execute(plan, ib, ob, info ? info : (rocfft_execution_info)h->info));
   return BCHMC_OK;
 }
 
@@ -802,12 +818,13 @@ double corr_dr(const Geo &g, uint64_t n_bin) {
 // measure_corr2D's geometry for n_bin, built when n_bin changes: the rows (i, j) sorted by nbin_perp and cut into slices,
 // the runs of |z| that make up the populated par bins, the counts (products of the two), and on the device the sums of
 // rtot.  The bin indices are computed here exactly as the tool does (IEEE sqrt and divide, no FMA contraction).
+// `c`, `g`: the handle's own tables and grid, or those of the fine grid of 2D_corr_fct_interp.cc, whose measure_corr2D
+// bins a cell only if rpar < L_max && rperp < L_max (:123, both strict): rows with rperp >= l_max leave the row list and
+// the par runs stop at the first kk with rpar >= l_max (rpar grows with kk).  l_max = infinity: no cut.
 // Synchronises (the tables are uploaded from local vectors).
-int corr2d_setup(bchmc_handle *h, uint64_t n_bin) {
+int corr2d_setup(bchmc_handle *h, bchmc_handle::Corr2 &c, const Geo &g, uint64_t n_bin, double l_max) {
 #pragma clang fp contract(off)
-  auto &c = h->corr2;
-  if (c.n_bin == n_bin) return BCHMC_OK;
-  const Geo &g = h->g;
+  if (c.n_bin == n_bin && c.n == g.n && c.l_max == l_max) return BCHMC_OK;
   const int n = g.n;
   const double dr = corr_dr(g, n_bin);
   HIPCHK(hipStreamSynchronize(h->stream));
@@ -820,8 +837,9 @@ int corr2d_setup(bchmc_handle *h, uint64_t n_bin) {
       const double x = corr_pos(i, n, g.d), y = corr_pos(j, n, g.d);
       const double rperp = std::sqrt(x * x + y * y);
       const unsigned long long b = (unsigned long long)(rperp / dr);
-      perp[(size_t)i * n + j] = b < n_bin ? (int)b : -1;
-      if (b < n_bin) c.row_cnt[b]++;
+      const bool in = rperp < l_max && b < n_bin;
+      perp[(size_t)i * n + j] = in ? (int)b : -1;
+      if (in) c.row_cnt[b]++;
     }
   std::vector<int> first(n_bin + 1, 0);
   for (uint64_t p = 0; p < n_bin; p++) first[p + 1] = first[p] + (int)c.row_cnt[p];
@@ -850,7 +868,7 @@ int corr2d_setup(bchmc_handle *h, uint64_t n_bin) {
     const double z = corr_pos(kk, n, g.d);
     const double rpar = std::sqrt(z * z);
     const unsigned long long b = (unsigned long long)(rpar / dr);
-    if (b >= n_bin) break;
+    if (!(rpar < l_max) || b >= n_bin) break;
     if (c.par_bin.empty() || c.par_bin.back() != (int)b) {
       par_start.push_back(kk);
       c.par_bin.push_back((int)b);
@@ -873,7 +891,112 @@ int corr2d_setup(bchmc_handle *h, uint64_t n_bin) {
   HIPCHK(hipStreamSynchronize(h->stream));  // idx and slices are local vectors
   c.rsum.clear();  // filled by the first measurement
   c.n_bin = n_bin;
+  c.n = n;
+  c.l_max = l_max;
   return BCHMC_OK;
+}
+
+// ---- the fine grid of bchmc_interp_upres / bchmc_measure_corr2d_interp (upres.hpp) ------------------------------------
+// Releases everything the fine grid holds: the plans and the execution info before the work buffer they point at.
+void upres_drop(bchmc_handle *h) {
+  auto &u = h->up;
+  u.r2c.reset();
+  u.c2r.reset();
+  u.info.reset();
+  (void)u.work.release();
+  (void)u.real.release();
+  (void)u.half.release();
+  (void)u.cell.release();
+  (void)u.dx.release();
+  u.bins = bchmc_handle::Corr2{};
+  u.n_out = 0;
+}
+
+// The fine grid for n_out: the two arrays, the plans at n_out in the handle's precision with a work buffer of their own,
+// and interp_field's table.  Nothing to do when the last call had the same n_out; another n_out replaces what is held.
+// A failure releases what was taken and leaves the handle as it was before its first fine-grid call.
+// The table holds getCICcells / getCICweights (interpolate_grid.cpp:27-79) of the centre of fine cell m, in the
+// reference's expressions and order, IEEE divide, no FMA contraction: the cell pair depends on the rounding of xpos / d.
+int upres_setup(bchmc_handle *h, int n_out) {
+#pragma clang fp contract(off)
+  auto &u = h->up;
+  if (u.n_out == n_out) return BCHMC_OK;
+  HIPCHK(hipStreamSynchronize(h->stream));
+  upres_drop(h);
+  auto build = [&]() -> int {
+    Geo &f = u.g;
+    f.n = n_out;
+    f.nh = n_out / 2 + 1;
+    f.N = (long long)n_out * n_out * n_out;
+    f.Nh = (long long)n_out * n_out * f.nh;
+    f.nhp = fft_row_stride(n_out, (int)h->esz);
+    f.Nhp = (long long)n_out * n_out * f.nhp;
+    f.L = h->g.L;
+    f.d = h->g.L / (double)n_out;
+    f.kfac = h->g.kfac;
+    const size_t e = h->esz;
+    CHK(dev_alloc(h, u.real, (size_t)f.N * e));
+    CHK(dev_alloc(h, u.half, 2 * (size_t)f.Nhp * e));
+    const size_t len[3] = {(size_t)n_out, (size_t)n_out, (size_t)n_out};
+    const rocfft_precision prec = h->f32 ? rocfft_precision_single : rocfft_precision_double;
+    const size_t rs[3] = {1, (size_t)n_out, (size_t)n_out * n_out}, cs[3] = {1, (size_t)f.nhp, (size_t)f.nhp * n_out};
+    rocfft_plan_description fwd = nullptr, inv = nullptr;
+    rocfft_status st = rocfft_plan_description_create(&fwd);
+    if (st == rocfft_status_success) st = rocfft_plan_description_create(&inv);
+    if (st == rocfft_status_success)
+      st = rocfft_plan_description_set_data_layout(fwd, rocfft_array_type_real, rocfft_array_type_hermitian_interleaved,
+                                                   nullptr, nullptr, 3, rs, (size_t)f.N, 3, cs, (size_t)f.Nhp);
+    if (st == rocfft_status_success)
+      st = rocfft_plan_description_set_data_layout(inv, rocfft_array_type_hermitian_interleaved, rocfft_array_type_real,
+                                                   nullptr, nullptr, 3, cs, (size_t)f.Nhp, 3, rs, (size_t)f.N);
+    if (st == rocfft_status_success)
+      st = u.r2c.create(rocfft_plan_create, rocfft_placement_notinplace, rocfft_transform_type_real_forward, prec, 3, len, 1,
+                        fwd);
+    if (st == rocfft_status_success)
+      st = u.c2r.create(rocfft_plan_create, rocfft_placement_notinplace, rocfft_transform_type_real_inverse, prec, 3, len, 1,
+                        inv);
+    if (fwd) rocfft_plan_description_destroy(fwd);
+    if (inv) rocfft_plan_description_destroy(inv);
+    if (st != rocfft_status_success) return h->fail(BCHMC_ERR_ROCFFT, "plans at n_out = %d: status %d", n_out, (int)st);
+    size_t wb = 0, wb2 = 0;
+    FFTCHK(rocfft_plan_get_work_buffer_size(u.r2c, &wb));
+    FFTCHK(rocfft_plan_get_work_buffer_size(u.c2r, &wb2));
+    wb = std::max(wb, wb2);
+    FFTCHK(u.info.create(rocfft_execution_info_create));
+    FFTCHK(rocfft_execution_info_set_stream(u.info, h->stream));
+    if (wb) {
+      CHK(alloc_rc(h, u.work.alloc(wb), wb));
+      FFTCHK(rocfft_execution_info_set_work_buffer(u.info, u.work, wb));
+    }
+    const int n = h->g.n;
+    const double L = h->g.L, d = h->g.d, d_out = f.d;
+    std::vector<int> cell(2 * (size_t)n_out);
+    std::vector<double> dx((size_t)n_out);
+    for (int m = 0; m < n_out; m++) {
+      const double pos = d_out * (0.5 + (double)m);  // interp_upres.cc:79
+      double xpos = pos - 0.5 * d;
+      if (xpos < 0.) {  // pacman_coordinate, pacman.cpp:20-28
+        xpos = std::fmod(xpos, L);
+        xpos += L;
+      }
+      if (xpos >= L) xpos = std::fmod(xpos, L);
+      unsigned long long c = (unsigned long long)(xpos / d);
+      c = (c + (unsigned long long)n) % (unsigned long long)n;
+      cell[m] = (int)c;
+      cell[n_out + m] = (int)((c + 1) % (unsigned long long)n);
+      dx[m] = xpos / d - (double)c;
+    }
+    CHK(dev_alloc(h, u.cell, cell.size()));
+    CHK(dev_alloc(h, u.dx, dx.size()));
+    HIPCHK(hipMemcpyAsync(u.cell, cell.data(), cell.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(u.dx, dx.data(), dx.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));  // cell and dx are local vectors
+    return BCHMC_OK;
+  };
+  const int rc = build();
+  if (rc) upres_drop(h);
+  else u.n_out = n_out;
+  return rc;
 }
 
 // ======================================================================================================
@@ -2130,13 +2253,12 @@ struct Pipe {
   }
 
   template <bool GEOM>
-  static int launch_corr2d_slices(bchmc_handle *h) {
-    auto &c = h->corr2;
-    const int n = h->g.n, bd = std::min(256, (n + 63) / 64 * 64), kpt = (n + bd - 1) / bd;
+  static int launch_corr2d_slices(bchmc_handle *h, bchmc_handle::Corr2 &c, const Geo &g, const T *A) {
+    const int n = g.n, bd = std::min(256, (n + 63) / 64 * 64), kpt = (n + bd - 1) / bd;
     const size_t lds = ((size_t)n + n / 2 + 1) * sizeof(double);
     const int *par_start = c.idx + c.nrows;
 #define BCHMC_LAUNCH_C2(KPT) \
-  k_corr2d_slices<T, KPT, GEOM><<<c.nsl, bd, lds, h->stream>>>(h->g, R(h->ioq), c.idx, c.slices, par_start, c.npb, c.part)
+  k_corr2d_slices<T, KPT, GEOM><<<c.nsl, bd, lds, h->stream>>>(g, A, c.idx, c.slices, par_start, c.npb, c.part)
     if (kpt == 1) BCHMC_LAUNCH_C2(1);
     else if (kpt == 2) BCHMC_LAUNCH_C2(2);
     else BCHMC_LAUNCH_C2(4);
@@ -2148,19 +2270,20 @@ struct Pipe {
     return BCHMC_OK;
   }
 
-  // The 2-D bin sums of A in ioq (corr2d_setup has run).  One synchronise.
-  static int corr2d_bins(bchmc_handle *h, uint64_t n_bin, double *rmode, uint64_t *nmode, double *corr) {
-    auto &c = h->corr2;
+  // The 2-D bin sums of A on grid g (corr2d_setup has run for c and g).  One synchronise.
+  static int corr2d_bins(bchmc_handle *h, bchmc_handle::Corr2 &c, const Geo &g, const void *A_T, uint64_t n_bin,
+                         double *rmode, uint64_t *nmode, double *corr) {
+    const T *A = reinterpret_cast<const T *>(A_T);
     const size_t nb = (size_t)n_bin, cells = nb * c.npb;
     const bool geom = c.rsum.empty();
     std::vector<double> hb(cells), hr(geom ? cells : 0);
     {
       ProfScope ps(h, BCHMC_K_OTHER);
       if (geom) {
-        CHK(launch_corr2d_slices<true>(h));
+        CHK(launch_corr2d_slices<true>(h, c, g, A));
         HIPCHK(hipMemcpyAsync(hr.data(), c.out, cells * sizeof(double), hipMemcpyDeviceToHost, h->stream));
       }
-      CHK(launch_corr2d_slices<false>(h));
+      CHK(launch_corr2d_slices<false>(h, c, g, A));
       HIPCHK(hipMemcpyAsync(hb.data(), c.out + cells, cells * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     }
     HIPCHK(hipStreamSynchronize(h->stream));
@@ -2168,7 +2291,7 @@ struct Pipe {
     std::memset(rmode, 0, nb * nb * sizeof(double));
     std::memset(corr, 0, nb * nb * sizeof(double));
     std::memset(nmode, 0, nb * nb * sizeof(uint64_t));
-    const double N = (double)h->g.N;
+    const double N = (double)g.N;
     for (size_t p = 0; p < nb; p++) {
       if (!c.row_cnt[p]) continue;
       for (int q = 0; q < c.npb; q++) {
@@ -2180,6 +2303,86 @@ struct Pipe {
       }
     }
     return BCHMC_OK;
+  }
+
+  // ---- interp_field and tools/2D_corr_fct_interp.cc on the fine grid (upres.hpp; upres_setup has run) -----------------
+  // The source as a real field of T in ioq, as corr_field takes it (a host signal is in dstage; the chain state goes
+  // through tC like chain_fetch's c2r_state).  Scratch only: tC, ioq.
+  static int upres_real(bchmc_handle *h, int src) {
+    if (src == BCHMC_CORR_HOST) return load_real(h, h->dstage, R(h->ioq));
+    if (src == BCHMC_CORR_CHAIN_STATE) return c2r_scaled(h, h->cq, h->ioq);
+    k_overdens<T><<<nblk_stride(h->g.N), 256, 0, h->stream>>>(h->g, R(h->rho), h->rho_part, R(h->ioq));
+    HIPCHK(hipGetLastError());
+    return BCHMC_OK;
+  }
+
+  // interp_field of the source onto the fine grid's real array
+  static int upres_interp(bchmc_handle *h, int src) {
+    auto &u = h->up;
+    CHK(upres_real(h, src));
+    ProfScope ps(h, BCHMC_K_OTHER);
+    const int n = h->g.n, no = u.n_out, bd = std::min(256, (no + 63) / 64 * 64);
+    k_interp_cic<T><<<no * no, bd, 4 * (size_t)n * sizeof(T), h->stream>>>(n, no, R(h->ioq), R(u.real), u.cell, u.cell + no,
+                                                                            u.dx);
+    HIPCHK(hipGetLastError());
+    return BCHMC_OK;
+  }
+
+  // the fine real array -> n_out^3 host doubles; returns when `out` is complete
+  static int upres_fetch(bchmc_handle *h, double *out) {
+    auto &u = h->up;
+    const size_t N = (size_t)u.g.N;
+    if (kDouble) return d2h(h, out, u.real, N * sizeof(double));
+    std::vector<T> tmp(N);
+    CHK(d2h(h, tmp.data(), u.real, N * sizeof(T)));
+    for (size_t i = 0; i < N; i++) out[i] = (double)tmp[i];
+    return BCHMC_OK;
+  }
+
+  // mode 0: A = C2R[|R2C interp_field(source)|^2 / N_out] into the fine real array
+  static int upres_corr_cic(bchmc_handle *h, int src) {
+    auto &u = h->up;
+    CHK(upres_interp(h, src));
+    CHK(fft_exec(h, u.r2c, u.real, u.half, BCHMC_K_FFT_R2C, u.info));
+    {
+      ProfScope ps(h, BCHMC_K_OTHER);
+      k_corr_abs2<T><<<nblk_stride(u.g.Nhp), 256, 0, h->stream>>>(u.g.Nhp, C(u.half), C(u.half), 1. / (double)u.g.N);
+      HIPCHK(hipGetLastError());
+    }
+    return fft_exec(h, u.c2r, u.half, u.real, BCHMC_K_FFT_C2R, u.info);
+  }
+
+  // mode 1: A = C2R[zero-padded |x^|^2 / N_out] into the fine real array; x^ as corr_field takes it (no transform for the
+  // chain state)
+  static int upres_corr_zeropad(bchmc_handle *h, int src) {
+    auto &u = h->up;
+    const void *xk = h->tC;
+    if (src == BCHMC_CORR_HOST) {
+      CHK(r2c_state(h, h->dstage, h->ioq, h->tC));
+    } else if (src == BCHMC_CORR_CHAIN_STATE) {
+      xk = h->cq;
+    } else {
+      CHK(upres_real(h, src));
+      CHK(fft_exec(h, h->r2c1, h->ioq, h->tC, BCHMC_K_FFT_R2C));
+    }
+    {
+      ProfScope ps(h, BCHMC_K_OTHER);
+      k_zeropad_embed<T><<<nblk_stride(u.g.Nhp), 256, 0, h->stream>>>(h->g, u.g, C(xk), C(u.half), 1. / (double)u.g.N);
+      HIPCHK(hipGetLastError());
+    }
+    return fft_exec(h, u.c2r, u.half, u.real, BCHMC_K_FFT_C2R, u.info);
+  }
+
+  // the transform of the source for bchmc_measure_spectrum_src, as corr_field takes it
+  static int spectrum_source(bchmc_handle *h, int src, const void **xk) {
+    *xk = h->tC;
+    if (src == BCHMC_CORR_HOST) return r2c_state(h, h->dstage, h->ioq, h->tC);
+    if (src == BCHMC_CORR_CHAIN_STATE) {
+      *xk = h->cq;
+      return BCHMC_OK;
+    }
+    CHK(upres_real(h, src));
+    return fft_exec(h, h->r2c1, h->ioq, h->tC, BCHMC_K_FFT_R2C);
   }
 
   static int gradient(bchmc_handle *h, const double *d_q, double *d_g) {
@@ -3391,10 +3594,10 @@ static int corr_measure(bchmc_handle *h, bool two_d, bchmc_corr_source src, cons
   if (src == BCHMC_CORR_DELTAX && !h->have_eval) return h->fail(BCHMC_ERR_STATE, "no forward evaluation to take deltaX from");
   // both kernels are laid out for n <= 1024: the 1-D limb sums hold N <= 2^30 cells, the 2-D slices 4 k per thread of 256
   if (h->g.n > 1024) return h->fail(BCHMC_ERR_UNSUPPORTED, "%s: n = %d > 1024", name, h->g.n);
-  if (two_d) CHK(corr2d_setup(h, n_bin));
+  if (two_d) CHK(corr2d_setup(h, h->corr2, h->g, n_bin, INFINITY));
   if (signal) CHK(h2d(h, h->dstage, signal, h->g.N * sizeof(double)));
   CHK(DISPATCH(h, corr_field(h, (int)src)));
-  return two_d ? DISPATCH(h, corr2d_bins(h, n_bin, rmode, nmode, corr)) : DISPATCH(h, corr1d_bins(h, n_bin, rmode, nmode, corr));
+  return two_d ? DISPATCH(h, corr2d_bins(h, h->corr2, h->g, h->ioq, n_bin, rmode, nmode, corr)) : DISPATCH(h, corr1d_bins(h, n_bin, rmode, nmode, corr));
 }
 
 int bchmc_measure_corr(bchmc_handle *h, bchmc_corr_source src, const double *signal, uint64_t n_bin, double *rmode,
@@ -3405,6 +3608,87 @@ int bchmc_measure_corr(bchmc_handle *h, bchmc_corr_source src, const double *sig
 int bchmc_measure_corr2d(bchmc_handle *h, bchmc_corr_source src, const double *signal, uint64_t n_bin, double *rmode,
                          uint64_t *nmode, double *corr) {
   return corr_measure(h, true, src, signal, n_bin, rmode, nmode, corr);
+}
+
+// What the entry points with a bchmc_corr_source check before anything is queued (bchmc_measure_corr2d's rules)
+static int source_args(bchmc_handle *h, const char *name, bchmc_corr_source src, const double *signal) {
+  if (src != BCHMC_CORR_HOST && src != BCHMC_CORR_CHAIN_STATE && src != BCHMC_CORR_DELTAX)
+    return h->fail(BCHMC_ERR_ARG, "%s: unknown source %d", name, (int)src);
+  if ((src == BCHMC_CORR_HOST) != (signal != nullptr))
+    return h->fail(BCHMC_ERR_ARG, "%s: signal must be given for BCHMC_CORR_HOST and NULL otherwise", name);
+  return BCHMC_OK;
+}
+static int source_state(bchmc_handle *h, bchmc_corr_source src) {
+  if (src == BCHMC_CORR_CHAIN_STATE && !h->have_cq)
+    return h->fail(BCHMC_ERR_STATE, "no chain state: call bchmc_chain_set_state first");
+  if (src == BCHMC_CORR_DELTAX && !h->have_eval) return h->fail(BCHMC_ERR_STATE, "no forward evaluation to take deltaX from");
+  return BCHMC_OK;
+}
+static int upres_n_out(bchmc_handle *h, const char *name, uint32_t n_out) {
+  // the 2-D slice kernel holds 4 k per thread of 256, interp_field's rows 4 n elements of LDS
+  if (n_out < 4 || n_out > 1024) return h->fail(BCHMC_ERR_ARG, "%s: n_out = %u outside 4..1024", name, n_out);
+  return BCHMC_OK;
+}
+
+int bchmc_interp_upres(bchmc_handle *h, bchmc_corr_source src, const double *signal, uint32_t n_out, double *out) {
+  if (!h || !out) return BCHMC_ERR_ARG;
+  const char *name = "interp_upres";
+  CHK(source_args(h, name, src, signal));
+  CHK(upres_n_out(h, name, n_out));
+  ENTER(h);
+  CHK(source_state(h, src));
+  if (h->g.n > 1024) return h->fail(BCHMC_ERR_UNSUPPORTED, "%s: n = %d > 1024", name, h->g.n);
+  CHK(upres_setup(h, (int)n_out));
+  if (signal) CHK(h2d(h, h->dstage, signal, h->g.N * sizeof(double)));
+  CHK(DISPATCH(h, upres_interp(h, (int)src)));
+  return DISPATCH(h, upres_fetch(h, out));
+}
+
+int bchmc_measure_corr2d_interp(bchmc_handle *h, bchmc_corr_source src, const double *signal, uint32_t n_out, int32_t mode,
+                                double l_max, uint64_t n_bin, double *rmode, uint64_t *nmode, double *corr) {
+  if (!h || !rmode || !nmode || !corr) return BCHMC_ERR_ARG;
+  const char *name = "measure_corr2d_interp";
+  if (n_bin == 0 || n_bin > 2048) return h->fail(BCHMC_ERR_ARG, "%s: n_bin = %llu outside 1..2048", name, (unsigned long long)n_bin);
+  CHK(source_args(h, name, src, signal));
+  CHK(upres_n_out(h, name, n_out));
+  if (mode != 0 && mode != 1) return h->fail(BCHMC_ERR_ARG, "%s: mode %d is neither 0 (CIC) nor 1 (zero padding)", name, (int)mode);
+  if (mode == 1 && (int)n_out < h->g.n)
+    return h->fail(BCHMC_ERR_ARG, "%s: zero padding needs n_out = %u >= n = %d", name, n_out, h->g.n);
+  if (mode == 0 && !(l_max > 0.)) return h->fail(BCHMC_ERR_ARG, "%s: l_max = %g is not > 0", name, l_max);
+  ENTER(h);
+  CHK(source_state(h, src));
+  if (h->g.n > 1024) return h->fail(BCHMC_ERR_UNSUPPORTED, "%s: n = %d > 1024", name, h->g.n);
+  CHK(upres_setup(h, (int)n_out));
+  auto &u = h->up;
+  if (const int rc = corr2d_setup(h, u.bins, u.g, n_bin, mode == 0 ? l_max : (double)INFINITY)) {
+    upres_drop(h);  // the tables did not fit: the fine grid goes too, the handle stays usable
+    return rc;
+  }
+  if (signal) CHK(h2d(h, h->dstage, signal, h->g.N * sizeof(double)));
+  CHK(mode == 0 ? DISPATCH(h, upres_corr_cic(h, (int)src)) : DISPATCH(h, upres_corr_zeropad(h, (int)src)));
+  return DISPATCH(h, corr2d_bins(h, u.bins, u.g, u.real, n_bin, rmode, nmode, corr));
+}
+
+int bchmc_upres_release(bchmc_handle *h) {
+  if (!h) return BCHMC_ERR_ARG;
+  ENTER(h);
+  HIPCHK(hipStreamSynchronize(h->stream));
+  upres_drop(h);
+  return BCHMC_OK;
+}
+
+int bchmc_measure_spectrum_src(bchmc_handle *h, bchmc_corr_source src, const double *signal, uint64_t n_bin, double *kmode,
+                               double *power) {
+  if (!h || !kmode || !power) return BCHMC_ERR_ARG;
+  const char *name = "measure_spectrum_src";
+  if (n_bin == 0 || n_bin > 2048) return h->fail(BCHMC_ERR_ARG, "%s: n_bin = %llu outside 1..2048", name, (unsigned long long)n_bin);
+  CHK(source_args(h, name, src, signal));
+  ENTER(h);
+  CHK(source_state(h, src));
+  if (signal) CHK(h2d(h, h->dstage, signal, h->g.N * sizeof(double)));
+  const void *xk = nullptr;
+  CHK(DISPATCH(h, spectrum_source(h, (int)src, &xk)));
+  return spectrum_bins(h, xk, n_bin, kmode, power);
 }
 
 int bchmc_chain_forward(bchmc_handle *h, int use_rsd) {

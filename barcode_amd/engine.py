@@ -90,10 +90,10 @@ EXPORTS = ("bchmc_create", "bchmc_destroy", "bchmc_strerror", "bchmc_last_error"
            "bchmc_comm_last_error", "bchmc_eps_exchange", "bchmc_comm_pending", "bchmc_comm_world", "bchmc_comm_rank",
            "bchmc_comm_transport", "bchmc_garfield_walk_index", "bchmc_hamiltonian_mass",
            "bchmc_setup_random_test", "bchmc_make_initial_guess", "bchmc_measure_corr", "bchmc_chain_forward",
-           "bchmc_probe_displacement")
+           "bchmc_probe_displacement", "bchmc_interp_upres", "bchmc_upres_release", "bchmc_measure_spectrum_src")
 # declared as well, listed apart: the header scan of the ABI test matches names of letters and underscores only
 EXPORTS_MT19937 = ("bchmc_chain_draw_momenta_mt19937", "bchmc_mt19937_jump")
-EXPORTS_CORR2D = ("bchmc_measure_corr2d",)  # a digit in the name, like the two above
+EXPORTS_CORR2D = ("bchmc_measure_corr2d", "bchmc_measure_corr2d_interp")  # a digit in the name, like the two above
 
 # bchmc_corr_source
 CORR_SOURCES = dict(host=0, chain=1, deltaX=2)
@@ -148,6 +148,11 @@ def load():
     lib.bchmc_hamiltonian_mass.argtypes = [vp, dp, C.POINTER(MassOpts), dp, dp]
     lib.bchmc_measure_corr.argtypes = [vp, C.c_int, dp, C.c_uint64, dp, C.POINTER(u64), dp]
     lib.bchmc_measure_corr2d.argtypes = [vp, C.c_int, dp, C.c_uint64, dp, C.POINTER(u64), dp]
+    lib.bchmc_interp_upres.argtypes = [vp, C.c_int, dp, C.c_uint32, dp]
+    lib.bchmc_measure_corr2d_interp.argtypes = [vp, C.c_int, dp, C.c_uint32, C.c_int32, C.c_double, C.c_uint64, dp,
+                                                C.POINTER(u64), dp]
+    lib.bchmc_upres_release.argtypes = [vp]
+    lib.bchmc_measure_spectrum_src.argtypes = [vp, C.c_int, dp, C.c_uint64, dp, dp]
     lib.bchmc_chain_forward.argtypes = [vp, C.c_int]
     lib.bchmc_probe_displacement.argtypes = [vp, dp, C.c_int, C.c_int]
     lib.bchmc_philox_kat.argtypes = [C.POINTER(C.c_uint32)] * 3
@@ -471,12 +476,17 @@ class Engine:
     def chain_accept(self, accepted):
         self._chk(self.lib.bchmc_chain_accept(self.h, int(bool(accepted))))
 
-    def measure_spectrum(self, signal=None, n_bin=200):
+    def measure_spectrum(self, signal=None, n_bin=200, source=None):
         """measure_spectrum (field_statistics.cpp:20-90) of a host field, or of the resident chain state when
-        ``signal`` is None (nothing but 2 x n_bin doubles crosses PCIe).  Returns (kmode, power)."""
+        ``signal`` is None (nothing but 2 x n_bin doubles crosses PCIe).  ``source``: "host", "chain" or "deltaX" (the
+        handle's deltaX, what barcoderunner.cc:87 measures) as in ``measure_corr``.  Returns (kmode, power)."""
         kmode, power = np.empty(n_bin), np.empty(n_bin)
         sig = None if signal is None else _p(self._in(signal))
-        self._chk(self.lib.bchmc_measure_spectrum(self.h, sig, int(n_bin), _p(kmode), _p(power)))
+        if source is None:
+            self._chk(self.lib.bchmc_measure_spectrum(self.h, sig, int(n_bin), _p(kmode), _p(power)))
+        else:
+            self._chk(self.lib.bchmc_measure_spectrum_src(self.h, CORR_SOURCES[source], sig, int(n_bin), _p(kmode),
+                                                          _p(power)))
         return kmode, power
 
     def _measure_corr(self, fn, cells, signal, n_bin, source):
@@ -501,6 +511,39 @@ class Engine:
         """measure_corr2D (tools/2D_corr_fct.cc:23-124), plane-parallel along z.  Returns (rmode, nmode, corr) shaped
         (n_bin, n_bin) with r_perp as the first axis (the tool's element ``par + n_bin * perp``)."""
         return self._measure_corr(self.lib.bchmc_measure_corr2d, 2, signal, n_bin, source)
+
+    def interp_upres(self, n_out, signal=None, source=None):
+        """interp_field (tools/interp_upres.cc:59-86): the source's field on an n_out^3 grid by CIC interpolation.
+        Sources as in ``measure_corr``.  Returns n_out^3 doubles."""
+        if source is None:
+            source = "chain" if signal is None else "host"
+        n_out = int(n_out)
+        out = np.empty(n_out ** 3 if 4 <= n_out <= 1024 else 1)  # out of range: the library refuses before it writes
+        sig = None if signal is None else _p(self._in(signal))
+        self._chk(self.lib.bchmc_interp_upres(self.h, CORR_SOURCES[source], sig, n_out, _p(out)))
+        return out
+
+    def measure_corr2d_interp(self, n_out, signal=None, n_bin=0, mode=0, l_max=np.inf, source=None):
+        """tools/2D_corr_fct_interp.cc: the source lifted to an n_out^3 grid by CIC interpolation (``mode=0``, binning
+        the cells with r_par < l_max and r_perp < l_max) or by zero padding of its power spectrum (``mode=1``, which
+        ignores l_max), then measure_corr2D there.  ``n_bin=0``: the tool's automatic count ceil(rmax / d_out).
+        Returns (rmode, nmode, corr) shaped (n_bin, n_bin) like ``measure_corr2d``."""
+        if source is None:
+            source = "chain" if signal is None else "host"
+        n_out = int(n_out)
+        n_bin = int(n_bin) if n_bin else corr_auto_nbin(max(n_out, 1), self.params.L)
+        size = n_bin ** 2 if 1 <= n_bin <= 2048 else 1
+        rmode, corr, nmode = np.empty(size), np.empty(size), np.empty(size, dtype=np.uint64)
+        sig = None if signal is None else _p(self._in(signal))
+        self._chk(self.lib.bchmc_measure_corr2d_interp(self.h, CORR_SOURCES[source], sig, n_out, int(mode), float(l_max),
+                                                       n_bin, _p(rmode), nmode.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                                       _p(corr)))
+        shape = (n_bin, n_bin)
+        return rmode.reshape(shape), nmode.reshape(shape), corr.reshape(shape)
+
+    def upres_release(self):
+        """Frees the fine grid's buffers, plans and tables; a later call rebuilds them."""
+        self._chk(self.lib.bchmc_upres_release(self.h))
 
     def chain_forward(self, rsd=-1):
         """Lag2Eul of the resident chain state: ``forward(chain_get_state(), rsd)`` without the field leaving the

@@ -133,6 +133,19 @@ def measure_corr_grid(hd, signal=None, N_bin=0, source=None):
     return hd.engine.measure_corr(signal, N_bin, source)
 
 
+def interp_field(hd, N_out, signal=None, source=None):
+    """tools/interp_upres.cc:59-86 -> the field on an N_out^3 grid (CIC interpolation)."""
+    return hd.engine.interp_upres(N_out, signal, source)
+
+
+def measure_corr2D_interp(hd, N_out, signal=None, N_bin=0, interp_mode=0, L_max=float("inf"), source=None, planepar=True):
+    """tools/2D_corr_fct_interp.cc -> (rmode, nmode, corr) shaped (N_bin, N_bin) of the field lifted to N_out^3:
+    ``interp_mode`` 0 CIC interpolation with the ``L_max`` cut, 1 zero padding of the power spectrum."""
+    if not planepar:
+        raise RuntimeError("non-plane-parallel option not yet implemented")  # 2D_corr_fct_interp.cc:120
+    return hd.engine.measure_corr2d_interp(N_out, signal, N_bin, interp_mode, L_max, source)
+
+
 def measure_corr2D(hd, signal=None, N_bin=0, source=None, planepar=True):
     """tools/2D_corr_fct.cc:23-124 -> (rmode, nmode, corr) shaped (N_bin, N_bin), r_perp first."""
     if not planepar:

@@ -88,6 +88,42 @@ def dump_corr(fname_out, rmode, corr, auto_nbin=False, n_bin=None):
     return tuple(add_extension_if_missing(n) for n in names)
 
 
+def interp_filename(fname_in, n_out):
+    """``tools/interp_upres.cc:45``: the default output name of the interpolated field."""
+    return "%s_interpCIC%d" % (fname_in, int(n_out))
+
+
+def dump_interp(fname_in, n_out, field):
+    """``quick_dump_scalar(result, N1_out, fname_out, 0, false)`` of ``tools/interp_upres.cc``: the raw array under
+    ``interp_filename``.  Returns the path written."""
+    name = interp_filename(fname_in, n_out)
+    write_array(name, np.asarray(field))
+    return add_extension_if_missing(name)
+
+
+def corr_interp_filenames(fname_in, n_out, n_bin, auto_nbin=False):
+    """The two files of ``tools/2D_corr_fct_interp.cc:338,397,427-428``: ``<in>_interpCIC<n_out>_corr2D[_Nbin<n>]`` +
+    ``_r`` / ``_eta`` (both interpolation modes write under this name)."""
+    return corr_filenames(interp_filename(fname_in, n_out) + "_corr2D", n_bin, auto_nbin)
+
+
+def dump_corr_interp(fname_in, n_out, rmode, corr, auto_nbin=False, n_bin=None):
+    """``dump_corr`` under the names of ``corr_interp_filenames``."""
+    return dump_corr(interp_filename(fname_in, n_out) + "_corr2D", rmode, corr, auto_nbin, n_bin)
+
+
+def pow_filename(fname_in):
+    """``tools/powspec.cc``: the measured spectrum of a field file goes to ``<in>_pow``."""
+    return fname_in + "_pow"
+
+
+def dump_pow(fname_in, kmode, power):
+    """``powspec.cc``'s output through the spectrum writer (``dump_measured_spec``).  Returns the path written."""
+    name = pow_filename(fname_in)
+    dump_measured_spec(kmode, power, name)
+    return name
+
+
 def dump_deltas(engine, directory, suffix=""):
     """``dump_deltas`` (IOfunctionsGen.cc:136-171) of the resident chain state: deltaLAG, then deltaEUL without
     ``rsd_model``, or deltaRSS (the configured forward model) and deltaEUL (a second Lag2Eul without RSD) with it.

@@ -26,7 +26,8 @@ SHIM_EXPORTS = ("bchmc_shim_Hamiltonian_EoM", "bchmc_shim_delta_Hamiltonian", "b
                 "bchmc_shim_inputs_changed", "bchmc_shim_mass_changed", "bchmc_shim_bootstrap_exchange_id",
                 "bchmc_shim_bootstrap_cleanup", "bchmc_shim_Hamiltonian_mass",
                 "bchmc_shim_setup_random_test", "bchmc_shim_make_initial_guess", "bchmc_shim_sizeof_mock",
-                "bchmc_shim_measure_corr_grid", "bchmc_shim_measure_corr2D", "bchmc_shim_chain_forward")
+                "bchmc_shim_measure_corr_grid", "bchmc_shim_measure_corr2D", "bchmc_shim_chain_forward",
+                "bchmc_shim_interp_field", "bchmc_shim_measure_corr2D_interp")
 
 _dp = C.POINTER(C.c_double)
 
@@ -121,6 +122,9 @@ def load():
     lib.bchmc_shim_Hamiltonian_mass.argtypes = [hv, _dp, _dp, _dp, C.c_char_p, sz]
     lib.bchmc_shim_measure_corr_grid.argtypes = [hv, _dp, ul, _dp, C.POINTER(ul), _dp, C.c_int, C.c_char_p, sz]
     lib.bchmc_shim_measure_corr2D.argtypes = [hv, _dp, ul, _dp, C.POINTER(ul), _dp, C.c_int, C.c_int, C.c_char_p, sz]
+    lib.bchmc_shim_interp_field.argtypes = [hv, _dp, C.c_uint, _dp, C.c_int, C.c_char_p, sz]
+    lib.bchmc_shim_measure_corr2D_interp.argtypes = [hv, _dp, C.c_uint, C.c_uint, C.c_double, ul, _dp, C.POINTER(ul), _dp,
+                                                     C.c_int, C.c_int, C.c_char_p, sz]
     lib.bchmc_shim_chain_forward.argtypes = [hv, C.c_int, C.c_char_p, sz]
     lib.bchmc_shim_chain_set_state.argtypes = [hv, _dp, C.c_char_p, sz]
     lib.bchmc_shim_chain_get_state.argtypes = [hv, _dp, C.c_char_p, sz]
@@ -304,6 +308,26 @@ class ShimHamil:
 
     def measure_corr2D(self, signal, N_bin, planepar=True, of_deltaX=False):
         return self._corr(2, signal, N_bin, of_deltaX, planepar)
+
+    def interp_field(self, signal, N_out, of_deltaX=False):
+        """bchmc_shim::interp_field at ``signal`` (None: the resident state, or deltaX) -> N_out^3 values."""
+        out = np.empty(int(N_out) ** 3 if 4 <= int(N_out) <= 1024 else 1)
+        sig = None if signal is None else _p(self._in(signal))
+        self._chk(self.lib.bchmc_shim_interp_field(C.byref(self.hd), sig, int(N_out), _p(out), int(bool(of_deltaX)),
+                                                   self._err, len(self._err)))
+        return out
+
+    def measure_corr2D_interp(self, signal, N_out, N_bin, interp_mode=0, L_max=np.inf, planepar=True, of_deltaX=False):
+        """bchmc_shim::measure_corr2D_interp -> (rmode, nmode, corr) shaped (N_bin, N_bin)."""
+        size = int(N_bin) ** 2 if 1 <= int(N_bin) <= 2048 else 1
+        rm, co, nm = np.empty(size), np.empty(size), np.empty(size, dtype=np.uint64)
+        sig = None if signal is None else _p(self._in(signal))
+        self._chk(self.lib.bchmc_shim_measure_corr2D_interp(
+            C.byref(self.hd), sig, int(N_out), int(interp_mode), float(L_max), int(N_bin), _p(rm),
+            nm.ctypes.data_as(C.POINTER(C.c_ulong)), _p(co), int(bool(planepar)), int(bool(of_deltaX)), self._err,
+            len(self._err)))
+        shape = (int(N_bin),) * 2
+        return rm.reshape(shape), nm.reshape(shape), co.reshape(shape)
 
     def chain_forward(self, use_rsd=-1):
         """bchmc_shim::chain_forward: Lag2Eul of the resident state; returns the view's deltaX array."""

@@ -268,6 +268,21 @@ void measure_corr2D(HamilView *hd, const real_prec *signal, ULONG N_bin, real_pr
   if (rc) fail(h, rc, "measure_corr2D");
 }
 
+void interp_field(HamilView *hd, const real_prec *signal, unsigned N_out, real_prec *output, bool of_deltaX) {
+  bchmc_handle *h = engine_for(hd);
+  const int rc = bchmc_interp_upres(h, corr_source(signal, of_deltaX), signal, N_out, output);
+  if (rc) fail(h, rc, "interp_field");
+}
+
+void measure_corr2D_interp(HamilView *hd, const real_prec *signal, unsigned N_out, unsigned interp_mode, real_prec L_max,
+                           ULONG N_bin, real_prec *rmode, ULONG *nmode, real_prec *corr, bool planepar, bool of_deltaX) {
+  if (!planepar) throw std::runtime_error("non-plane-parallel option not yet implemented");  // 2D_corr_fct_interp.cc:120
+  bchmc_handle *h = engine_for(hd);
+  const int rc = bchmc_measure_corr2d_interp(h, corr_source(signal, of_deltaX), signal, N_out, (int32_t)interp_mode, L_max,
+                                             N_bin, rmode, reinterpret_cast<uint64_t *>(nmode), corr);
+  if (rc) fail(h, rc, "measure_corr2D_interp");
+}
+
 void chain_forward(HamilView *hd, int use_rsd) {
   bchmc_handle *h = engine_for(hd);
   const int rc = bchmc_chain_forward(h, use_rsd);
@@ -750,6 +765,18 @@ int bchmc_shim_measure_corr2D(bchmc_shim::HamilView *hd, const double *signal, u
                                    size_t errlen) {
   return guarded(err, errlen, [&] {
     bchmc_shim::measure_corr2D(hd, signal, N_bin, rmode, nmode, corr, planepar != 0, of_deltaX != 0);
+  });
+}
+int bchmc_shim_interp_field(bchmc_shim::HamilView *hd, const double *signal, unsigned N_out, double *output, int of_deltaX,
+                            char *err, size_t errlen) {
+  return guarded(err, errlen, [&] { bchmc_shim::interp_field(hd, signal, N_out, output, of_deltaX != 0); });
+}
+int bchmc_shim_measure_corr2D_interp(bchmc_shim::HamilView *hd, const double *signal, unsigned N_out, unsigned interp_mode,
+                                     double L_max, unsigned long N_bin, double *rmode, unsigned long *nmode, double *corr,
+                                     int planepar, int of_deltaX, char *err, size_t errlen) {
+  return guarded(err, errlen, [&] {
+    bchmc_shim::measure_corr2D_interp(hd, signal, N_out, interp_mode, L_max, N_bin, rmode, nmode, corr, planepar != 0,
+                                      of_deltaX != 0);
   });
 }
 int bchmc_shim_chain_forward(bchmc_shim::HamilView *hd, int use_rsd, char *err, size_t errlen) {

@@ -249,6 +249,39 @@ int bchmc_measure_corr(bchmc_handle *h, bchmc_corr_source src, const double *sig
  * arrays of n_bin * n_bin, element nbin_par + n_bin * nbin_perp */
 int bchmc_measure_corr2d(bchmc_handle *h, bchmc_corr_source src, const double *signal, uint64_t n_bin, double *rmode,
                          uint64_t *nmode, double *corr);
+/* ---- the up-resolved 2-D correlation function (upstream: tools/2D_corr_fct_interp.cc, tools/interp_upres.cc) ------------
+ * The tool lifts a field from the chain's n^3 grid to a finer n_out^3 one and runs measure_corr2D there.  Sources, their
+ * errors and what a call leaves untouched are those of bchmc_measure_corr2d above (all checked before anything is queued).
+ * n_out: 4..1024 (BCHMC_ERR_ARG outside: the 2-D slice kernel is laid out for <= 1024).  The fine grid -- a real n_out^3
+ * array, a half-complex one, R2C / C2R plans at n_out in the handle's precision, interp_field's table and the 2-D bin
+ * tables -- is built on first use, kept for the next call with the same n_out, replaced by a call with another one, and
+ * freed by bchmc_upres_release and bchmc_destroy; bchmc_live_resources counts it.  If it cannot be allocated the call
+ * returns the allocation's error, releases what it took and leaves the handle usable. */
+/* interp_field (tools/interp_upres.cc:59-86): the source's n^3 field on an n_out^3 grid by interpolate_CIC
+ * (interpolate_grid.cpp:27-103), cell pairs and weights in the reference's own double expressions, the eight terms in
+ * its operand order without FMA contraction: bit for bit the tool's output on fp64 handles for a host source.  n_out < n
+ * (down-sampling) is legal, as in the tool.  out: n_out^3 host doubles. */
+int bchmc_interp_upres(bchmc_handle *h, bchmc_corr_source src, const double *signal, uint32_t n_out, double *out);
+/* tools/2D_corr_fct_interp.cc.  mode 0: interp_field, then its measure_corr2D (:66-174), which bins a cell only if
+ * rpar < l_max && rperp < l_max (both strict); l_max must be > 0 (BCHMC_ERR_ARG otherwise, NaN included; +infinity: no
+ * cut -- a small deviation: the tool writes all-zero output for l_max <= 0).  mode 1: measure_corr2D_FFTzeropad
+ * (:177-312; l_max is ignored, as the tool ignores it); needs n_out >= n (BCHMC_ERR_ARG: the tool's index map folds onto
+ * itself below).  Any other mode: BCHMC_ERR_ARG.  n_bin: 1..2048.  Arrays of n_bin * n_bin, element
+ * nbin_par + n_bin * nbin_perp; rmode / nmode are kept with the bin tables per (n_out, n_bin, l_max-or-none).
+ * Three properties of mode 1:
+ *  U1 The tool sends its row i = n / 2 to frequency -n / 2 only, so for n_out > n the K = 0 plane it builds is not
+ *     Hermitian; its complex-to-real transform returns the transform of the Hermitian part.  The engine writes that part,
+ *     (P(I, J, 0) + P(-I, -J, 0)) / 2, and never hands the transform anything else: same numbers.
+ *  U2 (immaterial) the i Im delta^ term of C2 above is dropped here too; it cancels inside every bin.
+ *  U3 (kept) the tool normalises by N_out twice, so mode 1's corr is (N / N_out)^2 times the correlation function: a
+ *     constant field c gives c^2 (n / n_out)^6 in every populated bin.  Kept bug for bug. */
+int bchmc_measure_corr2d_interp(bchmc_handle *h, bchmc_corr_source src, const double *signal, uint32_t n_out,
+                                int32_t mode, double l_max, uint64_t n_bin, double *rmode, uint64_t *nmode, double *corr);
+int bchmc_upres_release(bchmc_handle *h); /* frees the fine grid's buffers, plans and tables; later calls rebuild them */
+/* measure_spectrum of any source (barcoderunner.cc:87 measures delta_eul): bchmc_measure_spectrum with the source enum,
+ * its errors those of bchmc_measure_corr2d */
+int bchmc_measure_spectrum_src(bchmc_handle *h, bchmc_corr_source src, const double *signal, uint64_t n_bin,
+                               double *kmode, double *power);
 /* Lag2Eul of the resident chain state: bchmc_forward without the host array (it starts from the chain's q^, so no field
  * crosses PCIe and no transform pair is spent).  use_rsd as there.  Leaves deltaX / pos* in the handle, synchronises and
  * adapts the binning's record slots like bchmc_forward; drops a pending proposal like it.  The chain state, the momenta

@@ -125,6 +125,14 @@ void measure_corr_grid(HamilView *hd, const real_prec *signal, ULONG N_bin, real
                        real_prec *corr, bool of_deltaX = false);
 void measure_corr2D(HamilView *hd, const real_prec *signal, ULONG N_bin, real_prec *rmode, ULONG *nmode, real_prec *corr,
                     bool planepar = true, bool of_deltaX = false);
+// tools/interp_upres.cc:59-86 and tools/2D_corr_fct_interp.cc on the device: the field (sources as above) on an N_out^3
+// grid by interpolate_CIC; its 2-D correlation function there, lifted by CIC interpolation (interp_mode 0, cells with
+// rpar < L_max && rperp < L_max) or by zero padding of the power spectrum (interp_mode 1, L_max ignored).  output:
+// N_out^3 values; rmode / corr as measure_corr2D's.  planepar == false throws like upstream.
+void interp_field(HamilView *hd, const real_prec *signal, unsigned N_out, real_prec *output, bool of_deltaX = false);
+void measure_corr2D_interp(HamilView *hd, const real_prec *signal, unsigned N_out, unsigned interp_mode, real_prec L_max,
+                           ULONG N_bin, real_prec *rmode, ULONG *nmode, real_prec *corr, bool planepar = true,
+                           bool of_deltaX = false);
 // Lag2Eul of the resident chain state (dump_deltas' second forward model, IOfunctionsGen.cc:158-169, with use_rsd = 0);
 // hd->deltaX / pos* <- this evaluation's.  use_rsd < 0: as configured.
 void chain_forward(HamilView *hd, int use_rsd);
@@ -262,6 +270,11 @@ int bchmc_shim_measure_corr_grid(bchmc_shim::HamilView *hd, const double *signal
 int bchmc_shim_measure_corr2D(bchmc_shim::HamilView *hd, const double *signal, unsigned long N_bin, double *rmode,
                                    unsigned long *nmode, double *corr, int planepar, int of_deltaX, char *err,
                                    size_t errlen);
+int bchmc_shim_interp_field(bchmc_shim::HamilView *hd, const double *signal, unsigned N_out, double *output, int of_deltaX,
+                            char *err, size_t errlen);
+int bchmc_shim_measure_corr2D_interp(bchmc_shim::HamilView *hd, const double *signal, unsigned N_out, unsigned interp_mode,
+                                     double L_max, unsigned long N_bin, double *rmode, unsigned long *nmode, double *corr,
+                                     int planepar, int of_deltaX, char *err, size_t errlen);
 int bchmc_shim_chain_forward(bchmc_shim::HamilView *hd, int use_rsd, char *err, size_t errlen);
 int bchmc_shim_chain_set_state(bchmc_shim::HamilView *hd, const double *x, char *err, size_t errlen);
 int bchmc_shim_chain_get_state(bchmc_shim::HamilView *hd, double *x, char *err, size_t errlen);
