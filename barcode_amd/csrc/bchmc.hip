@@ -1178,6 +1178,16 @@ struct Pipe {
     return size_ok && h->tiled && h->sort_direct && h->planes_ok && h->xtw && h->c.mk == 3 && h->c.calc_h == 2 &&
            !env_on("BCHMC_NO_ZBIN");  // (mk 3 + calc_h 2 on tiles: nothing but the fallback sort reads Psi after the binning)
   }
+  // the first of zbin_ok's conditions that does not hold, in words (bchmc_probe_displacement_z's refusal); nullptr: all do
+  static const char *zbin_why_not(const bchmc_handle *h) {
+    if (zbin_ok(h)) return nullptr;
+    if (env_on("BCHMC_NO_ZBIN")) return "BCHMC_NO_ZBIN is set";
+    if (h->g.n == 128 && !env_on("BCHMC_ZBIN_128")) return "Nx = 128 takes it with BCHMC_ZBIN_128=1 only";
+    if (!(h->g.n == 128 || h->g.n == 256 || h->g.n == 512)) return "it exists for Nx = 128, 256 and 512";
+    if (h->c.mk != 3 || h->c.calc_h != 2) return "it needs masskernel 3 with calc_h 2";
+    if (!h->tiled || !h->sort_direct) return "the one-pass tile binning is not in use";
+    return "the planes-mode transforms are not available";
+  }
 
   // the engine's own row + column passes of the planes-mode R2C: where rocFFT's column kernel is the slower one (n = 512)
   static bool yfwd_ok(const bchmc_handle *h) {
@@ -1220,8 +1230,8 @@ struct Pipe {
 
   // Everything of the forward model after the C2R of Psi: binning (one-pass, or the two-pass sort + subsort after an
   // overflow), mass assignment, fixed-point conversion, sum of rho.  Reads Psi from h->psi -- unless `zbin`, where
-  // k_zbin_direct takes the z pass of Psi^ (Ck) on its way (forward_rest only: bchmc_probe_displacement, the other
-  // caller, has no Psi^ to give it).
+  // k_zbin_direct takes the z pass of Psi^ (Ck) on its way (forward_rest, and bchmc_probe_displacement_z, which makes
+  // that Psi^ from a real-space displacement with k_zr2c; bchmc_probe_displacement has no Psi^ to give it).
   static int particle_stage(bchmc_handle *h, int rsd, EvalMode m, bool zbin) {
     h->sorted_valid = false;
     bool rho_cleared = false;  // by k_bin_direct, on its way through the lattice
@@ -2163,6 +2173,25 @@ struct Pipe {
   static int probe(bchmc_handle *h, int rsd, bool with_force) {
     EvalMode m;
     CHK(particle_stage(h, rsd, m, false));
+    int like_mode = 0;
+    if (with_force) CHK(like_force(h, m, &like_mode, false));
+    return BCHMC_OK;
+  }
+  // bchmc_probe_displacement_z: the same through the fused z pass + binning.  Psi / n (exact: n is a power of two) goes
+  // through k_zr2c into Ck, in the layout k_ypass leaves there; particle_stage then runs its own BCHMC_LAUNCH_Z.
+  static int probe_z(bchmc_handle *h, int rsd, bool with_force, bool store_psi) {
+    const int n = h->g.n;
+    const size_t zl = ((size_t)n * 6 + n / 2) * sizeof(CT);
+    const CT *tw = C(h->xtw);
+    k_scale_r<T><<<nblk_stride(3 * h->g.N), 256, 0, h->stream>>>(3 * h->g.N, R(h->psi), T(1) / T(n));
+    HIPCHK(hipGetLastError());
+    if (n == 128) CHK(launch_lds(h, k_zr2c<T, 128>, (n / 2) * (n / 2), 128, zl, h->g, h->log2n, tw, R(h->psi), C(h->Ck)));
+    else if (n == 256) CHK(launch_lds(h, k_zr2c<T, 256>, (n / 2) * (n / 2), 256, zl, h->g, h->log2n, tw, R(h->psi), C(h->Ck)));
+    else CHK(launch_lds(h, k_zr2c<T, 512>, (n / 2) * (n / 2), 512, zl, h->g, h->log2n, tw, R(h->psi), C(h->Ck)));
+    EvalMode m;
+    m.planes_c2r = true;
+    m.psi_unread = !store_psi;
+    CHK(particle_stage(h, rsd, m, true));
     int like_mode = 0;
     if (with_force) CHK(like_force(h, m, &like_mode, false));
     return BCHMC_OK;
@@ -3415,6 +3444,29 @@ int bchmc_probe_displacement(bchmc_handle *h, const double *psi, int use_rsd, in
   return read_ctl(h, nullptr);  // synchronises; adapts the binning's record slots like bchmc_forward
 }
 
+int bchmc_probe_displacement_z(bchmc_handle *h, const double *psi, int use_rsd, int with_force, int store_psi) {
+  if (!h || !psi) return BCHMC_ERR_ARG;
+  ENTER(h);
+  const int rsd = use_rsd < 0 ? h->c.rsd_model : (use_rsd ? 1 : 0);
+  if (const char *why = DISPATCH(h, zbin_why_not(h)))
+    return h->fail(BCHMC_ERR_UNSUPPORTED, "the fused z pass + binning does not run on this handle: %s", why);
+  if (rsd && !h->c.planepar) return h->fail(BCHMC_ERR_RSD_NOT_PLANEPAR, "non-plane-parallel RSD is not implemented");
+  if (with_force) {
+    if (h->c.likelihood == 3)
+      return h->fail(BCHMC_ERR_UNSUPPORTED, "the GRF likelihood's force has no particle stage to probe");
+    CHK(check_inputs(h));
+  }
+  clobber_proposal(h);
+  h->cg_valid = false;
+  const size_t N = (size_t)h->g.N;
+  for (int c = 0; c < 3; c++) {
+    CHK(h2d(h, h->dstage, psi + c * N, N * sizeof(double)));
+    CHK(DISPATCH(h, probe_load(h, c)));
+  }
+  CHK(DISPATCH(h, probe_z(h, rsd, with_force != 0, store_psi != 0)));
+  return read_ctl(h, nullptr);  // synchronises; adapts the binning's record slots like bchmc_forward
+}
+
 int bchmc_gradient(bchmc_handle *h, const double *q, double *gout) {
   if (!h || !q || !gout) return BCHMC_ERR_ARG;
   ENTER(h);
@@ -3852,7 +3904,7 @@ int bchmc_tile_info(bchmc_handle *h, int32_t out[8]) {
   out[2] = h->tp.cap;
   out[3] = (int32_t)std::min<long long>(h->cap_alloc, INT32_MAX);
   out[4] = h->slot_watch ? 1 : 0;
-  out[5] = 0;  // reserved
+  out[5] = h->tiled ? (h->tp.tx | (h->tp.ty << 8) | (h->tp.tz << 16)) : 0;
   out[6] = h->std81 ? 1 : 0;
   out[7] = (h->c2r2d_2 != nullptr) ? 1 : 0;
   return BCHMC_OK;

@@ -171,10 +171,10 @@ template <typename T> int ypass(int n, int inverse, void *ck) {
   return pr.finish({{1, ck}});
 }
 
-// k_zr2c<T, 512> as the planes-mode R2C at 512^3 launches it; ck goes in as well, so that the row padding the kernel
-// leaves alone comes back as it went in
+// k_zr2c<T, 512> as the planes-mode R2C at 512^3 launches it, <T, 128> and <T, 256> as bchmc_probe_displacement_z does;
+// ck goes in as well, so that the row padding the kernel leaves alone comes back as it went in
 template <typename T> int zr2c(int n, const void *V, void *ck) {
-  if (n != 512) return -1;
+  if (!(n == 128 || n == 256 || n == 512)) return -1;
   const Geo g = probe_geo(n, (int)sizeof(T));
   Probe pr;
   const C2<T> *tw = pr.twiddles<T>(n);
@@ -182,8 +182,15 @@ template <typename T> int zr2c(int n, const void *V, void *ck) {
   C2<T> *dc = static_cast<C2<T> *>(pr.alloc((size_t)3 * g.Nhp * sizeof(C2<T>), ck));
   if (pr.err) return pr.err;
   const size_t zl = ((size_t)n * 6 + n / 2) * sizeof(C2<T>);
-  auto kz = k_zr2c<T, 512>;
-  if (lds_attr(pr, kz, zl)) kz<<<(n / 2) * (n / 2), 512, zl, 0>>>(g, ilog2(n), tw, dv, dc);
+#define PROBE_LAUNCH_ZR(NZ)                                                                     \
+  do {                                                                                          \
+    auto kz = k_zr2c<T, NZ>;                                                                    \
+    if (lds_attr(pr, kz, zl)) kz<<<(n / 2) * (n / 2), NZ, zl, 0>>>(g, ilog2(n), tw, dv, dc);    \
+  } while (0)
+  if (n == 128) PROBE_LAUNCH_ZR(128);
+  else if (n == 256) PROBE_LAUNCH_ZR(256);
+  else PROBE_LAUNCH_ZR(512);
+#undef PROBE_LAUNCH_ZR
   return pr.finish({{2, ck}});
 }
 

@@ -4,7 +4,8 @@
 // Reference work these two kernels cover: the last two of the three passes of each of theta2vel's inverse transforms
 // (EqSolvers.cc:274-276 -> fftC2Rplanned, fftwrapper.cc:88-102; the x pass is in k_step_boundary_x), and everything
 // k_bin_direct covers (disp_part.cc:55-126, pacman.cpp:20-28, rsd.cc:28-68 + the tile binning, which has no counterpart
-// upstream).  Same numbers as the rocFFT path to transform round-off (tests/test_gpu_large.py::*z_pass_inside_the_binning*).
+// upstream).  Same numbers as the rocFFT path to transform round-off (tests/test_gpu_large.py::*z_pass_inside_the_binning*);
+// the binning of k_zbin_direct on chosen positions: tests/test_gpu_zbin_positions.py.
 // Part of the bchmc engine's kernel set; include through kernels.hpp (after step_boundary_x.hpp and tiles.hpp).
 #pragma once
 #include "common.hpp"
@@ -256,6 +257,8 @@ k_zbin_direct(Geo g, PosPar pp, SphPar sp, TilePar tp, int log2n, const C2<T> *_
 // Output layout: element (i, j, k) at k + nhp (j + n i) of each component, like rocFFT's row pass inside the 2-D plan;
 // the row padding k > n / 2 is left as it is (columns of the later passes are independent, reductions skip it).
 // Replaces the z part of fftR2Cplanned (fftwrapper.cc:104-119) for HMC_models.cc:342-349's three transforms of V.
+// The 128 and 256 instantiations are launched by bchmc_probe_displacement_z only (tests: a chosen displacement on its
+// way into k_zbin_direct); the hot path uses 512.
 // ======================================================================================================
 template <typename T, int NZ>
 __global__ void __launch_bounds__(NZ)
@@ -307,6 +310,13 @@ k_zr2c(Geo g, int log2n, const C2<T> *__restrict__ twiddle, const T *__restrict_
       ck[(long long)c * g.Nhp + row + g.nhp + n / 2] = bh;
     }
   }
+}
+
+// x *= s in place (bchmc_probe_displacement_z: the 1 / n that makes k_zr2c + k_zbin_direct's unnormalised inverse a round trip)
+template <typename T>
+__global__ void k_scale_r(long long n, T *x, T s) {
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
+    x[i] *= s;
 }
 
 // dynamic LDS of k_zbin_direct

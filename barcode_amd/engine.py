@@ -90,7 +90,7 @@ EXPORTS = ("bchmc_create", "bchmc_destroy", "bchmc_strerror", "bchmc_last_error"
            "bchmc_comm_last_error", "bchmc_eps_exchange", "bchmc_comm_pending", "bchmc_comm_world", "bchmc_comm_rank",
            "bchmc_comm_transport", "bchmc_garfield_walk_index", "bchmc_hamiltonian_mass",
            "bchmc_setup_random_test", "bchmc_make_initial_guess", "bchmc_measure_corr", "bchmc_chain_forward",
-           "bchmc_probe_displacement", "bchmc_interp_upres", "bchmc_upres_release", "bchmc_measure_spectrum_src")
+           "bchmc_probe_displacement", "bchmc_probe_displacement_z", "bchmc_interp_upres", "bchmc_upres_release", "bchmc_measure_spectrum_src")
 # declared as well, listed apart: the header scan of the ABI test matches names of letters and underscores only
 EXPORTS_MT19937 = ("bchmc_chain_draw_momenta_mt19937", "bchmc_mt19937_jump")
 EXPORTS_CORR2D = ("bchmc_measure_corr2d", "bchmc_measure_corr2d_interp")  # a digit in the name, like the two above
@@ -155,6 +155,7 @@ def load():
     lib.bchmc_measure_spectrum_src.argtypes = [vp, C.c_int, dp, C.c_uint64, dp, dp]
     lib.bchmc_chain_forward.argtypes = [vp, C.c_int]
     lib.bchmc_probe_displacement.argtypes = [vp, dp, C.c_int, C.c_int]
+    lib.bchmc_probe_displacement_z.argtypes = [vp, dp, C.c_int, C.c_int, C.c_int]
     lib.bchmc_philox_kat.argtypes = [C.POINTER(C.c_uint32)] * 3
     lib.bchmc_kinetic_term.argtypes = [vp, dp, dp]
     lib.bchmc_psi.argtypes = [vp, dp, dp]
@@ -368,6 +369,16 @@ class Engine:
             raise ValueError("psi must hold 3 N = %d values, got %d" % (3 * self.N, psi.size))
         self._chk(self.lib.bchmc_probe_displacement(self.h, _p(psi), int(rsd), int(bool(with_force))))
 
+    def probe_displacement_z(self, psi, rsd, with_force=False, store_psi=True):
+        """Tests: ``probe_displacement`` through the fused z pass + binning (k_zbin_direct; 256^3, 512^3, 128^3 under
+        BCHMC_ZBIN_128=1; BchmcError UNSUPPORTED elsewhere).  ``store_psi``: Psi is stored on the way (``fetch("psix")``
+        is what the kernel used: psi after the z round trip); without it the interior-step variant runs."""
+        psi = np.ascontiguousarray(psi, dtype=np.float64).reshape(-1)
+        if psi.size != 3 * self.N:
+            raise ValueError("psi must hold 3 N = %d values, got %d" % (3 * self.N, psi.size))
+        self._chk(self.lib.bchmc_probe_displacement_z(self.h, _p(psi), int(rsd), int(bool(with_force)),
+                                                      int(bool(store_psi))))
+
     # ---- device-resident entry points (torch tensors on the engine's device, float64, contiguous) ----
     @staticmethod
     def _dptr(t):
@@ -566,8 +577,11 @@ class Engine:
     def tile_info(self):
         out = (C.c_int32 * 8)()
         self._chk(self.lib.bchmc_tile_info(self.h, out))
-        keys = ("tiled", "one_pass", "cap", "cap_alloc", "watch", "reserved", "unrolled81", "alpt_planes")
-        return dict(zip(keys, [int(v) for v in out]))
+        keys = ("tiled", "one_pass", "cap", "cap_alloc", "watch", "tile_shape", "unrolled81", "alpt_planes")
+        info = dict(zip(keys, [int(v) for v in out]))
+        w = info["tile_shape"]
+        info["tile_shape"] = (w & 255, (w >> 8) & 255, (w >> 16) & 255)  # (tx, ty, tz) in cells; zeros without tiles
+        return info
 
     # ---- measurement ---------------------------------------------------------------------------
     def profile(self, enable):

@@ -346,7 +346,8 @@ int bchmc_philox_kat(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[
 
 /* Diagnostic (tests, logs): how the particle-mesh path is currently set up.  out = { tile-sorted path in use, one-pass
  * binning in use, record slots per tile in use, record slots per tile allocated, long trajectories poll the slot words,
- * reserved (0), unrolled 81-cell kernels in use, ALPT planes pipeline available }. */
+ * tile shape in cells tx | ty << 8 | tz << 16 (0 without tiles), unrolled 81-cell kernels in use, ALPT planes pipeline
+ * available }. */
 int bchmc_tile_info(bchmc_handle *h, int32_t out[8]);
 
 /* Diagnostic (tests): what all handles and communicators of this process hold on the device right now.  out = { device
@@ -367,10 +368,27 @@ int bchmc_live_resources(uint64_t out[4]);
  * Ends like bchmc_forward: synchronises and adapts the binning's record slots; a pending proposal and the chain's
  * carried gradient / -log L are dropped; the chain state and the momenta are untouched.  Afterwards bchmc_fetch gives
  * POS*, PSI*, RHO, DELTAX and, after with_force, PART_LIKE and V* of this evaluation.
- * Not reachable through it: the fused z pass + binning of interior trajectory steps at 128^3 and above (k_zbin_direct),
- * which takes Psi^ from k-space; its binning half is the code of k_bin_direct, which this entry does reach.
+ * Not reachable through it: the fused z pass + binning of the trajectory steps at 128^3 and above (k_zbin_direct),
+ * which takes Psi^ from k-space.  Its binning half is an implementation of its own (a hash table of 4 Nx slots that can
+ * run full, keyed on pairs of counters whose two counts share one 64-bit word, one 64-bit global reservation per pair);
+ * bchmc_probe_displacement_z below reaches it, tests/test_gpu_zbin_positions.py holds it to the same bounds.
  * (Added within ABI version 4: no struct or existing entry point changed.) */
 int bchmc_probe_displacement(bchmc_handle *h, const double *psi, int use_rsd, int with_force);
+
+/* Diagnostic (tests): the same through the fused z pass + binning (k_zbin_direct), the binning of every force evaluation
+ * at 256^3 and 512^3 (at 128^3 under BCHMC_ZBIN_128=1).  psi, use_rsd and with_force as above.  psi is converted to the
+ * handle's field type, scaled by 1 / Nx (exact: Nx is a power of two here) and transformed along z by k_zr2c into the
+ * layout the engine's y pass leaves behind; then the particle stage runs as in a trajectory, with the engine's own
+ * k_zbin_direct launches.  store_psi != 0: the variant that stores Psi on the way, as the evaluations at the ends of a
+ * trajectory do (PSI* and POS* can be fetched; Psi is what the kernel used: psi after the z round trip, bitwise psi where
+ * psi is constant along each z row).  store_psi == 0: the interior-step variant, followed by the launch that returns at
+ * once unless a segment overflowed and then writes Psi for the two-pass sort (PSI* / POS* are meaningful after an
+ * overflow only).  Ends like bchmc_probe_displacement.
+ * BCHMC_ERR_UNSUPPORTED, naming the reason, wherever the engine itself would not take this path (Nx other than 256 / 512
+ * / 128 with BCHMC_ZBIN_128=1, masskernel != 3 or calc_h != 2, no tile binning, BCHMC_NO_ZBIN=1); then nothing is
+ * queued and the handle's state is as before, a pending proposal included.
+ * (Added within ABI version 4: no struct or existing entry point changed.) */
+int bchmc_probe_displacement_z(bchmc_handle *h, const double *psi, int use_rsd, int with_force, int store_psi);
 
 /* ---- measurement hooks (bench.py): per-kernel-class HIP-event timing on the engine's stream ---- */
 enum {

@@ -102,14 +102,15 @@ def _accumulate(S, cnt, idx, w, near=None):
     np.add.at(cnt, idx, 1 if near is None else near.astype(np.int64))
 
 
-def sph_density(pos, geo, h, q_slack=0.0, dtype=np.float64, skip=None):
+def sph_density(pos, geo, h, q_slack=0.0, dtype=np.float64, skip=None, cells=None):
     """getDensity_SPH.  pos: [x, y, z] exact in double.  Every particle in the domain adds W_4(r / h) / (pi h^3) to every
     cell whose centre is at r / h <= 2, searched in the (2 reach + 1)^3 cube around its home cell (reach = int(2 h / d) + 1
     covers the sphere from any point of the home cell), indices wrapped periodically.  The home cell is the storage-type
     one (`dtype`); the distances are exact.
     Returns (S, cnt, total): per cell the sum and the number of particles with q <= 2 + q_slack (a storage-type
     evaluation may find such a particle on either side of the cut-off; pm_bound charges it like a contributing one),
-    and the sum over all cells.  skip: boolean mask of particles to leave out (mutants)."""
+    and the sum over all cells.  skip: boolean mask of particles to leave out (mutants).  cells: flat indices; S and cnt
+    are then kept for these cells only, in this order (what lands elsewhere is dropped before it is added)."""
     n, d = geo.n, LD(geo.d)
     h = LD(h)
     w_norm = 1 / _pi() / (h * h * h)
@@ -120,8 +121,12 @@ def sph_density(pos, geo, h, q_slack=0.0, dtype=np.float64, skip=None):
     x = [np.asarray(c, dtype=np.float64)[sel] for c in pos]
     hc = [home_cell(c, geo.d, dtype) for c in x]
     xl = [c.astype(LD) for c in x]
-    S = np.zeros(geo.N, dtype=LD)
-    cnt = np.zeros(geo.N, dtype=np.int64)
+    slot = None
+    if cells is not None:
+        slot = np.full(geo.N, -1, dtype=np.int64)
+        slot[cells] = np.arange(len(cells))
+    S = np.zeros(geo.N if slot is None else len(cells), dtype=LD)
+    cnt = np.zeros(len(S), dtype=np.int64)
     reach = int(2 * float(h) / geo.d) + 1
     lim = (2 + LD(q_slack)) ** 2 * h * h
     for i1 in range(-reach, reach + 1):
@@ -144,10 +149,75 @@ def sph_density(pos, geo, h, q_slack=0.0, dtype=np.float64, skip=None):
                 m3 = r2 <= lim
                 if not m3.any():
                     continue
-                q = np.sqrt(r2[m3]) / h
                 idx = row[m3] + (hc[2][m2][m3] + i3) % n
+                r2 = r2[m3]
+                if slot is not None:
+                    idx = slot[idx]
+                    r2, idx = r2[idx >= 0], idx[idx >= 0]
+                q = np.sqrt(r2) / h
                 _accumulate(S, cnt, idx, sph_w(q, w_norm))
     return S, cnt, S.sum()
+
+
+def sph_density_at(pos, geo, h, cells, q_slack=0.0, dtype=np.float64, threads=1):
+    """S and cnt of sph_density on the chosen cells (flat indices), from the particles that can reach them: those whose
+    home cell is within the search cube's reach of a chosen cell.  The particles left out add nothing to a chosen cell and
+    the others keep their order, so every chosen cell sees the same additions in the same order as in the full
+    evaluation: bitwise its values (tests/test_pm_bounds.py).  threads > 1: the particles are split into that many
+    runs, evaluated side by side (numpy's longdouble loops release the interpreter lock) and the partial sums added in
+    longdouble -- the same sums in another order, 2^-64 relative apart.  Returns (S[cells], cnt[cells])."""
+    n = geo.n
+    cells = np.asarray(cells, dtype=np.int64)
+    reach = int(2 * float(h) / geo.d) + 1
+    chosen = np.zeros((n, n, n), dtype=bool)
+    chosen.reshape(-1)[cells] = True
+    grown = chosen.copy()
+    for axis in range(3):  # the cube of side 2 reach + 1 around every chosen cell, periodic
+        acc = grown.copy()
+        for s in range(1, min(reach, n // 2) + 1):
+            acc |= np.roll(grown, s, axis) | np.roll(grown, -s, axis)
+        grown = acc
+    ok = in_domain(pos, geo)
+    idx = np.flatnonzero(ok)
+    hc = [home_cell(np.asarray(c, dtype=np.float64)[idx], geo.d, dtype) % n for c in pos]
+    near = idx[grown[hc[0], hc[1], hc[2]]]
+
+    def run(part):
+        take = np.ones(geo.N, dtype=bool)
+        take[part] = False
+        return sph_density(pos, geo, h, q_slack, dtype, skip=take, cells=cells)[:2]
+
+    if threads <= 1 or len(near) < 4096 * threads:
+        return run(near)
+    from concurrent.futures import ThreadPoolExecutor
+    with ThreadPoolExecutor(threads) as pool:
+        parts = list(pool.map(run, np.array_split(near, threads)))
+    return sum(p[0] for p in parts), sum(p[1] for p in parts)
+
+
+def reachable_cells(pos, geo, h, dtype=np.float64):
+    """Boolean (N): the cells that can have a particle within 2 h of their centre -- the home cells of the particles in
+    the domain, grown by every offset whose nearest approach to a point of the home cell, max(0, |i| - 1/2) d per axis,
+    is within 2 h (taken 1e-6 wider).  A cell outside it has cnt_c = 0 wherever the particles sit inside their home cells:
+    it must be exactly 0."""
+    n = geo.n
+    ok = in_domain(pos, geo)
+    hc = [home_cell(np.asarray(c, dtype=np.float64)[ok], geo.d, dtype) % n for c in pos]
+    occ = np.zeros((n, n, n), dtype=bool)
+    occ[hc[0], hc[1], hc[2]] = True
+    out = np.zeros_like(occ)
+    reach = int(2 * float(h) / geo.d) + 1
+    gap = [max(0.0, abs(i) - 0.5) * geo.d for i in range(-reach, reach + 1)]
+    lim = (2 * float(h)) ** 2 * (1 + 1e-6)
+    for a, i1 in enumerate(range(-reach, reach + 1)):
+        for b, i2 in enumerate(range(-reach, reach + 1)):
+            ks = [i3 for c, i3 in enumerate(range(-reach, reach + 1)) if gap[a] ** 2 + gap[b] ** 2 + gap[c] ** 2 <= lim]
+            if not ks:
+                continue
+            col = np.roll(occ, (i1, i2), (0, 1))
+            for i3 in ks:
+                out |= np.roll(col, i3, 2)
+    return out.reshape(-1)
 
 
 def _pi():
@@ -248,22 +318,49 @@ def sph_adjoint_gather(pos, plike, geo, h, rho_c, rsd=False, f1=0.0, q_slack=0.0
     be within it) (x_pc: particle minus cell centre), V_z (1 + f1) under RSD.  Particles with a non-finite position get 0.
     Returns (V, A, P, ncell): V (3, N); A (3, N) = sum_c |part_like_c g x / h| with the same factors as V; P (N) = sum of
     |part_like_c| over the cells with q <= 2 + q_slack, times rho_c d^3; ncell (N) = number of those cells."""
-    n, d = geo.n, LD(geo.d)
-    h = LD(h)
-    norm = 1 / (_pi() * h ** 4)
-    normalize = LD(rho_c) * LD(geo.L) ** 3 / LD(geo.N)
-    plike = np.asarray(plike, dtype=np.float64).astype(LD)
     fin = np.ones(geo.N, dtype=bool)
     for c in pos:
         fin &= np.isfinite(c)
     sel = np.flatnonzero(fin)
-    x = [np.asarray(c, dtype=np.float64)[sel] for c in pos]
-    hc = [home_cell(c, geo.d, dtype) for c in x]
-    xl = [c.astype(LD) for c in x]
     V = np.zeros((3, geo.N), dtype=LD)
     A = np.zeros((3, geo.N), dtype=LD)
     P = np.zeros(geo.N, dtype=LD)
     ncell = np.zeros(geo.N, dtype=np.int64)
+    V[:, sel], A[:, sel], P[sel], ncell[sel] = _gather_of(pos, plike, geo, h, rho_c, sel, rsd, f1, q_slack, dtype)
+    return V, A, P, ncell
+
+
+def sph_adjoint_gather_at(pos, plike, geo, h, rho_c, particles, rsd=False, f1=0.0, q_slack=0.0, dtype=np.float64):
+    """sph_adjoint_gather for the chosen particles only (index array), at the cost of those particles: the gather is a
+    sum per particle, so these are the same operations in the same order.  Returns (V, A, P, ncell) of shapes (3, m),
+    (3, m), (m), (m) in the order of `particles`; a particle with a non-finite position gets zeros."""
+    particles = np.asarray(particles, dtype=np.int64)
+    fin = np.ones(len(particles), dtype=bool)
+    for c in pos:
+        fin &= np.isfinite(np.asarray(c)[particles])
+    V = np.zeros((3, len(particles)), dtype=LD)
+    A = np.zeros((3, len(particles)), dtype=LD)
+    P = np.zeros(len(particles), dtype=LD)
+    ncell = np.zeros(len(particles), dtype=np.int64)
+    V[:, fin], A[:, fin], P[fin], ncell[fin] = _gather_of(pos, plike, geo, h, rho_c, particles[fin], rsd, f1, q_slack,
+                                                          dtype)
+    return V, A, P, ncell
+
+
+def _gather_of(pos, plike, geo, h, rho_c, sel, rsd, f1, q_slack, dtype):
+    """The sums of sph_adjoint_gather for the particles `sel` (all with finite positions), compact."""
+    n, d = geo.n, LD(geo.d)
+    h = LD(h)
+    norm = 1 / (_pi() * h ** 4)
+    normalize = LD(rho_c) * LD(geo.L) ** 3 / LD(geo.N)
+    plike = np.asarray(plike, dtype=np.float64)
+    x = [np.asarray(c, dtype=np.float64)[sel] for c in pos]
+    hc = [home_cell(c, geo.d, dtype) for c in x]
+    xl = [c.astype(LD) for c in x]
+    V = np.zeros((3, len(sel)), dtype=LD)
+    A = np.zeros((3, len(sel)), dtype=LD)
+    P = np.zeros(len(sel), dtype=LD)
+    ncell = np.zeros(len(sel), dtype=np.int64)
     lim = (2 + LD(q_slack)) ** 2
     for i1, i2, lo, hi in hull_columns(float(h), geo.d):
         xh = (xl[0] - (hc[0] + i1 + LD(0.5)) * d) / h
@@ -279,8 +376,8 @@ def sph_adjoint_gather(pos, plike, geo, h, rho_c, rsd=False, f1=0.0, q_slack=0.0
             m3 = np.flatnonzero(q2 <= lim)
             if not len(m3):
                 continue
-            p = sel[m2[m3]]
-            pl = plike[row[m3] + (hc[2][m2][m3] + i3) % n]
+            p = m2[m3]
+            pl = plike[row[m3] + (hc[2][m2][m3] + i3) % n].astype(LD)
             g = pl * sph_grad_over_q(np.sqrt(q2[m3]), norm)
             for e, comp in enumerate((xh[m2[m3]], yh[m2[m3]], zh[m3])):
                 V[e, p] += g * comp  # p has no duplicates within one offset

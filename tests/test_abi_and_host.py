@@ -41,6 +41,27 @@ def test_library_exports_every_declared_symbol(built_lib):
     assert sorted(engine.EXPORTS) == declared
 
 
+def test_probe_displacement_z_is_declared_with_its_refusals(built_lib):
+    """bchmc_probe_displacement_z: exported, five arguments in the header and in the Python binding, BCHMC_ERR_ARG for a
+    null handle or array without touching a device, and the header documents the refusal (BCHMC_ERR_UNSUPPORTED = 5,
+    nothing queued) that tests/test_gpu_zbin_positions.py checks on a handle."""
+    from barcode_amd import engine
+    lib = C.CDLL(built_lib)
+    fn = lib.bchmc_probe_displacement_z
+    fn.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_int, C.c_int, C.c_int]
+    x = (C.c_double * 3)()
+    assert fn(None, x, 0, 0, 1) == 1 and fn(None, None, 0, 0, 0) == 1  # BCHMC_ERR_ARG
+    lib.bchmc_strerror.restype = C.c_char_p
+    assert lib.bchmc_strerror(5)  # BCHMC_ERR_UNSUPPORTED has a text
+    text = open(os.path.join(ROOT, "include", "bchmc.h")).read()
+    decl = re.search(r"int bchmc_probe_displacement_z\(([^)]*)\);", text).group(1)
+    assert [a.strip().split()[-1].lstrip("*") for a in decl.split(",")] == ["h", "psi", "use_rsd", "with_force", "store_psi"]
+    doc = text[:text.index("int bchmc_probe_displacement_z(")].rsplit("/*", 1)[1]
+    assert "BCHMC_ERR_UNSUPPORTED" in doc and "nothing is\n * queued" in doc.replace("\r", "")
+    assert "bchmc_probe_displacement_z" in engine.EXPORTS
+    assert re.search(r"BCHMC_ERR_ARG\s*=\s*1\b", text) and re.search(r"BCHMC_ERR_UNSUPPORTED\s*=\s*5\b", text)
+
+
 def test_config_struct_layout_matches_header():
     """Field order of BchmcConfig must be the header's; compile a tiny C probe for sizeof/offsetof."""
     from barcode_amd.engine import BchmcConfig, EpsRecord

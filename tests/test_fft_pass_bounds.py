@@ -11,11 +11,15 @@ complex column and k_zr2c's R2C unpacking.
 (b) The same checker rejects each of four plausible kernel bugs: float64 twiddles rounded to float32, the second-stage
     twiddle conjugated in one direction, one twiddle index off by one, the n / 2 term of the C2R packing dropped.
     Without (b) nobody would know whether tests/test_gpu_fft_passes.py can fail.
+(c) The z round trip of bchmc_probe_displacement_z (x / n through k_zr2c, back through k_zbin_direct's inverse) at
+    n = 128, 256, 512: the constant of fft_bound's two-pass form is measured here, rows that are constant along z come
+    back bit for bit, and the two-pass checker rejects a conjugate taken with the wrong sign in the R2C unpacking and
+    the k = n / 2 element taken from the wrong row of the pair.
 """
 import numpy as np
 import pytest
 
-from tests.fft_bound import worst_ratio
+from tests.fft_bound import MEASURED_ROUNDTRIP, MARGIN_ROUNDTRIP, C_ROUNDTRIP, worst_ratio, worst_ratio_roundtrip
 
 NS = [32, 64, 128, 256, 512]
 DTYPES = [np.float32, np.float64]
@@ -120,7 +124,11 @@ def zr2c(a, b, dtype, mutation=None):
     h = dtype(0.5)
     Ar, Ai = h * (zr[k] + zr[km]), h * (zi[k] - zi[km])
     Br, Bi = h * (zi[k] + zi[km]), dtype(-0.5) * (zr[k] - zr[km])
+    if mutation == "unpack_conj_sign":  # conj(Z[n - k]) taken as Z[n - k] in A's imaginary part
+        Ai = h * (zi[k] + zi[km])
     Ar[n // 2], Ai[n // 2], Br[n // 2], Bi[n // 2] = zr[n // 2], 0, zi[n // 2], 0
+    if mutation == "nyquist_wrong_row":  # the k = n / 2 terms of the two rows of the pair swapped
+        Ar[n // 2], Br[n // 2] = zi[n // 2], zr[n // 2]
     return (Ar.astype(np.float64) + 1j * Ai.astype(np.float64), Br.astype(np.float64) + 1j * Bi.astype(np.float64))
 
 
@@ -227,3 +235,71 @@ def test_bound_rejects_twiddle_index_off_by_one(n, dtype):
 def test_bound_rejects_dropped_nyquist_term_of_the_c2r(n, dtype):
     """(b) k_zbin_direct's packing without Z[n/2] = A[n/2] + i B[n/2]."""
     assert c2r_ratio(n, dtype, "drop_nyquist") > 1.0
+
+
+# ---- (c) the z round trip ----------------------------------------------------------------------------------------------
+
+RT_NS = [128, 256, 512]
+
+
+def roundtrip(a, b, dtype, mutation=None):
+    """Rows a, b (n, cols): scaled by 1 / n (exact), k_zr2c, then k_zbin_direct's inverse.  Returns (a', b')."""
+    n = a.shape[0]
+    s = dtype(1) / dtype(n)
+    A, B = zr2c(a.astype(dtype) * s, b.astype(dtype) * s, dtype, mutation)
+    return zc2r(A, B, dtype)
+
+
+def roundtrip_rows(n, seed=4):
+    """White rows, rows many box lengths out mixed with small ones, an impulse against a zero partner, a constant pair."""
+    rng = np.random.default_rng(seed)
+    a = rng.standard_normal((n, 12))
+    b = rng.standard_normal((n, 12))
+    a[:, 8] += 1e3 * rng.integers(-7, 8, n)
+    b[:, 9] *= 1e-3
+    a[:, 10], b[:, 10] = 0, 0
+    a[n // 2 + 1, 10] = 1.0
+    a[:, 11], b[:, 11] = -1.5625, 0.3
+    return a, b
+
+
+def roundtrip_ratio(n, dtype, mutation=None):
+    a, b = roundtrip_rows(n)
+    a, b = rounded(a, dtype), rounded(b, dtype)
+    ga, gb = roundtrip(a, b, dtype, mutation)
+    got = np.concatenate([ga, gb], axis=0).astype(np.float64)
+    return worst_ratio_roundtrip(got, np.concatenate([a, b], axis=0), n, dtype, axis=0)
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=["fp32", "fp64"])
+def test_roundtrip_constant_is_the_measured_one(dtype):
+    """The worst fraction of log2(n) u ||x|| the restated round trip reaches is the figure fft_bound records (rounded
+    up to two digits), and the constant in use is four times it."""
+    name = np.dtype(dtype).name
+    worst = max(roundtrip_ratio(n, dtype) for n in RT_NS) * C_ROUNDTRIP[name]
+    print("z round trip %s: worst fraction of log2(n) u ||x|| %.3f" % (name, worst))
+    assert 0.8 * MEASURED_ROUNDTRIP[name] <= worst <= MEASURED_ROUNDTRIP[name]
+    assert C_ROUNDTRIP[name] == MARGIN_ROUNDTRIP * MEASURED_ROUNDTRIP[name] and MARGIN_ROUNDTRIP == 4.0
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=["fp32", "fp64"])
+@pytest.mark.parametrize("n", RT_NS)
+def test_rows_constant_along_z_survive_the_roundtrip_bitwise(n, dtype):
+    """Every non-trivial twiddle meets an exact zero and the remaining butterflies are doublings: cell fractions,
+    nextafter(L, 0) - d / 2, -ulp, many box lengths, a pair of very different sizes."""
+    T = np.dtype(dtype).type
+    L = 200.0 * n / 64.0
+    vals = np.array([0.0, -0.5 * L / n, float(np.nextafter(T(L), T(0))) - 0.5 * L / n,
+                     -float(np.nextafter(T(0.5 * L / n), T(L))), 17 * L + 0.3, -21 * L - 1e-3, 1e-30, 3.0])
+    a = np.broadcast_to(vals.astype(dtype)[None, :], (n, len(vals))).copy()
+    b = np.broadcast_to(vals.astype(dtype)[None, ::-1], (n, len(vals))).copy()
+    ga, gb = roundtrip(a, b, dtype)
+    assert np.array_equal(ga, a) and np.array_equal(gb, b)
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=["fp32", "fp64"])
+@pytest.mark.parametrize("n", RT_NS)
+@pytest.mark.parametrize("mutation", ["unpack_conj_sign", "nyquist_wrong_row"])
+def test_roundtrip_bound_rejects_wrong_unpacking(mutation, n, dtype):
+    assert roundtrip_ratio(n, dtype) <= 1.0
+    assert roundtrip_ratio(n, dtype, mutation) > 1.0

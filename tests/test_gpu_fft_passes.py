@@ -5,7 +5,8 @@ bound of tests/fft_bound.py.
 - xfft_inplace (the radix-4 core of k_step_boundary_x, k_ypass, k_zbin_direct, k_zr2c) at n = 32 .. 512, with the
   interleave KB of the x / y passes (8 fp64, 16 fp32) and of the z passes (6), both directions;
 - k_ypass inverse at 128 / 256 / 512 and forward at 512 over three whole n^2 nhp components;
-- k_zr2c<T, 512>, the z R2C of the planes-mode forward transform at 512^3;
+- k_zr2c<T, 512>, the z R2C of the planes-mode forward transform at 512^3, and <T, 128> / <T, 256>, which only
+  bchmc_probe_displacement_z launches (tests/test_gpu_zbin_positions.py stands on them);
 - k_zbin_direct<T, NZ, true> (the overflow fallback, *ovf set), the z C2R of three components at 128 / 256 / 512.
 
 Inputs: white complex Gaussian data in every column, unit impulses at 0, 1, n/2 - 1, n/2, n/2 + 1, n - 1 in the first
@@ -170,8 +171,19 @@ def z_impulse_rows(n):
 def test_k_zr2c_512(lib, prec):
     """k_zr2c<T, 512>: V (3, n, n, n) real -> half-complex (3, n, n, nhp); every k <= n/2 written (the output array
     goes in as NaN), the row padding returned bit for bit."""
+    check_k_zr2c(lib, prec, 512)
+
+
+@pytest.mark.parametrize("n", [128, 256])
+@pytest.mark.parametrize("prec", ["fp64", "fp32"])
+def test_k_zr2c(lib, prec, n):
+    """k_zr2c<T, 128> and <T, 256>, the instantiations bchmc_probe_displacement_z feeds k_zbin_direct through: the same
+    inputs and the same bound as at 512."""
+    check_k_zr2c(lib, prec, n)
+
+
+def check_k_zr2c(lib, prec, n):
     p, rdt, cdt = PREC[prec]
-    n = 512
     rng = np.random.default_rng(300)
     V = rng.standard_normal((3, n, n, n)).astype(rdt)
     for k, row, partner in z_impulse_rows(n):
@@ -193,7 +205,7 @@ def test_k_zr2c_512(lib, prec):
     for c, i in sample_rows(np.random.default_rng(8), n):
         ref = np.fft.rfft(V[c, i].astype(np.longdouble), axis=-1)
         worst = max(worst, worst_ratio(pairs(ck[None, c, i:i + 1, :, :nh]), pairs(ref[None, None]), n, rdt, axis=-1))
-    report("k_zr2c<%s,512>" % prec, worst)
+    report("k_zr2c<%s,%d>" % (prec, n), worst)
 
 
 @pytest.mark.parametrize("n", [128, 256, 512])

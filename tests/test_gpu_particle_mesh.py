@@ -7,8 +7,10 @@ longdouble reference under the bound of tests/pm_bound.py (a cell or particle th
 0), and the oracle's getDensity / likelihood_calc_V_SPH run as a second reference at TOL_FIELD / 10 TOL_FIELD.  Each
 check prints its worst fraction of the bound ("PM <kernel family><type> n=.. <set>: worst fraction of the bound ..").
 
-Not reachable through the entry point, and so not covered: the binning half of k_zbin_direct (it takes Psi^ from
-k-space).  calc_h = 3's interpolation is covered at oracle precision only: its convolved fields cannot be fetched.
+Not reachable through this entry point: k_zbin_direct, which takes Psi^ from k-space.  Its binning half is not
+k_bin_direct's code but an implementation of its own (a hash table of 4 n slots on pairs of counters, two counts packed
+in one 64-bit word, 64-bit global reservations); bchmc_probe_displacement_z reaches it and
+tests/test_gpu_zbin_positions.py holds it to the same checks.  calc_h = 3's interpolation is covered at oracle precision only: its convolved fields cannot be fetched.
 """
 import numpy as np
 import pytest

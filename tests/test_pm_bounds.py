@@ -537,3 +537,115 @@ def test_low_order_restatements_and_their_home_cell_mutant(mk, dtype):
                 print("PMCPU mutant home_low mk=%d<%s> %s: %.3g x the bound" % (mk, name32, name, f))
                 assert f > 1
     assert worst <= pm_bound.MEASURED["low"][name32]
+
+
+# ---- the host side of tests/test_gpu_zbin_positions.py -------------------------------------------------------------------
+
+from tests import zbin_sets  # noqa: E402
+
+
+@pytest.mark.parametrize("name", ("mixed", "collapse_corner"))
+def test_subset_evaluators_are_bitwise_the_full_reference(name):
+    """sph_density_at / sph_adjoint_gather_at on chosen cells and particles against the full evaluation at 32^3, with an
+    offset domain so that dropped particles are among the neighbours."""
+    n, dtype = 32, np.float64
+    geo = ref.Geometry(n, 100.0, (0.5 * 3.125, -0.25 * 3.125, 0.25 * 3.125))
+    psi = ref.position_sets(geo, dtype, names=(name,))[name]
+    psi[0, 5], psi[2, 777] = np.nan, np.inf
+    pos = [c.astype(np.float64) for c in ref.positions(psi, geo, 0, dtype)]
+    h, slack = geo.d, pm_bound.q_slack(dtype, n, 1.0)
+    cells, hist = zbin_sets.cell_subset(pos, geo, (8, 8, 16), dtype, extra=[17, 30000])
+    assert len(cells) >= 4096 and hist.sum() == ref.in_domain(pos, geo).sum()
+    S, cnt, _ = ref.sph_density(pos, geo, h, slack, dtype)
+    Sa, cnta = ref.sph_density_at(pos, geo, h, cells, slack, dtype)
+    assert np.array_equal(Sa, S[cells]) and np.array_equal(cnta, cnt[cells])
+    assert np.array_equal(np.sort(np.argsort(hist, kind="stable")[-64:]), np.intersect1d(cells, np.argsort(hist, kind="stable")[-64:]))
+    assert not np.any(cnt[~ref.reachable_cells(pos, geo, h, dtype)])
+    parts = zbin_sets.particle_subset(pos, geo, dtype, hist, extra=[123])
+    assert len(parts) >= 4096 and {5, 777, 123, 0, geo.N - 1} <= set(parts.tolist())
+    plike = np.random.default_rng(3).standard_normal(geo.N)
+    full = ref.sph_adjoint_gather(pos, plike, geo, h, 1.3, True, 0.4, slack, dtype)
+    sub = ref.sph_adjoint_gather_at(pos, plike, geo, h, 1.3, parts, True, 0.4, slack, dtype)
+    for a, b in zip(full, sub):
+        assert np.array_equal(a[..., parts], b)
+
+
+def test_reachable_cells_leave_out_exactly_the_far_ones():
+    """One particle: the cells farther than the stencil from its home cell, and only those, are unreachable; every
+    cell with cnt > 0 is reachable wherever the particle sits in its home cell."""
+    n = 16
+    geo = ref.Geometry(n, 50.0)
+    for frac in ((0.0, 0.0, 0.0), (0.999, 0.999, 0.999), (0.5, 0.0, 0.999)):
+        pos = [np.array([(5 + f) * geo.d]) for f in frac]
+        reach = ref.reachable_cells(pos, geo, geo.d)
+        _, cnt, _ = ref.sph_density(pos, geo, geo.d)
+        assert not np.any(cnt[~reach]) and reach.sum() < 7 ** 3 and cnt.sum() > 0
+    corners = sum((ref.sph_density([np.array([(5 + a) * geo.d * (1 - 1e-12) if a else 5 * geo.d]) for a in f], geo, geo.d)[1] > 0)
+                  for f in np.ndindex(2, 2, 2))
+    assert np.array_equal(corners > 0, ref.reachable_cells([np.array([5.5 * geo.d])] * 3, geo, geo.d) & (corners > 0))
+
+
+def test_counter_pairs_of_a_hand_made_case():
+    """n = 4, tiles of 2 x 2 x 2: workgroup 0 owns the rows (0..1, 0..1, :).  Its 16 particles are put into known
+    counters; every other particle goes to one far counter."""
+    n = 4
+    geo = ref.Geometry(n, 4.0)  # d = 1
+    tile = (2, 2, 2)
+    pos = [np.full(geo.N, 3.25), np.full(geo.N, 3.25), np.full(geo.N, 3.25)]  # tile 7, bits 000: key 56, pair 28
+    i, j, k = ref.lattice_index(n)
+    wg0 = np.flatnonzero((i < 2) & (j < 2))
+    assert len(wg0) == 16
+    # four particles each: cell (0, 0, 0) lower z half (key 0), the same cell upper z half (key 1: the other half of pair
+    # 0), cell (0, 0, 2) = tile 1 with x upper (b = 4: octant 7, pair 7 of tile 1 = pair 7), and a NaN
+    for m, p in enumerate(wg0):
+        x, y, z = ((0.25, 0.25, 0.25), (0.25, 0.25, 0.75), (0.75, 0.25, 2.25), (np.nan, 0.0, 0.0))[m // 4]
+        pos[0][p], pos[1][p], pos[2][p] = x, y, z
+    key = zbin_sets.counter_keys(pos, geo, tile, np.float64)
+    assert sorted(set(key[wg0].tolist())) == [-1, 0, 1, 15]
+    assert set(key[np.setdiff1d(np.arange(geo.N), wg0)].tolist()) == {56}
+    per = zbin_sets.distinct_pairs_per_workgroup(key, n)
+    assert per.tolist() == [2, 1, 1, 1]
+    pairs, even, odd = zbin_sets.pair_halves_per_workgroup(key, n)
+    assert pairs.tolist()[:2] == [0, 7] and even.tolist()[:2] == [4, 0] and odd.tolist()[:2] == [4, 4]
+    assert np.array_equal(zbin_sets.workgroup_index(n)[wg0], np.zeros(16, dtype=np.int64))
+
+
+@pytest.mark.parametrize("dtype", (np.float32, np.float64), ids=("fp32", "fp64"))
+def test_zbin_sets_do_what_they_are_for(dtype):
+    """32^3 with 8 x 8 x 16 tiles: one_counter gives every workgroup one counter of its own, both_halves fills both halves
+    of every pair alike, the z-constant sets are constant along z, scrambled meets many pairs (the 0.9 of the GPU test
+    needs the tile count of 128^3: here 256 pairs for 128 particles)."""
+    n, tile = 32, (8, 8, 16)
+    geo = ref.Geometry(n, 100.0)
+    names = ("one_counter", "both_halves", "scrambled", "faces", "far_out_zc", "tiny_negative_zc", "upper_edge_zc")
+    sets = zbin_sets.z_position_sets(geo, dtype, tile, names)
+    keys = {}
+    for name in names:
+        pos = [c.astype(np.float64) for c in ref.positions(sets[name], geo, 0, dtype)]
+        keys[name] = zbin_sets.counter_keys(pos, geo, tile, dtype)
+        if name in zbin_sets.EXACT_SETS:
+            q = sets[name].reshape(3, n, n, n)
+            assert np.array_equal(q, np.broadcast_to(q[..., :1], q.shape)), name
+    wg = zbin_sets.workgroup_index(n)
+    one = keys["one_counter"]
+    assert np.all(zbin_sets.distinct_pairs_per_workgroup(one, n) == 1)
+    first = one[np.unique(wg, return_index=True)[1]]
+    assert np.array_equal(one, first[wg]) and len(np.unique(first)) == (n // 2) ** 2
+    pairs, even, odd = zbin_sets.pair_halves_per_workgroup(keys["both_halves"], n)
+    assert np.all(even == 2 * tile[2]) and np.all(odd == 2 * tile[2]) and len(pairs) == (n // 2) ** 2 * (n // tile[2])
+    assert zbin_sets.distinct_pairs_per_workgroup(keys["scrambled"], n).max() >= 0.55 * 4 * n
+    faces = ref.positions(sets["faces"], geo, 0, dtype)
+    on_face = [np.mean(np.fmod(c.astype(np.float64), geo.d) == 0) for c in faces]
+    assert all(0.2 < f < 0.5 for f in on_face)
+
+
+def test_scrambled_fills_the_table_of_the_128_instantiation():
+    """The GPU test asserts >= 0.9 * 4 n distinct pairs in the fullest workgroup; here the same count on the host for the
+    positions as given (before the z round trip), 128^3 with 8 x 8 x 16 tiles."""
+    n, tile, dtype = 128, (8, 8, 16), np.float64
+    geo = ref.Geometry(n, 400.0)
+    psi = zbin_sets.z_position_sets(geo, dtype, tile, ("scrambled",))["scrambled"]
+    pos = [c.astype(np.float64) for c in ref.positions(psi, geo, 0, dtype)]
+    per = zbin_sets.distinct_pairs_per_workgroup(zbin_sets.counter_keys(pos, geo, tile, dtype), n)
+    print("scrambled 128^3: distinct pairs per workgroup mean %.1f, largest %d of %d" % (per.mean(), per.max(), 4 * n))
+    assert per.max() >= 0.9 * 4 * n
