@@ -165,23 +165,17 @@ struct bchmc_handle {
   Event ev_q;
 
   DevBuf<int4> hull;
-  int hull_n = 0;
-  int reach = 0;
-  int hull_maxlen = 0;      // longest k-range of a hull column
-  bool hull_exact = false;  // no cell of the (2 reach + 1)^3 cube outside the hull can pass r/h <= 2
-  // tile-sorted particle-mesh path
-  bool tiled = false;
+  // tile-sorted particle-mesh path: the partition (plan.tp is what the kernels take) and the state of the record-slot
+  // policy, both decided in tile_plan.hpp
+  TilePlan plan;
   // "planes" mode of the interior step boundary: 2-D (y, z) transforms by rocFFT, x passes inside k_step_boundary_x
   FftPlan r2c2d, c2r2d;                          // batch 3 n planes
   DevBytes xtw;                                  // n / 2 twiddles exp(-2 pi i r / n), C2<T>
   int log2n = 0;
   bool planes_ok = false;                        // plans + kernel available for this grid
-  bool sort_direct = false;  // one-pass tile binning into fixed slots (two-pass sort as overflow fallback)
   FftPlan r2c2d_2, c2r2d_2;  // 2-D plans over 2 n planes: delta(1) | Phi and A | B of the ALPT model
   bool alpt_plans_failed = false;
   double alpt_wtot = 0.;     // kernelcomp's normalisation (sum of the real-space kernel), computed on first use
-  bool std81 = false;  // standard 81-cell hull on 8 x 8 x 16 tiles with halo 2: fully unrolled scatter/gather kernels
-  TilePar tp{};
   DevBuf<int> t_cnt, t_woff;                 // 9 ntiles + 2 (one-pass counts per (tile, octant), fallback counts per tile,
                                              // overflow flags), ntiles + 1
   DevBuf<int4> t_oct;                        // 2 ntiles: octant segment starts of every tile (k_scan_tiles)
@@ -190,12 +184,6 @@ struct bchmc_handle {
   DevBuf<int2> t_rank;                                         // N
   DevBytes srec;         // tile-sorted particle records { x, y, z, original index | flags }: 4 * sizeof(T) bytes each
   bool sorted_valid = false;
-  long long cap_alloc = 0;  // record slots per tile the array srec was allocated for; tp.cap <= cap_alloc is the part in use
-  long long cap_wanted = 0; // > cap_alloc: what the next synchronising call should reallocate to (0 = nothing pending)
-  bool cap_pinned = false;  // BCHMC_SORT_CAP_FIXED=1: the partition never adapts (A/B runs)
-  long long cap_budget = 0; // most record slots per tile the array may ever be reallocated for (a quarter of the device)
-  bool slot_watch = true;   // the populations seen last were close to the segment size (or unknown yet): a long
-                            // trajectory polls the binning's flag every few steps instead of only at its end
   PinnedBuf<int> h_slots;   // pinned: two snapshots of {sticky overflow stamp, largest population} for those polls
   Event slot_ev[2];
   bool cnt_clean = false;   // t_cnt[0 .. 2 ntiles] was cleared by the last k_scatter_tile81 (no fill launch needed)
@@ -380,7 +368,7 @@ SphPar make_sph(const bchmc_handle *h) {
   sp.min1 = h->c.min1;
   sp.min2 = h->c.min2;
   sp.min3 = h->c.min3;
-  sp.reach = h->reach;
+  sp.reach = h->plan.reach;
   return sp;
 }
 
@@ -399,39 +387,13 @@ HullPar make_hull(const bchmc_handle *h) {
   HullPar hp;
   const double hh = h->c.particle_kernel_h;
   hp.cols = h->hull;
-  hp.ncol = h->hull_n;
+  hp.ncol = h->plan.hull_n;
   hp.h_inv = 1. / hh;
   hp.d_h = h->g.d * hp.h_inv;
   hp.norm = 1. / (M_PI * (hh * hh) * (hh * hh));
   hp.normalize = h->c.rho_c * h->g.L * h->g.L * h->g.L / (double)h->g.N;
   hp.f1 = fgrow1(h->c.ascale, h->c.OM, h->c.OL);
   return hp;
-}
-
-// SPH stencil -> (i, j) column hull: SPH_kernel_3D_cells (SPH_kernel.cpp:62-102) + hull_1 (110-139)
-void build_hull(double hh, double d, std::vector<int4> &cols, int &reach_out) {
-  const double reach = hh * 2;
-  const int r = (int)(reach / d) + 1;
-  reach_out = r;
-  const double reach_sq = reach * reach;
-  cols.clear();
-  for (int i1 = -r; i1 <= r; ++i1)
-    for (int i2 = -r; i2 <= r; ++i2)
-      for (int i3 = -r; i3 <= r; ++i3) {
-        const double dx = (std::fabs((double)i1) - 0.5) * d, dy = (std::fabs((double)i2) - 0.5) * d,
-                     dz = (std::fabs((double)i3) - 0.5) * d;
-        if (dx * dx + dy * dy + dz * dz <= reach_sq) {
-          bool found = false;
-          for (auto &c : cols)
-            if (c.x == i1 && c.y == i2) {
-              c.z = std::min(c.z, i3);
-              c.w = std::max(c.w, i3);
-              found = true;
-              break;
-            }
-          if (!found) cols.push_back(make_int4(i1, i2, i3, i3));
-        }
-      }
 }
 
 int need_input(bchmc_handle *h, int f, const char *name) {
@@ -449,50 +411,43 @@ int check_inputs(bchmc_handle *h) {
   return BCHMC_OK;
 }
 
-// One-pass tile binning, sizing of the record slots.  Every (tile, octant) owns tp.cap / 8 slots of an array allocated for
-// cap_alloc slots per tile (16x the mean occupancy to start with); k_scan_tiles leaves the largest (tile, octant)
-// population of each binning in a device word, k_bin_direct stamps a sticky flag with the segment size when a segment
-// was too small (that force evaluation then ran the exact two-pass sort).  The host reads both words wherever it
-// synchronises anyway (read_ctl: bchmc_steps_done, bchmc_sync, bchmc_forward, the end of a chain attempt).  When a
-// segment overflowed or is more than 7/8 full, the partition grows to the WHOLE allocation, and if 1.5x the largest
-// population does not fit that either, the array is reallocated for it (+25 %) -- sized from what was measured, not
-// doubled blindly (VERDICT r2 items 2 ii and 7).  It never shrinks: denser slots were measured to buy 0.01 ms per
-// binning (profiles/r03_ab_slots.txt), and a partition fitted to a quiet start field overflowed in the middle of a
-// 1100-step trajectory whose populations doubled on the way (profiles/r03_sustained_ab.txt: 311 against 336 steps/s).
-// A partition smaller than the allocation (BCHMC_SORT_CAP) is also extended inside a trajectory, by a lagging poll
-// every few steps (poll_slots).
+// One-pass tile binning, sizing of the record slots: the rules are SlotPolicy's (tile_plan.hpp).  Here the slot words are
+// read wherever the host synchronises anyway (read_ctl: bchmc_steps_done, bchmc_sync, bchmc_forward, the end of a chain
+// attempt) and by a lagging poll inside a trajectory (poll_slots), and what the policy asks for is carried out.
 RecQuad *recs(const bchmc_handle *h) { return static_cast<RecQuad *>(h->srec.get()); }  // the records, as the kernels take them
-int *slot_words(bchmc_handle *h) { return h->t_cnt + (kOct + 1) * (size_t)h->tp.ntiles + 1; }  // {sticky stamp, max}
+int *slot_words(bchmc_handle *h) { return h->t_cnt + (kOct + 1) * (size_t)h->plan.tp.ntiles + 1; }  // {sticky stamp, max}
 
-int realloc_slots(bchmc_handle *h, long long cap) {
+void repartition(bchmc_handle *h) {
+  h->plan.tp.cap = h->plan.slots.cap;
+  h->sorted_valid = false;
+}
+
+int realloc_slots(bchmc_handle *h, long long want) {
   HIPCHK(hipStreamSynchronize(h->stream));  // rare path: the record slots are about to be replaced
+  SlotPolicy &sl = h->plan.slots;
   const bool verbose = env_on("BCHMC_VERBOSE");
-  // Memory budget: the records may take a quarter of the device (or what they took at creation).  A field clustered
-  // beyond that -- the mock-data truth field at 512^3 has a (tile, octant) of 3661 particles, 29x the mean, and 1.5x
-  // that would be 231 GB of slots -- keeps the array at the budget: the evaluations that overflow run the exact two-pass
-  // sort (512^3 fp64: binning 2.7 -> 6.6 ms, scatter 6.5 -> 8.5 ms for those evaluations only), all others stay on
-  // the one-pass path (one exceptional field, e.g. the truth field of a mock-data run, must not cost the chain that).
-  if (cap > h->cap_budget || cap >= (1ll << 30)) cap = std::min<long long>(h->cap_budget, (1ll << 30) - kOct) / kOct * kOct;
-  if (cap <= h->cap_alloc) {
+  const long long cap = sl.clamp_to_budget(want);
+  if (!cap) {
     if (verbose) fprintf(stderr, "bchmc: record slots stay at %lld per tile (memory budget %lld): overflowing evaluations "
-                                 "run the two-pass sort\n", h->cap_alloc, h->cap_budget);
+                                 "run the two-pass sort\n", sl.cap_alloc, sl.cap_budget);
+    sl.after_realloc(SlotGot::kOldSize, cap);
     return BCHMC_OK;
   }
   // The old array goes first (its contents are rebuilt by the next binning anyway): at 512^3 fp64 it is 69 GB, and the
-  // new one next to it would not fit.  Never fewer than N records: the two-pass sort packs all particles.
+  // new one next to it would not fit.
   (void)h->srec.release();
   h->sorted_valid = false;
-  for (long long c : {cap, h->cap_alloc, 0ll}) {
-    const size_t nrec = std::max<size_t>((size_t)h->g.N, (size_t)c * h->tp.ntiles);
+  for (SlotGot got : {SlotGot::kWanted, SlotGot::kOldSize, SlotGot::kRecordsOnly}) {
+    const size_t nrec = record_count(h->g.N, sl.rung(got, cap), h->plan.tp.ntiles);
     if (h->srec.alloc(nrec * 4 * h->esz) == hipSuccess) {
-      if (c == cap) {
-        h->cap_alloc = cap;
+      if (got == SlotGot::kWanted) {
         if (verbose) fprintf(stderr, "bchmc: record array reallocated for %lld slots per tile\n", cap);
       } else {
         if (verbose) fprintf(stderr, "bchmc: no memory for %lld record slots per tile: %s\n", cap,
-                             c ? "kept the old size, overflowing steps run the two-pass sort" : "one-pass binning given up");
-        if (c == 0) h->sort_direct = false;
+                             got == SlotGot::kOldSize ? "kept the old size, overflowing steps run the two-pass sort"
+                                                      : "one-pass binning given up");
       }
+      sl.after_realloc(got, cap);
       return BCHMC_OK;
     }
     (void)hipGetLastError();
@@ -500,40 +455,17 @@ int realloc_slots(bchmc_handle *h, long long cap) {
   return h->fail(BCHMC_ERR_NOMEM, "no device memory for the particle records");
 }
 
-// sticky: segment size stamped by an overflowing binning (0 = none); maxc: largest (tile, octant) population since the
-// words were last cleared (0 = no binning ran).
 int adapt_slots(bchmc_handle *h, int sticky, int maxc, bool may_realloc) {
-  if (!h->tiled || !h->sort_direct || h->cap_pinned) return BCHMC_OK;
-  const long long seg = h->tp.cap / kOct;
-  const bool ovf = sticky != 0 && sticky >= seg;  // a smaller stamp predates the last re-partitioning
-  if (maxc <= 0 && !ovf) return BCHMC_OK;
-  const long long whole = h->cap_alloc - h->cap_alloc % kOct;
-  h->slot_watch = h->tp.cap < whole && (ovf || 4ll * maxc > 3 * seg);  // room left to extend into: keep an eye on it
-  // extend into the allocation when a segment is 7/8 full; reallocate only for one that actually overflowed
-  if (!ovf && !(h->tp.cap < whole && 8ll * maxc > 7 * seg)) return BCHMC_OK;
-  long long want = ((3ll * maxc) / 2 + 16 + 7) / 8 * 8;  // segments of 1.5x the largest population
-  if (want <= seg) want = 2 * seg;                        // overflow without a population figure: double
-  long long ncap = std::max(want * kOct, whole);          // at least everything that is allocated
-  if (ncap > whole) {
-    if (!ovf) {
-      ncap = whole;
-    } else if (may_realloc) {
-      CHK(realloc_slots(h, ncap + ncap / 4));  // may keep the array as it is (memory budget)
-      if (!h->sort_direct) return BCHMC_OK;
-      h->cap_wanted = 0;
-      ncap = h->cap_alloc - h->cap_alloc % kOct;
-    } else {
-      h->cap_wanted = ncap;  // the next synchronising call reallocates; until then the largest partition that fits
-      ncap = whole;
-    }
-  }
-  h->slot_watch = false;     // nothing left to extend into
-  if (ncap == h->tp.cap) return BCHMC_OK;
+  if (!h->plan.tiled) return BCHMC_OK;
+  SlotPolicy &sl = h->plan.slots;
+  const int old = sl.cap;
+  const SlotAction a = sl.observe(sticky, maxc, may_realloc);
+  if (a.kind == SlotAction::kRealloc) CHK(realloc_slots(h, a.cap));  // the partition follows the array
+  if (sl.cap == old) return BCHMC_OK;
   if (env_on("BCHMC_VERBOSE"))
-    fprintf(stderr, "bchmc: record slots per tile %d -> %lld (largest (tile, octant) population %d%s)\n", h->tp.cap, ncap,
-            maxc, ovf ? ", a segment overflowed" : "");
-  h->tp.cap = (int)ncap;
-  h->sorted_valid = false;
+    fprintf(stderr, "bchmc: record slots per tile %d -> %lld (largest (tile, octant) population %d%s)\n", old,
+            (long long)sl.cap, maxc, a.overflowed ? ", a segment overflowed" : "");
+  repartition(h);
   return BCHMC_OK;
 }
 
@@ -542,7 +474,7 @@ int adapt_slots(bchmc_handle *h, int sticky, int maxc, bool may_realloc) {
 int read_ctl(bchmc_handle *h, unsigned long long *steps_done) {
   unsigned long long sd = 0;
   int words[2] = {0, 0}, sat = 0;
-  const bool slots = h->tiled && h->sort_direct;
+  const bool slots = h->plan.tiled && h->plan.slots.sort_direct;
   if (steps_done) HIPCHK(hipMemcpyAsync(&sd, h->steps_done, sizeof sd, hipMemcpyDeviceToHost, h->stream));
   if (h->fix_sat) HIPCHK(hipMemcpyAsync(&sat, h->fix_sat, sizeof(int), hipMemcpyDeviceToHost, h->stream));
   if (slots) HIPCHK(hipMemcpyAsync(words, slot_words(h), sizeof words, hipMemcpyDeviceToHost, h->stream));
@@ -550,11 +482,9 @@ int read_ctl(bchmc_handle *h, unsigned long long *steps_done) {
   if (steps_done) *steps_done = sd;
   if (slots) {
     if (words[0] || words[1]) HIPCHK(hipMemsetAsync(slot_words(h), 0, sizeof words, h->stream));
-    if (h->cap_wanted > h->cap_alloc) {  // a poll inside a trajectory could not grow the array: do it now
-      CHK(realloc_slots(h, h->cap_wanted + h->cap_wanted / 4));
-      h->cap_wanted = 0;
-      h->tp.cap = (int)(h->cap_alloc - h->cap_alloc % kOct);
-      h->sorted_valid = false;
+    if (const long long want = h->plan.slots.pending()) {  // a poll inside a trajectory could not grow the array: do it now
+      CHK(realloc_slots(h, want));
+      repartition(h);
     }
     CHK(adapt_slots(h, words[0], words[1], true));
   }
@@ -1012,7 +942,7 @@ struct Pipe {
   static const CT *C(const void *p) { return reinterpret_cast<const CT *>(p); }
 
   static size_t tile_lds(const bchmc_handle *h, int ncol, size_t cell_bytes) {
-    const size_t ncell = (size_t)h->tp.lx * h->tp.ly * h->tp.lz;
+    const size_t ncell = (size_t)h->plan.tp.lx * h->plan.tp.ly * h->plan.tp.lz;
     return ((ncell * cell_bytes + 15) & ~(size_t)15) + (size_t)ncol * sizeof(int4);
   }
 
@@ -1175,7 +1105,7 @@ struct Pipe {
     // (128^3: measured 2 % slower -- 4096 small workgroups, the binning part grows by more than rocFFT's row pass
     // costs there -- so rocFFT keeps it unless BCHMC_ZBIN_128=1, which the tests use for the n = 128 instantiation)
     const bool size_ok = h->g.n == 256 || h->g.n == 512 || (h->g.n == 128 && env_on("BCHMC_ZBIN_128"));
-    return size_ok && h->tiled && h->sort_direct && h->planes_ok && h->xtw && h->c.mk == 3 && h->c.calc_h == 2 &&
+    return size_ok && h->plan.tiled && h->plan.slots.sort_direct && h->planes_ok && h->xtw && h->c.mk == 3 && h->c.calc_h == 2 &&
            !env_on("BCHMC_NO_ZBIN");  // (mk 3 + calc_h 2 on tiles: nothing but the fallback sort reads Psi after the binning)
   }
   // the first of zbin_ok's conditions that does not hold, in words (bchmc_probe_displacement_z's refusal); nullptr: all do
@@ -1185,7 +1115,7 @@ struct Pipe {
     if (h->g.n == 128 && !env_on("BCHMC_ZBIN_128")) return "Nx = 128 takes it with BCHMC_ZBIN_128=1 only";
     if (!(h->g.n == 128 || h->g.n == 256 || h->g.n == 512)) return "it exists for Nx = 128, 256 and 512";
     if (h->c.mk != 3 || h->c.calc_h != 2) return "it needs masskernel 3 with calc_h 2";
-    if (!h->tiled || !h->sort_direct) return "the one-pass tile binning is not in use";
+    if (!h->plan.tiled || !h->plan.slots.sort_direct) return "the one-pass tile binning is not in use";
     return "the planes-mode transforms are not available";
   }
 
@@ -1237,18 +1167,18 @@ struct Pipe {
     bool rho_cleared = false;  // by k_bin_direct, on its way through the lattice
     const PosPar pp = make_pos(h, rsd);
     const SphPar sp = make_sph(h);
-    if (h->tiled) {
+    if (h->plan.tiled) {
       // counting sort of the particles by the Eulerian tile of their home cell
       ProfScope ps(h, BCHMC_K_SORT);
       // one-pass binning into fixed slots per tile; the two-pass kernels run only if a tile overflowed
-      const int nt = h->tp.ntiles, nbricks = nblk_full(h->g.N);
+      const int nt = h->plan.tp.ntiles, nbricks = nblk_full(h->g.N);
       int *cnt1 = h->t_cnt, *cnt2 = h->t_cnt + kOct * nt, *ovf = h->t_cnt + (kOct + 1) * nt;  // ovf[1], ovf[2]: the host's slot words, see adapt_slots
       if (!h->cnt_clean) HIPCHK(hipMemsetAsync(h->t_cnt, 0, ((kOct + 1) * (size_t)nt + 1) * sizeof(int), h->stream));
       h->cnt_clean = false;
       // the two fallback kernels return at once unless a tile overflowed; when one did (every step until the slots are
       // doubled at the next trajectory start) they must still fill the chip, so the grid is capped, not tiny: with 512
       // workgroups a 512^3 step in fallback mode took 69 ms instead of 22 (and the no-op launches cost 18-20 us either way)
-      const int fb_grid = h->sort_direct ? std::min(nbricks, 4096) : nbricks;
+      const int fb_grid = h->plan.slots.sort_direct ? std::min(nbricks, 4096) : nbricks;
       if (zbin) {
         const int n = h->g.n, zgrid = (n / 2) * (n / 2);
         const size_t zlds = zbin_lds<T>(n);
@@ -1257,11 +1187,11 @@ struct Pipe {
         // below needs Psi after all (returns at once otherwise)
 #define BCHMC_LAUNCH_Z(NZ)                                                                                          \
   do {                                                                                                              \
-    CHK(launch_lds(h, k_zbin_direct<T, NZ>, zgrid, NZ, zlds, h->g, pp, sp, h->tp, h->log2n, tw, C(h->Ck), cnt1, ovf, \
+    CHK(launch_lds(h, k_zbin_direct<T, NZ>, zgrid, NZ, zlds, h->g, pp, sp, h->plan.tp, h->log2n, tw, C(h->Ck), cnt1, ovf, \
                    recs(h), R(h->V), h->rho_part, h->fix ? nullptr : R(h->rho),                          \
                    h->fix ? h->rho_fix : nullptr, m.psi_unread ? nullptr : R(h->psi)));                             \
     if (m.psi_unread)                                                                                               \
-      CHK(launch_lds(h, k_zbin_direct<T, NZ, true>, zgrid, NZ, zlds, h->g, pp, sp, h->tp, h->log2n, tw, C(h->Ck),   \
+      CHK(launch_lds(h, k_zbin_direct<T, NZ, true>, zgrid, NZ, zlds, h->g, pp, sp, h->plan.tp, h->log2n, tw, C(h->Ck),   \
                      cnt1, ovf, nullptr, nullptr, nullptr, nullptr, nullptr, R(h->psi)));                           \
   } while (0)
         if (n == 128) BCHMC_LAUNCH_Z(128);
@@ -1269,9 +1199,9 @@ struct Pipe {
         else BCHMC_LAUNCH_Z(512);
 #undef BCHMC_LAUNCH_Z
         rho_cleared = true;
-      } else if (h->sort_direct) {
+      } else if (h->plan.slots.sort_direct) {
         const int nsuper = (nbricks + kBinPer - 1) / kBinPer;
-        k_bin_direct<T><<<nsuper, BCHMC_BIN_THREADS, 0, h->stream>>>(h->g, pp, sp, h->tp, nsuper, R(h->psi), cnt1, ovf,
+        k_bin_direct<T><<<nsuper, BCHMC_BIN_THREADS, 0, h->stream>>>(h->g, pp, sp, h->plan.tp, nsuper, R(h->psi), cnt1, ovf,
                                                        recs(h), R(h->V), h->rho_part,
                                                        h->fix ? nullptr : R(h->rho),
                                                        h->fix ? h->rho_fix : nullptr);
@@ -1279,8 +1209,8 @@ struct Pipe {
       } else {
         HIPCHK(hipMemsetAsync(ovf, 1, 1, h->stream));  // non-zero flag: two-pass sort only
       }
-      k_bin<T><<<fb_grid, 256, 0, h->stream>>>(h->g, pp, sp, h->tp, nbricks, R(h->psi), cnt2, ovf, h->t_rank, R(h->V));
-      k_scan_tiles<<<(nt + 1023) / 1024, 1024, 0, h->stream>>>(h->tp, cnt1, cnt2, ovf, h->t_off, h->t_end, h->t_woff,
+      k_bin<T><<<fb_grid, 256, 0, h->stream>>>(h->g, pp, sp, h->plan.tp, nbricks, R(h->psi), cnt2, ovf, h->t_rank, R(h->V));
+      k_scan_tiles<<<(nt + 1023) / 1024, 1024, 0, h->stream>>>(h->plan.tp, cnt1, cnt2, ovf, h->t_off, h->t_end, h->t_woff,
                                                                h->t_oct, h->t_seg, ovf + 2);
       k_reorder<T><<<fb_grid, 256, 0, h->stream>>>(h->g, pp, nbricks, R(h->psi), h->t_rank, h->t_off, ovf,
                                                    recs(h));
@@ -1289,7 +1219,7 @@ struct Pipe {
     }
     {
       ProfScope ps(h, BCHMC_K_SCATTER);
-      const bool tile_path = (h->c.mk == 3 && h->tiled), tile_low = (h->c.mk >= 0 && h->c.mk <= 2 && h->tiled);
+      const bool tile_path = (h->c.mk == 3 && h->plan.tiled), tile_low = (h->c.mk >= 0 && h->c.mk <= 2 && h->plan.tiled);
       // fixed point (deterministic mode): scale = 2^46 / largest single contribution (W(0) = 1/(pi h^3) for the SPH
       // kernel, 1 for NGP / CIC / TSC weights)
       const double fix_scale = h->c.mk == 3 ? 70368744177664. / sp.w_norm : 70368744177664.;
@@ -1302,49 +1232,49 @@ struct Pipe {
       if (tile_path) {
         // the tile kernels also leave sum(rho) in rho_part (partial sums of what they flush): no pass over rho
         // (k_bin<DIRECT> has cleared the partials; without the one-pass binning a fill does)
-        if (!h->sort_direct && !h->fix) HIPCHK(hipMemsetAsync(h->rho_part, 0, kRedBlocks * sizeof(double), h->stream));
-        const int grid = h->tp.ntiles + (int)(h->g.N / h->tp.chunk) + 1;  // upper bound on (tile, chunk) work items
-        const int ncol = h->hull_exact ? h->hull_n : 0;
+        if (!h->plan.slots.sort_direct && !h->fix) HIPCHK(hipMemsetAsync(h->rho_part, 0, kRedBlocks * sizeof(double), h->stream));
+        const int grid = h->plan.tp.ntiles + (int)(h->g.N / h->plan.tp.chunk) + 1;  // upper bound on (tile, chunk) work items
+        const int ncol = h->plan.hull_exact ? h->plan.hull_n : 0;
         // sub-cell ordering inside each work item: two binary digits per axis
-        const int reorder = (h->tp.chunk > 2048) ? 0 : 2;
+        const int reorder = (h->plan.tp.chunk > 2048) ? 0 : 2;
         if (reorder) {  // orders the records only after a fallback sort; returns at once otherwise
-          k_subsort<T><<<std::min(grid, 8192), 256, 0, h->stream>>>(h->g, h->tp, reorder, recs(h), h->t_off, h->t_end, h->t_woff,
+          k_subsort<T><<<std::min(grid, 8192), 256, 0, h->stream>>>(h->g, h->plan.tp, reorder, recs(h), h->t_off, h->t_end, h->t_woff,
                                                    h->t_oct, h->t_seg);
           HIPCHK(hipGetLastError());
         }
-        if (h->std81) {
+        if (h->plan.std81) {
           if (h->fix)
             k_scatter_tile81<T, 12, 20, true><<<grid, kTile81Threads, tile_lds(h, 0, sizeof(double)), h->stream>>>(
-                h->g, sp, h->tp, recs(h), h->t_off, h->t_end, h->t_woff,
+                h->g, sp, h->plan.tp, recs(h), h->t_off, h->t_end, h->t_woff,
                 h->t_oct, h->t_seg, h->rho_fix, h->rho_part, h->t_cnt,
-                (kOct + 1) * h->tp.ntiles + 1, fix_scale);
+                (kOct + 1) * h->plan.tp.ntiles + 1, fix_scale);
           else
             k_scatter_tile81<T, 12, 20, false><<<grid, kTile81Threads, tile_lds(h, 0, sizeof(double)), h->stream>>>(
-                h->g, sp, h->tp, recs(h), h->t_off, h->t_end, h->t_woff,
+                h->g, sp, h->plan.tp, recs(h), h->t_off, h->t_end, h->t_woff,
                 h->t_oct, h->t_seg, R(h->rho), h->rho_part, h->t_cnt,
-                (kOct + 1) * h->tp.ntiles + 1, fix_scale);
+                (kOct + 1) * h->plan.tp.ntiles + 1, fix_scale);
           h->cnt_clean = true;
         } else if (h->fix) {
           k_scatter_tile<T, true><<<grid, 256, tile_lds(h, ncol, sizeof(double)), h->stream>>>(
-              h->g, sp, h->tp, h->hull, ncol, recs(h), h->t_off, h->t_end,
+              h->g, sp, h->plan.tp, h->hull, ncol, recs(h), h->t_off, h->t_end,
               h->t_woff, h->t_oct, h->t_seg, h->rho_fix, h->rho_part, fix_scale);
         } else {
           k_scatter_tile<T, false><<<grid, 256, tile_lds(h, ncol, sizeof(double)), h->stream>>>(
-              h->g, sp, h->tp, h->hull, ncol, recs(h), h->t_off, h->t_end,
+              h->g, sp, h->plan.tp, h->hull, ncol, recs(h), h->t_off, h->t_end,
               h->t_woff, h->t_oct, h->t_seg, R(h->rho), h->rho_part, fix_scale);
         }
       } else if (tile_low) {
         // NGP / CIC / TSC on the (tile, octant) records: LDS image of the tile + a one-cell halo, one flush
-        if (!h->sort_direct && !h->fix) HIPCHK(hipMemsetAsync(h->rho_part, 0, kRedBlocks * sizeof(double), h->stream));
-        const int grid = h->tp.ntiles + (int)(h->g.N / h->tp.chunk) + 1;
-        const size_t lds = (size_t)(h->tp.tx + 2) * (h->tp.ty + 2) * (h->tp.tz + 2) * sizeof(double);
-        const int ncnt = (kOct + 1) * h->tp.ntiles + 1;
+        if (!h->plan.slots.sort_direct && !h->fix) HIPCHK(hipMemsetAsync(h->rho_part, 0, kRedBlocks * sizeof(double), h->stream));
+        const int grid = h->plan.tp.ntiles + (int)(h->g.N / h->plan.tp.chunk) + 1;
+        const size_t lds = (size_t)(h->plan.tp.tx + 2) * (h->plan.tp.ty + 2) * (h->plan.tp.tz + 2) * sizeof(double);
+        const int ncnt = (kOct + 1) * h->plan.tp.ntiles + 1;
         if (h->fix)
-          k_scatter_tile_low<T, true><<<grid, 256, lds, h->stream>>>(h->g, h->tp, h->c.mk, recs(h), h->t_off,
+          k_scatter_tile_low<T, true><<<grid, 256, lds, h->stream>>>(h->g, h->plan.tp, h->c.mk, recs(h), h->t_off,
                                                                      h->t_end, h->t_woff, h->t_oct, h->t_seg, h->rho_fix,
                                                                      h->rho_part, h->t_cnt, ncnt, fix_scale);
         else
-          k_scatter_tile_low<T, false><<<grid, 256, lds, h->stream>>>(h->g, h->tp, h->c.mk, recs(h), h->t_off,
+          k_scatter_tile_low<T, false><<<grid, 256, lds, h->stream>>>(h->g, h->plan.tp, h->c.mk, recs(h), h->t_off,
                                                                       h->t_end, h->t_woff, h->t_oct, h->t_seg, R(h->rho),
                                                                       h->rho_part, h->t_cnt, ncnt, fix_scale);
         h->cnt_clean = true;
@@ -1370,7 +1300,7 @@ struct Pipe {
         HIPCHK(hipGetLastError());
       }
     }
-    if (!h->tiled && !h->fix) {
+    if (!h->plan.tiled && !h->fix) {
       ProfScope ps(h, BCHMC_K_MEAN_PARTIAL);
       k_sum<T><<<kRedBlocks, 256, 0, h->stream>>>(R(h->rho), h->g.N, h->rho_part);
       HIPCHK(hipGetLastError());
@@ -1451,10 +1381,10 @@ struct Pipe {
       CHK(fft_exec(h, h->c2r3, h->Ck, h->conv, BCHMC_K_FFT_C2R));
       {
         ProfScope ps(h, BCHMC_K_GATHER);
-        if (h->tiled && h->sorted_valid && !env_on("BCHMC_NO_TILES_LOW")) {
-          const int grid = h->tp.ntiles + (int)(N / h->tp.chunk) + 1;
-          const size_t lds = 3 * (size_t)(h->tp.tx + 2) * (h->tp.ty + 2) * (h->tp.tz + 2) * sizeof(T);
-          k_interp_tsc_tile<T><<<grid, 256, lds, h->stream>>>(h->g, h->tp, h->last_rsd, fgrow1(h->c.ascale, h->c.OM, h->c.OL),
+        if (h->plan.tiled && h->sorted_valid && !env_on("BCHMC_NO_TILES_LOW")) {
+          const int grid = h->plan.tp.ntiles + (int)(N / h->plan.tp.chunk) + 1;
+          const size_t lds = 3 * (size_t)(h->plan.tp.tx + 2) * (h->plan.tp.ty + 2) * (h->plan.tp.tz + 2) * sizeof(T);
+          k_interp_tsc_tile<T><<<grid, 256, lds, h->stream>>>(h->g, h->plan.tp, h->last_rsd, fgrow1(h->c.ascale, h->c.OM, h->c.OL),
                                                               recs(h), h->t_off, h->t_end, h->t_woff,
                                                               h->t_oct, h->t_seg, R(h->conv), R(h->V));
         } else {
@@ -1467,15 +1397,15 @@ struct Pipe {
     } else {
       ProfScope ps(h, BCHMC_K_GATHER);
       HullPar hp = make_hull(h);
-      if (h->tiled && h->sorted_valid) {
-        const int grid = h->tp.ntiles + (int)(N / h->tp.chunk) + 1;
-        if (h->std81)
+      if (h->plan.tiled && h->sorted_valid) {
+        const int grid = h->plan.tp.ntiles + (int)(N / h->plan.tp.chunk) + 1;
+        if (h->plan.std81)
           k_gather_tile81<T, 12, 20><<<grid, kTile81Threads, tile_lds(h, 0, sizeof(T)), h->stream>>>(
-              h->g, hp, h->tp, h->last_rsd, recs(h), h->t_off, h->t_end, h->t_woff,
+              h->g, hp, h->plan.tp, h->last_rsd, recs(h), h->t_off, h->t_end, h->t_woff,
               h->t_oct, h->t_seg, R(h->plike), R(h->V));
         else
           k_gather_tile<T><<<grid, 256, tile_lds(h, hp.ncol, sizeof(T)), h->stream>>>(
-              h->g, hp, h->tp, h->last_rsd, recs(h), h->t_off, h->t_end, h->t_woff,
+              h->g, hp, h->plan.tp, h->last_rsd, recs(h), h->t_off, h->t_end, h->t_woff,
               h->t_oct, h->t_seg, R(h->plike), R(h->V));
       } else {
         k_gather_sph<T><<<nblk_full(N), 256, hp.ncol * sizeof(int4), h->stream>>>(h->g, make_pos(h, h->last_rsd), hp,
@@ -1810,7 +1740,7 @@ struct Pipe {
         HIPCHK(hipEventRecord(h->ev_q, h->stream));
         h->early_q_done = true;
       }
-      if (h->slot_watch && h->tiled && h->sort_direct && s > 0 && s % kSlotPoll == 0)
+      if (h->plan.slots.slot_watch && h->plan.tiled && h->plan.slots.sort_direct && s > 0 && s % kSlotPoll == 0)
         CHK(poll_slots(h, s / kSlotPoll));
       EvalMode m;
       m.planes_c2r = planes && (s > 0 || ends);  // Psi^ left by k_step_boundary_x still needs only the (y, z) passes
@@ -2948,6 +2878,95 @@ int mt_place_momenta(bchmc_handle *h) { return DISPATCH(h, mt_place(h)); }
 int mock_place_truth(bchmc_handle *h) { return DISPATCH(h, mock_place(h, h->qk)); }
 int mock_place_guess(bchmc_handle *h) { return DISPATCH(h, mock_place(h, h->cq)); }
 
+// The handle's stream; BCHMC_CU_MASK restricts it to a subset of the CUs
+int create_stream(bchmc_handle *h) {
+  if (const char *cm = std::getenv("BCHMC_CU_MASK")) {
+    // experiment: restrict this handle's stream to a subset of the CUs (two chains per GPU on disjoint halves).
+    // "lo" / "hi": first / second half of the mask bits; "even" / "odd": alternating groups of 32 bits (XCD-sized)
+    hipDeviceProp_t prop;
+    HIPCHK(hipGetDeviceProperties(&prop, h->c.device));
+    const int ncu = prop.multiProcessorCount, words = (ncu + 31) / 32;
+    std::vector<uint32_t> mask(words, 0u);
+    const std::string mode(cm);
+    for (int cu = 0; cu < ncu; cu++) {
+      bool on = true;
+      if (mode == "lo") on = cu < ncu / 2;
+      else if (mode == "hi") on = cu >= ncu / 2;
+      else if (mode == "even") on = ((cu / 32) & 1) == 0;
+      else if (mode == "odd") on = ((cu / 32) & 1) == 1;
+      else if (mode == "evencu") on = (cu & 1) == 0;
+      else if (mode == "oddcu") on = (cu & 1) == 1;
+      if (on) mask[cu / 32] |= 1u << (cu % 32);
+    }
+    hipStream_t masked = nullptr;
+    HIPCHK(hipExtStreamCreateWithCUMask(&masked, (uint32_t)words, mask.data()));
+    h->stream.reset(masked);
+  } else {
+    HIPCHK(h->stream.create(hipStreamNonBlocking));
+  }
+  return BCHMC_OK;
+}
+
+// The 3-D real transforms of the whole grid, one field and three fields at a time
+int make_plans_3d(bchmc_handle *h) {
+  const Geo &g = h->g;
+  const size_t len[3] = {(size_t)g.n, (size_t)g.n, (size_t)g.n};  // fastest first; cubic
+  const rocfft_precision prec = h->f32 ? rocfft_precision_single : rocfft_precision_double;
+  // real side contiguous (n, n^2), half-complex side with row stride nhp
+  const size_t rs[3] = {1, (size_t)g.n, (size_t)g.n * g.n}, cs[3] = {1, (size_t)g.nhp, (size_t)g.nhp * g.n};
+  rocfft_plan_description fwd = nullptr, inv = nullptr;
+  FFTCHK(rocfft_plan_description_create(&fwd));
+  FFTCHK(rocfft_plan_description_create(&inv));
+  FFTCHK(rocfft_plan_description_set_data_layout(fwd, rocfft_array_type_real, rocfft_array_type_hermitian_interleaved,
+                                                 nullptr, nullptr, 3, rs, (size_t)g.N, 3, cs, (size_t)g.Nhp));
+  FFTCHK(rocfft_plan_description_set_data_layout(inv, rocfft_array_type_hermitian_interleaved, rocfft_array_type_real,
+                                                 nullptr, nullptr, 3, cs, (size_t)g.Nhp, 3, rs, (size_t)g.N));
+  FFTCHK(h->r2c1.create(rocfft_plan_create, rocfft_placement_notinplace, rocfft_transform_type_real_forward, prec, 3, len,
+                        1, fwd));
+  FFTCHK(h->c2r1.create(rocfft_plan_create, rocfft_placement_notinplace, rocfft_transform_type_real_inverse, prec, 3, len,
+                        1, inv));
+  FFTCHK(h->r2c3.create(rocfft_plan_create, rocfft_placement_notinplace, rocfft_transform_type_real_forward, prec, 3, len,
+                        3, fwd));
+  FFTCHK(h->c2r3.create(rocfft_plan_create, rocfft_placement_notinplace, rocfft_transform_type_real_inverse, prec, 3, len,
+                        3, inv));
+  rocfft_plan_description_destroy(fwd);
+  rocfft_plan_description_destroy(inv);
+  return BCHMC_OK;
+}
+
+// The SPH hull and the tile partition (tile_plan.hpp decides both), and the buffers of the tile-sorted path
+int make_tiles(bchmc_handle *h) {
+  const bchmc_config &c = h->c;
+  const size_t N = (size_t)h->g.N;
+  const Hull hull = build_hull(c.particle_kernel_h, h->g.d);
+  CHK(dev_alloc(h, h->hull, hull.cols.size()));
+  HIPCHK(hipMemcpyAsync(h->hull, hull.cols.data(), hull.cols.size() * sizeof(HullCol), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  TileSwitches sw;
+  sw.no_tiles = env_on("BCHMC_NO_TILES");
+  sw.no_tiles_low = env_on("BCHMC_NO_TILES_LOW");
+  if (const char *ev = std::getenv("BCHMC_CHUNK")) sw.chunk = std::max(atoi(ev), 1);  // set: the plan clamps it to 64..2048
+  if (const char *ev = std::getenv("BCHMC_SORT_CAP")) {
+    sw.has_cap = true;
+    sw.cap = atoll(ev);
+  }
+  sw.cap_fixed = env_on("BCHMC_SORT_CAP_FIXED");
+  size_t free_b = 0, total_b = 0;
+  HIPCHK(hipMemGetInfo(&free_b, &total_b));
+  h->plan = plan_tiles(h->g.n, c.mk, c.min1, c.min2, c.min3, c.particle_kernel_h, h->g.d, h->g.N, h->esz, hull, sw, total_b);
+  if (!h->plan.tiled) return BCHMC_OK;
+  const size_t nt = (size_t)h->plan.tp.ntiles;
+  CHK(dev_alloc(h, h->t_cnt, (kOct + 1) * nt + 3));
+  CHK(dev_alloc(h, h->t_oct, 2 * nt));
+  CHK(dev_alloc(h, h->t_seg, (size_t)1));
+  CHK(dev_alloc(h, h->t_off, nt));
+  CHK(dev_alloc(h, h->t_end, nt));
+  CHK(dev_alloc(h, h->t_woff, nt + 1));
+  CHK(dev_alloc(h, h->t_rank, N));
+  CHK(dev_alloc(h, h->srec, h->plan.nrec * 4 * h->esz));
+  return BCHMC_OK;
+}
+
 }  // namespace
 
 // ======================================================================================================
@@ -3014,52 +3033,9 @@ int bchmc_create(const bchmc_config *cfg, bchmc_handle **out) {
 
   auto run = [&]() -> int {
     HIPCHK(hipSetDevice(cfg->device));
-    if (const char *cm = std::getenv("BCHMC_CU_MASK")) {
-      // experiment: restrict this handle's stream to a subset of the CUs (two chains per GPU on disjoint halves).
-      // "lo" / "hi": first / second half of the mask bits; "even" / "odd": alternating groups of 32 bits (XCD-sized)
-      hipDeviceProp_t prop;
-      HIPCHK(hipGetDeviceProperties(&prop, cfg->device));
-      const int ncu = prop.multiProcessorCount, words = (ncu + 31) / 32;
-      std::vector<uint32_t> mask(words, 0u);
-      const std::string mode(cm);
-      for (int cu = 0; cu < ncu; cu++) {
-        bool on = true;
-        if (mode == "lo") on = cu < ncu / 2;
-        else if (mode == "hi") on = cu >= ncu / 2;
-        else if (mode == "even") on = ((cu / 32) & 1) == 0;
-        else if (mode == "odd") on = ((cu / 32) & 1) == 1;
-        else if (mode == "evencu") on = (cu & 1) == 0;
-        else if (mode == "oddcu") on = (cu & 1) == 1;
-        if (on) mask[cu / 32] |= 1u << (cu % 32);
-      }
-      hipStream_t masked = nullptr;
-      HIPCHK(hipExtStreamCreateWithCUMask(&masked, (uint32_t)words, mask.data()));
-      h->stream.reset(masked);
-    } else {
-      HIPCHK(h->stream.create(hipStreamNonBlocking));
-    }
+    CHK(create_stream(h));
     FFTCHK(h->fft_user.acquire());
-    const size_t len[3] = {(size_t)g.n, (size_t)g.n, (size_t)g.n};  // fastest first; cubic
-    const rocfft_precision prec = h->f32 ? rocfft_precision_single : rocfft_precision_double;
-    // real side contiguous (n, n^2), half-complex side with row stride nhp
-    const size_t rs[3] = {1, (size_t)g.n, (size_t)g.n * g.n}, cs[3] = {1, (size_t)g.nhp, (size_t)g.nhp * g.n};
-    rocfft_plan_description fwd = nullptr, inv = nullptr;
-    FFTCHK(rocfft_plan_description_create(&fwd));
-    FFTCHK(rocfft_plan_description_create(&inv));
-    FFTCHK(rocfft_plan_description_set_data_layout(fwd, rocfft_array_type_real, rocfft_array_type_hermitian_interleaved,
-                                                   nullptr, nullptr, 3, rs, (size_t)g.N, 3, cs, (size_t)g.Nhp));
-    FFTCHK(rocfft_plan_description_set_data_layout(inv, rocfft_array_type_hermitian_interleaved, rocfft_array_type_real,
-                                                   nullptr, nullptr, 3, cs, (size_t)g.Nhp, 3, rs, (size_t)g.N));
-    FFTCHK(h->r2c1.create(rocfft_plan_create, rocfft_placement_notinplace, rocfft_transform_type_real_forward, prec, 3, len,
-                          1, fwd));
-    FFTCHK(h->c2r1.create(rocfft_plan_create, rocfft_placement_notinplace, rocfft_transform_type_real_inverse, prec, 3, len,
-                          1, inv));
-    FFTCHK(h->r2c3.create(rocfft_plan_create, rocfft_placement_notinplace, rocfft_transform_type_real_forward, prec, 3, len,
-                          3, fwd));
-    FFTCHK(h->c2r3.create(rocfft_plan_create, rocfft_placement_notinplace, rocfft_transform_type_real_inverse, prec, 3, len,
-                          3, inv));
-    rocfft_plan_description_destroy(fwd);
-    rocfft_plan_description_destroy(inv);
+    CHK(make_plans_3d(h));
     {
       // planes mode (k_step_boundary_x): n a power of two, whole 128-byte k-groups per row, a supported per-thread count
       const int KB = 128 / (int)(2 * h->esz);
@@ -3125,106 +3101,7 @@ int bchmc_create(const bchmc_config *cfg, bchmc_handle **out) {
     CHK(dev_alloc(h, h->steps_done, (size_t)1));
     HIPCHK(hipMemsetAsync(h->stop, 0, sizeof(int), h->stream));
     HIPCHK(h->h_part.alloc(kRedBlocks));
-    std::vector<int4> cols;
-    build_hull(cfg->particle_kernel_h, g.d, cols, h->reach);
-    h->hull_n = (int)cols.size();
-    for (auto &c : cols) h->hull_maxlen = std::max(h->hull_maxlen, c.w - c.z + 1);
-    {
-      // getDensity_SPH visits the whole cube (massFunctions.cc:443-445); the hull may replace it only if every
-      // cell outside the hull is farther than 2h from ANY point of the home cell (true for h = d).
-      bool exact = true;
-      const double hh = cfg->particle_kernel_h, lim = 4. * hh * hh * (1. + 1e-4);
-      for (int i1 = -h->reach; i1 <= h->reach; ++i1)
-        for (int i2 = -h->reach; i2 <= h->reach; ++i2)
-          for (int i3 = -h->reach; i3 <= h->reach; ++i3) {
-            bool in_hull = false;
-            for (auto &c : cols)
-              if (c.x == i1 && c.y == i2 && i3 >= c.z && i3 <= c.w) in_hull = true;
-            if (in_hull) continue;
-            auto mind = [&](int i) { return std::max(std::abs(i) - 0.5 - 1e-4, 0.) * g.d; };  // home offset in [-d/2, d/2]
-            const double m2 = mind(i1) * mind(i1) + mind(i2) * mind(i2) + mind(i3) * mind(i3);
-            if (m2 <= lim) exact = false;
-          }
-      h->hull_exact = exact;
-    }
-    CHK(dev_alloc(h, h->hull, cols.size()));
-    HIPCHK(hipMemcpyAsync(h->hull, cols.data(), cols.size() * sizeof(int4), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    // tile-sorted particle-mesh path: tiles of 8 x 8 x 16 cells (z fastest) when they divide the grid
-    {
-      TilePar &tp = h->tp;
-      const int n = g.n;
-      tp.tx = tp.ty = (n % 8 == 0) ? 8 : ((n % 4 == 0) ? 4 : 0);
-      tp.tz = (n % 16 == 0) ? 16 : tp.tx;
-      // mk 0 / 1 / 2 (NGP / CIC / TSC) share the binning when the grid origin is 0: their cells are floor((x - min) / d),
-      // the records are keyed on floor(x / d) (tiles_low.hpp); BCHMC_NO_TILES_LOW=1 keeps them on the direct kernels
-      const bool low_ok = cfg->mk >= 0 && cfg->mk <= 2 && cfg->min1 == 0. && cfg->min2 == 0. && cfg->min3 == 0. &&
-                          !env_on("BCHMC_NO_TILES_LOW");
-      const bool want = (cfg->mk == 3 || low_ok) && tp.tx > 0 && !env_on("BCHMC_NO_TILES");
-      if (want) {
-        tp.ntx = n / tp.tx;
-        tp.nty = n / tp.ty;
-        tp.ntz = n / tp.tz;
-        tp.ntiles = tp.ntx * tp.nty * tp.ntz;
-        // halo: the farthest stencil offset when the hull is exact (2 for h = d), else the cube's reach
-        int hull_max = 0;
-        for (auto &c : cols) hull_max = std::max({hull_max, std::abs(c.x), std::abs(c.y), std::abs(c.z), std::abs(c.w)});
-        tp.R = h->hull_exact ? hull_max : h->reach;
-        tp.lx = tp.tx + 2 * tp.R;
-        tp.ly = tp.ty + 2 * tp.R;
-        tp.lz = tp.tz + 2 * tp.R;
-        // particles per work item: 2048 fills the chip at 256^3 (8192+ items); smaller grids get smaller items
-        tp.chunk = g.N >= (1ll << 23) ? 2048 : (g.N >= (1ll << 20) ? 1024 : 256);
-        if (const char *ev = std::getenv("BCHMC_CHUNK")) tp.chunk = std::min(std::max(atoi(ev), 64), 2048);
-        const size_t lds = (size_t)tp.lx * tp.ly * tp.lz * sizeof(double) + cols.size() * sizeof(int4) + 128;
-        // N < 2^30 and halo <= n also keep the 32-bit cell indices of the image walk in range (tile_walk.hpp)
-        if (lds <= 64 * 1024 && g.N < (1ll << 30) && tp.R <= n) {
-          h->tiled = true;
-          // the unrolled kernels hard-code this stencil and tile shape
-          bool is81 = h->hull_exact && cols.size() == 21 && tp.tx == 8 && tp.ty == 8 && tp.tz == 16 && tp.R == 2;
-          for (auto &c : cols) {
-            const int zw = (std::abs(c.x) <= 2 && std::abs(c.y) <= 2) ? hull81_zw(c.x + 2, c.y + 2) : -1;
-            if (zw < 0 || c.z != -zw || c.w != zw) is81 = false;
-          }
-          // ... and which spline branch a candidate can take (k_scatter_tile81): the home cell must stay at q <= 1,
-          // i.e. h >= (sqrt(3) / 2) d -- the 81-cell hull alone would also admit 0.83 d <= h < 0.866 d
-          if (cfg->particle_kernel_h < 0.8661 * g.d) is81 = false;
-          h->std81 = is81 && cfg->mk == 3;
-          // One-pass binning: the record array holds cap_alloc = 16x the mean occupancy in slots per tile (the 288 GB
-          // of HBM pay for a whole pass over the particles: 8.6 GB at 256^3 fp64), all of it in use as eight octant
-          // segments of cap / 8; it is reallocated for 1.5x the largest (tile, octant) population the binning reports
-          // when that does not fit (adapt_slots).  BCHMC_SORT_CAP overrides the starting partition (a tiny value forces
-          // the two-pass fallback in tests; 0 disables the one-pass path), BCHMC_SORT_CAP_FIXED=1 keeps it for good.
-          const long long mean_occ = (long long)tp.tx * tp.ty * tp.tz;
-          long long cap = std::max<long long>(8 * mean_occ, 64);
-          if (const char *ev = std::getenv("BCHMC_SORT_CAP")) cap = atoll(ev);
-          cap -= cap % kOct;  // eight octant segments per tile
-          h->cap_pinned = env_on("BCHMC_SORT_CAP_FIXED");
-          size_t nrec = N;
-          h->sort_direct = cap > 0 && cap < (1ll << 30);  // record offsets are 64-bit, per-tile ranges 32-bit
-          if (h->sort_direct) {
-            h->cap_alloc = h->cap_pinned ? cap : std::max<long long>(cap, std::max<long long>(16 * mean_occ, 128));
-            // the whole allocation is in use unless BCHMC_SORT_CAP asked for a smaller start (tests of the growth paths)
-            tp.cap = (int)(std::getenv("BCHMC_SORT_CAP") ? cap : h->cap_alloc - h->cap_alloc % kOct);
-            nrec = std::max<size_t>(N, (size_t)h->cap_alloc * tp.ntiles);
-            h->slot_watch = tp.cap < h->cap_alloc - h->cap_alloc % kOct;
-            {
-              size_t free_b = 0, total_b = 0;
-              HIPCHK(hipMemGetInfo(&free_b, &total_b));
-              h->cap_budget = std::max<long long>(h->cap_alloc, (long long)(total_b / 4 / ((size_t)tp.ntiles * 4 * e)));
-            }
-          }
-          CHK(dev_alloc(h, h->t_cnt, (kOct + 1) * (size_t)tp.ntiles + 3));
-          CHK(dev_alloc(h, h->t_oct, 2 * (size_t)tp.ntiles));
-          CHK(dev_alloc(h, h->t_seg, (size_t)1));
-          CHK(dev_alloc(h, h->t_off, (size_t)tp.ntiles));
-          CHK(dev_alloc(h, h->t_end, (size_t)tp.ntiles));
-          CHK(dev_alloc(h, h->t_woff, (size_t)tp.ntiles + 1));
-          CHK(dev_alloc(h, h->t_rank, N));
-          CHK(dev_alloc(h, h->srec, nrec * 4 * e));
-        }
-      }
-    }
+    CHK(make_tiles(h));
     HIPCHK(hipStreamSynchronize(h->stream));
     return BCHMC_OK;
   };
@@ -3899,13 +3776,13 @@ int bchmc_philox_kat(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[
 
 int bchmc_tile_info(bchmc_handle *h, int32_t out[8]) {
   if (!h || !out) return BCHMC_ERR_ARG;
-  out[0] = h->tiled ? 1 : 0;
-  out[1] = h->sort_direct ? 1 : 0;
-  out[2] = h->tp.cap;
-  out[3] = (int32_t)std::min<long long>(h->cap_alloc, INT32_MAX);
-  out[4] = h->slot_watch ? 1 : 0;
-  out[5] = h->tiled ? (h->tp.tx | (h->tp.ty << 8) | (h->tp.tz << 16)) : 0;
-  out[6] = h->std81 ? 1 : 0;
+  out[0] = h->plan.tiled ? 1 : 0;
+  out[1] = h->plan.slots.sort_direct ? 1 : 0;
+  out[2] = h->plan.tp.cap;
+  out[3] = (int32_t)std::min<long long>(h->plan.slots.cap_alloc, INT32_MAX);
+  out[4] = h->plan.slots.slot_watch ? 1 : 0;
+  out[5] = h->plan.tiled ? (h->plan.tp.tx | (h->plan.tp.ty << 8) | (h->plan.tp.tz << 16)) : 0;
+  out[6] = h->plan.std81 ? 1 : 0;
   out[7] = (h->c2r2d_2 != nullptr) ? 1 : 0;
   return BCHMC_OK;
 }

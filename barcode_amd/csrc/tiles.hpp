@@ -2,6 +2,7 @@
 // Part of the bchmc engine's kernel set; include through kernels.hpp (definition order matters).
 #pragma once
 #include "common.hpp"
+#include "tile_plan.hpp"
 #include "tile_walk.hpp"
 
 namespace bchmc {
@@ -21,18 +22,7 @@ namespace bchmc {
 // The (particle, cell) pair set is identical to the direct kernels above, which stay as the fallback; the
 // spline evaluations use fast_rsqrt (<= 2 ulp) instead of IEEE sqrt + divide.
 // ======================================================================================================
-struct TilePar {
-  int tx, ty, tz;     // tile shape in cells (z fastest)
-  int ntx, nty, ntz;  // tiles per axis
-  int ntiles;
-  int R;              // halo = farthest stencil offset
-  int lx, ly, lz;     // LDS tile shape = t + 2R
-  int chunk;          // max particles per work item
-  int cap;            // record slots reserved per tile by the one-pass binning (k_bin<DIRECT>), a multiple of 8:
-                      // the tile's slots are eight segments of cap / 8, one per sub-cell octant of the particle
-};
-
-constexpr int kOct = 8;  // sub-cell octants: (x, y, z) in the upper half of the home cell -> bits 2, 1, 0
+// TilePar, the partition every kernel here takes, and kOct are in tile_plan.hpp, with the arithmetic that fills them.
 
 // Sub-cell octant of a position: the 64 lanes of a wave should share most of the stencil cells that can pass the
 // `r/h <= 2` test, and a wave pays for every candidate ANY of its lanes needs (81 unsorted, ~51 within one octant).
@@ -801,11 +791,7 @@ k_gather_tile(Geo g, HullPar hp, TilePar tp, int rsd, const RecQuad *__restrict_
 // has an immediate offset, and a rejected candidate costs add + compare + branch.  Same (particle, cell) pairs
 // and the same kernel evaluations as the generic kernels above; r^2 differs from theirs by rounding only.
 // ------------------------------------------------------------------------------------------------------
-// z half-width of hull column (a - 2, b - 2): -1 = not in the hull
-__host__ __device__ constexpr int hull81_zw(int a, int b) {
-  const int i1 = a < 2 ? 2 - a : a - 2, i2 = b < 2 ? 2 - b : b - 2;
-  return (i1 == 2 && i2 == 2) ? -1 : ((i1 == 2 || i2 == 2) ? 1 : 2);
-}
+// hull81_zw (tile_plan.hpp): z half-width of hull column (a - 2, b - 2), -1 = not in the hull
 
 // Register budgets (waves per SIMD the compiler must leave room for), A/B'd at 256^3 fp64 on one box
 // (gpurun_out/ab*.json, r02): scatter 4 / 5 / 6 waves -> 1.042 / 0.997 / 0.983 ms per launch (6 waves = 80 VGPRs spills
