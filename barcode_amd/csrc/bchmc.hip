@@ -11,6 +11,7 @@
 #include "kernels.hpp"
 #include "fft_host.hpp"
 #include "owned.hpp"
+#include "pass_launch.hpp"
 
 #include <rocfft/rocfft.h>
 #include <rocprofiler-sdk-roctx/roctx.h>
@@ -257,15 +258,6 @@ struct EvalMode {             // how ONE force evaluation runs; decided by the c
   bool alpt_pending = false;  // Ck[0], Ck[1] hold delta(1)^ | Phi^ planes left by k_step_boundary_x<ALPT>
   bool psi_unread = false;    // interior step: nobody reads Psi / positions, the z pass may end in the binning
 };
-
-// Launch with `lds` bytes of dynamic LDS: above the 48 KiB every kernel may use, the kernel's own limit is raised first.
-template <typename... P, typename... A>
-int launch_lds(bchmc_handle *h, void (*kern)(P...), int grid, int threads, size_t lds, const A &...args) {
-  if (lds > 48 * 1024)
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  kern<<<grid, threads, lds, h->stream>>>(args...);
-  return BCHMC_OK;
-}
 
 // ---- profiling ------------------------------------------------------------------------------------
 // roctx range names: the kernel ids of SURVEY.md 2.1 that each launch group replaces, so that a
@@ -945,6 +937,10 @@ struct Pipe {
     const size_t ncell = (size_t)h->plan.tp.lx * h->plan.tp.ly * h->plan.tp.lz;
     return ((ncell * cell_bytes + 15) & ~(size_t)15) + (size_t)ncol * sizeof(int4);
   }
+  // upper bound on the (tile, chunk) work items of the tile kernels
+  static int tile_grid(const bchmc_handle *h) { return h->plan.tp.ntiles + (int)(h->g.N / h->plan.tp.chunk) + 1; }
+  // the engine's own FFT passes (pass_launch.hpp) on this handle
+  static PassCtx<T> pass_ctx(const bchmc_handle *h) { return {h->stream, h->g, h->log2n, C(h->xtw)}; }
 
   // ---- ABI (double) <-> storage (T) on the device ----
   static int load_real(bchmc_handle *h, const double *d_src, T *dst) {
@@ -1047,7 +1043,7 @@ struct Pipe {
     if (planes) {
       CHK(fft_exec(h, h->r2c2d_2, h->V, Ck, BCHMC_K_FFT_R2C));         // A^, B^ of every (y, z) plane
       ProfScope ps(h, BCHMC_K_KSPACE_DRIFT_ZA);
-      CHK(launch_alpt_mix_x(h));
+      HIPCHK(launch_alpt_mix_x<T>(pass_ctx(h), Ck, h->c.kth, 1. / h->alpt_wtot, 1. / (double)N));
     } else {
       CHK(fft_exec(h, h->r2c1, a_out, Ck, BCHMC_K_FFT_R2C));           // A^ = FFT[D1 delta(1) - D2 delta(2)]
       CHK(fft_exec(h, h->r2c1, b_out, Ck + Nhp, BCHMC_K_FFT_R2C));     // B^ = FFT[spherical-collapse source]
@@ -1065,8 +1061,9 @@ struct Pipe {
       {
         ProfScope ps(h, BCHMC_K_KSPACE_DRIFT_ZA);
         StepCtl nc{h->stop, h->steps_done, nullptr, 0., 0};
-        CHK((launch_boundary_x<BX_FIRST, true>(h, C(h->qk), nullptr, nullptr, nullptr, nullptr, 0., 0., 0., 0., scale,
-                                               nullptr, nc, nullptr, nullptr)));
+        BoundaryX<T> bx;
+        bx.qi = C(h->qk), bx.c_za = scale, bx.ctl = nc;
+        CHK((launch_boundary_x<BX_FIRST, true>(h, bx)));
       }
       return alpt_middle(h, true);
     }
@@ -1076,28 +1073,6 @@ struct Pipe {
       HIPCHK(hipGetLastError());
     }
     return alpt_middle(h, false);
-  }
-
-  static int launch_alpt_mix_x(bchmc_handle *h) {
-    constexpr int KB = 128 / (int)sizeof(CT);
-    constexpr int NT_BIG = sizeof(T) == 8 ? 256 : 512, NT_SMALL = NT_BIG / 4;
-    const int n = h->g.n, grid = n * (h->g.nhp / KB);
-    const size_t lds = ((size_t)n * KB + n / 2) * sizeof(CT);
-    const CT *tw = C(h->xtw);
-#define BCHMC_LAUNCH_AX(NT, PER)                                                                                 \
-  CHK(launch_lds(h, k_alpt_mix_x<T, NT, PER>, grid, NT, lds, h->g, h->log2n, tw, C(h->Ck), h->c.kth, 1. / h->alpt_wtot, \
-                 1. / (double)h->g.N))
-    switch (n) {
-      case 32: BCHMC_LAUNCH_AX(NT_SMALL, 4); break;
-      case 64: BCHMC_LAUNCH_AX(NT_SMALL, 8); break;
-      case 128: BCHMC_LAUNCH_AX(NT_BIG, 4); break;
-      case 256: BCHMC_LAUNCH_AX(2 * NT_BIG, 4); break;
-      case 512: BCHMC_LAUNCH_AX(2 * NT_BIG, 8); break;
-      default: return h->fail(BCHMC_ERR_STATE, "planes mode is not available for n = %d", n);
-    }
-#undef BCHMC_LAUNCH_AX
-    HIPCHK(hipGetLastError());
-    return BCHMC_OK;
   }
 
   // the fused z pass + binning exists for the benchmark grids (one lattice site along z per thread of k_zbin_direct)
@@ -1140,17 +1115,7 @@ struct Pipe {
       zbin = planes && zbin_ok(h);
       if (zbin) {
         ProfScope ps(h, BCHMC_K_FFT_C2R);
-        constexpr int KB = 128 / (int)sizeof(CT);
-        const int n = h->g.n, ygrid = 3 * n * (h->g.nhp / KB);
-        const size_t lds = ((size_t)n * KB + n / 2) * sizeof(CT);
-        const CT *tw = C(h->xtw);
-#define BCHMC_LAUNCH_Y(NT, NN) \
-  CHK(launch_lds(h, k_ypass<T, NT, NN * KB / NT, BCHMC_YPASS_NT>, ygrid, NT, lds, h->g, h->log2n, tw, C(h->Ck)))
-        if (n == 128) BCHMC_LAUNCH_Y(256, 128);
-        else if (n == 256) BCHMC_LAUNCH_Y(512, 256);
-        else BCHMC_LAUNCH_Y(512, 512);
-#undef BCHMC_LAUNCH_Y
-        HIPCHK(hipGetLastError());
+        HIPCHK(launch_ypass<T>(pass_ctx(h), C(h->Ck)));
       } else {
         CHK(fft_exec(h, planes ? h->c2r2d : h->c2r3, h->Ck, h->psi, BCHMC_K_FFT_C2R));
       }
@@ -1180,24 +1145,14 @@ struct Pipe {
       // workgroups a 512^3 step in fallback mode took 69 ms instead of 22 (and the no-op launches cost 18-20 us either way)
       const int fb_grid = h->plan.slots.sort_direct ? std::min(nbricks, 4096) : nbricks;
       if (zbin) {
-        const int n = h->g.n, zgrid = (n / 2) * (n / 2);
-        const size_t zlds = zbin_lds<T>(n);
-        const CT *tw = C(h->xtw);
+        HIPCHK(launch_zbin<T>(pass_ctx(h), pp, sp, h->plan.tp, C(h->Ck), cnt1, ovf, recs(h), R(h->V), h->rho_part,
+                              h->fix ? nullptr : R(h->rho), h->fix ? h->rho_fix : nullptr,
+                              m.psi_unread ? nullptr : R(h->psi)));
         // second launch (interior steps, where Psi is not stored on the way): a segment overflowed -> the two-pass sort
         // below needs Psi after all (returns at once otherwise)
-#define BCHMC_LAUNCH_Z(NZ)                                                                                          \
-  do {                                                                                                              \
-    CHK(launch_lds(h, k_zbin_direct<T, NZ>, zgrid, NZ, zlds, h->g, pp, sp, h->plan.tp, h->log2n, tw, C(h->Ck), cnt1, ovf, \
-                   recs(h), R(h->V), h->rho_part, h->fix ? nullptr : R(h->rho),                          \
-                   h->fix ? h->rho_fix : nullptr, m.psi_unread ? nullptr : R(h->psi)));                             \
-    if (m.psi_unread)                                                                                               \
-      CHK(launch_lds(h, k_zbin_direct<T, NZ, true>, zgrid, NZ, zlds, h->g, pp, sp, h->plan.tp, h->log2n, tw, C(h->Ck),   \
-                     cnt1, ovf, nullptr, nullptr, nullptr, nullptr, nullptr, R(h->psi)));                           \
-  } while (0)
-        if (n == 128) BCHMC_LAUNCH_Z(128);
-        else if (n == 256) BCHMC_LAUNCH_Z(256);
-        else BCHMC_LAUNCH_Z(512);
-#undef BCHMC_LAUNCH_Z
+        if (m.psi_unread)
+          HIPCHK((launch_zbin<T, true>(pass_ctx(h), pp, sp, h->plan.tp, C(h->Ck), cnt1, ovf, nullptr, nullptr, nullptr,
+                                       nullptr, nullptr, R(h->psi))));
         rho_cleared = true;
       } else if (h->plan.slots.sort_direct) {
         const int nsuper = (nbricks + kBinPer - 1) / kBinPer;
@@ -1233,7 +1188,7 @@ struct Pipe {
         // the tile kernels also leave sum(rho) in rho_part (partial sums of what they flush): no pass over rho
         // (k_bin<DIRECT> has cleared the partials; without the one-pass binning a fill does)
         if (!h->plan.slots.sort_direct && !h->fix) HIPCHK(hipMemsetAsync(h->rho_part, 0, kRedBlocks * sizeof(double), h->stream));
-        const int grid = h->plan.tp.ntiles + (int)(h->g.N / h->plan.tp.chunk) + 1;  // upper bound on (tile, chunk) work items
+        const int grid = tile_grid(h);
         const int ncol = h->plan.hull_exact ? h->plan.hull_n : 0;
         // sub-cell ordering inside each work item: two binary digits per axis
         const int reorder = (h->plan.tp.chunk > 2048) ? 0 : 2;
@@ -1266,7 +1221,7 @@ struct Pipe {
       } else if (tile_low) {
         // NGP / CIC / TSC on the (tile, octant) records: LDS image of the tile + a one-cell halo, one flush
         if (!h->plan.slots.sort_direct && !h->fix) HIPCHK(hipMemsetAsync(h->rho_part, 0, kRedBlocks * sizeof(double), h->stream));
-        const int grid = h->plan.tp.ntiles + (int)(h->g.N / h->plan.tp.chunk) + 1;
+        const int grid = tile_grid(h);
         const size_t lds = (size_t)(h->plan.tp.tx + 2) * (h->plan.tp.ty + 2) * (h->plan.tp.tz + 2) * sizeof(double);
         const int ncnt = (kOct + 1) * h->plan.tp.ntiles + 1;
         if (h->fix)
@@ -1382,7 +1337,7 @@ struct Pipe {
       {
         ProfScope ps(h, BCHMC_K_GATHER);
         if (h->plan.tiled && h->sorted_valid && !env_on("BCHMC_NO_TILES_LOW")) {
-          const int grid = h->plan.tp.ntiles + (int)(N / h->plan.tp.chunk) + 1;
+          const int grid = tile_grid(h);
           const size_t lds = 3 * (size_t)(h->plan.tp.tx + 2) * (h->plan.tp.ty + 2) * (h->plan.tp.tz + 2) * sizeof(T);
           k_interp_tsc_tile<T><<<grid, 256, lds, h->stream>>>(h->g, h->plan.tp, h->last_rsd, fgrow1(h->c.ascale, h->c.OM, h->c.OL),
                                                               recs(h), h->t_off, h->t_end, h->t_woff,
@@ -1398,7 +1353,7 @@ struct Pipe {
       ProfScope ps(h, BCHMC_K_GATHER);
       HullPar hp = make_hull(h);
       if (h->plan.tiled && h->sorted_valid) {
-        const int grid = h->plan.tp.ntiles + (int)(N / h->plan.tp.chunk) + 1;
+        const int grid = tile_grid(h);
         if (h->plan.std81)
           k_gather_tile81<T, 12, 20><<<grid, kTile81Threads, tile_lds(h, 0, sizeof(T)), h->stream>>>(
               h->g, hp, h->plan.tp, h->last_rsd, recs(h), h->t_off, h->t_end, h->t_woff,
@@ -1418,14 +1373,8 @@ struct Pipe {
       // 512^3: the engine's own row and column passes (rocFFT's length-512 column kernel runs at 2.3 TB/s, its 1-D row
       // plan alone at half the speed of the same pass inside the 2-D plan: k_zr2c + k_ypass<forward>, zpass.hpp)
       ProfScope ps(h, BCHMC_K_FFT_R2C);
-      constexpr int KB = 128 / (int)sizeof(CT);
-      const int n = h->g.n;
-      const CT *tw = C(h->xtw);
-      const size_t zl = ((size_t)n * 6 + n / 2) * sizeof(CT), yl = ((size_t)n * KB + n / 2) * sizeof(CT);
-      CHK(launch_lds(h, k_zr2c<T, 512>, (n / 2) * (n / 2), 512, zl, h->g, h->log2n, tw, R(h->V), C(h->Ck)));
-      CHK(launch_lds(h, k_ypass<T, 512, 512 * KB / 512, BCHMC_YPASS_NT, false>, 3 * n * (h->g.nhp / KB), 512, yl, h->g,
-                     h->log2n, tw, C(h->Ck)));
-      HIPCHK(hipGetLastError());
+      HIPCHK(launch_zr2c<T>(pass_ctx(h), R(h->V), C(h->Ck)));
+      HIPCHK((launch_ypass<T, false>(pass_ctx(h), C(h->Ck))));
     } else {
       CHK(fft_exec(h, m.planes_r2c ? h->r2c2d : h->r2c3, h->V, h->Ck, BCHMC_K_FFT_R2C));
     }
@@ -1575,12 +1524,10 @@ struct Pipe {
       StepCtl nc{h->stop, h->steps_done, nullptr, 0., 0};
       {
         ProfScope ps(h, BCHMC_K_KSPACE_DRIFT_ZA);
-        if (pl.alpt_x)
-          CHK((launch_boundary_x<BX_FIRST, true>(h, C(h->qk), nullptr, nullptr, nullptr, nullptr, 0., 0., 0., 0., pl.c_za,
-                                                 nullptr, nc, nullptr, nullptr)));
-        else
-          CHK(launch_boundary_x<BX_FIRST>(h, C(h->qk), nullptr, nullptr, nullptr, nullptr, 0., 0., 0., 0., pl.c_za, nullptr,
-                                          nc, nullptr, nullptr));
+        BoundaryX<T> bx;
+        bx.qi = C(h->qk), bx.c_za = pl.c_za, bx.ctl = nc;
+        if (pl.alpt_x) CHK((launch_boundary_x<BX_FIRST, true>(h, bx)));
+        else CHK(launch_boundary_x<BX_FIRST>(h, bx));
       }
       EvalMode m;
       m.planes_c2r = m.planes_r2c = true;
@@ -1590,8 +1537,9 @@ struct Pipe {
       if (like_i) CHK(tap_loglike(h, like_i));
       h->prop_g_valid = false;
       ProfScope ps(h, BCHMC_K_KSPACE_FORCE_KICK);
-      CHK(launch_boundary_x<BX_LAST>(h, C(h->qk), nullptr, nullptr, nullptr, nullptr, pl.a, b, 0., 0., 0., nullptr, nc,
-                                     nullptr, C(h->gk)));
+      BoundaryX<T> bx;
+      bx.qi = C(h->qk), bx.a = pl.a, bx.b = b, bx.ctl = nc, bx.g_out = C(h->gk);
+      CHK(launch_boundary_x<BX_LAST>(h, bx));
     } else {
       CHK(force_sources(h, false, EvalMode{}, &like_mode, &b));
       if (like_i) CHK(tap_loglike(h, like_i));
@@ -1657,47 +1605,21 @@ struct Pipe {
     return BCHMC_OK;
   }
 
-  // k_step_boundary_x for this grid: n == PER * NT / KB with KB = 8 (fp64, NT = 256) or 16 (fp32, NT = 512)
+  // k_step_boundary_x for this grid, or the two-tile formulation where that is the faster one
   template <int MODE = BX_INTERIOR, bool ALPT = false>
-  static int launch_boundary_x(bchmc_handle *h, const CT *qi, const CT *pi, CT *qo, CT *po, const double *wM, double a,
-                               double b, double half_eps, double eps, double c_za, double *guard_slot, StepCtl ctl,
-                               const CT *g_in = nullptr, CT *g_out = nullptr) {
-    constexpr int KB = 128 / (int)sizeof(CT);
-    constexpr int NT_BIG = sizeof(T) == 8 ? 256 : 512, NT_SMALL = NT_BIG / 4;  // small: n = 32, 64 (tests)
-    const int n = h->g.n, grid = n * (h->g.nhp / KB);
-    const size_t lds = ((size_t)n * KB + n / 2) * sizeof(CT);
-    const CT *tw = C(h->xtw);
-#define BCHMC_LAUNCH_X(NT, PER)                                                                                      \
-  CHK(launch_lds(h, k_step_boundary_x<T, NT, PER, MODE, ALPT>, grid, NT, lds, h->g, h->log2n, tw, C(h->Ck), qi, pi, qo, \
-                 po, h->wS, wM, a, b, half_eps, eps, c_za, guard_slot, ctl, g_in, g_out))
+  static int launch_boundary_x(bchmc_handle *h, const BoundaryX<T> &bx) {
+    const int n = h->g.n;
     // interior Zel'dovich boundary with fp32 fields: the two-tile formulation (k_step_boundary_x2).  A 1024-thread
     // workgroup is alone on its CU there and the first formulation leaves its memory phases exposed: 0.283 -> 0.231 ms
     // at 256^3.  With fp64 fields (two 512-thread workgroups per CU) both formulations take the same 0.329 ms --
     // 4.7 TB/s is what this access pattern (128-byte segments, one per DRAM row) gets however much is in flight -- and
     // the first one stays (BCHMC_BX_V2=1 selects the second for fp64 too; profiles/r03_ab_bx2.txt).
     const bool want_x2 = (sizeof(T) == 4 && !env_on("BCHMC_BX_V1")) || (sizeof(T) == 8 && n <= 256 && env_on("BCHMC_BX_V2"));
-    if (MODE == BX_INTERIOR && !ALPT && (n == 128 || n == 256) && want_x2 &&  // (512^3 fp32: no difference, v1 stays)
-        (unsigned long long)h->g.Nhp * sizeof(CT) < (1ull << 32)) {  // its lane offsets are 32-bit byte offsets
-      const size_t lds2 = ((size_t)2 * n * KB + n / 2) * sizeof(CT);
-#define BCHMC_LAUNCH_X2(NT, PER)                                                                                   \
-  CHK(launch_lds(h, k_step_boundary_x2<T, NT, PER>, grid, NT, lds2, h->g, h->log2n, tw, C(h->Ck), qi, pi, qo, po, h->wS, \
-                 wM, a, b, half_eps, eps, c_za, guard_slot, ctl))
-      if (n == 128) BCHMC_LAUNCH_X2(NT_BIG, 4);
-      else BCHMC_LAUNCH_X2(2 * NT_BIG, 4);
-#undef BCHMC_LAUNCH_X2
-      HIPCHK(hipGetLastError());
-      return BCHMC_OK;
-    }
-    switch (n) {
-      case 32: BCHMC_LAUNCH_X(NT_SMALL, 4); break;
-      case 64: BCHMC_LAUNCH_X(NT_SMALL, 8); break;
-      case 128: BCHMC_LAUNCH_X(NT_BIG, 4); break;
-      case 256: BCHMC_LAUNCH_X(2 * NT_BIG, 4); break;  // 4 elements per thread: a little faster than 8 x NT_BIG
-      case 512: BCHMC_LAUNCH_X(2 * NT_BIG, 8); break;
-      default: return h->fail(BCHMC_ERR_STATE, "planes mode is not available for n = %d", n);
-    }
-#undef BCHMC_LAUNCH_X
-    HIPCHK(hipGetLastError());
+    if (MODE == BX_INTERIOR && !ALPT && x2_shape(sizeof(T), n).nt && want_x2 &&  // (512^3 fp32: no difference, v1 stays)
+        (unsigned long long)h->g.Nhp * sizeof(CT) < (1ull << 32))  // its lane offsets are 32-bit byte offsets
+      HIPCHK(launch_step_boundary_x2<T>(pass_ctx(h), C(h->Ck), h->wS, bx));
+    else
+      HIPCHK((launch_step_boundary_x<T, MODE, ALPT>(pass_ctx(h), C(h->Ck), h->wS, bx)));
     return BCHMC_OK;
   }
 
@@ -1718,12 +1640,13 @@ struct Pipe {
     {
       StepCtl ctl{h->stop, h->steps_done, nullptr, guard_limit, 0};
       ProfScope ps(h, BCHMC_K_KSPACE_DRIFT_ZA);
+      BoundaryX<T> bx;
+      bx.qi = bx.qo = C(q0), bx.pi = bx.po = C(p0), bx.wM = wM, bx.half_eps = 0.5 * eps, bx.eps = eps, bx.c_za = c_za;
+      bx.ctl = ctl, bx.g_in = C(g_first);
       if (ends && alpt_x) {
-        CHK((launch_boundary_x<BX_FIRST, true>(h, C(q0), C(p0), C(q0), C(p0), wM, 0., 0., 0.5 * eps, eps, c_za, nullptr,
-                                               ctl, C(g_first), nullptr)));
+        CHK((launch_boundary_x<BX_FIRST, true>(h, bx)));
       } else if (ends) {
-        CHK(launch_boundary_x<BX_FIRST>(h, C(q0), C(p0), C(q0), C(p0), wM, 0., 0., 0.5 * eps, eps, c_za, nullptr, ctl,
-                                        C(g_first), nullptr));
+        CHK(launch_boundary_x<BX_FIRST>(h, bx));
       } else {
         k_kick_drift_za<T, true><<<nblk_stride(h->g.Nhp), 256, 0, h->stream>>>(h->g, C(q0), C(p0), C(g_first), wM,
                                                                              nullptr, C(h->Ck), 0.5 * eps, eps, c_za, ctl);
@@ -1753,19 +1676,21 @@ struct Pipe {
       StepCtl ctl{h->stop, h->steps_done, s > 0 ? h->guard + (s - 1) : nullptr, guard_limit, s};
       void *qi = cur ? q1 : q0, *pi = cur ? p1 : p0, *qo = cur ? q0 : q1, *po = cur ? p0 : p1;
       ProfScope ps(h, BCHMC_K_KSPACE_FORCE_KICK);
+      BoundaryX<T> bx;  // the interior boundary; the last one writes p in place, no q, and leaves the gradient in gk
+      bx.qi = C(qi), bx.pi = C(pi), bx.qo = C(qo), bx.po = C(po), bx.wM = wM, bx.a = a, bx.b = b, bx.half_eps = 0.5 * eps;
+      bx.eps = eps, bx.c_za = c_za, bx.guard_slot = h->guard + s, bx.ctl = ctl;
       if (last && xmode) {
-        CHK(launch_boundary_x<BX_LAST>(h, C(qi), C(pi), nullptr, C(pi), wM, a, b, 0.5 * eps, eps, c_za, h->guard + s, ctl,
-                                       nullptr, C(h->gk)));
+        bx.qo = nullptr, bx.po = C(pi), bx.g_out = C(h->gk);
+        CHK(launch_boundary_x<BX_LAST>(h, bx));
       } else if (last) {
         k_step_boundary<T, true><<<nblk_stride(h->g.Nhp), 256, 0, h->stream>>>(
             h->g, C(h->Ck), C(qi), C(pi), C(qi), C(pi), C(h->gk), h->wS, wM, a, b, like_mode, 0.5 * eps, eps, c_za,
             h->guard + s, ctl);
       } else if (xmode && alpt_x) {
-        CHK((launch_boundary_x<BX_INTERIOR, true>(h, C(qi), C(pi), C(qo), C(po), wM, a, b, 0.5 * eps, eps, c_za,
-                                                  h->guard + s, ctl)));
+        CHK((launch_boundary_x<BX_INTERIOR, true>(h, bx)));
         cur ^= 1;
       } else if (xmode) {
-        CHK(launch_boundary_x(h, C(qi), C(pi), C(qo), C(po), wM, a, b, 0.5 * eps, eps, c_za, h->guard + s, ctl));
+        CHK(launch_boundary_x(h, bx));
         cur ^= 1;
       } else {
         k_step_boundary<T, false><<<nblk_stride(h->g.Nhp), 256, 0, h->stream>>>(
@@ -2108,16 +2033,12 @@ struct Pipe {
     return BCHMC_OK;
   }
   // bchmc_probe_displacement_z: the same through the fused z pass + binning.  Psi / n (exact: n is a power of two) goes
-  // through k_zr2c into Ck, in the layout k_ypass leaves there; particle_stage then runs its own BCHMC_LAUNCH_Z.
+  // through k_zr2c into Ck, in the layout k_ypass leaves there; particle_stage then runs its own launch_zbin.
   static int probe_z(bchmc_handle *h, int rsd, bool with_force, bool store_psi) {
     const int n = h->g.n;
-    const size_t zl = ((size_t)n * 6 + n / 2) * sizeof(CT);
-    const CT *tw = C(h->xtw);
     k_scale_r<T><<<nblk_stride(3 * h->g.N), 256, 0, h->stream>>>(3 * h->g.N, R(h->psi), T(1) / T(n));
     HIPCHK(hipGetLastError());
-    if (n == 128) CHK(launch_lds(h, k_zr2c<T, 128>, (n / 2) * (n / 2), 128, zl, h->g, h->log2n, tw, R(h->psi), C(h->Ck)));
-    else if (n == 256) CHK(launch_lds(h, k_zr2c<T, 256>, (n / 2) * (n / 2), 256, zl, h->g, h->log2n, tw, R(h->psi), C(h->Ck)));
-    else CHK(launch_lds(h, k_zr2c<T, 512>, (n / 2) * (n / 2), 512, zl, h->g, h->log2n, tw, R(h->psi), C(h->Ck)));
+    HIPCHK(launch_zr2c<T>(pass_ctx(h), R(h->psi), C(h->Ck)));
     EvalMode m;
     m.planes_c2r = true;
     m.psi_unread = !store_psi;
@@ -3037,11 +2958,10 @@ int bchmc_create(const bchmc_config *cfg, bchmc_handle **out) {
     FFTCHK(h->fft_user.acquire());
     CHK(make_plans_3d(h));
     {
-      // planes mode (k_step_boundary_x): n a power of two, whole 128-byte k-groups per row, a supported per-thread count
-      const int KB = 128 / (int)(2 * h->esz);
+      // planes mode (k_step_boundary_x): an n its table has (powers of two), whole 128-byte k-groups per row
       int l2 = 0;
       while ((1 << l2) < g.n) l2++;
-      if ((1 << l2) == g.n && g.n >= 32 && g.n <= 512 && g.nhp % KB == 0) {
+      if (x_shape((int)h->esz, g.n).nt && g.nhp % pass_kb((int)h->esz) == 0) {
         h->log2n = l2;
         const bool ok2 = make_plans_2d(h, 3 * (size_t)g.n, h->r2c2d, h->c2r2d) == BCHMC_OK;
         // twiddles exp(-2 pi i r / n), r < n / 2, from the host's libm (fft_host.hpp)

@@ -2,10 +2,11 @@
 // compare them with a high-precision DFT (tests/test_gpu_fft_passes.py).  Not part of the product: nothing in the
 // engine or bench.py loads it.
 //
-// It includes kernels.hpp, so every pass below is the engine's kernel code itself, and each entry point repeats the
-// engine's launch of it (bchmc.hip: launch_boundary_x, forward_rest, the planes-mode R2C): template arguments, grid,
-// block, dynamic LDS and the hipFuncSetAttribute call above 48 KB.  Row stride and twiddles come from fft_host.hpp,
-// which the engine uses too.  The only kernel of its own is k_probe_xfft, a bare wrapper around xfft_inplace.
+// Every pass below is the engine's kernel code itself (kernels.hpp), and its launch is the engine's launch: the typed
+// launchers of pass_launch.hpp that bchmc.hip calls (forward_rest, particle_stage, the planes-mode R2C, probe_z) choose
+// template arguments, grid, block and dynamic LDS here too, on the null stream.  Row stride and twiddles come from
+// fft_host.hpp, which the engine uses too.  The only kernel of its own is k_probe_xfft, a bare wrapper around
+// xfft_inplace, on the block size of the engine's tables.
 //
 // Every device array is followed by kCanary bytes of a known pattern; an entry point copies its host arrays in,
 // launches, synchronises, copies back and checks the canaries.  Return value: 0 = ok, -1 = arguments outside the
@@ -13,6 +14,7 @@
 // then the arrays in argument order).
 #include "kernels.hpp"
 #include "fft_host.hpp"
+#include "pass_launch.hpp"
 
 #include <cmath>
 #include <cstring>
@@ -43,6 +45,12 @@ k_probe_xfft(int n, int log2n, int kb, int inverse, const C2<T> *__restrict__ tw
   __syncthreads();
   xfft_inplace<T>(s, tw, n, log2n, kb, inverse != 0);
   for (int e = threadIdx.x; e < n * kb; e += NT) col[e] = s[e];
+}
+
+int ilog2(int n) {
+  int l = 0;
+  while ((1 << l) < n) l++;
+  return (1 << l) == n ? l : -1;
 }
 
 struct Probe {
@@ -85,13 +93,9 @@ struct Probe {
     const std::vector<T> tw = fft_twiddles<T>(n);
     return static_cast<const C2<T> *>(alloc(tw.size() * sizeof(T), tw.data()));
   }
+  // what the engine's launchers take: the null stream, the geometry, the twiddle table (device array 0)
+  template <typename T> PassCtx<T> ctx(const Geo &g) { return {nullptr, g, ilog2(g.n), twiddles<T>(g.n)}; }
 };
-
-int ilog2(int n) {
-  int l = 0;
-  while ((1 << l) < n) l++;
-  return (1 << l) == n ? l : -1;
-}
 
 Geo probe_geo(int n, int esz) {
   Geo g;
@@ -107,28 +111,17 @@ Geo probe_geo(int n, int esz) {
   return g;
 }
 
-template <typename K> bool lds_attr(Probe &pr, K kern, size_t lds) {
-  if (lds > 48 * 1024)
-    return pr.ok(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)lds));
-  return true;
-}
-
 template <typename T, int NT>
 void launch_xfft(Probe &pr, int groups, int n, int kb, int inverse, const C2<T> *tw, C2<T> *d) {
   const size_t lds = ((size_t)n * kb + n / 2) * sizeof(C2<T>);
-  auto kern = k_probe_xfft<T, NT>;
-  if (!lds_attr(pr, kern, lds)) return;
-  kern<<<groups, NT, lds, 0>>>(n, ilog2(n), kb, inverse, tw, d);
+  pr.ok(launch_dyn_lds(nullptr, k_probe_xfft<T, NT>, groups, NT, lds, n, ilog2(n), kb, inverse, tw, d));
 }
 
 template <typename T> int xfft(int n, int kb, int inverse, int groups, void *data) {
-  constexpr int KB = 128 / (int)sizeof(C2<T>);
-  constexpr int NT_BIG = sizeof(T) == 8 ? 256 : 512, NT_SMALL = NT_BIG / 4;
-  if (ilog2(n) < 5 || n > 512 || groups < 1 || (kb != KB && kb != 6)) return -1;
+  if (ilog2(n) < 5 || n > 512 || groups < 1 || (kb != pass_kb(sizeof(T)) && kb != 6)) return -1;
   // the engine's block size for this n: k_step_boundary_x / k_alpt_mix_x / k_ypass (kb = KB), one thread per element
   // of a z row in k_zbin_direct / k_zr2c (kb = 6)
-  const int nt = kb == 6 ? n : (n <= 64 ? NT_SMALL : (n == 128 ? NT_BIG : 2 * NT_BIG));
+  const int nt = kb == 6 ? n : x_shape(sizeof(T), n).nt;
   Probe pr;
   const size_t bytes = (size_t)groups * n * kb * sizeof(C2<T>);
   const C2<T> *tw = pr.twiddles<T>(n);
@@ -146,82 +139,47 @@ template <typename T> int xfft(int n, int kb, int inverse, int groups, void *dat
   return pr.finish({{1, data}});
 }
 
-// k_ypass as forward_rest (inverse, BCHMC_LAUNCH_Y) and the planes-mode R2C at 512^3 (forward) launch it
+// k_ypass as forward_rest (inverse) and the planes-mode R2C at 512^3 (forward) launch it
 template <typename T> int ypass(int n, int inverse, void *ck) {
-  constexpr int KB = 128 / (int)sizeof(C2<T>);
-  if (!(n == 128 || n == 256 || n == 512) || (!inverse && n != 512)) return -1;
+  if (!y_shape(sizeof(T), n).nt || (!inverse && n != 512)) return -1;
   const Geo g = probe_geo(n, (int)sizeof(T));
-  if (g.nhp % KB) return -1;
+  if (g.nhp % pass_kb(sizeof(T))) return -1;
   Probe pr;
-  const C2<T> *tw = pr.twiddles<T>(n);
+  const PassCtx<T> x = pr.ctx<T>(g);
   C2<T> *d = static_cast<C2<T> *>(pr.alloc((size_t)3 * g.Nhp * sizeof(C2<T>), ck));
   if (pr.err) return pr.err;
-  const int ygrid = 3 * n * (g.nhp / KB);
-  const size_t lds = ((size_t)n * KB + n / 2) * sizeof(C2<T>);
-#define PROBE_LAUNCH_Y(NT, NN, INV)                                           \
-  do {                                                                        \
-    auto kern = k_ypass<T, NT, NN * KB / NT, BCHMC_YPASS_NT, INV>;            \
-    if (lds_attr(pr, kern, lds)) kern<<<ygrid, NT, lds, 0>>>(g, ilog2(n), tw, d); \
-  } while (0)
-  if (!inverse) PROBE_LAUNCH_Y(512, 512, false);
-  else if (n == 128) PROBE_LAUNCH_Y(256, 128, true);
-  else if (n == 256) PROBE_LAUNCH_Y(512, 256, true);
-  else PROBE_LAUNCH_Y(512, 512, true);
-#undef PROBE_LAUNCH_Y
+  pr.ok(inverse ? launch_ypass<T>(x, d) : launch_ypass<T, false>(x, d));
   return pr.finish({{1, ck}});
 }
 
-// k_zr2c<T, 512> as the planes-mode R2C at 512^3 launches it, <T, 128> and <T, 256> as bchmc_probe_displacement_z does;
+// k_zr2c as the planes-mode R2C at 512^3 launches it, and as bchmc_probe_displacement_z does at 128^3 and 256^3;
 // ck goes in as well, so that the row padding the kernel leaves alone comes back as it went in
 template <typename T> int zr2c(int n, const void *V, void *ck) {
-  if (!(n == 128 || n == 256 || n == 512)) return -1;
+  if (!z_shape(sizeof(T), n).nt) return -1;
   const Geo g = probe_geo(n, (int)sizeof(T));
   Probe pr;
-  const C2<T> *tw = pr.twiddles<T>(n);
+  const PassCtx<T> x = pr.ctx<T>(g);
   const T *dv = static_cast<const T *>(pr.alloc((size_t)3 * g.N * sizeof(T), V));
   C2<T> *dc = static_cast<C2<T> *>(pr.alloc((size_t)3 * g.Nhp * sizeof(C2<T>), ck));
   if (pr.err) return pr.err;
-  const size_t zl = ((size_t)n * 6 + n / 2) * sizeof(C2<T>);
-#define PROBE_LAUNCH_ZR(NZ)                                                                     \
-  do {                                                                                          \
-    auto kz = k_zr2c<T, NZ>;                                                                    \
-    if (lds_attr(pr, kz, zl)) kz<<<(n / 2) * (n / 2), NZ, zl, 0>>>(g, ilog2(n), tw, dv, dc);    \
-  } while (0)
-  if (n == 128) PROBE_LAUNCH_ZR(128);
-  else if (n == 256) PROBE_LAUNCH_ZR(256);
-  else PROBE_LAUNCH_ZR(512);
-#undef PROBE_LAUNCH_ZR
+  pr.ok(launch_zr2c<T>(x, dv, dc));
   return pr.finish({{2, ck}});
 }
 
-// k_zbin_direct<T, NZ, true> as forward_rest launches it after an overflowed binning (*ovf set): the z C2R of the three
+// k_zbin_direct<T, NZ, true> as particle_stage launches it after an overflowed binning (*ovf set): the z C2R of the three
 // displacement components into psi (3 n^3 reals).  Its positions / binning arguments are not read on this path.
 template <typename T> int zc2r(int n, const void *ck, void *psi) {
-  if (!(n == 128 || n == 256 || n == 512)) return -1;
+  if (!z_shape(sizeof(T), n).nt) return -1;
   const Geo g = probe_geo(n, (int)sizeof(T));
   Probe pr;
-  const C2<T> *tw = pr.twiddles<T>(n);
+  const PassCtx<T> x = pr.ctx<T>(g);
   const C2<T> *dc = static_cast<const C2<T> *>(pr.alloc((size_t)3 * g.Nhp * sizeof(C2<T>), ck));
   const int ovf_h[3] = {1, 0, 0};
   int *ovf = static_cast<int *>(pr.alloc(sizeof(ovf_h), ovf_h));
   T *dp = static_cast<T *>(pr.alloc((size_t)3 * g.N * sizeof(T), nullptr));
   if (pr.err) return pr.err;
-  const int zgrid = (n / 2) * (n / 2);
-  const size_t zlds = zbin_lds<T>(n);
-  const PosPar pp{};
-  const SphPar sp{};
-  const TilePar tp{};
-#define PROBE_LAUNCH_Z(NZ)                                                                                      \
-  do {                                                                                                          \
-    auto kpsi = k_zbin_direct<T, NZ, true>;                                                                     \
-    if (lds_attr(pr, kpsi, zlds))                                                                               \
-      kpsi<<<zgrid, NZ, zlds, 0>>>(g, pp, sp, tp, ilog2(n), tw, dc, nullptr, ovf, nullptr, nullptr, nullptr, nullptr, \
-                                   nullptr, dp);                                                                \
-  } while (0)
-  if (n == 128) PROBE_LAUNCH_Z(128);
-  else if (n == 256) PROBE_LAUNCH_Z(256);
-  else PROBE_LAUNCH_Z(512);
-#undef PROBE_LAUNCH_Z
+  pr.ok((launch_zbin<T, true>(x, PosPar{}, SphPar{}, TilePar{}, dc, nullptr, ovf, nullptr, nullptr, nullptr, nullptr, nullptr,
+                              dp)));
   return pr.finish({{3, psi}});
 }
 

@@ -396,7 +396,8 @@ def test_planes_mode_other_likelihoods(monkeypatch, kw):
     e.close()
 
 
-@pytest.mark.parametrize("nx,precision", [(32, 0), (32, 1), (64, 0)], ids=["n32_fp64", "n32_fp32", "n64_fp64"])
+@pytest.mark.parametrize("nx,precision", [(32, 0), (32, 1), (64, 0), (64, 1)],
+                         ids=["n32_fp64", "n32_fp32", "n64_fp64", "n64_fp32"])
 def test_planes_mode_step_boundary(monkeypatch, nx, precision):
     """Interior step boundaries in "planes" mode (2-D rocFFT transforms of the (y, z) planes, the x passes fused into
     k_step_boundary_x; its BX_FIRST / BX_LAST variants at the ends of the trajectory and for the force evaluation before
