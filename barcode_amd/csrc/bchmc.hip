@@ -12,6 +12,7 @@
 #include "fft_host.hpp"
 #include "owned.hpp"
 #include "pass_launch.hpp"
+#include "eval_plan.hpp"
 
 #include <rocfft/rocfft.h>
 #include <rocprofiler-sdk-roctx/roctx.h>
@@ -48,6 +49,8 @@ struct bchmc_handle {
   bool f32 = false;   // storage type of the field arrays
   size_t esz = 8;     // sizeof(T)
   int mass_fs = 0, mass_rs = 0;
+  PathSwitches sw;            // the path switches of eval_plan.hpp, as the environment had them at create (read_path_switches)
+  bool no_tiles_low = false;  // BCHMC_NO_TILES_LOW, as make_tiles read it
   std::string err;
   // Every resource below is an owner of owned.hpp, and bchmc_destroy only deletes the handle: members are destroyed
   // in reverse declaration order, and three things depend on that order.  The stream is declared before every buffer
@@ -251,13 +254,6 @@ inline bool env_on(const char *name) {
 
 inline int nblk_stride(long long n) { return (int)std::min<long long>((n + 255) / 256, 2048); }
 inline int nblk_full(long long n) { return (int)((n + 255) / 256); }
-
-struct EvalMode {             // how ONE force evaluation runs; decided by the caller
-  bool planes_c2r = false;    // Psi^ in Ck is in planes space: only the (y, z) passes remain
-  bool planes_r2c = false;    // V^ is wanted in planes space
-  bool alpt_pending = false;  // Ck[0], Ck[1] hold delta(1)^ | Phi^ planes left by k_step_boundary_x<ALPT>
-  bool psi_unread = false;    // interior step: nobody reads Psi / positions, the z pass may end in the binning
-};
 
 // ---- profiling ------------------------------------------------------------------------------------
 // roctx range names: the kernel ids of SURVEY.md 2.1 that each launch group replaces, so that a
@@ -559,6 +555,39 @@ int make_plans_2d(bchmc_handle *h, size_t batch, FftPlan &r2c, FftPlan &c2r) {
     return BCHMC_ERR_ROCFFT;
   }
   return BCHMC_OK;
+}
+
+// The path switches of eval_plan.hpp from the environment: bchmc_create's, once per handle.
+PathSwitches read_path_switches() {
+  PathSwitches s;
+  s.no_planes = env_on("BCHMC_NO_PLANES");
+  s.no_planes_ends = env_on("BCHMC_NO_PLANES_ENDS");
+  s.no_fuse = env_on("BCHMC_NO_FUSE");
+  s.no_alpt_planes = env_on("BCHMC_NO_ALPT_PLANES");
+  s.no_zbin = env_on("BCHMC_NO_ZBIN");
+  s.zbin_128 = env_on("BCHMC_ZBIN_128");
+  s.yfwd_f64 = env_on("BCHMC_YFWD_F64");
+  s.bx_v1 = env_on("BCHMC_BX_V1");
+  s.bx_v2 = env_on("BCHMC_BX_V2");
+  return s;
+}
+
+// What eval_plan.hpp's decisions read, as the handle is now; gathered for every decision, never kept.  rsd: of the forward
+// evaluation the caller is deciding (a trajectory's and everything else's: the configuration's rsd_model).  The only place
+// that makes the ALPT pipeline's plans over 2 n planes late: a forward evaluation that wants them and finds none --
+// bchmc_forward or a log-likelihood without RSD on a handle configured with it; bchmc_create made them for rsd_model.
+PathFacts path_facts(bchmc_handle *h, int rsd) {
+  PathFacts f;
+  f.n = h->g.n, f.esz = (int)h->esz, f.Nhp = h->g.Nhp;
+  f.planes_ok = h->planes_ok && h->xtw;
+  f.tiled = h->plan.tiled, f.sort_direct = h->plan.slots.sort_direct;
+  f.mk = h->c.mk, f.calc_h = h->c.calc_h, f.likelihood = h->c.likelihood, f.sfmodel = h->c.sfmodel;
+  f.rsd_model = h->c.rsd_model, f.mass_rs = h->mass_rs != 0;
+  if (alpt_planes_wanted(f, h->sw, rsd) && !h->c2r2d_2 && !h->alpt_plans_failed &&
+      make_plans_2d(h, 2 * (size_t)h->g.n, h->r2c2d_2, h->c2r2d_2) != BCHMC_OK)
+    h->alpt_plans_failed = true;
+  f.alpt_plans = h->c2r2d_2 != nullptr;
+  return f;
 }
 
 // Sum kRedBlocks device partials on the host (synchronises the stream).
@@ -977,16 +1006,12 @@ struct Pipe {
     return BCHMC_OK;
   }
 
-  // Which structure-formation model a forward evaluation uses (dispatcher Lag2Eul.cc:325-331; the RSD routine is
-  // Zel'dovich whatever sfmodel says, HMC_models.cc:395-405).
-  static bool uses_alpt(const bchmc_handle *h, int rsd) { return !rsd && h->c.sfmodel != 1; }
-
   // Psi^ of the forward model selected by (sfmodel, rsd) from the current q^; *psi_planes: it is left in planes space
   // (EvalMode::planes_c2r of the forward_rest that follows)
   static int displacement(bchmc_handle *h, double dq_factor, int rsd, bool *psi_planes) {
-    const bool alpt = uses_alpt(h, rsd);
-    *psi_planes = alpt && alpt_planes(h);
-    return alpt ? launch_alpt(h, dq_factor, *psi_planes) : launch_za(h, dq_factor);
+    const PathFacts f = path_facts(h, rsd);
+    *psi_planes = alpt_on_planes(f, h->sw, rsd);
+    return uses_alpt(f, rsd) ? launch_alpt(h, dq_factor, *psi_planes) : launch_za(h, dq_factor);
   }
 
   // kernelcomp: wtot = sum over the box of the inverse transform of the kernel table (= K(0) up to round-off)
@@ -1006,15 +1031,6 @@ struct Pipe {
     CHK(host_sum(h, h->partA, &v));
     *wtot = v / (double)h->g.N;
     return BCHMC_OK;
-  }
-
-  // ALPT on the 2-D plans (alpt_x.hpp): the SPH-adjoint path's planes mode plus two plans over 2 n planes
-  static bool alpt_planes(bchmc_handle *h) {
-    if (!planes_everywhere(h) || env_on("BCHMC_NO_ALPT_PLANES")) return false;
-    if (!h->c2r2d_2 && !h->alpt_plans_failed) {
-      if (make_plans_2d(h, 2 * (size_t)h->g.n, h->r2c2d_2, h->c2r2d_2) != BCHMC_OK) h->alpt_plans_failed = true;
-    }
-    return h->c2r2d_2 != nullptr;
   }
 
   // ALPT displacement (Lag2Eul_non_zeldovich, Lag2Eul.cc:160-267), second part: from delta(1)^ and Phi^ in Ck[0], Ck[1]
@@ -1054,7 +1070,7 @@ struct Pipe {
     return BCHMC_OK;
   }
 
-  // ALPT displacement from the current q^, on the 2-D plans (`planes` = alpt_planes(h)) or the 3-D ones.
+  // ALPT displacement from the current q^, on the 2-D plans (`planes`: alpt_on_planes, eval_plan.hpp) or the 3-D ones.
   static int launch_alpt(bchmc_handle *h, double dq_factor, bool planes) {
     const double scale = dq_factor / (double)h->g.N;
     if (planes) {
@@ -1075,50 +1091,16 @@ struct Pipe {
     return alpt_middle(h, false);
   }
 
-  // the fused z pass + binning exists for the benchmark grids (one lattice site along z per thread of k_zbin_direct)
-  static bool zbin_ok(const bchmc_handle *h) {
-    // (128^3: measured 2 % slower -- 4096 small workgroups, the binning part grows by more than rocFFT's row pass
-    // costs there -- so rocFFT keeps it unless BCHMC_ZBIN_128=1, which the tests use for the n = 128 instantiation)
-    const bool size_ok = h->g.n == 256 || h->g.n == 512 || (h->g.n == 128 && env_on("BCHMC_ZBIN_128"));
-    return size_ok && h->plan.tiled && h->plan.slots.sort_direct && h->planes_ok && h->xtw && h->c.mk == 3 && h->c.calc_h == 2 &&
-           !env_on("BCHMC_NO_ZBIN");  // (mk 3 + calc_h 2 on tiles: nothing but the fallback sort reads Psi after the binning)
-  }
-  // the first of zbin_ok's conditions that does not hold, in words (bchmc_probe_displacement_z's refusal); nullptr: all do
-  static const char *zbin_why_not(const bchmc_handle *h) {
-    if (zbin_ok(h)) return nullptr;
-    if (env_on("BCHMC_NO_ZBIN")) return "BCHMC_NO_ZBIN is set";
-    if (h->g.n == 128 && !env_on("BCHMC_ZBIN_128")) return "Nx = 128 takes it with BCHMC_ZBIN_128=1 only";
-    if (!(h->g.n == 128 || h->g.n == 256 || h->g.n == 512)) return "it exists for Nx = 128, 256 and 512";
-    if (h->c.mk != 3 || h->c.calc_h != 2) return "it needs masskernel 3 with calc_h 2";
-    if (!h->plan.tiled || !h->plan.slots.sort_direct) return "the one-pass tile binning is not in use";
-    return "the planes-mode transforms are not available";
-  }
-
-  // the engine's own row + column passes of the planes-mode R2C: where rocFFT's column kernel is the slower one (n = 512)
-  static bool yfwd_ok(const bchmc_handle *h) {
-    // fp32 fields: R2C class 2.59 -> 1.85 ms per step (17.96 -> 17.35 ms, +3.5 %); fp64: rocFFT's double-precision
-    // column kernel is as fast as the pair (3.14 against 3.16 ms) and stays unless BCHMC_YFWD_F64=1
-    return h->g.n == 512 && (sizeof(T) == 4 || env_on("BCHMC_YFWD_F64")) && h->planes_ok && h->xtw;
-  }
-
   // C2R of the three displacement components, mass assignment, sum of rho.  Lag2Eul.cc:90-131 / 363-423.
   // Reads m.planes_c2r (where the caller or `displacement` left Psi^) and m.psi_unread.
   static int forward_rest(bchmc_handle *h, int rsd, EvalMode m) {
     if (rsd && !h->c.planepar) return h->fail(BCHMC_ERR_RSD_NOT_PLANEPAR, "non-plane-parallel RSD is not implemented");
-    bool zbin = false;
-    {
-      const bool planes = m.planes_c2r;
-      // Interior steps of a trajectory at 128^3 / 256^3 / 512^3 (nobody reads Psi or the positions of such a step): the engine's own y
-      // pass, and the z pass inside the binning kernel below -- Psi does not go through HBM (zpass.hpp).
-      // The other planes-space evaluations (the one before the first step, the last step) use the same kernels and
-      // store Psi on the way (0.385 against 0.45 ms at 256^3): their positions may be fetched.
-      zbin = planes && zbin_ok(h);
-      if (zbin) {
-        ProfScope ps(h, BCHMC_K_FFT_C2R);
-        HIPCHK(launch_ypass<T>(pass_ctx(h), C(h->Ck)));
-      } else {
-        CHK(fft_exec(h, planes ? h->c2r2d : h->c2r3, h->Ck, h->psi, BCHMC_K_FFT_C2R));
-      }
+    const bool zbin = eval_zbin(path_facts(h, rsd), h->sw, m);  // the z pass of Psi^ is particle_stage's
+    if (zbin) {
+      ProfScope ps(h, BCHMC_K_FFT_C2R);
+      HIPCHK(launch_ypass<T>(pass_ctx(h), C(h->Ck)));
+    } else {
+      CHK(fft_exec(h, m.planes_c2r ? h->c2r2d : h->c2r3, h->Ck, h->psi, BCHMC_K_FFT_C2R));
     }
     return particle_stage(h, rsd, m, zbin);
   }
@@ -1336,7 +1318,7 @@ struct Pipe {
       CHK(fft_exec(h, h->c2r3, h->Ck, h->conv, BCHMC_K_FFT_C2R));
       {
         ProfScope ps(h, BCHMC_K_GATHER);
-        if (h->plan.tiled && h->sorted_valid && !env_on("BCHMC_NO_TILES_LOW")) {
+        if (h->plan.tiled && h->sorted_valid && !h->no_tiles_low) {
           const int grid = tile_grid(h);
           const size_t lds = 3 * (size_t)(h->plan.tp.tx + 2) * (h->plan.tp.ty + 2) * (h->plan.tp.tz + 2) * sizeof(T);
           k_interp_tsc_tile<T><<<grid, 256, lds, h->stream>>>(h->g, h->plan.tp, h->last_rsd, fgrow1(h->c.ascale, h->c.OM, h->c.OL),
@@ -1369,7 +1351,7 @@ struct Pipe {
       HIPCHK(hipGetLastError());
     }
     if (!transform) {
-    } else if (m.planes_r2c && yfwd_ok(h)) {
+    } else if (eval_yfwd(path_facts(h, h->c.rsd_model), h->sw, m)) {
       // 512^3: the engine's own row and column passes (rocFFT's length-512 column kernel runs at 2.3 TB/s, its 1-D row
       // plan alone at half the speed of the same pass inside the 2-D plan: k_zr2c + k_ypass<forward>, zpass.hpp)
       ProfScope ps(h, BCHMC_K_FFT_R2C);
@@ -1487,63 +1469,61 @@ struct Pipe {
     return BCHMC_OK;
   }
 
-  // planes mode: the SPH-adjoint path (three V components) with a supported grid
-  static bool planes_on(const bchmc_handle *h) {
-    return h->planes_ok && h->c.calc_h == 2 && h->c.mk == 3 && !env_on("BCHMC_NO_PLANES");
-  }
-  // ... also for the force evaluation before the first step and for the first and the last step (BX_FIRST / BX_LAST
-  // variants of k_step_boundary_x); BCHMC_NO_PLANES_ENDS=1 keeps those on the 3-D plans
-  static bool planes_everywhere(const bchmc_handle *h) { return planes_on(h) && !env_on("BCHMC_NO_PLANES_ENDS"); }
-
-  // How a trajectory runs on this handle: which model produces the displacement, whether the fused step boundary
-  // applies, the constant that turns q^ into the model's k-space input.
-  struct TrajPlan {
+  // How a trajectory runs on this handle now (eval_plan.hpp), and the two constants its kernels take: a, the prior
+  // factor, and c_za, which turns q^ into the displacement model's k-space input.  Lives for one call: nothing that opening,
+  // step_mode and closing read changes inside a trajectory (sort_direct may: forward_rest gathers the facts again).
+  struct Traj {
+    PathFacts f;
+    TrajPlan p;
     double a, c_za;
-    bool alpt_x, fused_za, fused;
   };
-  static TrajPlan traj_plan(bchmc_handle *h) {
-    TrajPlan tp;
-    tp.a = h->c.grad_psi_prior_factor;
-    // the k-space kernels produce the Zel'dovich Psi^ as a by-product; the ALPT model needs its own pipeline
-    // ... on the 2-D plans (alpt_planes) the step boundary leaves that pipeline's two input fields instead of Psi^
-    const bool alpt = uses_alpt(h, h->c.rsd_model) && h->c.likelihood != 3;
-    tp.alpt_x = alpt && !h->mass_rs && !env_on("BCHMC_NO_FUSE") && alpt_planes(h);
-    tp.fused_za = (h->c.likelihood != 3) && !alpt;
-    tp.c_za = tp.alpt_x ? h->c.deltaQ_factor / (double)h->g.N : -h->c.D1 * h->c.deltaQ_factor / (double)h->g.N;
-    tp.fused = (tp.fused_za || tp.alpt_x) && !h->mass_rs && !env_on("BCHMC_NO_FUSE");
-    return tp;
+  static Traj traj(bchmc_handle *h) {
+    Traj t;
+    t.f = path_facts(h, h->c.rsd_model);
+    t.p = traj_plan(t.f, h->sw);
+    t.a = h->c.grad_psi_prior_factor;
+    t.c_za = (t.p.c_za == CZa::kAlptInput ? 1. : -h->c.D1) * h->c.deltaQ_factor / (double)h->g.N;
+    return t;
+  }
+
+  // k_step_boundary_x for this grid, one tile per workgroup
+  template <int MODE, bool ALPT = false>
+  static int launch_boundary_x(bchmc_handle *h, const BoundaryX<T> &bx) {
+    HIPCHK((launch_step_boundary_x<T, MODE, ALPT>(pass_ctx(h), C(h->Ck), h->wS, bx)));
+    return BCHMC_OK;
   }
 
   // gradient_psi at the trajectory's start state q^ = qk (HMC.cc:279-280) into gk; needs nothing of the momenta.
   // like_i: where to leave the -log L partials of this evaluation's forward model (may be null).
-  static int initial_force(bchmc_handle *h, const TrajPlan &pl, double *like_i, void *g0_out) {
+  static int initial_force(bchmc_handle *h, const Traj &t, double *like_i, void *g0_out) {
     int like_mode = 2;
     double b = 0.;
-    if (pl.fused && planes_everywhere(h)) {
+    const InitialEval kind = initial_eval(t.f, h->sw, t.p);
+    if (kind == InitialEval::k3d) {
+      CHK(force_sources(h, false, EvalMode{}, &like_mode, &b));
+      if (like_i) CHK(tap_loglike(h, like_i));
+      CHK(launch_assemble<false>(h, t.a, b, like_mode, 0., nullptr));
+    } else {
       // the same evaluation on the 2-D plans: Psi^ with its inverse x passes, V^ assembled after forward x passes
       StepCtl nc{h->stop, h->steps_done, nullptr, 0., 0};
       {
         ProfScope ps(h, BCHMC_K_KSPACE_DRIFT_ZA);
         BoundaryX<T> bx;
-        bx.qi = C(h->qk), bx.c_za = pl.c_za, bx.ctl = nc;
-        if (pl.alpt_x) CHK((launch_boundary_x<BX_FIRST, true>(h, bx)));
+        bx.qi = C(h->qk), bx.c_za = t.c_za, bx.ctl = nc;
+        if (kind == InitialEval::kBxFirstAlpt) CHK((launch_boundary_x<BX_FIRST, true>(h, bx)));
         else CHK(launch_boundary_x<BX_FIRST>(h, bx));
       }
       EvalMode m;
       m.planes_c2r = m.planes_r2c = true;
-      m.alpt_pending = pl.alpt_x;
+      m.alpt_pending = t.p.alpt_x;
       CHK(force_sources(h, true, m, &like_mode, &b));
       if (like_mode != 0) return h->fail(BCHMC_ERR_STATE, "planes mode without the three V components");
       if (like_i) CHK(tap_loglike(h, like_i));
       h->prop_g_valid = false;
       ProfScope ps(h, BCHMC_K_KSPACE_FORCE_KICK);
       BoundaryX<T> bx;
-      bx.qi = C(h->qk), bx.a = pl.a, bx.b = b, bx.ctl = nc, bx.g_out = C(h->gk);
+      bx.qi = C(h->qk), bx.a = t.a, bx.b = b, bx.ctl = nc, bx.g_out = C(h->gk);
       CHK(launch_boundary_x<BX_LAST>(h, bx));
-    } else {
-      CHK(force_sources(h, false, EvalMode{}, &like_mode, &b));
-      if (like_i) CHK(tap_loglike(h, like_i));
-      CHK(launch_assemble<false>(h, pl.a, b, like_mode, 0., nullptr));
     }
     if (g0_out)
       HIPCHK(hipMemcpyAsync(g0_out, h->gk, 2 * (size_t)h->g.Nhp * sizeof(T), hipMemcpyDeviceToDevice, h->stream));
@@ -1562,32 +1542,30 @@ struct Pipe {
     k_init_ctl<<<1, 1, 0, h->stream>>>(h->stop, h->steps_done, (unsigned long long)neps);
     HIPCHK(hipGetLastError());
 
-    const TrajPlan pl = traj_plan(h);
-    const double a = pl.a, c_za = pl.c_za;
-    const bool alpt_x = pl.alpt_x, fused_za = pl.fused_za, fused = pl.fused;
+    const Traj t = traj(h);
     int like_mode = 2;
     double b = 0.;
     // 0) gradient at t = 0 (HMC.cc:279-280)
-    if (!g0_in) CHK(initial_force(h, pl, tap ? tap->like_i : nullptr, g0_out));
+    if (!g0_in) CHK(initial_force(h, t, tap ? tap->like_i : nullptr, g0_out));
     const void *g_first = g0_in ? g0_in : h->gk;
     if (neps == 0) return BCHMC_OK;  // HMC.cc:284 loops zero times: the state is returned as it came
 
+    if (t.p.fused) return trajectory_fused(h, eps, neps, tap, t, g_first);
     const double *wM = h->mass_fs ? h->wM : nullptr;
     const double guard_limit = 1e50 * (double)h->g.N;
-    if (fused) return trajectory_fused(h, eps, neps, tap, a, wM, c_za, g_first, alpt_x);
     for (uint64_t s = 0; s < neps; s++) {
       StepCtl ctl{h->stop, h->steps_done, s > 0 ? h->guard + (s - 1) : nullptr, guard_limit, s};
       if (!h->mass_rs) {
         ProfScope ps(h, BCHMC_K_KSPACE_DRIFT_ZA);
         k_kick_drift_za<T, true><<<nblk_stride(h->g.Nhp), 256, 0, h->stream>>>(
-            h->g, C(h->qk), C(h->pk), C(s == 0 ? g_first : h->gk), wM, nullptr, C(h->Ck), 0.5 * eps, eps, c_za, ctl);
+            h->g, C(h->qk), C(h->pk), C(s == 0 ? g_first : h->gk), wM, nullptr, C(h->Ck), 0.5 * eps, eps, t.c_za, ctl);
         HIPCHK(hipGetLastError());
       } else {
         // kick first (needs p in real space for the mass_r term), then drift with the extra term
         {
           ProfScope ps(h, BCHMC_K_KSPACE_DRIFT_ZA);
           k_kick_drift_za<T, true><<<nblk_stride(h->g.Nhp), 256, 0, h->stream>>>(
-              h->g, C(h->qk), C(h->pk), C(s == 0 ? g_first : h->gk), nullptr, nullptr, C(h->Ck), 0.5 * eps, 0., c_za,
+              h->g, C(h->qk), C(h->pk), C(s == 0 ? g_first : h->gk), nullptr, nullptr, C(h->Ck), 0.5 * eps, 0., t.c_za,
               ctl);
           HIPCHK(hipGetLastError());
         }
@@ -1595,39 +1573,23 @@ struct Pipe {
         StepCtl ctl2{h->stop, h->steps_done, nullptr, 0., s};
         ProfScope ps(h, BCHMC_K_KSPACE_DRIFT_ZA);
         k_kick_drift_za<T, true><<<nblk_stride(h->g.Nhp), 256, 0, h->stream>>>(h->g, C(h->qk), C(h->pk), C(h->gk), wM,
-                                                                             C(h->tC), C(h->Ck), 0., eps, c_za, ctl2);
+                                                                             C(h->tC), C(h->Ck), 0., eps, t.c_za, ctl2);
         HIPCHK(hipGetLastError());
       }
-      CHK(force_sources(h, fused_za, EvalMode{}, &like_mode, &b));
+      CHK(force_sources(h, t.p.fused_za, EvalMode{}, &like_mode, &b));
       if (tap && tap->like_f && s + 1 == neps) CHK(tap_loglike(h, tap->like_f));
-      CHK(launch_assemble<true>(h, a, b, like_mode, 0.5 * eps, h->guard + s));
+      CHK(launch_assemble<true>(h, t.a, b, like_mode, 0.5 * eps, h->guard + s));
     }
-    return BCHMC_OK;
-  }
-
-  // k_step_boundary_x for this grid, or the two-tile formulation where that is the faster one
-  template <int MODE = BX_INTERIOR, bool ALPT = false>
-  static int launch_boundary_x(bchmc_handle *h, const BoundaryX<T> &bx) {
-    const int n = h->g.n;
-    // interior Zel'dovich boundary with fp32 fields: the two-tile formulation (k_step_boundary_x2).  A 1024-thread
-    // workgroup is alone on its CU there and the first formulation leaves its memory phases exposed: 0.283 -> 0.231 ms
-    // at 256^3.  With fp64 fields (two 512-thread workgroups per CU) both formulations take the same 0.329 ms --
-    // 4.7 TB/s is what this access pattern (128-byte segments, one per DRAM row) gets however much is in flight -- and
-    // the first one stays (BCHMC_BX_V2=1 selects the second for fp64 too; profiles/r03_ab_bx2.txt).
-    const bool want_x2 = (sizeof(T) == 4 && !env_on("BCHMC_BX_V1")) || (sizeof(T) == 8 && n <= 256 && env_on("BCHMC_BX_V2"));
-    if (MODE == BX_INTERIOR && !ALPT && x2_shape(sizeof(T), n).nt && want_x2 &&  // (512^3 fp32: no difference, v1 stays)
-        (unsigned long long)h->g.Nhp * sizeof(CT) < (1ull << 32))  // its lane offsets are 32-bit byte offsets
-      HIPCHK(launch_step_boundary_x2<T>(pass_ctx(h), C(h->Ck), h->wS, bx));
-    else
-      HIPCHK((launch_step_boundary_x<T, MODE, ALPT>(pass_ctx(h), C(h->Ck), h->wS, bx)));
     return BCHMC_OK;
   }
 
   // The same trajectory with every interior "second half kick | first half kick + drift + Zel'dovich" pair done by
   // one kernel (k_step_boundary) on ping-pong state buffers.  Used for k-space masses and forward-model likelihoods.
-  static int trajectory_fused(bchmc_handle *h, double eps, uint64_t neps, const Tap *tap, double a, const double *wM,
-                              double c_za, const void *g_first, bool alpt_x = false) {
-    const double guard_limit = 1e50 * (double)h->g.N;
+  // Which kernel opens it, how each step's force evaluation runs and which kernel closes the step: eval_plan.hpp.
+  static int trajectory_fused(bchmc_handle *h, double eps, uint64_t neps, const Tap *tap, const Traj &t,
+                              const void *g_first) {
+    const double *wM = h->mass_fs ? h->wM : nullptr;
+    const double guard_limit = 1e50 * (double)h->g.N, a = t.a, c_za = t.c_za;
     if (!h->qk2) {
       CHK(dev_alloc(h, h->qk2, 2 * (size_t)h->g.Nhp * sizeof(T)));
       CHK(dev_alloc(h, h->pk2, 2 * (size_t)h->g.Nhp * sizeof(T)));
@@ -1636,20 +1598,19 @@ struct Pipe {
     int like_mode = 2;
     double b = 0.;
     int cur = 0;  // boundary j reads pair j % 2
-    const bool planes = planes_on(h), ends = planes_everywhere(h);
     {
       StepCtl ctl{h->stop, h->steps_done, nullptr, guard_limit, 0};
       ProfScope ps(h, BCHMC_K_KSPACE_DRIFT_ZA);
       BoundaryX<T> bx;
       bx.qi = bx.qo = C(q0), bx.pi = bx.po = C(p0), bx.wM = wM, bx.half_eps = 0.5 * eps, bx.eps = eps, bx.c_za = c_za;
       bx.ctl = ctl, bx.g_in = C(g_first);
-      if (ends && alpt_x) {
-        CHK((launch_boundary_x<BX_FIRST, true>(h, bx)));
-      } else if (ends) {
-        CHK(launch_boundary_x<BX_FIRST>(h, bx));
-      } else {
-        k_kick_drift_za<T, true><<<nblk_stride(h->g.Nhp), 256, 0, h->stream>>>(h->g, C(q0), C(p0), C(g_first), wM,
-                                                                             nullptr, C(h->Ck), 0.5 * eps, eps, c_za, ctl);
+      switch (opening(t.f, h->sw, t.p)) {
+        case Opening::kBxFirstAlpt: CHK((launch_boundary_x<BX_FIRST, true>(h, bx))); break;
+        case Opening::kBxFirst: CHK(launch_boundary_x<BX_FIRST>(h, bx)); break;
+        case Opening::kKickDriftZa:
+          k_kick_drift_za<T, true><<<nblk_stride(h->g.Nhp), 256, 0, h->stream>>>(h->g, C(q0), C(p0), C(g_first), wM,
+                                                                               nullptr, C(h->Ck), 0.5 * eps, eps, c_za, ctl);
+          break;
       }
       HIPCHK(hipGetLastError());
     }
@@ -1665,13 +1626,7 @@ struct Pipe {
       }
       if (h->plan.slots.slot_watch && h->plan.tiled && h->plan.slots.sort_direct && s > 0 && s % kSlotPoll == 0)
         CHK(poll_slots(h, s / kSlotPoll));
-      EvalMode m;
-      m.planes_c2r = planes && (s > 0 || ends);  // Psi^ left by k_step_boundary_x still needs only the (y, z) passes
-      m.planes_r2c = planes && (!last || ends);  // ... and V^ for it gets only those
-      m.alpt_pending = alpt_x;                   // ... or delta(1)^ | Phi^ planes for the ALPT pipeline
-      m.psi_unread = !last;
-      CHK(force_sources(h, true, m, &like_mode, &b));
-      const bool xmode = m.planes_r2c && like_mode == 0;
+      CHK(force_sources(h, true, step_mode(t.f, h->sw, t.p, s, neps), &like_mode, &b));
       if (tap && tap->like_f && last) CHK(tap_loglike(h, tap->like_f));
       StepCtl ctl{h->stop, h->steps_done, s > 0 ? h->guard + (s - 1) : nullptr, guard_limit, s};
       void *qi = cur ? q1 : q0, *pi = cur ? p1 : p0, *qo = cur ? q0 : q1, *po = cur ? p0 : p1;
@@ -1679,25 +1634,26 @@ struct Pipe {
       BoundaryX<T> bx;  // the interior boundary; the last one writes p in place, no q, and leaves the gradient in gk
       bx.qi = C(qi), bx.pi = C(pi), bx.qo = C(qo), bx.po = C(po), bx.wM = wM, bx.a = a, bx.b = b, bx.half_eps = 0.5 * eps;
       bx.eps = eps, bx.c_za = c_za, bx.guard_slot = h->guard + s, bx.ctl = ctl;
-      if (last && xmode) {
-        bx.qo = nullptr, bx.po = C(pi), bx.g_out = C(h->gk);
-        CHK(launch_boundary_x<BX_LAST>(h, bx));
-      } else if (last) {
-        k_step_boundary<T, true><<<nblk_stride(h->g.Nhp), 256, 0, h->stream>>>(
-            h->g, C(h->Ck), C(qi), C(pi), C(qi), C(pi), C(h->gk), h->wS, wM, a, b, like_mode, 0.5 * eps, eps, c_za,
-            h->guard + s, ctl);
-      } else if (xmode && alpt_x) {
-        CHK((launch_boundary_x<BX_INTERIOR, true>(h, bx)));
-        cur ^= 1;
-      } else if (xmode) {
-        CHK(launch_boundary_x(h, bx));
-        cur ^= 1;
-      } else {
-        k_step_boundary<T, false><<<nblk_stride(h->g.Nhp), 256, 0, h->stream>>>(
-            h->g, C(h->Ck), C(qi), C(pi), C(qo), C(po), C(h->gk), h->wS, wM, a, b, like_mode, 0.5 * eps, eps, c_za,
-            h->guard + s, ctl);
-        cur ^= 1;
+      switch (closing(t.f, h->sw, t.p, s, neps, like_mode)) {
+        case Closing::kBxLast:
+          bx.qo = nullptr, bx.po = C(pi), bx.g_out = C(h->gk);
+          CHK(launch_boundary_x<BX_LAST>(h, bx));
+          break;
+        case Closing::kStepBoundaryLast:
+          k_step_boundary<T, true><<<nblk_stride(h->g.Nhp), 256, 0, h->stream>>>(
+              h->g, C(h->Ck), C(qi), C(pi), C(qi), C(pi), C(h->gk), h->wS, wM, a, b, like_mode, 0.5 * eps, eps, c_za,
+              h->guard + s, ctl);
+          break;
+        case Closing::kBxInteriorAlpt: CHK((launch_boundary_x<BX_INTERIOR, true>(h, bx))); break;
+        case Closing::kBxInterior: CHK(launch_boundary_x<BX_INTERIOR>(h, bx)); break;
+        case Closing::kBxInteriorTwoTile: HIPCHK(launch_step_boundary_x2<T>(pass_ctx(h), C(h->Ck), h->wS, bx)); break;
+        case Closing::kStepBoundary:
+          k_step_boundary<T, false><<<nblk_stride(h->g.Nhp), 256, 0, h->stream>>>(
+              h->g, C(h->Ck), C(qi), C(pi), C(qo), C(po), C(h->gk), h->wS, wM, a, b, like_mode, 0.5 * eps, eps, c_za,
+              h->guard + s, ctl);
+          break;
       }
+      if (buffers_flip(s, neps)) cur ^= 1;
       HIPCHK(hipGetLastError());
     }
     {
@@ -1917,7 +1873,7 @@ struct Pipe {
     k_init_ctl<<<1, 1, 0, h->stream>>>(h->stop, h->steps_done, 0ull);  // a stop flag left by an earlier trajectory
     HIPCHK(hipGetLastError());
     CHK(r2c_state(h, h->dstage, h->ioq, h->qk));
-    return initial_force(h, traj_plan(h), h->part6 + 2 * kRedBlocks, nullptr);
+    return initial_force(h, traj(h), h->part6 + 2 * kRedBlocks, nullptr);
   }
   // the same for the plain trajectory (bchmc_leapfrog): no energies, so no -log L partials to keep
   static int plain_prologue(bchmc_handle *h) {
@@ -1925,7 +1881,7 @@ struct Pipe {
     k_init_ctl<<<1, 1, 0, h->stream>>>(h->stop, h->steps_done, 0ull);
     HIPCHK(hipGetLastError());
     CHK(r2c_state(h, h->dstage, h->ioq, h->qk));
-    return initial_force(h, traj_plan(h), nullptr, nullptr);
+    return initial_force(h, traj(h), nullptr, nullptr);
   }
   static bool host_prologue_applies(const bchmc_handle *h, uint64_t neps) {
     return attempt_is_fast(h, neps) && !env_on("BCHMC_NO_UPLOAD_OVERLAP");
@@ -2865,7 +2821,7 @@ int make_tiles(bchmc_handle *h) {
   HIPCHK(hipStreamSynchronize(h->stream));
   TileSwitches sw;
   sw.no_tiles = env_on("BCHMC_NO_TILES");
-  sw.no_tiles_low = env_on("BCHMC_NO_TILES_LOW");
+  sw.no_tiles_low = h->no_tiles_low = env_on("BCHMC_NO_TILES_LOW");
   if (const char *ev = std::getenv("BCHMC_CHUNK")) sw.chunk = std::max(atoi(ev), 1);  // set: the plan clamps it to 64..2048
   if (const char *ev = std::getenv("BCHMC_SORT_CAP")) {
     sw.has_cap = true;
@@ -3021,7 +2977,8 @@ int bchmc_create(const bchmc_config *cfg, bchmc_handle **out) {
     CHK(dev_alloc(h, h->steps_done, (size_t)1));
     HIPCHK(hipMemsetAsync(h->stop, 0, sizeof(int), h->stream));
     HIPCHK(h->h_part.alloc(kRedBlocks));
-    CHK(make_tiles(h));
+    CHK(make_tiles(h));            // reads the tile switches ...
+    h->sw = read_path_switches();  // ... and this the path switches: from here on the environment's do not matter
     HIPCHK(hipStreamSynchronize(h->stream));
     return BCHMC_OK;
   };
@@ -3245,7 +3202,7 @@ int bchmc_probe_displacement_z(bchmc_handle *h, const double *psi, int use_rsd, 
   if (!h || !psi) return BCHMC_ERR_ARG;
   ENTER(h);
   const int rsd = use_rsd < 0 ? h->c.rsd_model : (use_rsd ? 1 : 0);
-  if (const char *why = DISPATCH(h, zbin_why_not(h)))
+  if (const char *why = zbin_why_not_text(zbin_why_not(path_facts(h, h->c.rsd_model), h->sw)))
     return h->fail(BCHMC_ERR_UNSUPPORTED, "the fused z pass + binning does not run on this handle: %s", why);
   if (rsd && !h->c.planepar) return h->fail(BCHMC_ERR_RSD_NOT_PLANEPAR, "non-plane-parallel RSD is not implemented");
   if (with_force) {

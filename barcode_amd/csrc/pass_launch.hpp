@@ -4,7 +4,7 @@
 // whose test (tests/test_gpu_fft_passes.py) thereby runs the engine's launch code and not a copy of it.
 //
 // First part: the arithmetic, plain C++ (no HIP types; tests/host/pass_launch_check.cpp proves it against literals).
-// Second part, for a HIP compile only: the launchers.  Which pass runs when is the engine's business and is not in here.
+// Second part, for a HIP compile only: the launchers.  Which pass runs when is not in here: eval_plan.hpp decides that.
 #pragma once
 
 #include <cstddef>

@@ -2,7 +2,7 @@
 
 Only here do the fp64 512^3 instantiations run inside the engine: k_step_boundary_x<double, 512, 8> on the interior
 boundary, k_ypass<double, 512, 8> inverse, k_zbin_direct<double, 512> and <double, 512, true> with their 53 KB of LDS
-(the hipFuncSetAttribute branch of forward_rest), and with BCHMC_YFWD_F64=1 k_zr2c<double, 512> +
+(above 48 KiB: launch_dyn_lds of pass_launch.hpp raises the kernel's limit first), and with BCHMC_YFWD_F64=1 k_zr2c<double, 512> +
 k_ypass<double, 512, 8, _, false>.  Component 2 of Ck starts 2.2 GB into the array at this size.
 
 A module of its own: the fp64 record array alone is about 69 GB at create, so test_gpu_large.py's fp32 512^3 engine must
