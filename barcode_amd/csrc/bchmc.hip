@@ -139,6 +139,18 @@ struct bchmc_handle {
     std::vector<int> par_bin;                // nbin_par of populated par bin c
     std::vector<double> rsum;                // n_bin * npb sums of rtot
   } corr2;
+  // measure_spec2D (spec2d.hpp): the bin tables of the last n_bin and the sums of ktot on them, kept like corr2's
+  struct Spec2 {
+    uint64_t n_bin = 0;        // the tables below are this bin count's (0: none yet)
+    DevBuf<int> idx;           // rows sorted by perp bin [n^2] | par_start [npb + 1] | perp_slice [n_bin + 1]
+    DevBuf<int2> slices;       // nsl: { first row, rows }
+    DevBuf<double> part;       // nsl * nh
+    DevBuf<double> out;        // n_bin * npb
+    int nsl = 0, npb = 0;
+    std::vector<uint64_t> row_cnt, par_w;  // rows of a perp bin, sum of hw over the run of k of a populated par bin
+    std::vector<int> par_bin;              // nbin_par of populated par bin c
+    std::vector<double> ksum;              // n_bin * npb sums of ktot, filled by the first measurement
+  } spec2;
   // bchmc_interp_upres / bchmc_measure_corr2d_interp (upres.hpp): the fine grid of the last n_out, built on first use,
   // kept for the next call with the same n_out, replaced for another one, freed by bchmc_upres_release.  The work buffer
   // is declared before the execution info and the plans that point at it, like the handle's own.
@@ -844,6 +856,88 @@ int corr2d_setup(bchmc_handle *h, bchmc_handle::Corr2 &c, const Geo &g, uint64_t
   c.n_bin = n_bin;
   c.n = n;
   c.l_max = l_max;
+  return BCHMC_OK;
+}
+
+// measure_spec2D's bin width (2D_powspec.cc:40-43): |k|_max / (N_bin - 1), +infinity for N_bin = 1 (property S2)
+double spec2d_dk(const Geo &g, uint64_t n_bin) {
+#pragma clang fp contract(off)
+  const double knyq = g.kfac * (double)(g.n / 2);
+  const double kmax = std::sqrt(knyq * knyq + knyq * knyq + knyq * knyq);
+  return kmax / (double)(n_bin - 1);
+}
+
+// measure_spec2D's tables for n_bin on the handle's half-complex layout, built when n_bin changes: the rows (i, j) sorted
+// by nbin_perp and cut into slices, the runs of k <= n / 2 that make up the populated par bins, and the mode counts
+// (rows of the perp bin times the Hermitian weights of the run).  The bin indices are computed here exactly as the tool
+// does (IEEE sqrt and divide, no FMA contraction).  Every mode is binned (S2), so every row is in the list and the runs
+// cover 0 .. n / 2.  Synchronises (the tables are uploaded from local vectors).
+int spec2d_setup(bchmc_handle *h, uint64_t n_bin) {
+#pragma clang fp contract(off)
+  auto &c = h->spec2;
+  if (c.n_bin == n_bin) return BCHMC_OK;
+  const Geo &g = h->g;
+  const int n = g.n;
+  const double dk = spec2d_dk(g, n_bin);
+  auto kv = [&](int i) { return (i <= n / 2) ? g.kfac * (double)i : -g.kfac * (double)(n - i); };  // calc_ki
+  HIPCHK(hipStreamSynchronize(h->stream));
+  c.n_bin = 0;
+  // rows by perp bin: a counting sort that keeps the row order inside a bin
+  std::vector<int> perp((size_t)n * n);
+  c.row_cnt.assign(n_bin, 0);
+  for (int i = 0; i < n; i++)
+    for (int j = 0; j < n; j++) {
+      const double kx = kv(i), ky = kv(j);
+      const double kperp = std::sqrt(kx * kx + ky * ky);
+      const unsigned long long b = (unsigned long long)(kperp / dk);
+      if (b >= n_bin) return h->fail(BCHMC_ERR_STATE, "measure_spectrum2d: perp bin %llu of row (%d, %d) >= n_bin", b, i, j);
+      perp[(size_t)i * n + j] = (int)b;
+      c.row_cnt[b]++;
+    }
+  std::vector<int> first(n_bin + 1, 0);
+  for (uint64_t p = 0; p < n_bin; p++) first[p + 1] = first[p] + (int)c.row_cnt[p];
+  std::vector<int> idx((size_t)n * n), fill(first.begin(), first.end() - 1);
+  for (int r = 0; r < n * n; r++) idx[fill[perp[r]]++] = r;
+  // slices of one perp bin: enough workgroups to fill the device, few enough partial rows to keep the reduce short, and
+  // at least kSpecUnroll rows for every wave of a full slice
+  const int per = std::max(kSpecWaves * kSpecUnroll, std::min(256, n * n / 2048));
+  std::vector<int2> slices;
+  std::vector<int> perp_slice(n_bin + 1, 0);
+  for (uint64_t p = 0; p < n_bin; p++) {
+    perp_slice[p] = (int)slices.size();
+    for (int o = 0; o < (int)c.row_cnt[p]; o += per) slices.push_back(make_int2(first[p] + o, std::min(per, (int)c.row_cnt[p] - o)));
+  }
+  perp_slice[n_bin] = (int)slices.size();
+  c.nsl = (int)slices.size();
+  // populated par bins: nbin_par is monotone in k <= n / 2, so every bin is one run of k
+  std::vector<int> par_start;
+  c.par_bin.clear();
+  c.par_w.clear();
+  for (int k = 0; k < g.nh; k++) {
+    const double kz = kv(k);
+    const double kpar = std::sqrt(kz * kz);
+    const unsigned long long b = (unsigned long long)(kpar / dk);
+    if (b >= n_bin) return h->fail(BCHMC_ERR_STATE, "measure_spectrum2d: par bin %llu of k = %d >= n_bin", b, k);
+    if (c.par_bin.empty() || c.par_bin.back() != (int)b) {
+      par_start.push_back(k);
+      c.par_bin.push_back((int)b);
+      c.par_w.push_back(0);
+    }
+    c.par_w.back() += (k == 0 || ((n & 1) == 0 && k == n / 2)) ? 1 : 2;
+  }
+  par_start.push_back(g.nh);
+  c.npb = (int)c.par_bin.size();
+  idx.insert(idx.end(), par_start.begin(), par_start.end());
+  idx.insert(idx.end(), perp_slice.begin(), perp_slice.end());
+  CHK(dev_alloc(h, c.idx, idx.size()));
+  CHK(dev_alloc(h, c.slices, slices.size()));
+  CHK(dev_alloc(h, c.part, (size_t)c.nsl * g.nh));
+  CHK(dev_alloc(h, c.out, (size_t)n_bin * c.npb));
+  HIPCHK(hipMemcpyAsync(c.idx, idx.data(), idx.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(c.slices, slices.data(), slices.size() * sizeof(int2), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));  // idx and slices are local vectors
+  c.ksum.clear();  // filled by the first measurement
+  c.n_bin = n_bin;
   return BCHMC_OK;
 }
 
@@ -2221,6 +2315,58 @@ struct Pipe {
     return fft_exec(h, h->r2c1, h->ioq, h->tC, BCHMC_K_FFT_R2C);
   }
 
+  // ---- measure_spec2D (spec2d.hpp; spec2d_setup has run for n_bin) ----------------------------------------------------
+  template <bool GEOM>
+  static int launch_spec2d(bchmc_handle *h, const CT *xk) {
+    auto &c = h->spec2;
+    const Geo &g = h->g;
+    const int *par_start = c.idx + (size_t)g.n * g.n, *perp_slice = par_start + c.npb + 1;
+    const dim3 grid((unsigned)c.nsl, (unsigned)((g.nh + kSpecChunk - 1) / kSpecChunk));
+    k_spec2d_slices<T, GEOM><<<grid, kSpecChunk * kSpecWaves, 0, h->stream>>>(g, xk, c.idx, c.slices, c.part);
+    k_spec2d_reduce<<<(unsigned)c.n_bin, 256, (size_t)g.nh * sizeof(double), h->stream>>>(g.n, g.nh, c.part, perp_slice,
+                                                                                          par_start, c.npb, c.out);
+    HIPCHK(hipGetLastError());
+    return BCHMC_OK;
+  }
+
+  // kmode, nmode (may be null) and power of the half-complex transform xk_T: arrays of n_bin^2, element
+  // par + n_bin * perp (2D_powspec.cc:94), normalised like :102-109.  One synchronise.
+  static int spec2d_bins(bchmc_handle *h, const void *xk_T, uint64_t n_bin, double *kmode, uint64_t *nmode, double *power) {
+    auto &c = h->spec2;
+    const Geo &g = h->g;
+    const CT *xk = reinterpret_cast<const CT *>(xk_T);
+    const size_t nb = (size_t)n_bin, cells = nb * c.npb;
+    const bool geom = c.ksum.empty();
+    std::vector<double> hb(cells), hk(geom ? cells : 0);
+    {
+      ProfScope ps(h, BCHMC_K_OTHER);
+      if (geom) {
+        CHK(launch_spec2d<true>(h, xk));
+        HIPCHK(hipMemcpyAsync(hk.data(), c.out, cells * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+      }
+      CHK(launch_spec2d<false>(h, xk));
+      HIPCHK(hipMemcpyAsync(hb.data(), c.out, cells * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    }
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (geom) c.ksum.swap(hk);
+    std::memset(kmode, 0, nb * nb * sizeof(double));
+    std::memset(power, 0, nb * nb * sizeof(double));
+    if (nmode) std::memset(nmode, 0, nb * nb * sizeof(uint64_t));
+    const double N = (double)g.N;
+    const double NORM = g.L * g.L * g.L / (4. * M_PI) / (N * N);  // 2D_powspec.cc:32, the 1 / (4 pi) included (S1)
+    for (size_t p = 0; p < nb; p++) {
+      if (!c.row_cnt[p]) continue;
+      for (int q = 0; q < c.npb; q++) {
+        const uint64_t nm = c.row_cnt[p] * c.par_w[q];
+        const size_t ii = (size_t)c.par_bin[q] + nb * p;
+        if (nmode) nmode[ii] = nm;
+        kmode[ii] = c.ksum[p * c.npb + q] / (double)nm;
+        power[ii] = NORM * hb[p * c.npb + q] / (double)nm;
+      }
+    }
+    return BCHMC_OK;
+  }
+
   static int gradient(bchmc_handle *h, const double *d_q, double *d_g) {
     const size_t N = (size_t)h->g.N;
     if (!h->gprior) {
@@ -3495,6 +3641,23 @@ int bchmc_measure_spectrum_src(bchmc_handle *h, bchmc_corr_source src, const dou
   const void *xk = nullptr;
   CHK(DISPATCH(h, spectrum_source(h, (int)src, &xk)));
   return spectrum_bins(h, xk, n_bin, kmode, power);
+}
+
+int bchmc_measure_spectrum2d(bchmc_handle *h, bchmc_corr_source src, const double *signal, uint64_t n_bin, double *kmode,
+                             uint64_t *nmode, double *power) {
+  if (!h || !kmode || !power) return BCHMC_ERR_ARG;
+  const char *name = "measure_spectrum2d";
+  if (n_bin == 0 || n_bin > 2048) return h->fail(BCHMC_ERR_ARG, "%s: n_bin = %llu outside 1..2048", name, (unsigned long long)n_bin);
+  CHK(source_args(h, name, src, signal));
+  ENTER(h);
+  CHK(source_state(h, src));
+  // the reduce kernel keeps a row's nh column sums in LDS and the tables are sized like the correlation functions'
+  if (h->g.n > 1024) return h->fail(BCHMC_ERR_UNSUPPORTED, "%s: n = %d > 1024", name, h->g.n);
+  CHK(spec2d_setup(h, n_bin));
+  if (signal) CHK(h2d(h, h->dstage, signal, h->g.N * sizeof(double)));
+  const void *xk = nullptr;
+  CHK(DISPATCH(h, spectrum_source(h, (int)src, &xk)));
+  return DISPATCH(h, spec2d_bins(h, xk, n_bin, kmode, nmode, power));
 }
 
 int bchmc_chain_forward(bchmc_handle *h, int use_rsd) {

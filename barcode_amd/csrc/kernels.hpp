@@ -23,6 +23,7 @@
 #include "alpt.hpp"  // ALPT displacement (Lag2Eul_non_zeldovich)
 #include "spectrum.hpp"  // measure_spectrum
 #include "corr.hpp"  // measure_corr_grid / measure_corr2D: |x^|^2, integer LDS histogram (1-D), sorted-row slices (2-D)
+#include "spec2d.hpp"  // measure_spec2D: sorted-row slices over chunks of k, Hermitian-weighted reduce
 #include "upres.hpp"  // interp_field (CIC gather onto another grid) and the zero-padded power spectrum of 2D_corr_fct_interp.cc
 #include "mock.hpp"  // setup_random_test / make_initial_guess: window, rank of windowed cells on the stream, noise, guesses
 #include "mass.hpp"  // Hamiltonian_mass: element-wise masses and the Jasche+13 first-order diagonal

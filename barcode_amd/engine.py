@@ -94,6 +94,7 @@ EXPORTS = ("bchmc_create", "bchmc_destroy", "bchmc_strerror", "bchmc_last_error"
 # declared as well, listed apart: the header scan of the ABI test matches names of letters and underscores only
 EXPORTS_MT19937 = ("bchmc_chain_draw_momenta_mt19937", "bchmc_mt19937_jump")
 EXPORTS_CORR2D = ("bchmc_measure_corr2d", "bchmc_measure_corr2d_interp")  # a digit in the name, like the two above
+EXPORTS_SPEC2D = ("bchmc_measure_spectrum2d",)  # likewise
 
 # bchmc_corr_source
 CORR_SOURCES = dict(host=0, chain=1, deltaX=2)
@@ -153,6 +154,7 @@ def load():
                                                 C.POINTER(u64), dp]
     lib.bchmc_upres_release.argtypes = [vp]
     lib.bchmc_measure_spectrum_src.argtypes = [vp, C.c_int, dp, C.c_uint64, dp, dp]
+    lib.bchmc_measure_spectrum2d.argtypes = [vp, C.c_int, dp, C.c_uint64, dp, C.POINTER(u64), dp]
     lib.bchmc_chain_forward.argtypes = [vp, C.c_int]
     lib.bchmc_probe_displacement.argtypes = [vp, dp, C.c_int, C.c_int]
     lib.bchmc_probe_displacement_z.argtypes = [vp, dp, C.c_int, C.c_int, C.c_int]
@@ -499,6 +501,22 @@ class Engine:
             self._chk(self.lib.bchmc_measure_spectrum_src(self.h, CORR_SOURCES[source], sig, int(n_bin), _p(kmode),
                                                           _p(power)))
         return kmode, power
+
+    def measure_spectrum2d(self, signal=None, n_bin=200, source=None):
+        """measure_spec2D (tools/2D_powspec.cc:25-110), plane-parallel along z: the anisotropic power spectrum of a host
+        field, of the resident chain state (the default without a signal) or of the handle's deltaX, sources as in
+        ``measure_corr``.  Returns (kmode, nmode, power) shaped (n_bin, n_bin) with k_perp as the first axis (the tool's
+        element ``par + n_bin * perp``); kmode is the mean 3-D |k| of a bin."""
+        if source is None:
+            source = "chain" if signal is None else "host"
+        n_bin = int(n_bin)
+        size = n_bin ** 2 if 1 <= n_bin <= 2048 else 1  # out of range: the library refuses before it writes
+        kmode, power, nmode = np.empty(size), np.empty(size), np.empty(size, dtype=np.uint64)
+        sig = None if signal is None else _p(self._in(signal))
+        self._chk(self.lib.bchmc_measure_spectrum2d(self.h, CORR_SOURCES[source], sig, n_bin, _p(kmode),
+                                                    nmode.ctypes.data_as(C.POINTER(C.c_uint64)), _p(power)))
+        shape = (n_bin, n_bin)
+        return kmode.reshape(shape), nmode.reshape(shape), power.reshape(shape)
 
     def _measure_corr(self, fn, cells, signal, n_bin, source):
         if source is None:

@@ -153,6 +153,14 @@ def measure_corr2D(hd, signal=None, N_bin=0, source=None, planepar=True):
     return hd.engine.measure_corr2d(signal, N_bin, source)
 
 
+def measure_spec2D(hd, signal=None, N_bin=200, source=None, planepar=True):
+    """tools/2D_powspec.cc:25-110 -> (kmode, nmode, power) shaped (N_bin, N_bin), k_perp first.  ``signal`` None = the
+    resident chain state, or with ``source="deltaX"`` the density of the last forward model."""
+    if not planepar:
+        raise RuntimeError("non-plane-parallel option not yet implemented")  # 2D_powspec.cc:71
+    return hd.engine.measure_spectrum2d(signal, N_bin, source)
+
+
 def Hamiltonian_mass(hd, signal=None):
     """HMC_mass.cc:315-368 on the device at ``signal`` (None: the resident chain state); the engine takes the new mass
     as if it had been uploaded.  Returns (mass_f, mass_r), None where the mass_type has none."""

@@ -4,6 +4,7 @@
   (``barlib/src/IOfunctionsGen.cc:185-229``), including the ``.dat`` extension rule (`add_extension_if_missing`).
 * Correlation-function tools: ``<name>_r`` / ``<name>_eta`` as such arrays (``tools/2D_corr_fct.cc:283-303``), and
   ``dump_deltas``' deltaLAG / deltaRSS / deltaEUL fields (``IOfunctionsGen.cc:136-171``).
+* ``tools/2D_powspec.cc``: ``<name>_k`` / ``<name>_P`` as such arrays (:162-163).
 * ``performance_log.txt``: one tab-separated row of 14 columns per attempt (``HMC.cc:40-60``) under the header
   written by ``barcoderunner.cc:357-358``.
 """
@@ -122,6 +123,22 @@ def dump_pow(fname_in, kmode, power):
     name = pow_filename(fname_in)
     dump_measured_spec(kmode, power, name)
     return name
+
+
+def pow2d_filenames(fname_in, fname_out=None):
+    """The two files of ``tools/2D_powspec.cc:130,162-163`` (before ``write_array``'s extension rule): ``<out>_k`` and
+    ``<out>_P``, ``<out>`` defaulting to ``<in>_pow2D``."""
+    base = fname_in + "_pow2D" if fname_out is None else fname_out
+    return base + "_k", base + "_P"
+
+
+def dump_pow2D(fname_in, kmode, power, fname_out=None):
+    """``dump_scalar(kmode2D, ...)``, ``dump_scalar(power2D, ...)`` of ``2D_powspec.cc``: raw ``real_prec`` arrays of
+    N_bin^2 values, element ``par + N_bin * perp``.  Returns the two paths written."""
+    names = pow2d_filenames(fname_in, fname_out)
+    for name, a in zip(names, (kmode, power)):
+        write_array(name, np.asarray(a))
+    return tuple(add_extension_if_missing(n) for n in names)
 
 
 def dump_deltas(engine, directory, suffix=""):

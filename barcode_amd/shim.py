@@ -27,7 +27,7 @@ SHIM_EXPORTS = ("bchmc_shim_Hamiltonian_EoM", "bchmc_shim_delta_Hamiltonian", "b
                 "bchmc_shim_bootstrap_cleanup", "bchmc_shim_Hamiltonian_mass",
                 "bchmc_shim_setup_random_test", "bchmc_shim_make_initial_guess", "bchmc_shim_sizeof_mock",
                 "bchmc_shim_measure_corr_grid", "bchmc_shim_measure_corr2D", "bchmc_shim_chain_forward",
-                "bchmc_shim_interp_field", "bchmc_shim_measure_corr2D_interp")
+                "bchmc_shim_interp_field", "bchmc_shim_measure_corr2D_interp", "bchmc_shim_measure_spec2D")
 
 _dp = C.POINTER(C.c_double)
 
@@ -125,6 +125,7 @@ def load():
     lib.bchmc_shim_interp_field.argtypes = [hv, _dp, C.c_uint, _dp, C.c_int, C.c_char_p, sz]
     lib.bchmc_shim_measure_corr2D_interp.argtypes = [hv, _dp, C.c_uint, C.c_uint, C.c_double, ul, _dp, C.POINTER(ul), _dp,
                                                      C.c_int, C.c_int, C.c_char_p, sz]
+    lib.bchmc_shim_measure_spec2D.argtypes = [hv, _dp, _dp, _dp, ul, C.c_int, C.c_int, C.c_char_p, sz]
     lib.bchmc_shim_chain_forward.argtypes = [hv, C.c_int, C.c_char_p, sz]
     lib.bchmc_shim_chain_set_state.argtypes = [hv, _dp, C.c_char_p, sz]
     lib.bchmc_shim_chain_get_state.argtypes = [hv, _dp, C.c_char_p, sz]
@@ -328,6 +329,17 @@ class ShimHamil:
             len(self._err)))
         shape = (int(N_bin),) * 2
         return rm.reshape(shape), nm.reshape(shape), co.reshape(shape)
+
+    def measure_spec2D(self, signal, N_bin=200, planepar=True, of_deltaX=False):
+        """bchmc_shim::measure_spec2D at ``signal`` (None: the resident state, or deltaX) -> (kmode, power) shaped
+        (N_bin, N_bin); the tool returns no mode counts."""
+        size = int(N_bin) ** 2 if 1 <= int(N_bin) <= 2048 else 1  # out of range: refused before anything is written
+        km, pw = np.empty(size), np.empty(size)
+        sig = None if signal is None else _p(self._in(signal))
+        self._chk(self.lib.bchmc_shim_measure_spec2D(C.byref(self.hd), sig, _p(km), _p(pw), int(N_bin),
+                                                     int(bool(planepar)), int(bool(of_deltaX)), self._err, len(self._err)))
+        shape = (int(N_bin),) * 2
+        return km.reshape(shape), pw.reshape(shape)
 
     def chain_forward(self, use_rsd=-1):
         """bchmc_shim::chain_forward: Lag2Eul of the resident state; returns the view's deltaX array."""

@@ -283,6 +283,14 @@ void measure_corr2D_interp(HamilView *hd, const real_prec *signal, unsigned N_ou
   if (rc) fail(h, rc, "measure_corr2D_interp");
 }
 
+void measure_spec2D(HamilView *hd, const real_prec *signal, real_prec *kmode, real_prec *power, ULONG N_bin, bool planepar,
+                    bool of_deltaX) {
+  if (!planepar) throw std::runtime_error("non-plane-parallel option not yet implemented");  // 2D_powspec.cc:71
+  bchmc_handle *h = engine_for(hd);
+  const int rc = bchmc_measure_spectrum2d(h, corr_source(signal, of_deltaX), signal, N_bin, kmode, nullptr, power);
+  if (rc) fail(h, rc, "measure_spec2D");
+}
+
 void chain_forward(HamilView *hd, int use_rsd) {
   bchmc_handle *h = engine_for(hd);
   const int rc = bchmc_chain_forward(h, use_rsd);
@@ -777,6 +785,12 @@ int bchmc_shim_measure_corr2D_interp(bchmc_shim::HamilView *hd, const double *si
   return guarded(err, errlen, [&] {
     bchmc_shim::measure_corr2D_interp(hd, signal, N_out, interp_mode, L_max, N_bin, rmode, nmode, corr, planepar != 0,
                                       of_deltaX != 0);
+  });
+}
+int bchmc_shim_measure_spec2D(bchmc_shim::HamilView *hd, const double *signal, double *kmode, double *power,
+                              unsigned long N_bin, int planepar, int of_deltaX, char *err, size_t errlen) {
+  return guarded(err, errlen, [&] {
+    bchmc_shim::measure_spec2D(hd, signal, kmode, power, N_bin, planepar != 0, of_deltaX != 0);
   });
 }
 int bchmc_shim_chain_forward(bchmc_shim::HamilView *hd, int use_rsd, char *err, size_t errlen) {

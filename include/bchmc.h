@@ -282,6 +282,36 @@ int bchmc_upres_release(bchmc_handle *h); /* frees the fine grid's buffers, plan
  * its errors those of bchmc_measure_corr2d */
 int bchmc_measure_spectrum_src(bchmc_handle *h, bchmc_corr_source src, const double *signal, uint64_t n_bin,
                                double *kmode, double *power);
+/* ---- the anisotropic power spectrum P(k_perp, k_par) (upstream: tools/2D_powspec.cc on a dumped field) ------------------
+ * measure_spec2D (tools/2D_powspec.cc:25-110), plane-parallel, line of sight = z (the axis rsd.cc:52-58 displaces): the
+ * Fourier-space twin of bchmc_measure_corr2d.  kmax = sqrt(3) k_Nyquist, dk = kmax / (n_bin - 1); every mode of the full
+ * complex grid goes to element nbin_par + n_bin * nbin_perp with nbin_perp = (ULONG)(sqrt(kx*kx + ky*ky) / dk) and
+ * nbin_par = (ULONG)(sqrt(kz*kz) / dk), IEEE sqrt and divide and no FMA contraction, so that every mode lands in the bin
+ * the host tool puts it in.  Per bin: kmode = mean |k|, nmode = modes, power = NORM sum |delta^|^2 / nmode with
+ * NORM = L^3 / (4 pi) / N^2; empty bins are 0.  The sums run over the half-complex transform with the Hermitian weight
+ * (1 for k = 0 and the Nyquist column of an even n, 2 otherwise): a mode and its conjugate partner share k_perp, k_par and
+ * |k|, so this is the full-grid sum bin by bin.
+ * Sources, their errors (all checked before anything is queued) and what a call leaves untouched are those of
+ * bchmc_measure_corr2d above; the source's transform is obtained exactly as bchmc_measure_spectrum_src obtains it (the
+ * chain state's q^ is used as it is, without a transform).  n_bin: 1..2048.  Nx <= 1024 (BCHMC_ERR_UNSUPPORTED above).
+ * Arrays of n_bin * n_bin; nmode may be NULL (the tool does not return it).  kmode / nmode depend on the grid and n_bin
+ * only: the bin tables and the sums of |k| are kept in the handle per n_bin (bchmc_live_resources counts the buffers,
+ * bchmc_destroy frees them), so repeated calls with one n_bin sum the power only.  The sums use no atomics and a fixed
+ * order: results are bitwise repeatable on every handle, which bchmc_measure_spectrum's are not.  fp32 handles: the
+ * transform in float, |delta^|^2 and the sums in double.  A field that is not finite gives NaN power in every populated
+ * bin (kmode and nmode are unaffected); a zero field gives 0.
+ * Four properties of the upstream tool:
+ *  S1 (kept) NORM carries a 1 / (4 pi) that measure_spectrum's L^3 / N^2 does not; upstream marks it "TODO: check"
+ *     (2D_powspec.cc:32-35).  Kept bug for bug: the power of one field through the two entry points differs by that
+ *     factor, apart from the binning.
+ *  S2 (kept) dk = kmax / (n_bin - 1), not / n_bin as in measure_spectrum.  k_perp <= sqrt(2) k_Nyquist and
+ *     k_par <= k_Nyquist are both below kmax, so the tool's bound test never fires: every mode is binned, sum nmode = N
+ *     (unlike C1 there is no out-of-range cell), and the top perp bin and the top par bin are always empty.  With
+ *     n_bin = 1, dk = +infinity and every mode lands in bin 0.
+ *  S3 (immaterial) ky comes from calc_kz(j, L2, N2) (2D_powspec.cc:59); on a cubic box that is the same number.
+ *  S4 kmode is the mean 3-D |k| of the bin's modes, not a (k_perp, k_par) pair. */
+int bchmc_measure_spectrum2d(bchmc_handle *h, bchmc_corr_source src, const double *signal, uint64_t n_bin, double *kmode,
+                             uint64_t *nmode, double *power);
 /* Lag2Eul of the resident chain state: bchmc_forward without the host array (it starts from the chain's q^, so no field
  * crosses PCIe and no transform pair is spent).  use_rsd as there.  Leaves deltaX / pos* in the handle, synchronises and
  * adapts the binning's record slots like bchmc_forward; drops a pending proposal like it.  The chain state, the momenta

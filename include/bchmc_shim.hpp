@@ -14,6 +14,8 @@
 //   void gradient_psi(HAMIL_DATA*, real_prec* signal, DATA*)          HMC.cc:146-206   -> bchmc_shim::gradient_psi
 //   real_prec kinetic_term(...), real_prec psi(...)                   HMC.cc:64-143    -> bchmc_shim::kinetic_term, psi
 //   void measure_spectrum(...)                      field_statistics.cpp:20-90         -> bchmc_shim::measure_spectrum
+//   void measure_spec2D(N1, N2, N3, L1, L2, L3, signal, kmode, power, N_bin, planepar)
+//                                                   tools/2D_powspec.cc:25-110         -> bchmc_shim::measure_spec2D
 // Errors are std::runtime_error, like the reference's (single catch in main.cc:195-197).
 #ifndef BCHMC_SHIM_HPP
 #define BCHMC_SHIM_HPP
@@ -133,6 +135,11 @@ void interp_field(HamilView *hd, const real_prec *signal, unsigned N_out, real_p
 void measure_corr2D_interp(HamilView *hd, const real_prec *signal, unsigned N_out, unsigned interp_mode, real_prec L_max,
                            ULONG N_bin, real_prec *rmode, ULONG *nmode, real_prec *corr, bool planepar = true,
                            bool of_deltaX = false);
+// tools/2D_powspec.cc:25-110 on the device: the anisotropic power spectrum P(k_perp, k_par), sources as above.  kmode /
+// power: N_bin * N_bin values, element nbin_par + N_bin * nbin_perp, kmode the mean 3-D |k| of the bin; the tool returns
+// no mode counts (bchmc_measure_spectrum2d does).  planepar == false throws like upstream.
+void measure_spec2D(HamilView *hd, const real_prec *signal, real_prec *kmode, real_prec *power, ULONG N_bin,
+                    bool planepar = true, bool of_deltaX = false);
 // Lag2Eul of the resident chain state (dump_deltas' second forward model, IOfunctionsGen.cc:158-169, with use_rsd = 0);
 // hd->deltaX / pos* <- this evaluation's.  use_rsd < 0: as configured.
 void chain_forward(HamilView *hd, int use_rsd);
@@ -275,6 +282,8 @@ int bchmc_shim_interp_field(bchmc_shim::HamilView *hd, const double *signal, uns
 int bchmc_shim_measure_corr2D_interp(bchmc_shim::HamilView *hd, const double *signal, unsigned N_out, unsigned interp_mode,
                                      double L_max, unsigned long N_bin, double *rmode, unsigned long *nmode, double *corr,
                                      int planepar, int of_deltaX, char *err, size_t errlen);
+int bchmc_shim_measure_spec2D(bchmc_shim::HamilView *hd, const double *signal, double *kmode, double *power,
+                              unsigned long N_bin, int planepar, int of_deltaX, char *err, size_t errlen);
 int bchmc_shim_chain_forward(bchmc_shim::HamilView *hd, int use_rsd, char *err, size_t errlen);
 int bchmc_shim_chain_set_state(bchmc_shim::HamilView *hd, const double *x, char *err, size_t errlen);
 int bchmc_shim_chain_get_state(bchmc_shim::HamilView *hd, double *x, char *err, size_t errlen);
