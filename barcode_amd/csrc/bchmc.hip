@@ -20,6 +20,7 @@
 #include <algorithm>
 #include <chrono>
 #include <cmath>
+#include <cfloat>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -165,6 +166,19 @@ struct bchmc_handle {
     DevBuf<double> dx;         // n_out
     Corr2 bins;                // the 2-D bin tables on the fine grid, keyed by (n_out, n_bin, l_max)
   } up;
+  // bchmc_density_particles (catalogue.hpp): one batch of kCatBatch particles at a time -- the staged columns, the tile of
+  // every particle, the tile-ordered records, the populations, offsets and fill cursors of the tiles, the work items and
+  // the status words with their pinned mirror.  Built by the first call, kept for the next, freed by
+  // bchmc_catalogue_release and bchmc_destroy.
+  struct Cat {
+    DevBuf<double> cols;                 // 4 kCatBatch: x | y | z | w
+    DevBuf<int> tile_of;                 // kCatBatch
+    DevBuf<CatRec> rec;                  // kCatBatch
+    DevBuf<unsigned> cnt, off, cursor;   // ntiles, ntiles + 1, ntiles
+    DevBuf<CatItem> items;               // ntiles + kCatBatch / chunk + 1
+    DevBuf<unsigned long long> stat;     // kCatWords
+    PinnedBuf<unsigned long long> h_stat;
+  } cat;
   // host-array entry points: caller arrays are pageable, so they cross PCIe through two pinned staging chunks
   // (N-thread memcpy into one chunk while the DMA of the other is in flight)
   PinnedBuf<void> stg[2];
@@ -1047,6 +1061,15 @@ int upres_setup(bchmc_handle *h, int n_out) {
 // ======================================================================================================
 // The pipeline, for storage type T
 // ======================================================================================================
+// What bchmc_density_particles asks of the pipe, after its checks: the source, the kernel and scale length in force, the
+// largest |w| (1 without weights), the caller's columns
+struct CatCall {
+  int src, mk, weighted, dest;
+  double hh, max_w;
+  const double *x, *y, *z, *w;
+  uint64_t n_part;
+};
+
 template <typename T>
 struct Pipe {
   using CT = C2<T>;
@@ -2687,6 +2710,152 @@ struct Pipe {
     HIPCHK(hipStreamSynchronize(h->stream));  // `power` is a local vector
     return BCHMC_OK;
   }
+
+  // ---- bchmc_density_particles (catalogue.hpp) ---------------------------------------------------------------------
+  template <int MK, bool FIX>
+  static void cat_launch(bchmc_handle *h, const SphPar &sp, bool tiled, int H, size_t lds, int m, const double *w,
+                         double fix_scale) {
+    using Cell = typename CatCell<FIX>::type;
+    auto &c = h->cat;
+    Cell *acc = reinterpret_cast<Cell *>(h->dstage + h->g.N);
+    const double *x = c.cols, *y = x + kCatBatch, *z = y + kCatBatch;
+    if (tiled) {
+      const int grid = h->plan.tp.ntiles + m / h->plan.tp.chunk + 1;  // upper bound on the work items of this batch
+      k_cat_scatter<T, MK, FIX><<<grid, 256, lds, h->stream>>>(h->g, sp, h->plan.tp, H, c.items, c.stat, c.rec, acc, fix_scale);
+    } else {
+      k_cat_direct<T, MK, FIX><<<nblk_full(m), 256, 0, h->stream>>>(h->g, sp, m, x, y, z, w, acc, fix_scale, c.stat);
+    }
+  }
+
+  // The whole call after its arguments were checked: batches of kCatBatch particles through count / scan / fill /
+  // scatter (or the direct kernel) into an accumulator in the upper half of the transfer staging, then the ABI's doubles
+  // in its lower half, from where they go to the host and, for dest = nobs, through upload() like a host array.
+  static int density_particles(bchmc_handle *h, const CatCall &cc, double *out, bchmc_density_stats *stats) {
+    auto &c = h->cat;
+    const Geo &g = h->g;
+    const TilePar &tp = h->plan.tp;
+    SphPar sp = make_sph(h);
+    sp.h = cc.hh;
+    sp.h_inv = 1. / sp.h;
+    sp.w_norm = 1. / M_PI / (sp.h * sp.h * sp.h);
+    sp.r2_lim = 4. * sp.h * sp.h * (1. + (h->f32 ? 1e-5 : 1e-12));
+    sp.reach = (int)(2. * sp.h / g.d) + 1;
+    // tiles: the handle's partition, where the home cells are those the partition was made for (origin 0) and the image
+    // of the tile and this kernel's halo leaves two workgroups per CU well inside the 160 KiB (64 KiB at most)
+    // SPH: where the stencil hull of this scale length is the standard 81-cell one and exact (h = d and its
+    // neighbourhood down to the 0.8661 d of plan_tiles) the unrolled hull kernel with the hull's halo, 2; else the cube
+    bool hull81 = false;
+    if (cc.mk == 3) {
+      const Hull hull = build_hull(sp.h, g.d);
+      hull81 = hull.exact && hull.cols.size() == 21 && hull.max_offset() == 2 && sp.h >= 0.8661 * g.d;
+      for (auto &col : hull.cols) {
+        const int zw = (std::abs(col.x) <= 2 && std::abs(col.y) <= 2) ? hull81_zw(col.x + 2, col.y + 2) : -1;
+        if (zw < 0 || col.z != -zw || col.w != zw) hull81 = false;
+      }
+    }
+    const int H = cc.mk == 0 ? 0 : (cc.mk == 3 ? (hull81 ? 2 : sp.reach) : 1);
+    const bool origin0 = h->c.min1 == 0. && h->c.min2 == 0. && h->c.min3 == 0.;
+    size_t lds = 0;
+    bool tiled = h->plan.tiled && origin0 && H <= g.n;
+    if (tiled) {
+      lds = (size_t)(tp.tx + 2 * H) * (tp.ty + 2 * H) * (tp.tz + 2 * H) * 8;
+      tiled = lds <= 64 * 1024;
+    }
+    // built with the first call, whichever path it takes, so that a later call allocates nothing; all or nothing: a
+    // failed allocation leaves no half-built set behind for the next call to trust
+    if (!c.cols) {
+      auto build = [&]() -> int {
+        CHK(dev_alloc(h, c.cols, 4 * (size_t)kCatBatch));
+        CHK(dev_alloc(h, c.stat, kCatWords));
+        HIPCHK(c.h_stat.alloc(kCatWords));
+        if (!h->plan.tiled) return BCHMC_OK;
+        CHK(dev_alloc(h, c.tile_of, kCatBatch));
+        CHK(dev_alloc(h, c.rec, kCatBatch));
+        CHK(dev_alloc(h, c.cnt, tp.ntiles));
+        CHK(dev_alloc(h, c.off, tp.ntiles + 1));
+        CHK(dev_alloc(h, c.cursor, tp.ntiles));
+        return dev_alloc(h, c.items, (size_t)tp.ntiles + kCatBatch / tp.chunk + 1);
+      };
+      if (const int rc = build()) {
+        h->cat = bchmc_handle::Cat{};
+        return rc;
+      }
+    }
+    const double k_max = cc.mk == 3 ? sp.w_norm : 1.;
+    const double fix_scale = 70368744177664. / ((cc.max_w > 0. ? cc.max_w : 1.) * k_max);  // 2^46 / largest contribution
+    double *acc = h->dstage + g.N;
+    // profiling: per batch the binning (positions, count, scan, fill) is a scope of the sort class and the scatter one of
+    // the scatter class; clearing and conversion go to "other".  The catalogue's way to the device (h2d synchronises on
+    // the host) lies between the scopes
+    {
+      ProfScope ps(h, BCHMC_K_OTHER);
+      HIPCHK(hipMemsetAsync(acc, 0, g.N * sizeof(double), h->stream));
+      HIPCHK(hipMemsetAsync(c.stat, 0, kCatWords * sizeof(unsigned long long), h->stream));
+    }
+    double *x = c.cols, *y = x + kCatBatch, *z = y + kCatBatch, *w = cc.weighted ? z + kCatBatch : nullptr;
+    const PosPar pp = make_pos(h, h->last_rsd);
+    for (uint64_t p0 = 0; p0 < cc.n_part; p0 += kCatBatch) {
+      const int m = (int)std::min<uint64_t>(kCatBatch, cc.n_part - p0);
+      if (cc.src != BCHMC_PART_FORWARD) {
+        CHK(h2d(h, x, cc.x + p0, m * sizeof(double)));
+        CHK(h2d(h, y, cc.y + p0, m * sizeof(double)));
+        CHK(h2d(h, z, cc.z + p0, m * sizeof(double)));
+        if (w) CHK(h2d(h, w, cc.w + p0, m * sizeof(double)));
+      }
+      if (cc.src == BCHMC_PART_FORWARD || tiled) {
+        ProfScope ps(h, BCHMC_K_SORT);
+        if (cc.src == BCHMC_PART_FORWARD)
+          k_cat_positions<T><<<nblk_full(m), 256, 0, h->stream>>>(g, pp, R(h->psi), (long long)p0, m, x, y, z);
+        if (tiled) {
+          HIPCHK(hipMemsetAsync(c.cnt, 0, tp.ntiles * sizeof(unsigned), h->stream));
+          k_cat_count<T><<<nblk_full(m), 256, 0, h->stream>>>(g, sp, tp, cc.mk, m, x, y, z, c.tile_of, c.cnt, c.stat);
+          k_cat_scan<<<1, 1024, 0, h->stream>>>(tp.ntiles, tp.chunk, c.cnt, c.off, c.cursor, c.items, c.stat);
+          k_cat_fill<T><<<nblk_full(m), 256, 0, h->stream>>>(m, x, y, z, w, c.tile_of, c.off, c.cursor, c.rec);
+        }
+        HIPCHK(hipGetLastError());
+      }
+      ProfScope ps(h, BCHMC_K_SCATTER);
+#define BCHMC_CAT_MK(MK)                                                          \
+  if (h->fix) cat_launch<MK, true>(h, sp, tiled, H, lds, m, w, fix_scale);       \
+  else cat_launch<MK, false>(h, sp, tiled, H, lds, m, w, fix_scale)
+      switch (cc.mk) {
+        case 0: BCHMC_CAT_MK(0); break;
+        case 1: BCHMC_CAT_MK(1); break;
+        case 2: BCHMC_CAT_MK(2); break;
+        default:
+          if (hull81) { BCHMC_CAT_MK(kCatSph81); }
+          else { BCHMC_CAT_MK(3); }
+          break;
+      }
+#undef BCHMC_CAT_MK
+      HIPCHK(hipGetLastError());
+    }
+    {
+      ProfScope ps(h, BCHMC_K_OTHER);
+      if (h->fix)
+        k_cat_finish<true><<<nblk_stride(g.N), 256, 0, h->stream>>>(g.N, reinterpret_cast<long long *>(acc), 1. / fix_scale,
+                                                                    h->fix_sat_limit, h->dstage, c.stat);
+      else
+        k_cat_finish<false><<<nblk_stride(g.N), 256, 0, h->stream>>>(g.N, acc, 1., 0, h->dstage, c.stat);
+      HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipMemcpyAsync(c.h_stat, c.stat, kCatWords * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (c.h_stat[kCatSat])
+      return h->fail(BCHMC_ERR_STATE, "density_particles: a fixed-point cell passed 2^16 maximal contributions "
+                                      "(deterministic mode); nothing was written");
+    if (stats) {
+      stats->n_in = c.h_stat[kCatIn];
+      stats->n_lost = cc.n_part - c.h_stat[kCatIn];
+      stats->max_per_tile = c.h_stat[kCatMaxTile];
+    }
+    if (out) CHK(d2h(h, out, h->dstage, g.N * sizeof(double)));
+    if (cc.dest == BCHMC_F_NOBS) {
+      CHK(upload(h, BCHMC_F_NOBS, h->dstage));
+      HIPCHK(hipStreamSynchronize(h->stream));
+    }
+    return BCHMC_OK;
+  }
 };
 
 #define DISPATCH(h, call) ((h)->f32 ? Pipe<float>::call : Pipe<double>::call)
@@ -3658,6 +3827,94 @@ int bchmc_measure_spectrum2d(bchmc_handle *h, bchmc_corr_source src, const doubl
   const void *xk = nullptr;
   CHK(DISPATCH(h, spectrum_source(h, (int)src, &xk)));
   return DISPATCH(h, spec2d_bins(h, xk, n_bin, kmode, nmode, power));
+}
+
+// max|w| and the first non-finite weight (*bad, -1: none) in one pass over the column, on the threads the staging copies
+// use: it costs a read of 8 B per particle beside the 32 B the transfer reads
+static double weights_pass(const double *w, uint64_t n, long long *bad) {
+  const int nt = n < (1u << 20) ? 1 : (int)std::min(8u, std::max(1u, std::thread::hardware_concurrency() / 2));
+  std::vector<double> mx(nt, 0.);
+  std::vector<long long> first(nt, -1);
+  auto run = [&](int t) {
+    const uint64_t b = n * t / nt, e = n * (t + 1) / nt;
+    double m = 0.;
+    for (uint64_t p = b; p < e; p++) {
+      const double a = std::fabs(w[p]);
+      if (!(a <= DBL_MAX)) {
+        first[t] = (long long)p;
+        break;
+      }
+      m = a > m ? a : m;
+    }
+    mx[t] = m;
+  };
+  std::vector<std::thread> th;
+  for (int t = 1; t < nt; t++) th.emplace_back(run, t);
+  run(0);
+  for (auto &t : th) t.join();
+  double m = 0.;
+  *bad = -1;
+  for (int t = nt - 1; t >= 0; t--) {
+    m = std::max(m, mx[t]);
+    if (first[t] >= 0) *bad = first[t];
+  }
+  return m;
+}
+
+int bchmc_density_particles(bchmc_handle *h, bchmc_part_source src, const double *x, const double *y, const double *z,
+                            const double *w, uint64_t n_part, const bchmc_density_opts *opts, double *out,
+                            bchmc_density_stats *stats) {
+  if (!h || !opts) return BCHMC_ERR_ARG;
+  const char *name = "density_particles";
+  if (src != BCHMC_PART_HOST && src != BCHMC_PART_FORWARD) return h->fail(BCHMC_ERR_ARG, "%s: unknown source %d", name, (int)src);
+  if (src == BCHMC_PART_HOST && n_part > 0 && (!x || !y || !z))
+    return h->fail(BCHMC_ERR_ARG, "%s: x, y and z must be given for BCHMC_PART_HOST", name);
+  if (src == BCHMC_PART_FORWARD && (x || y || z || w))
+    return h->fail(BCHMC_ERR_ARG, "%s: x, y, z and w must be NULL for BCHMC_PART_FORWARD", name);
+  if (opts->weightmass != 0 && opts->weightmass != 1)
+    return h->fail(BCHMC_ERR_ARG, "%s: weightmass = %d is neither 0 nor 1", name, (int)opts->weightmass);
+  const bool weighted = opts->weightmass == 1 && src == BCHMC_PART_HOST;
+  if (weighted && !w && n_part > 0) return h->fail(BCHMC_ERR_ARG, "%s: weightmass = 1 without w", name);
+  if (opts->mk < -1 || opts->mk > 3) return h->fail(BCHMC_ERR_ARG, "%s: mk = %d outside -1..3", name, (int)opts->mk);
+  const int mk = opts->mk < 0 ? h->c.mk : opts->mk;
+  if (!(opts->kernel_h >= 0.) || !std::isfinite(opts->kernel_h) || opts->kernel_h > h->g.L / 4)
+    return h->fail(BCHMC_ERR_ARG, "%s: kernel_h = %g is negative, not finite or above L / 4", name, opts->kernel_h);
+  const double hh = opts->kernel_h > 0. ? opts->kernel_h : h->c.particle_kernel_h;
+  if (mk == 3 && !(hh > 0. && hh <= h->g.L / 4))
+    return h->fail(BCHMC_ERR_ARG, "%s: the handle's particle_kernel_h = %g is not in (0, L / 4]", name, hh);
+  if (opts->dest != -1 && opts->dest != BCHMC_F_NOBS)
+    return h->fail(BCHMC_ERR_ARG, "%s: dest = %d is neither -1 nor BCHMC_F_NOBS", name, (int)opts->dest);
+  if (!out && opts->dest == -1) return h->fail(BCHMC_ERR_ARG, "%s: no destination (out is NULL and dest is -1)", name);
+  if (n_part > 2147483647ull) return h->fail(BCHMC_ERR_ARG, "%s: n_part = %llu > 2^31 - 1", name, (unsigned long long)n_part);
+  if (mk == 3 && (h->c.min1 < 0. || h->c.min2 < 0. || h->c.min3 < 0.))
+    return h->fail(BCHMC_ERR_UNSUPPORTED, "%s: getDensity_SPH casts x / d to an unsigned index, undefined below 0 "
+                                          "(min = %g, %g, %g)", name, h->c.min1, h->c.min2, h->c.min3);
+  if (src == BCHMC_PART_FORWARD && !h->have_eval)
+    return h->fail(BCHMC_ERR_STATE, "%s: no forward evaluation to take the particles from", name);
+  if (src == BCHMC_PART_FORWARD) n_part = (uint64_t)h->g.N;
+  // the weights' own pass: a non-finite one refuses the call, the largest magnitude scales the fixed point
+  double max_w = 1.;
+  if (weighted) {
+    long long bad = -1;
+    max_w = weights_pass(w, n_part, &bad);
+    if (bad >= 0) return h->fail(BCHMC_ERR_ARG, "%s: w[%lld] is not finite", name, bad);
+  }
+  ENTER(h);
+  const CatCall cc{(int)src, mk, weighted ? 1 : 0, (int)opts->dest, hh, max_w, x, y, z, w, n_part};
+  CHK(h->f32 ? Pipe<float>::density_particles(h, cc, out, stats) : Pipe<double>::density_particles(h, cc, out, stats));
+  if (opts->dest == BCHMC_F_NOBS) {  // exactly what bchmc_upload(BCHMC_F_NOBS) does to the handle
+    h->have[BCHMC_F_NOBS] = true;
+    h->cg_valid = h->prop_g_valid = false;
+  }
+  return BCHMC_OK;
+}
+
+int bchmc_catalogue_release(bchmc_handle *h) {
+  if (!h) return BCHMC_ERR_ARG;
+  ENTER(h);
+  HIPCHK(hipStreamSynchronize(h->stream));
+  h->cat = bchmc_handle::Cat{};
+  return BCHMC_OK;
 }
 
 int bchmc_chain_forward(bchmc_handle *h, int use_rsd) {

@@ -56,6 +56,22 @@ class MockOpts(C.Structure):
                 ("random_test_rsd", C.c_int32), ("sigma_min", C.c_double), ("sigma_fac", C.c_double)]
 
 
+class DensityOpts(C.Structure):
+    """bchmc_density_opts: kernel, weights, SPH scale length and destination of bchmc_density_particles."""
+    _fields_ = [("mk", C.c_int32), ("weightmass", C.c_int32), ("kernel_h", C.c_double), ("dest", C.c_int32),
+                ("reserved0", C.c_int32)]
+
+
+class DensityStats(C.Structure):
+    """bchmc_density_stats."""
+    _fields_ = [("n_in", C.c_uint64), ("n_lost", C.c_uint64), ("max_per_tile", C.c_uint64)]
+
+
+# bchmc_part_source
+PART_SOURCES = dict(host=0, forward=1)
+F_NOBS = 3  # BCHMC_F_NOBS
+
+
 # which mass arrays a mass_type has (struct_hamil.h:272-313)
 MASS_F_TYPES = (1, 2, 3, 4, 5)
 MASS_R_TYPES = (0, 5, 6, 60)
@@ -90,7 +106,8 @@ EXPORTS = ("bchmc_create", "bchmc_destroy", "bchmc_strerror", "bchmc_last_error"
            "bchmc_comm_last_error", "bchmc_eps_exchange", "bchmc_comm_pending", "bchmc_comm_world", "bchmc_comm_rank",
            "bchmc_comm_transport", "bchmc_garfield_walk_index", "bchmc_hamiltonian_mass",
            "bchmc_setup_random_test", "bchmc_make_initial_guess", "bchmc_measure_corr", "bchmc_chain_forward",
-           "bchmc_probe_displacement", "bchmc_probe_displacement_z", "bchmc_interp_upres", "bchmc_upres_release", "bchmc_measure_spectrum_src")
+           "bchmc_probe_displacement", "bchmc_probe_displacement_z", "bchmc_interp_upres", "bchmc_upres_release", "bchmc_measure_spectrum_src",
+           "bchmc_density_particles", "bchmc_catalogue_release")
 # declared as well, listed apart: the header scan of the ABI test matches names of letters and underscores only
 EXPORTS_MT19937 = ("bchmc_chain_draw_momenta_mt19937", "bchmc_mt19937_jump")
 EXPORTS_CORR2D = ("bchmc_measure_corr2d", "bchmc_measure_corr2d_interp")  # a digit in the name, like the two above
@@ -156,6 +173,9 @@ def load():
     lib.bchmc_measure_spectrum_src.argtypes = [vp, C.c_int, dp, C.c_uint64, dp, dp]
     lib.bchmc_measure_spectrum2d.argtypes = [vp, C.c_int, dp, C.c_uint64, dp, C.POINTER(u64), dp]
     lib.bchmc_chain_forward.argtypes = [vp, C.c_int]
+    lib.bchmc_density_particles.argtypes = [vp, C.c_int, dp, dp, dp, dp, u64, C.POINTER(DensityOpts), dp,
+                                            C.POINTER(DensityStats)]
+    lib.bchmc_catalogue_release.argtypes = [vp]
     lib.bchmc_probe_displacement.argtypes = [vp, dp, C.c_int, C.c_int]
     lib.bchmc_probe_displacement_z.argtypes = [vp, dp, C.c_int, C.c_int, C.c_int]
     lib.bchmc_philox_kat.argtypes = [C.POINTER(C.c_uint32)] * 3
@@ -573,6 +593,34 @@ class Engine:
     def upres_release(self):
         """Frees the fine grid's buffers, plans and tables; a later call rebuilds them."""
         self._chk(self.lib.bchmc_upres_release(self.h))
+
+    def density_particles(self, x=None, y=None, z=None, w=None, mk=None, kernel_h=0.0, to_nobs=False, source="host",
+                          download=True):
+        """getDensity_NGP / _CIC / _TSC / _SPH (massFunctions.cc:49-495) of a free particle catalogue on the device: the raw
+        density of the particles (x, y, z), each counting ``w[p]`` (1 without ``w``), on the handle's grid.  ``mk``: 0 NGP,
+        1 CIC, 2 TSC, 3 SPH, None: the handle's.  ``kernel_h``: SPH scale length, 0: the handle's.  ``to_nobs``: the field
+        also becomes the handle's nobs, as if uploaded.  ``source="forward"``: the handle's own particles after the last
+        forward model (no columns).  ``download=False`` (with ``to_nobs``): the field stays on the device, nothing grid-sized
+        crosses PCIe, and rho is None.  Returns (rho, stats), stats = dict(n_in, n_lost, max_per_tile)."""
+        cols = [None if a is None else np.ascontiguousarray(a, dtype=np.float64).reshape(-1) for a in (x, y, z, w)]
+        n_part = 0 if cols[0] is None else cols[0].size
+        for a in cols[1:]:
+            if a is not None and a.size != n_part:
+                raise ValueError("catalogue columns differ in length")
+        opts = DensityOpts(-1 if mk is None else int(mk), 0 if w is None else 1, float(kernel_h),
+                           F_NOBS if to_nobs else -1, 0)
+        st = DensityStats()
+        if not download and not to_nobs:
+            raise ValueError("download=False leaves the field nowhere unless to_nobs is set")
+        out = np.empty(self.N) if download else None
+        ptr = [None if a is None else _p(a) for a in cols]
+        self._chk(self.lib.bchmc_density_particles(self.h, PART_SOURCES[source], ptr[0], ptr[1], ptr[2], ptr[3], n_part,
+                                                   C.byref(opts), None if out is None else _p(out), C.byref(st)))
+        return out, dict(n_in=int(st.n_in), n_lost=int(st.n_lost), max_per_tile=int(st.max_per_tile))
+
+    def catalogue_release(self):
+        """Frees the catalogue buffers of ``density_particles``; a later call rebuilds them."""
+        self._chk(self.lib.bchmc_catalogue_release(self.h))
 
     def chain_forward(self, rsd=-1):
         """Lag2Eul of the resident chain state: ``forward(chain_get_state(), rsd)`` without the field leaving the

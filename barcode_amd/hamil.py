@@ -161,6 +161,17 @@ def measure_spec2D(hd, signal=None, N_bin=200, source=None, planepar=True):
     return hd.engine.measure_spectrum2d(signal, N_bin, source)
 
 
+def getDensity(hd, mk, xp, yp, zp, Par_mass=None, weightmass=False, kernel_h=0.0, to_nobs=False):
+    """getDensity_NGP / _CIC / _TSC / _SPH (massFunctions.cc:49-495; ``mk`` 0 .. 3 picks the one, None the handle's) of a
+    free particle list on ``hd``'s grid, upstream's argument order from ``xp`` on -> (delta, stats).  ``weightmass``
+    False: every particle counts 1 whatever ``Par_mass`` holds (CIC and SPH upstream; NGP and TSC always read Par_mass
+    there, so pass True with it for those).  ``kernel_h`` 0: the handle's scale length."""
+    w = Par_mass if weightmass else None
+    if weightmass and Par_mass is None:
+        raise ValueError("weightmass without Par_mass")
+    return hd.engine.density_particles(xp, yp, zp, w, mk=mk, kernel_h=kernel_h, to_nobs=to_nobs)
+
+
 def Hamiltonian_mass(hd, signal=None):
     """HMC_mass.cc:315-368 on the device at ``signal`` (None: the resident chain state); the engine takes the new mass
     as if it had been uploaded.  Returns (mass_f, mass_r), None where the mass_type has none."""

@@ -141,6 +141,13 @@ def dump_pow2D(fname_in, kmode, power, fname_out=None):
     return tuple(add_extension_if_missing(n) for n in names)
 
 
+def dump_density(density, fname_out="density"):
+    """``quick_dump_scalar(density, N1, fname_out, 0, false)`` of ``tools/density.cc:84``: the raw array of N values under
+    ``fname_out`` (the tool's default name, ``density``).  Returns the path written."""
+    write_array(fname_out, np.asarray(density))
+    return add_extension_if_missing(fname_out)
+
+
 def dump_deltas(engine, directory, suffix=""):
     """``dump_deltas`` (IOfunctionsGen.cc:136-171) of the resident chain state: deltaLAG, then deltaEUL without
     ``rsd_model``, or deltaRSS (the configured forward model) and deltaEUL (a second Lag2Eul without RSD) with it.

@@ -27,7 +27,8 @@ SHIM_EXPORTS = ("bchmc_shim_Hamiltonian_EoM", "bchmc_shim_delta_Hamiltonian", "b
                 "bchmc_shim_bootstrap_cleanup", "bchmc_shim_Hamiltonian_mass",
                 "bchmc_shim_setup_random_test", "bchmc_shim_make_initial_guess", "bchmc_shim_sizeof_mock",
                 "bchmc_shim_measure_corr_grid", "bchmc_shim_measure_corr2D", "bchmc_shim_chain_forward",
-                "bchmc_shim_interp_field", "bchmc_shim_measure_corr2D_interp", "bchmc_shim_measure_spec2D")
+                "bchmc_shim_interp_field", "bchmc_shim_measure_corr2D_interp", "bchmc_shim_measure_spec2D",
+                "bchmc_shim_getDensity")
 
 _dp = C.POINTER(C.c_double)
 
@@ -126,6 +127,7 @@ def load():
     lib.bchmc_shim_measure_corr2D_interp.argtypes = [hv, _dp, C.c_uint, C.c_uint, C.c_double, ul, _dp, C.POINTER(ul), _dp,
                                                      C.c_int, C.c_int, C.c_char_p, sz]
     lib.bchmc_shim_measure_spec2D.argtypes = [hv, _dp, _dp, _dp, ul, C.c_int, C.c_int, C.c_char_p, sz]
+    lib.bchmc_shim_getDensity.argtypes = [hv, C.c_int, _dp, _dp, _dp, _dp, ul, _dp, C.c_int, C.c_double, C.c_char_p, sz]
     lib.bchmc_shim_chain_forward.argtypes = [hv, C.c_int, C.c_char_p, sz]
     lib.bchmc_shim_chain_set_state.argtypes = [hv, _dp, C.c_char_p, sz]
     lib.bchmc_shim_chain_get_state.argtypes = [hv, _dp, C.c_char_p, sz]
@@ -340,6 +342,22 @@ class ShimHamil:
                                                      int(bool(planepar)), int(bool(of_deltaX)), self._err, len(self._err)))
         shape = (int(N_bin),) * 2
         return km.reshape(shape), pw.reshape(shape)
+
+    def getDensity(self, mk, xp, yp, zp, Par_mass=None, weightmass=False, kernel_h=0.0):
+        """bchmc_shim::getDensity_NGP / _CIC / _TSC / _SPH (``mk`` 0 .. 3) of a free particle list on the view's grid ->
+        delta (N values, the raw density).  NGP and TSC always read ``Par_mass`` like upstream (ones when None)."""
+        cols = [np.ascontiguousarray(a, dtype=np.float64).reshape(-1) for a in (xp, yp, zp)]
+        n_obj = cols[0].size
+        if Par_mass is None:
+            Par_mass = np.ones(n_obj)
+        mass = np.ascontiguousarray(Par_mass, dtype=np.float64).reshape(-1)
+        if any(a.size != n_obj for a in cols[1:] + [mass]):
+            raise ValueError("catalogue columns differ in length")
+        delta = np.empty(self.N)
+        self._chk(self.lib.bchmc_shim_getDensity(C.byref(self.hd), int(mk), _p(cols[0]), _p(cols[1]), _p(cols[2]), _p(mass),
+                                                 n_obj, _p(delta), int(bool(weightmass)), float(kernel_h), self._err,
+                                                 len(self._err)))
+        return delta
 
     def chain_forward(self, use_rsd=-1):
         """bchmc_shim::chain_forward: Lag2Eul of the resident state; returns the view's deltaX array."""

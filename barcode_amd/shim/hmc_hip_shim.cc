@@ -291,6 +291,62 @@ void measure_spec2D(HamilView *hd, const real_prec *signal, real_prec *kmode, re
   if (rc) fail(h, rc, "measure_spec2D");
 }
 
+namespace {
+// One getDensity_* call: the caller's grid must be the handle's, then bchmc_density_particles
+void density_on_handle(HamilView *hd, const char *name, int mk, ULONG N1, ULONG N2, ULONG N3, real_prec L1, real_prec L2,
+                       real_prec L3, real_prec d1, real_prec d2, real_prec d3, real_prec min1, real_prec min2,
+                       real_prec min3, const real_prec *xp, const real_prec *yp, const real_prec *zp, const real_prec *mass,
+                       ULONG N_OBJ, real_prec *delta, bool weightmass, real_prec kernel_h) {
+  const HamilNumericalView *n = hd->numerical;
+  const real_prec d = n->L1 / (real_prec)n->N1;
+  if (N1 != n->N1 || N2 != n->N1 || N3 != n->N1 || L1 != n->L1 || L2 != n->L1 || L3 != n->L1 || d1 != d || d2 != d ||
+      d3 != d || min1 != n->min1 || min2 != n->min2 || min3 != n->min3)
+    throw std::runtime_error(std::string(name) + ": the grid passed in is not the handle's");
+  bchmc_handle *h = engine_for(hd);
+  bchmc_density_opts o{};
+  o.mk = mk;
+  o.weightmass = weightmass ? 1 : 0;
+  o.kernel_h = kernel_h;
+  o.dest = -1;
+  const int rc = bchmc_density_particles(h, BCHMC_PART_HOST, xp, yp, zp, weightmass ? mass : nullptr, N_OBJ, &o, delta,
+                                         nullptr);
+  if (rc) fail(h, rc, name);
+}
+}  // namespace
+
+void getDensity_NGP(HamilView *hd, unsigned N1, unsigned N2, unsigned N3, real_prec L1, real_prec L2, real_prec L3,
+                    real_prec d1, real_prec d2, real_prec d3, real_prec min1, real_prec min2, real_prec min3,
+                    const real_prec *xp, const real_prec *yp, const real_prec *zp, const real_prec *Par_mass, ULONG N_OBJ,
+                    real_prec *delta) {
+  density_on_handle(hd, "getDensity_NGP", 0, N1, N2, N3, L1, L2, L3, d1, d2, d3, min1, min2, min3, xp, yp, zp, Par_mass,
+                    N_OBJ, delta, true, 0.);  // massFunctions.cc:88 always reads Par_mass
+}
+
+void getDensity_CIC(HamilView *hd, ULONG N1, ULONG N2, ULONG N3, real_prec L1, real_prec L2, real_prec L3, real_prec d1,
+                    real_prec d2, real_prec d3, real_prec min1, real_prec min2, real_prec min3, const real_prec *xp,
+                    const real_prec *yp, const real_prec *zp, const real_prec *Par_mass, ULONG N_OBJ, real_prec *delta,
+                    bool weightmass) {
+  density_on_handle(hd, "getDensity_CIC", 1, N1, N2, N3, L1, L2, L3, d1, d2, d3, min1, min2, min3, xp, yp, zp, Par_mass,
+                    N_OBJ, delta, weightmass, 0.);
+}
+
+void getDensity_TSC(HamilView *hd, unsigned N1, unsigned N2, unsigned N3, real_prec L1, real_prec L2, real_prec L3,
+                    real_prec d1, real_prec d2, real_prec d3, real_prec min1, real_prec min2, real_prec min3,
+                    const real_prec *xp, const real_prec *yp, const real_prec *zp, const real_prec *Par_mass, ULONG N_OBJ,
+                    real_prec *delta) {
+  density_on_handle(hd, "getDensity_TSC", 2, N1, N2, N3, L1, L2, L3, d1, d2, d3, min1, min2, min3, xp, yp, zp, Par_mass,
+                    N_OBJ, delta, true, 0.);  // massFunctions.cc:242 always reads Par_mass
+}
+
+void getDensity_SPH(HamilView *hd, ULONG N1, ULONG N2, ULONG N3, real_prec L1, real_prec L2, real_prec L3, real_prec d1,
+                    real_prec d2, real_prec d3, real_prec min1, real_prec min2, real_prec min3, const real_prec *xp,
+                    const real_prec *yp, const real_prec *zp, const real_prec *Par_mass, ULONG N_OBJ, real_prec *delta,
+                    bool weightmass, real_prec kernel_h) {
+  if (!(kernel_h > 0.)) throw std::runtime_error("getDensity_SPH: kernel_h must be positive");
+  density_on_handle(hd, "getDensity_SPH", 3, N1, N2, N3, L1, L2, L3, d1, d2, d3, min1, min2, min3, xp, yp, zp, Par_mass,
+                    N_OBJ, delta, weightmass, kernel_h);
+}
+
 void chain_forward(HamilView *hd, int use_rsd) {
   bchmc_handle *h = engine_for(hd);
   const int rc = bchmc_chain_forward(h, use_rsd);
@@ -791,6 +847,22 @@ int bchmc_shim_measure_spec2D(bchmc_shim::HamilView *hd, const double *signal, d
                               unsigned long N_bin, int planepar, int of_deltaX, char *err, size_t errlen) {
   return guarded(err, errlen, [&] {
     bchmc_shim::measure_spec2D(hd, signal, kmode, power, N_bin, planepar != 0, of_deltaX != 0);
+  });
+}
+int bchmc_shim_getDensity(bchmc_shim::HamilView *hd, int mk, const double *xp, const double *yp, const double *zp,
+                          const double *Par_mass, unsigned long N_OBJ, double *delta, int weightmass, double kernel_h,
+                          char *err, size_t errlen) {
+  return guarded(err, errlen, [&] {
+    const bchmc_shim::HamilNumericalView *n = hd->numerical;
+    const unsigned N1 = n->N1;
+    const double L = n->L1, d = L / (double)N1, m1 = n->min1, m2 = n->min2, m3 = n->min3;
+    switch (mk) {
+      case 0: bchmc_shim::getDensity_NGP(hd, N1, N1, N1, L, L, L, d, d, d, m1, m2, m3, xp, yp, zp, Par_mass, N_OBJ, delta); break;
+      case 1: bchmc_shim::getDensity_CIC(hd, N1, N1, N1, L, L, L, d, d, d, m1, m2, m3, xp, yp, zp, Par_mass, N_OBJ, delta, weightmass != 0); break;
+      case 2: bchmc_shim::getDensity_TSC(hd, N1, N1, N1, L, L, L, d, d, d, m1, m2, m3, xp, yp, zp, Par_mass, N_OBJ, delta); break;
+      case 3: bchmc_shim::getDensity_SPH(hd, N1, N1, N1, L, L, L, d, d, d, m1, m2, m3, xp, yp, zp, Par_mass, N_OBJ, delta, weightmass != 0, kernel_h); break;
+      default: throw std::runtime_error("getDensity: mk outside 0..3");
+    }
   });
 }
 int bchmc_shim_chain_forward(bchmc_shim::HamilView *hd, int use_rsd, char *err, size_t errlen) {

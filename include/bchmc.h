@@ -312,6 +312,78 @@ int bchmc_measure_spectrum_src(bchmc_handle *h, bchmc_corr_source src, const dou
  *  S4 kmode is the mean 3-D |k| of the bin's modes, not a (k_perp, k_par) pair. */
 int bchmc_measure_spectrum2d(bchmc_handle *h, bchmc_corr_source src, const double *signal, uint64_t n_bin, double *kmode,
                              uint64_t *nmode, double *power);
+/* ---- a particle catalogue onto the grid (upstream: getDensity_NGP / _CIC / _TSC / _SPH, massFunctions.cc:49-495, as
+ * tools/density.cc, tools/poisson_upres.cc and Lag2Eul.cc:117-126 call them) ---------------------------------------------
+ * The raw density of a free list of n_part particles -- no overdens, no normalisation -- on the handle's grid, L and
+ * min1..3, by the masskernel opts->mk, assigned on the device.  n_part has nothing to do with N: the catalogue crosses
+ * PCIe in batches of 2^20 particles, so the device memory of a call does not grow with it; n_part = 0 gives a zero field.
+ * Seven properties:
+ *  D1 Domain test.  NGP, CIC and SPH keep a particle with min <= x < min + L on every axis; TSC's test is closed above
+ *     (massFunctions.cc:195: x == min + L is kept and lands in cell 0).  A non-finite coordinate fails both.  stats->n_in /
+ *     n_lost count the particles that passed / failed the test of the kernel in force.
+ *  D2 Cell index.  NGP and TSC: floor((x - min) / d) mod n.  CIC: getCICcells / getCICweights, the coordinate shifted by
+ *     d / 2 and folded, min not subtracted.  SPH: (ULONG)(x / d) without min, cell centres at (ix + 0.5) d
+ *     (massFunctions.cc:434-440) -- each exactly as the handle's own scatter of the same mk treats it.  SPH with a
+ *     negative min is refused (BCHMC_ERR_UNSUPPORTED): upstream's cast of a negative double is undefined.
+ *  D3 Weights.  weightmass = 0: every particle counts 1 (tools/density.cc, poisson_upres.cc; for NGP and TSC, which always
+ *     read Par_mass upstream, a mass array of ones).  weightmass = 1: w[p] is upstream's `mass` (Lag2Eul.cc), any sign.
+ *  D4 Precision.  fp64 handles: double throughout.  fp32 handles: the positions are converted to float first (the domain
+ *     test, the cell and the weights see the float's value), the arithmetic is that of the handle's own direct kernels of
+ *     the mk (double, the CIC / TSC products rounded to float once); every handle accumulates in double, in LDS and on
+ *     the grid, and `out` is not rounded to float (the nobs of dest = BCHMC_F_NOBS is, like an uploaded array).
+ *  D5 Deterministic handles accumulate in 64-bit fixed point, scale 2^46 / (max|w| x the largest kernel value: W(0) for
+ *     SPH, 1 otherwise), and convert each cell once: `out` is bitwise equal across calls, across
+ *     bchmc_catalogue_release, across handles and under any permutation of the catalogue.  A cell whose RUNNING sum
+ *     passes 2^16 maximal contributions in magnitude makes THIS call return BCHMC_ERR_STATE, with nothing written to out
+ *     or nobs: every add to the grid is looked at as it lands, so that no count of particles can wrap the 64-bit sum
+ *     unseen.  With weights of one sign the running sum never exceeds the final one and the answer depends on the data
+ *     alone; with both signs a cell whose partial sums can pass the limit while its final sum does not (|S_c| below,
+ *     A_c = sum |w W| above 2^16 max|w| times the kernel's largest value) may be refused in one order of arrival and
+ *     accepted in another -- the field, when one is returned, is the same bits either way.
+ *     Other handles use hardware float atomics: last bits vary with the order, like the reference's OpenMP build.
+ *  D6 What a call leaves alone: the chain state, the momenta, a pending proposal, deltaX, rho, Psi, pos* and the record
+ *     slots of the trajectory (it uses the transfer staging and buffers of its own).  dest = BCHMC_F_NOBS invalidates
+ *     exactly what bchmc_upload(BCHMC_F_NOBS) invalidates -- the carried gradient and -log L -- and nothing more.
+ *  D7 Where the handle has a tile partition and min is 0, the particles are sorted by the tile of their home cell and a
+ *     tile's records are cut into work items of bounded length, so a cell holding any number of particles is spread over
+ *     many workgroups; stats->max_per_tile is the largest tile population of a batch (of the catalogue up to 2^20
+ *     particles; beyond that it depends on how the catalogue's order spreads a tile over the batches).  Otherwise (odd
+ *     Nx, min != 0, an SPH scale length whose halo does not fit) one thread per particle adds to the grid directly, in
+ *     the same arithmetic, and max_per_tile is 0.  SPH at h = d (any h whose stencil hull is the standard 81-cell one)
+ *     visits the 81 cells of the hull with the folded spline of the handle's own tile kernels, on either path; other scale lengths
+ *     walk upstream's (2 reach + 1)^3 cube.
+ * BCHMC_PART_FORWARD with mk = 1 on an SPH handle is tools/LAG2EULer.cc's output for the handle's cosmology (its ascale
+ * argument is the handle's ascale and D1).
+ * The buffers (bchmc_live_resources counts them) are built by the first call, kept for the next, and freed by
+ * bchmc_catalogue_release and bchmc_destroy.
+ * Refused before anything is queued, the handle untouched: x, y or z NULL with BCHMC_PART_HOST, or any of x, y, z, w given
+ * with BCHMC_PART_FORWARD; weightmass = 1 with w == NULL; weightmass other than 0 / 1; mk outside -1..3; kernel_h
+ * negative, not finite or above L / 4; dest other than -1 or BCHMC_F_NOBS; out == NULL with dest == -1; n_part > 2^31 - 1;
+ * a non-finite weight (found by a threaded pass over w on the host, which also yields max|w|, before the device sees
+ * the call) -- all BCHMC_ERR_ARG;
+ * BCHMC_PART_FORWARD when no forward model has run: BCHMC_ERR_STATE. */
+typedef enum { BCHMC_PART_HOST = 0,     /* x, y, z (and w) are host arrays of n_part doubles */
+               BCHMC_PART_FORWARD = 1   /* the handle's own particles after the last forward model: the positions
+                                           bchmc_fetch(BCHMC_F_POSX..Z) would return; x, y, z, w must be NULL */
+} bchmc_part_source;
+
+typedef struct bchmc_density_opts {
+  int32_t mk;            /* 0 NGP, 1 CIC, 2 TSC, 3 SPH; -1: the handle's mk */
+  int32_t weightmass;    /* 0: every particle counts 1 (w ignored, may be NULL); 1: w[p] */
+  double  kernel_h;      /* SPH scale length; 0: the handle's particle_kernel_h.  Refused above L / 4 */
+  int32_t dest;          /* -1: host array `out` only; BCHMC_F_NOBS: also becomes the handle's nobs, as if uploaded */
+  int32_t reserved0;
+} bchmc_density_opts;
+
+typedef struct bchmc_density_stats {
+  uint64_t n_in, n_lost;     /* passed / failed the kernel's own domain test (non-finite positions are lost) */
+  uint64_t max_per_tile;     /* largest tile population met in one batch of 2^20 particles (0 on the direct path) */
+} bchmc_density_stats;
+
+int bchmc_density_particles(bchmc_handle *h, bchmc_part_source src, const double *x, const double *y, const double *z,
+                            const double *w, uint64_t n_part, const bchmc_density_opts *opts, double *out /* N or NULL */,
+                            bchmc_density_stats *stats /* or NULL */);
+int bchmc_catalogue_release(bchmc_handle *h);   /* frees the catalogue buffers; a later call rebuilds them */
 /* Lag2Eul of the resident chain state: bchmc_forward without the host array (it starts from the chain's q^, so no field
  * crosses PCIe and no transform pair is spent).  use_rsd as there.  Leaves deltaX / pos* in the handle, synchronises and
  * adapts the binning's record slots like bchmc_forward; drops a pending proposal like it.  The chain state, the momenta

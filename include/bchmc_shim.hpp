@@ -16,6 +16,8 @@
 //   void measure_spectrum(...)                      field_statistics.cpp:20-90         -> bchmc_shim::measure_spectrum
 //   void measure_spec2D(N1, N2, N3, L1, L2, L3, signal, kmode, power, N_bin, planepar)
 //                                                   tools/2D_powspec.cc:25-110         -> bchmc_shim::measure_spec2D
+//   void getDensity_NGP / _CIC / _TSC / _SPH(N1, N2, N3, L1, L2, L3, d1, d2, d3, min1, min2, min3, xp, yp, zp, Par_mass,
+//                        N_OBJ, delta[, weightmass[, kernel_h]])      massFunctions.cc:49-495 -> bchmc_shim::getDensity_NGP ..
 // Errors are std::runtime_error, like the reference's (single catch in main.cc:195-197).
 #ifndef BCHMC_SHIM_HPP
 #define BCHMC_SHIM_HPP
@@ -140,6 +142,26 @@ void measure_corr2D_interp(HamilView *hd, const real_prec *signal, unsigned N_ou
 // no mode counts (bchmc_measure_spectrum2d does).  planepar == false throws like upstream.
 void measure_spec2D(HamilView *hd, const real_prec *signal, real_prec *kmode, real_prec *power, ULONG N_bin,
                     bool planepar = true, bool of_deltaX = false);
+// massFunctions.cc:49-495 on the device (bchmc_density_particles): a free list of N_OBJ particles onto the grid, upstream's
+// argument lists behind the view.  The grid is the handle's: N1 .. min3 must be the view's own values (std::runtime_error
+// otherwise -- these functions do not assign onto another grid).  NGP and TSC always read Par_mass, like upstream; CIC and
+// SPH read it when weightmass is set.  delta: N values, the raw density.
+void getDensity_NGP(HamilView *hd, unsigned N1, unsigned N2, unsigned N3, real_prec L1, real_prec L2, real_prec L3,
+                    real_prec d1, real_prec d2, real_prec d3, real_prec min1, real_prec min2, real_prec min3,
+                    const real_prec *xp, const real_prec *yp, const real_prec *zp, const real_prec *Par_mass, ULONG N_OBJ,
+                    real_prec *delta);
+void getDensity_CIC(HamilView *hd, ULONG N1, ULONG N2, ULONG N3, real_prec L1, real_prec L2, real_prec L3, real_prec d1,
+                    real_prec d2, real_prec d3, real_prec min1, real_prec min2, real_prec min3, const real_prec *xp,
+                    const real_prec *yp, const real_prec *zp, const real_prec *Par_mass, ULONG N_OBJ, real_prec *delta,
+                    bool weightmass);
+void getDensity_TSC(HamilView *hd, unsigned N1, unsigned N2, unsigned N3, real_prec L1, real_prec L2, real_prec L3,
+                    real_prec d1, real_prec d2, real_prec d3, real_prec min1, real_prec min2, real_prec min3,
+                    const real_prec *xp, const real_prec *yp, const real_prec *zp, const real_prec *Par_mass, ULONG N_OBJ,
+                    real_prec *delta);
+void getDensity_SPH(HamilView *hd, ULONG N1, ULONG N2, ULONG N3, real_prec L1, real_prec L2, real_prec L3, real_prec d1,
+                    real_prec d2, real_prec d3, real_prec min1, real_prec min2, real_prec min3, const real_prec *xp,
+                    const real_prec *yp, const real_prec *zp, const real_prec *Par_mass, ULONG N_OBJ, real_prec *delta,
+                    bool weightmass, real_prec kernel_h);
 // Lag2Eul of the resident chain state (dump_deltas' second forward model, IOfunctionsGen.cc:158-169, with use_rsd = 0);
 // hd->deltaX / pos* <- this evaluation's.  use_rsd < 0: as configured.
 void chain_forward(HamilView *hd, int use_rsd);
@@ -284,6 +306,10 @@ int bchmc_shim_measure_corr2D_interp(bchmc_shim::HamilView *hd, const double *si
                                      int planepar, int of_deltaX, char *err, size_t errlen);
 int bchmc_shim_measure_spec2D(bchmc_shim::HamilView *hd, const double *signal, double *kmode, double *power,
                               unsigned long N_bin, int planepar, int of_deltaX, char *err, size_t errlen);
+/* getDensity_NGP / _CIC / _TSC / _SPH (mk 0 .. 3) with the view's own geometry */
+int bchmc_shim_getDensity(bchmc_shim::HamilView *hd, int mk, const double *xp, const double *yp, const double *zp,
+                          const double *Par_mass, unsigned long N_OBJ, double *delta, int weightmass, double kernel_h,
+                          char *err, size_t errlen);
 int bchmc_shim_chain_forward(bchmc_shim::HamilView *hd, int use_rsd, char *err, size_t errlen);
 int bchmc_shim_chain_set_state(bchmc_shim::HamilView *hd, const double *x, char *err, size_t errlen);
 int bchmc_shim_chain_get_state(bchmc_shim::HamilView *hd, double *x, char *err, size_t errlen);
