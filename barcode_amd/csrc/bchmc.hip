@@ -13,6 +13,7 @@
 #include "owned.hpp"
 #include "pass_launch.hpp"
 #include "eval_plan.hpp"
+#include "interp_plan.hpp"
 
 #include <rocfft/rocfft.h>
 #include <rocprofiler-sdk-roctx/roctx.h>
@@ -179,6 +180,23 @@ struct bchmc_handle {
     DevBuf<unsigned long long> stat;     // kCatWords
     PinnedBuf<unsigned long long> h_stat;
   } cat;
+  // bchmc_interp_particles (interp_particles.hpp): the staged sources -- n_fields grid arrays of the storage type, grown
+  // when a call asks for more fields -- and one batch of kCatBatch particles at a time: the columns, the results, and for
+  // the tile kernel the tile of every particle, the indexed records, the tiles' populations, offsets and cursors and the
+  // work items.  None of it is the catalogue's.  Built by the first call, kept for the next, freed by
+  // bchmc_interp_release and bchmc_destroy.
+  struct Itp {
+    DevBytes src;                        // fields_held N elements of T
+    int fields_held = 0;
+    DevBuf<double> cols;                 // 3 kCatBatch: x | y | z
+    DevBuf<double> out;                  // kItpMaxFields kCatBatch, field-major
+    DevBuf<int> tile_of;                 // kCatBatch
+    DevBuf<ItpRec> rec;                  // kCatBatch
+    DevBuf<unsigned> cnt, off, cursor;   // ntiles, ntiles + 1, ntiles
+    DevBuf<CatItem> items;               // ntiles + kCatBatch / chunk + 1
+    DevBuf<unsigned long long> stat;     // kCatWords
+    PinnedBuf<unsigned long long> h_stat;
+  } itp;
   // host-array entry points: caller arrays are pageable, so they cross PCIe through two pinned staging chunks
   // (N-thread memcpy into one chunk while the DMA of the other is in flight)
   PinnedBuf<void> stg[2];
@@ -413,6 +431,45 @@ HullPar make_hull(const bchmc_handle *h) {
 int need_input(bchmc_handle *h, int f, const char *name) {
   if (!h->have[f]) return h->fail(BCHMC_ERR_STATE, "input array %s was never uploaded", name);
   return BCHMC_OK;
+}
+
+// Where bchmc_fetch takes a field from, or why it cannot: the one statement of it, for Pipe::fetch and for an entry point
+// that must refuse before anything is queued.  A field that a kernel makes first lands in ioq.
+struct FieldSource {
+  enum Made { kAsHeld, kOverdens, kPositions };
+  void *base = nullptr;  // the buffer, in the storage type
+  size_t offset = 0;     // elements into it
+  Made made = kAsHeld;
+};
+int field_source(bchmc_handle *h, int field, FieldSource *fs) {
+  const size_t N = (size_t)h->g.N;
+  *fs = FieldSource{};
+  switch (field) {
+    case BCHMC_F_SIGNAL_PS: case BCHMC_F_MASS_F: case BCHMC_F_MASS_R:
+    case BCHMC_F_NOBS: case BCHMC_F_NOISE: case BCHMC_F_WINDOW:
+      fs->base = h->in_arr[field].get();
+      break;
+    case BCHMC_F_DELTAX: fs->base = h->ioq.get(), fs->made = FieldSource::kOverdens; break;
+    case BCHMC_F_POSX: case BCHMC_F_POSY: case BCHMC_F_POSZ: fs->base = h->ioq.get(), fs->made = FieldSource::kPositions; break;
+    case BCHMC_F_RHO: fs->base = h->rho.get(); break;
+    case BCHMC_F_PART_LIKE: fs->base = h->plike.get(); break;
+    case BCHMC_F_VX: case BCHMC_F_VY: case BCHMC_F_VZ: fs->base = h->V.get(), fs->offset = (size_t)(field - BCHMC_F_VX) * N; break;
+    case BCHMC_F_PSIX: case BCHMC_F_PSIY: case BCHMC_F_PSIZ:
+      fs->base = h->psi.get(), fs->offset = (size_t)(field - BCHMC_F_PSIX) * N;
+      break;
+    case BCHMC_F_GRAD_PRIOR: fs->base = h->gprior.get(); break;
+    case BCHMC_F_GRAD_LIKE: fs->base = h->glike.get(); break;
+    default: return h->fail(BCHMC_ERR_ARG, "unknown field %d", field);
+  }
+  if (!fs->base) return h->fail(BCHMC_ERR_STATE, "field %d has not been computed", field);
+  return BCHMC_OK;
+}
+// bchmc_fetch's refusals of a field, all of them: the outputs of a forward evaluation need one
+int fetch_ready(bchmc_handle *h, int field) {
+  if (field >= BCHMC_F_DELTAX && field <= BCHMC_F_PSIZ && !h->have_eval)
+    return h->fail(BCHMC_ERR_STATE, "no forward evaluation to fetch from");
+  FieldSource fs;
+  return field_source(h, field, &fs);
 }
 
 int check_inputs(bchmc_handle *h) {
@@ -1067,6 +1124,15 @@ struct CatCall {
   int src, mk, weighted, dest;
   double hh, max_w;
   const double *x, *y, *z, *w;
+  uint64_t n_part;
+};
+
+// What bchmc_interp_particles asks of the pipe, after its checks: the position source, the kernel, the path decided by
+// interp_plan.hpp, the fields and the columns.
+struct ItpCall {
+  int psrc, kernel, tiled, n_fields;
+  const bchmc_interp_field *fields;
+  const double *x, *y, *z;
   uint64_t n_part;
 };
 
@@ -2411,34 +2477,15 @@ struct Pipe {
 
   // Fill the double staging array with one output field.
   static int fetch(bchmc_handle *h, bchmc_field field, double *d_out) {
-    const size_t N = (size_t)h->g.N;
-    const T *src = nullptr;
-    switch (field) {
-      case BCHMC_F_SIGNAL_PS: case BCHMC_F_MASS_F: case BCHMC_F_MASS_R:
-      case BCHMC_F_NOBS: case BCHMC_F_NOISE: case BCHMC_F_WINDOW:
-        src = R(h->in_arr[field]);
-        break;
-      case BCHMC_F_DELTAX:
-        k_overdens<T><<<nblk_stride(h->g.N), 256, 0, h->stream>>>(h->g, R(h->rho), h->rho_part, R(h->ioq));
-        HIPCHK(hipGetLastError());
-        src = R(h->ioq);
-        break;
-      case BCHMC_F_POSX: case BCHMC_F_POSY: case BCHMC_F_POSZ:
-        k_positions<T><<<nblk_stride(h->g.N), 256, 0, h->stream>>>(h->g, make_pos(h, h->last_rsd), R(h->psi), R(h->ioq),
-                                                                   (int)field - (int)BCHMC_F_POSX);
-        HIPCHK(hipGetLastError());
-        src = R(h->ioq);
-        break;
-      case BCHMC_F_RHO: src = R(h->rho); break;
-      case BCHMC_F_PART_LIKE: src = R(h->plike); break;
-      case BCHMC_F_VX: case BCHMC_F_VY: case BCHMC_F_VZ: src = R(h->V) + ((int)field - (int)BCHMC_F_VX) * N; break;
-      case BCHMC_F_PSIX: case BCHMC_F_PSIY: case BCHMC_F_PSIZ: src = R(h->psi) + ((int)field - (int)BCHMC_F_PSIX) * N; break;
-      case BCHMC_F_GRAD_PRIOR: src = R(h->gprior); break;
-      case BCHMC_F_GRAD_LIKE: src = R(h->glike); break;
-      default: return h->fail(BCHMC_ERR_ARG, "unknown field %d", (int)field);
-    }
-    if (!src) return h->fail(BCHMC_ERR_STATE, "field %d has not been computed", (int)field);
-    return store_real(h, src, d_out);
+    FieldSource fs;
+    CHK(field_source(h, (int)field, &fs));
+    if (fs.made == FieldSource::kOverdens)
+      k_overdens<T><<<nblk_stride(h->g.N), 256, 0, h->stream>>>(h->g, R(h->rho), h->rho_part, R(h->ioq));
+    if (fs.made == FieldSource::kPositions)
+      k_positions<T><<<nblk_stride(h->g.N), 256, 0, h->stream>>>(h->g, make_pos(h, h->last_rsd), R(h->psi), R(h->ioq),
+                                                                 (int)field - (int)BCHMC_F_POSX);
+    if (fs.made != FieldSource::kAsHeld) HIPCHK(hipGetLastError());
+    return store_real(h, R(fs.base) + fs.offset, d_out);
   }
 
   // Momenta from the Gaussians of an exact draw (mt_draw.hpp): cp = G of create_GARFIELD placed directly (the R2C of
@@ -2853,6 +2900,126 @@ struct Pipe {
     if (cc.dest == BCHMC_F_NOBS) {
       CHK(upload(h, BCHMC_F_NOBS, h->dstage));
       HIPCHK(hipStreamSynchronize(h->stream));
+    }
+    return BCHMC_OK;
+  }
+  // ---- bchmc_interp_particles (interp_particles.hpp) ----------------------------------------------------------------
+  template <int MK, int K>
+  static void itp_launch(bchmc_handle *h, bool tiled, size_t lds, int m) {
+    auto &c = h->itp;
+    const double *x = c.cols, *y = x + kCatBatch, *z = y + kCatBatch;
+    if (tiled) {
+      const int grid = h->plan.tp.ntiles + m / h->plan.tp.chunk + 1;  // upper bound on the work items of this batch
+      k_itp_gather_tile<T, MK, K><<<grid, 256, lds, h->stream>>>(h->g, h->plan.tp, c.items, c.stat, c.rec, R(c.src), c.out);
+    } else {
+      k_itp_gather_direct<T, MK, K><<<nblk_full(m), 256, 0, h->stream>>>(h->g, m, x, y, z, R(c.src), c.out, c.stat);
+    }
+  }
+  template <int MK>
+  static void itp_launch_k(bchmc_handle *h, int K, bool tiled, size_t lds, int m) {
+    switch (K) {
+      case 1: itp_launch<MK, 1>(h, tiled, lds, m); break;
+      case 2: itp_launch<MK, 2>(h, tiled, lds, m); break;
+      case 3: itp_launch<MK, 3>(h, tiled, lds, m); break;
+      default: itp_launch<MK, 4>(h, tiled, lds, m); break;
+    }
+  }
+
+  // The whole call after its arguments were checked.  The sources are staged once, each as bchmc_upload /
+  // bchmc_chain_get_state / bchmc_fetch would hold or return it, into the feature's own grid arrays; then batches of
+  // kCatBatch particles go through count / scan / fill / gather (or the direct kernel) into a batch-ordered result array
+  // that crosses PCIe as one contiguous copy per field.
+  static int interp_particles(bchmc_handle *h, const ItpCall &ic, double *out, bchmc_interp_stats *stats) {
+    auto &c = h->itp;
+    const Geo &g = h->g;
+    const TilePar &tp = h->plan.tp;
+    const size_t N = (size_t)g.N;
+    const int K = ic.n_fields;
+    const bool tiled = ic.tiled != 0;
+    // all or nothing, like the catalogue's: a failed allocation leaves no half-built set behind
+    if (!c.cols || (tiled && !c.tile_of)) {
+      auto build = [&]() -> int {
+        if (!c.cols) {
+          CHK(dev_alloc(h, c.cols, 3 * (size_t)kCatBatch));
+          CHK(dev_alloc(h, c.out, kItpMaxFields * (size_t)kCatBatch));
+          CHK(dev_alloc(h, c.stat, kCatWords));
+          HIPCHK(c.h_stat.alloc(kCatWords));
+        }
+        if (!h->plan.tiled) return BCHMC_OK;
+        CHK(dev_alloc(h, c.tile_of, kCatBatch));
+        CHK(dev_alloc(h, c.rec, kCatBatch));
+        CHK(dev_alloc(h, c.cnt, tp.ntiles));
+        CHK(dev_alloc(h, c.off, tp.ntiles + 1));
+        CHK(dev_alloc(h, c.cursor, tp.ntiles));
+        return dev_alloc(h, c.items, (size_t)tp.ntiles + kCatBatch / tp.chunk + 1);
+      };
+      if (const int rc = build()) {
+        h->itp = bchmc_handle::Itp{};
+        return rc;
+      }
+    }
+    if (c.fields_held < K) {
+      c.fields_held = 0;
+      CHK(dev_reserve(h, c.src, (size_t)K * N * sizeof(T)));
+      c.fields_held = K;
+    }
+    for (int f = 0; f < K; f++) {
+      const bchmc_interp_field &fd = ic.fields[f];
+      T *dst = R(c.src) + (size_t)f * N;
+      if (fd.source == BCHMC_CORR_HOST) {
+        CHK(h2d(h, h->dstage, fd.host, N * sizeof(double)));
+        CHK(load_real(h, h->dstage, dst));
+      } else if (fd.source == BCHMC_CORR_CHAIN_STATE) {
+        CHK(c2r_scaled(h, h->cq, dst));
+      } else {
+        ProfScope ps(h, BCHMC_K_OTHER);
+        CHK(fetch(h, fd.source == BCHMC_CORR_DELTAX ? BCHMC_F_DELTAX : (bchmc_field)fd.field, h->dstage));
+        CHK(load_real(h, h->dstage, dst));
+      }
+    }
+    HIPCHK(hipMemsetAsync(c.stat, 0, kCatWords * sizeof(unsigned long long), h->stream));
+    double *x = c.cols, *y = x + kCatBatch, *z = y + kCatBatch;
+    const PosPar pp = make_pos(h, h->last_rsd);
+    const size_t lds = tiled ? (size_t)(tp.tx + 2 * kItpHalo) * (tp.ty + 2 * kItpHalo) * (tp.tz + 2 * kItpHalo) * sizeof(T) * K : 0;
+    for (uint64_t p0 = 0; p0 < ic.n_part; p0 += kCatBatch) {
+      const int m = (int)std::min<uint64_t>(kCatBatch, ic.n_part - p0);
+      if (ic.psrc != BCHMC_PART_FORWARD) {
+        CHK(h2d(h, x, ic.x + p0, m * sizeof(double)));
+        CHK(h2d(h, y, ic.y + p0, m * sizeof(double)));
+        CHK(h2d(h, z, ic.z + p0, m * sizeof(double)));
+      }
+      if (ic.psrc == BCHMC_PART_FORWARD || tiled) {
+        ProfScope ps(h, BCHMC_K_SORT);
+        if (ic.psrc == BCHMC_PART_FORWARD)
+          k_cat_positions<T><<<nblk_full(m), 256, 0, h->stream>>>(g, pp, R(h->psi), (long long)p0, m, x, y, z);
+        if (tiled) {
+          HIPCHK(hipMemsetAsync(c.cnt, 0, tp.ntiles * sizeof(unsigned), h->stream));
+          if (ic.kernel == 1)
+            k_itp_count<T, 1><<<nblk_full(m), 256, 0, h->stream>>>(g, tp, m, K, x, y, z, c.tile_of, c.cnt, c.out, c.stat);
+          else
+            k_itp_count<T, 2><<<nblk_full(m), 256, 0, h->stream>>>(g, tp, m, K, x, y, z, c.tile_of, c.cnt, c.out, c.stat);
+          k_cat_scan<<<1, 1024, 0, h->stream>>>(tp.ntiles, tp.chunk, c.cnt, c.off, c.cursor, c.items, c.stat);
+          k_itp_fill<T><<<nblk_full(m), 256, 0, h->stream>>>(m, x, y, z, c.tile_of, c.off, c.cursor, c.rec);
+        }
+        HIPCHK(hipGetLastError());
+      }
+      {
+        ProfScope ps(h, BCHMC_K_GATHER);
+        if (ic.kernel == 1) itp_launch_k<1>(h, K, tiled, lds, m);
+        else itp_launch_k<2>(h, K, tiled, lds, m);
+        HIPCHK(hipGetLastError());
+      }
+      for (int f = 0; f < K; f++)
+        CHK(d2h(h, out + (size_t)f * ic.n_part + p0, c.out + (size_t)f * kCatBatch, m * sizeof(double)));
+    }
+    HIPCHK(hipMemcpyAsync(c.h_stat, c.stat, kCatWords * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (stats) {
+      stats->n_in = c.h_stat[kCatIn];
+      stats->n_lost = ic.n_part - c.h_stat[kCatIn];
+      stats->max_per_tile = tiled ? c.h_stat[kCatMaxTile] : 0;
+      stats->path_used = tiled ? kInterpTile : kInterpDirect;
+      stats->reserved = 0;
     }
     return BCHMC_OK;
   }
@@ -3552,8 +3719,7 @@ int bchmc_fetch(bchmc_handle *h, bchmc_field field, double *host, size_t n) {
   if (!h || !host) return BCHMC_ERR_ARG;
   ENTER(h);
   if (n != (size_t)h->g.N) return h->fail(BCHMC_ERR_ARG, "fetch size %zu != N = %lld", n, h->g.N);
-  const bool needs_eval = (field >= BCHMC_F_DELTAX && field <= BCHMC_F_PSIZ);
-  if (needs_eval && !h->have_eval) return h->fail(BCHMC_ERR_STATE, "no forward evaluation to fetch from");
+  CHK(fetch_ready(h, (int)field));
   CHK(DISPATCH(h, fetch(h, field, h->dstage)));
   CHK(d2h(h, host, h->dstage, n * sizeof(double)));
   return BCHMC_OK;
@@ -3914,6 +4080,80 @@ int bchmc_catalogue_release(bchmc_handle *h) {
   ENTER(h);
   HIPCHK(hipStreamSynchronize(h->stream));
   h->cat = bchmc_handle::Cat{};
+  return BCHMC_OK;
+}
+
+// A handle field, asked before anything is queued: bchmc_fetch's own refusals (fetch_ready), and one of this entry
+// point's on top of them, since an input's buffer is there before its first upload.
+static int interp_field_ready(bchmc_handle *h, const char *name, int f, int field) {
+  CHK(fetch_ready(h, field));
+  if (field <= BCHMC_F_WINDOW && !h->have[field])
+    return h->fail(BCHMC_ERR_STATE, "%s: field %d: input array (bchmc_field %d) was never uploaded", name, f, field);
+  return BCHMC_OK;
+}
+
+int bchmc_interp_particles(bchmc_handle *h, bchmc_part_source psrc, const double *x, const double *y, const double *z,
+                           uint64_t n_part, const bchmc_interp_field *fields, int32_t n_fields,
+                           const bchmc_interp_opts *opts, double *out, bchmc_interp_stats *stats) {
+  if (!h) return BCHMC_ERR_ARG;
+  const char *name = "interp_particles";
+  if (!opts) return h->fail(BCHMC_ERR_ARG, "%s: opts is NULL", name);
+  if (opts->kernel != 1 && opts->kernel != 2)
+    return h->fail(BCHMC_ERR_ARG, "%s: kernel = %d is neither 1 (CIC) nor 2 (TSC)", name, (int)opts->kernel);
+  if (opts->path < -1 || opts->path > 1) return h->fail(BCHMC_ERR_ARG, "%s: path = %d outside -1..1", name, (int)opts->path);
+  if (n_fields < 1 || n_fields > BCHMC_INTERP_MAX_FIELDS)
+    return h->fail(BCHMC_ERR_ARG, "%s: n_fields = %d outside 1..%d", name, (int)n_fields, (int)BCHMC_INTERP_MAX_FIELDS);
+  if (!fields) return h->fail(BCHMC_ERR_ARG, "%s: fields is NULL", name);
+  if (psrc != BCHMC_PART_HOST && psrc != BCHMC_PART_FORWARD) return h->fail(BCHMC_ERR_ARG, "%s: unknown source %d", name, (int)psrc);
+  if (psrc == BCHMC_PART_HOST && n_part > 0 && (!x || !y || !z))
+    return h->fail(BCHMC_ERR_ARG, "%s: x, y and z must be given for BCHMC_PART_HOST", name);
+  if (psrc == BCHMC_PART_FORWARD && (x || y || z))
+    return h->fail(BCHMC_ERR_ARG, "%s: x, y and z must be NULL for BCHMC_PART_FORWARD", name);
+  if (psrc == BCHMC_PART_FORWARD && n_part != (uint64_t)h->g.N)
+    return h->fail(BCHMC_ERR_ARG, "%s: n_part = %llu != N = %lld with BCHMC_PART_FORWARD", name, (unsigned long long)n_part, h->g.N);
+  if (n_part > 2147483647ull) return h->fail(BCHMC_ERR_ARG, "%s: n_part = %llu > 2^31 - 1", name, (unsigned long long)n_part);
+  if (!out && n_part > 0) return h->fail(BCHMC_ERR_ARG, "%s: out is NULL", name);
+  for (int f = 0; f < n_fields; f++) {
+    const bchmc_interp_field &fd = fields[f];
+    if (fd.source < 0 || fd.source > BCHMC_INTERP_HANDLE_FIELD)
+      return h->fail(BCHMC_ERR_ARG, "%s: field %d: unknown source %d", name, f, (int)fd.source);
+    if ((fd.source == BCHMC_CORR_HOST) != (fd.host != nullptr))
+      return h->fail(BCHMC_ERR_ARG, "%s: field %d: host must be given for BCHMC_CORR_HOST and NULL otherwise", name, f);
+    if (fd.source == BCHMC_INTERP_HANDLE_FIELD && (fd.field < 0 || fd.field >= BCHMC_F_COUNT))
+      return h->fail(BCHMC_ERR_ARG, "%s: field %d: unknown bchmc_field %d", name, f, (int)fd.field);
+  }
+  for (int f = 0; f < n_fields; f++) {
+    const bchmc_interp_field &fd = fields[f];
+    if (fd.source == BCHMC_CORR_CHAIN_STATE || fd.source == BCHMC_CORR_DELTAX) CHK(source_state(h, (bchmc_corr_source)fd.source));
+    if (fd.source == BCHMC_INTERP_HANDLE_FIELD) CHK(interp_field_ready(h, name, f, fd.field));
+  }
+  if (psrc == BCHMC_PART_FORWARD && !h->have_eval)
+    return h->fail(BCHMC_ERR_STATE, "%s: no forward evaluation to take the particles from", name);
+  InterpFacts facts;
+  facts.tiled = h->plan.tiled;
+  facts.tx = h->plan.tp.tx, facts.ty = h->plan.tp.ty, facts.tz = h->plan.tp.tz, facts.ntiles = h->plan.tp.ntiles;
+  facts.esz = (int)h->esz, facts.kernel = opts->kernel, facts.n_fields = n_fields, facts.n_part = n_part;
+  facts.own_particles = psrc == BCHMC_PART_FORWARD;
+  const int path = interp_path(facts, opts->path);
+  if (path == kInterpNoTiles && !(facts.tiled && facts.ntiles > 0))
+    return h->fail(BCHMC_ERR_UNSUPPORTED, "%s: path = 1 on a handle without a tile partition (Nx = %d)", name, h->g.n);
+  if (path == kInterpNoTiles)  // no tile shape of tile_plan.hpp comes near it today: 8 x 8 x 16, four fp64 fields, 57.6 KB
+    return h->fail(BCHMC_ERR_UNSUPPORTED, "%s: path = 1 with tile images of %zu bytes of LDS for %d fields, above %zu", name,
+                   interp_image_bytes(facts), (int)n_fields, kInterpLdsLimit);
+  if (n_part == 0) {
+    if (stats) *stats = bchmc_interp_stats{0, 0, 0, path, 0};
+    return BCHMC_OK;
+  }
+  ENTER(h);
+  const ItpCall ic{(int)psrc, (int)opts->kernel, path == kInterpTile ? 1 : 0, (int)n_fields, fields, x, y, z, n_part};
+  return h->f32 ? Pipe<float>::interp_particles(h, ic, out, stats) : Pipe<double>::interp_particles(h, ic, out, stats);
+}
+
+int bchmc_interp_release(bchmc_handle *h) {
+  if (!h) return BCHMC_ERR_ARG;
+  ENTER(h);
+  HIPCHK(hipStreamSynchronize(h->stream));
+  h->itp = bchmc_handle::Itp{};
   return BCHMC_OK;
 }
 

@@ -21,6 +21,7 @@
 #include "tiles.hpp"  // Tile-sorted particle-mesh path: binning, scan, LDS scatter / gather kernels
 #include "tiles_low.hpp"  // NGP / CIC / TSC mass assignment and calc_h = 3's TSC interpolation on the same records
 #include "catalogue.hpp"  // bchmc_density_particles: a free, weighted particle catalogue onto the grid (count, scan, fill, LDS scatter, direct)
+#include "interp_particles.hpp"  // bchmc_interp_particles: grid fields read at a free particle catalogue (count, fill, LDS gather, direct)
 #include "alpt.hpp"  // ALPT displacement (Lag2Eul_non_zeldovich)
 #include "spectrum.hpp"  // measure_spectrum
 #include "corr.hpp"  // measure_corr_grid / measure_corr2D: |x^|^2, integer LDS histogram (1-D), sorted-row slices (2-D)

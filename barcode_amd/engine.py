@@ -67,6 +67,27 @@ class DensityStats(C.Structure):
     _fields_ = [("n_in", C.c_uint64), ("n_lost", C.c_uint64), ("max_per_tile", C.c_uint64)]
 
 
+class InterpField(C.Structure):
+    """bchmc_interp_field: one source of bchmc_interp_particles."""
+    _fields_ = [("source", C.c_int32), ("field", C.c_int32), ("host", C.POINTER(C.c_double))]
+
+
+class InterpOpts(C.Structure):
+    """bchmc_interp_opts."""
+    _fields_ = [("kernel", C.c_int32), ("path", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+class InterpStats(C.Structure):
+    """bchmc_interp_stats."""
+    _fields_ = [("n_in", C.c_uint64), ("n_lost", C.c_uint64), ("max_per_tile", C.c_uint64), ("path_used", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+INTERP_MAX_FIELDS = 4       # BCHMC_INTERP_MAX_FIELDS
+INTERP_HANDLE_FIELD = 3     # BCHMC_INTERP_HANDLE_FIELD
+INTERP_KERNELS = dict(cic=1, tsc=2)
+INTERP_PATHS = {None: -1, "direct": 0, "tile": 1, -1: -1, 0: 0, 1: 1}
+
 # bchmc_part_source
 PART_SOURCES = dict(host=0, forward=1)
 F_NOBS = 3  # BCHMC_F_NOBS
@@ -107,7 +128,7 @@ EXPORTS = ("bchmc_create", "bchmc_destroy", "bchmc_strerror", "bchmc_last_error"
            "bchmc_comm_transport", "bchmc_garfield_walk_index", "bchmc_hamiltonian_mass",
            "bchmc_setup_random_test", "bchmc_make_initial_guess", "bchmc_measure_corr", "bchmc_chain_forward",
            "bchmc_probe_displacement", "bchmc_probe_displacement_z", "bchmc_interp_upres", "bchmc_upres_release", "bchmc_measure_spectrum_src",
-           "bchmc_density_particles", "bchmc_catalogue_release")
+           "bchmc_density_particles", "bchmc_catalogue_release", "bchmc_interp_particles", "bchmc_interp_release")
 # declared as well, listed apart: the header scan of the ABI test matches names of letters and underscores only
 EXPORTS_MT19937 = ("bchmc_chain_draw_momenta_mt19937", "bchmc_mt19937_jump")
 EXPORTS_CORR2D = ("bchmc_measure_corr2d", "bchmc_measure_corr2d_interp")  # a digit in the name, like the two above
@@ -176,6 +197,9 @@ def load():
     lib.bchmc_density_particles.argtypes = [vp, C.c_int, dp, dp, dp, dp, u64, C.POINTER(DensityOpts), dp,
                                             C.POINTER(DensityStats)]
     lib.bchmc_catalogue_release.argtypes = [vp]
+    lib.bchmc_interp_particles.argtypes = [vp, C.c_int, dp, dp, dp, u64, C.POINTER(InterpField), C.c_int32,
+                                           C.POINTER(InterpOpts), dp, C.POINTER(InterpStats)]
+    lib.bchmc_interp_release.argtypes = [vp]
     lib.bchmc_probe_displacement.argtypes = [vp, dp, C.c_int, C.c_int]
     lib.bchmc_probe_displacement_z.argtypes = [vp, dp, C.c_int, C.c_int, C.c_int]
     lib.bchmc_philox_kat.argtypes = [C.POINTER(C.c_uint32)] * 3
@@ -621,6 +645,50 @@ class Engine:
     def catalogue_release(self):
         """Frees the catalogue buffers of ``density_particles``; a later call rebuilds them."""
         self._chk(self.lib.bchmc_catalogue_release(self.h))
+
+    def interp_particles(self, x=None, y=None, z=None, fields=(), kernel="cic", path=None, source="host"):
+        """interpolate_CIC / interpolate_TSC / interpolate_TSC_multi (interpolate_grid.cpp:108-286) on the device: one to
+        four grid fields read at the particles (x, y, z).  A field is an array of N values, ``"chain"`` (the resident chain
+        state), ``"deltax"`` or a bchmc_field name (``FIELDS``: ``"psix"``, ``"Vx"``, ``"window"`` ...).  ``kernel``:
+        ``"cic"`` or ``"tsc"``.  ``path``: None the engine decides, ``"direct"`` / 0, ``"tile"`` / 1.
+        ``source="forward"``: the handle's own particles after the last forward model (no columns).  A lost particle (TSC
+        outside its domain, a non-finite coordinate) is NaN in every field.
+        Returns (values[n_fields, n_part], stats), stats = dict(n_in, n_lost, max_per_tile, path_used)."""
+        cols = [None if a is None else np.ascontiguousarray(a, dtype=np.float64).reshape(-1) for a in (x, y, z)]
+        n_part = self.N if source == "forward" else (0 if cols[0] is None else cols[0].size)
+        for a in cols[1:]:
+            if a is not None and cols[0] is not None and a.size != cols[0].size:
+                raise ValueError("catalogue columns differ in length")
+        fields = list(fields)
+        keep, fd = [], (InterpField * max(len(fields), 1))()
+        lower = {k.lower(): v for k, v in FIELDS.items()}
+        for k, f in enumerate(fields):
+            if isinstance(f, str):
+                name = f.lower()
+                if name == "chain":
+                    fd[k] = InterpField(CORR_SOURCES["chain"], 0, None)
+                elif name == "deltax":
+                    fd[k] = InterpField(CORR_SOURCES["deltaX"], 0, None)
+                elif name in lower:
+                    fd[k] = InterpField(INTERP_HANDLE_FIELD, lower[name], None)
+                else:
+                    raise ValueError("unknown field %r" % f)
+            else:
+                keep.append(self._in(f))
+                fd[k] = InterpField(CORR_SOURCES["host"], 0, _p(keep[-1]))
+        out = np.empty((len(fields), n_part))
+        opts = InterpOpts(INTERP_KERNELS[kernel] if isinstance(kernel, str) else int(kernel), INTERP_PATHS[path])
+        st = InterpStats()
+        ptr = [None if a is None else _p(a) for a in cols]
+        self._chk(self.lib.bchmc_interp_particles(self.h, PART_SOURCES[source], ptr[0], ptr[1], ptr[2], n_part, fd,
+                                                  len(fields), C.byref(opts), _p(out.reshape(-1)) if out.size else None,
+                                                  C.byref(st)))
+        return out, dict(n_in=int(st.n_in), n_lost=int(st.n_lost), max_per_tile=int(st.max_per_tile),
+                         path_used=int(st.path_used))
+
+    def interp_release(self):
+        """Frees the buffers of ``interp_particles``; a later call rebuilds them."""
+        self._chk(self.lib.bchmc_interp_release(self.h))
 
     def chain_forward(self, rsd=-1):
         """Lag2Eul of the resident chain state: ``forward(chain_get_state(), rsd)`` without the field leaving the

@@ -172,6 +172,24 @@ def getDensity(hd, mk, xp, yp, zp, Par_mass=None, weightmass=False, kernel_h=0.0
     return hd.engine.density_particles(xp, yp, zp, w, mk=mk, kernel_h=kernel_h, to_nobs=to_nobs)
 
 
+def interpolate_CIC(hd, xp, yp, zp, field_grid, path=None):
+    """interpolate_CIC (interpolate_grid.cpp:108-120) of a field at a free particle list on ``hd``'s grid, upstream's
+    argument order from ``xp`` on -> N_OBJ values.  ``field_grid``: an array of N values, ``"chain"``, ``"deltax"`` or a
+    bchmc_field name (``"psix"``, ``"window"`` ...), read on the device."""
+    return hd.engine.interp_particles(xp, yp, zp, [field_grid], kernel="cic", path=path)[0][0]
+
+
+def interpolate_TSC(hd, xp, yp, zp, field_grid, path=None):
+    """interpolate_TSC (interpolate_grid.cpp:194-202) -> N_OBJ values, NaN for a particle outside the kernel's domain."""
+    return hd.engine.interp_particles(xp, yp, zp, [field_grid], kernel="tsc", path=path)[0][0]
+
+
+def interpolate_TSC_multi(hd, xp, yp, zp, field_grids, path=None):
+    """interpolate_TSC_multi (interpolate_grid.cpp:271-286) of 1 .. 4 fields -> (N_fields, N_OBJ): one set of cells and
+    weights per particle serves all of them."""
+    return hd.engine.interp_particles(xp, yp, zp, list(field_grids), kernel="tsc", path=path)[0]
+
+
 def Hamiltonian_mass(hd, signal=None):
     """HMC_mass.cc:315-368 on the device at ``signal`` (None: the resident chain state); the engine takes the new mass
     as if it had been uploaded.  Returns (mass_f, mass_r), None where the mass_type has none."""

@@ -28,7 +28,7 @@ SHIM_EXPORTS = ("bchmc_shim_Hamiltonian_EoM", "bchmc_shim_delta_Hamiltonian", "b
                 "bchmc_shim_setup_random_test", "bchmc_shim_make_initial_guess", "bchmc_shim_sizeof_mock",
                 "bchmc_shim_measure_corr_grid", "bchmc_shim_measure_corr2D", "bchmc_shim_chain_forward",
                 "bchmc_shim_interp_field", "bchmc_shim_measure_corr2D_interp", "bchmc_shim_measure_spec2D",
-                "bchmc_shim_getDensity")
+                "bchmc_shim_getDensity", "bchmc_shim_interpolate")
 
 _dp = C.POINTER(C.c_double)
 
@@ -128,6 +128,7 @@ def load():
                                                      C.c_int, C.c_int, C.c_char_p, sz]
     lib.bchmc_shim_measure_spec2D.argtypes = [hv, _dp, _dp, _dp, ul, C.c_int, C.c_int, C.c_char_p, sz]
     lib.bchmc_shim_getDensity.argtypes = [hv, C.c_int, _dp, _dp, _dp, _dp, ul, _dp, C.c_int, C.c_double, C.c_char_p, sz]
+    lib.bchmc_shim_interpolate.argtypes = [hv, C.c_int, _dp, _dp, _dp, ul, _dp, C.c_int, _dp, C.c_char_p, sz]
     lib.bchmc_shim_chain_forward.argtypes = [hv, C.c_int, C.c_char_p, sz]
     lib.bchmc_shim_chain_set_state.argtypes = [hv, _dp, C.c_char_p, sz]
     lib.bchmc_shim_chain_get_state.argtypes = [hv, _dp, C.c_char_p, sz]
@@ -358,6 +359,30 @@ class ShimHamil:
                                                  n_obj, _p(delta), int(bool(weightmass)), float(kernel_h), self._err,
                                                  len(self._err)))
         return delta
+
+    def _interpolate(self, which, xp, yp, zp, fields):
+        cols = [np.ascontiguousarray(a, dtype=np.float64).reshape(-1) for a in (xp, yp, zp)]
+        n_obj = cols[0].size
+        if any(a.size != n_obj for a in cols[1:]):
+            raise ValueError("catalogue columns differ in length")
+        grids = np.ascontiguousarray([self._in(f) for f in fields])
+        out = np.empty((len(fields), n_obj))
+        self._chk(self.lib.bchmc_shim_interpolate(C.byref(self.hd), which, _p(cols[0]), _p(cols[1]), _p(cols[2]), n_obj,
+                                                  _p(grids.reshape(-1)), len(fields), _p(out.reshape(-1)), self._err,
+                                                  len(self._err)))
+        return out
+
+    def interpolate_CIC(self, xp, yp, zp, field_grid):
+        """bchmc_shim::interpolate_CIC of a host grid at a free particle list -> N_OBJ values."""
+        return self._interpolate(1, xp, yp, zp, [field_grid])[0]
+
+    def interpolate_TSC(self, xp, yp, zp, field_grid):
+        """bchmc_shim::interpolate_TSC -> N_OBJ values (NaN outside TSC's domain)."""
+        return self._interpolate(2, xp, yp, zp, [field_grid])[0]
+
+    def interpolate_TSC_multi(self, xp, yp, zp, field_grids):
+        """bchmc_shim::interpolate_TSC_multi of 1 .. 4 host grids -> (N_fields, N_OBJ)."""
+        return self._interpolate(3, xp, yp, zp, list(field_grids))
 
     def chain_forward(self, use_rsd=-1):
         """bchmc_shim::chain_forward: Lag2Eul of the resident state; returns the view's deltaX array."""

@@ -347,6 +347,52 @@ void getDensity_SPH(HamilView *hd, ULONG N1, ULONG N2, ULONG N3, real_prec L1, r
                     N_OBJ, delta, weightmass, kernel_h);
 }
 
+namespace {
+// One interpolate_* call: the caller's grid must be the handle's, then bchmc_interp_particles on host fields
+void interp_on_handle(HamilView *hd, const char *name, int kernel, ULONG N1, ULONG N2, ULONG N3, real_prec d1, real_prec d2,
+                      real_prec d3, const real_prec *xp, const real_prec *yp, const real_prec *zp, ULONG N_OBJ,
+                      const real_prec *const *grids, int n_fields, real_prec *out) {
+  const HamilNumericalView *n = hd->numerical;
+  const real_prec d = n->L1 / (real_prec)n->N1;
+  if (N1 != n->N1 || N2 != n->N1 || N3 != n->N1 || d1 != d || d2 != d || d3 != d)
+    throw std::runtime_error(std::string(name) + ": the grid passed in is not the handle's");
+  if (n_fields < 1 || n_fields > BCHMC_INTERP_MAX_FIELDS) throw std::runtime_error(std::string(name) + ": N_fields outside 1..4");
+  bchmc_handle *h = engine_for(hd);
+  bchmc_interp_field f[BCHMC_INTERP_MAX_FIELDS];
+  for (int k = 0; k < n_fields; k++) f[k] = bchmc_interp_field{BCHMC_CORR_HOST, 0, grids[k]};
+  bchmc_interp_opts o{};
+  o.kernel = kernel;
+  o.path = -1;
+  const int rc = bchmc_interp_particles(h, BCHMC_PART_HOST, xp, yp, zp, N_OBJ, f, n_fields, &o, out, nullptr);
+  if (rc) fail(h, rc, name);
+}
+}  // namespace
+
+void interpolate_CIC(HamilView *hd, ULONG N1, ULONG N2, ULONG N3, real_prec L1, real_prec L2, real_prec L3, real_prec d1,
+                     real_prec d2, real_prec d3, const real_prec *xp, const real_prec *yp, const real_prec *zp,
+                     const real_prec *field_grid, ULONG N_OBJ, real_prec *interpolation) {
+  const real_prec L = hd->numerical->L1;
+  if (L1 != L || L2 != L || L3 != L) throw std::runtime_error("interpolate_CIC: the grid passed in is not the handle's");
+  interp_on_handle(hd, "interpolate_CIC", 1, N1, N2, N3, d1, d2, d3, xp, yp, zp, N_OBJ, &field_grid, 1, interpolation);
+}
+
+void interpolate_TSC(HamilView *hd, ULONG N1, ULONG N2, ULONG N3, real_prec d1, real_prec d2, real_prec d3,
+                     const real_prec *xp, const real_prec *yp, const real_prec *zp, const real_prec *field_grid, ULONG N_OBJ,
+                     real_prec *interpolation) {
+  interp_on_handle(hd, "interpolate_TSC", 2, N1, N2, N3, d1, d2, d3, xp, yp, zp, N_OBJ, &field_grid, 1, interpolation);
+}
+
+void interpolate_TSC_multi(HamilView *hd, ULONG N1, ULONG N2, ULONG N3, real_prec d1, real_prec d2, real_prec d3,
+                           real_prec *xp, real_prec *yp, real_prec *zp, ULONG N_OBJ, real_prec **field_grids,
+                           real_prec **interpolations, int N_fields) {
+  if (N_fields < 1 || N_fields > BCHMC_INTERP_MAX_FIELDS) throw std::runtime_error("interpolate_TSC_multi: N_fields outside 1..4");
+  // upstream's results are one array per field; the engine's are one field-major block
+  std::vector<real_prec> block((size_t)N_fields * N_OBJ);
+  interp_on_handle(hd, "interpolate_TSC_multi", 2, N1, N2, N3, d1, d2, d3, xp, yp, zp, N_OBJ, field_grids, N_fields,
+                   block.data());
+  for (int k = 0; k < N_fields; k++) std::copy(block.begin() + (size_t)k * N_OBJ, block.begin() + (size_t)(k + 1) * N_OBJ, interpolations[k]);
+}
+
 void chain_forward(HamilView *hd, int use_rsd) {
   bchmc_handle *h = engine_for(hd);
   const int rc = bchmc_chain_forward(h, use_rsd);
@@ -862,6 +908,27 @@ int bchmc_shim_getDensity(bchmc_shim::HamilView *hd, int mk, const double *xp, c
       case 2: bchmc_shim::getDensity_TSC(hd, N1, N1, N1, L, L, L, d, d, d, m1, m2, m3, xp, yp, zp, Par_mass, N_OBJ, delta); break;
       case 3: bchmc_shim::getDensity_SPH(hd, N1, N1, N1, L, L, L, d, d, d, m1, m2, m3, xp, yp, zp, Par_mass, N_OBJ, delta, weightmass != 0, kernel_h); break;
       default: throw std::runtime_error("getDensity: mk outside 0..3");
+    }
+  });
+}
+int bchmc_shim_interpolate(bchmc_shim::HamilView *hd, int which, const double *xp, const double *yp, const double *zp,
+                           unsigned long N_OBJ, const double *fields, int n_fields, double *out, char *err, size_t errlen) {
+  return guarded(err, errlen, [&] {
+    const bchmc_shim::HamilNumericalView *n = hd->numerical;
+    const unsigned long N1 = n->N1, N = N1 * N1 * N1;
+    const double L = n->L1, d = L / (double)N1;
+    if (which == 1 || which == 2) {
+      if (n_fields != 1) throw std::runtime_error("interpolate: one field for interpolate_CIC / interpolate_TSC");
+      if (which == 1) bchmc_shim::interpolate_CIC(hd, N1, N1, N1, L, L, L, d, d, d, xp, yp, zp, fields, N_OBJ, out);
+      else bchmc_shim::interpolate_TSC(hd, N1, N1, N1, d, d, d, xp, yp, zp, fields, N_OBJ, out);
+    } else if (which == 3) {
+      if (n_fields < 1 || n_fields > 4) throw std::runtime_error("interpolate: N_fields outside 1..4");
+      double *grids[4], *outs[4];
+      for (int k = 0; k < n_fields; k++) grids[k] = const_cast<double *>(fields) + (size_t)k * N, outs[k] = out + (size_t)k * N_OBJ;
+      bchmc_shim::interpolate_TSC_multi(hd, N1, N1, N1, d, d, d, const_cast<double *>(xp), const_cast<double *>(yp),
+                                        const_cast<double *>(zp), N_OBJ, grids, outs, n_fields);
+    } else {
+      throw std::runtime_error("interpolate: which outside 1..3");
     }
   });
 }

@@ -384,6 +384,70 @@ int bchmc_density_particles(bchmc_handle *h, bchmc_part_source src, const double
                             const double *w, uint64_t n_part, const bchmc_density_opts *opts, double *out /* N or NULL */,
                             bchmc_density_stats *stats /* or NULL */);
 int bchmc_catalogue_release(bchmc_handle *h);   /* frees the catalogue buffers; a later call rebuilds them */
+
+/* ---- interpolate_CIC / interpolate_TSC / interpolate_TSC_multi of a free particle catalogue (interpolate_grid.cpp:82-120,
+ * 134-202, 207-286; HMC_models_unused.cpp:22-25 reads deltaX, nobs, noise and window this way) --------------------------
+ * One to four grid fields read at the positions of n_part particles, on the device: the reverse direction of
+ * bchmc_density_particles.  out[f * n_part + p] is field f at particle p.  Seven properties:
+ *  I1 Positions.  BCHMC_PART_HOST: host columns, which cross PCIe in the catalogue's batches of 2^20 particles; the results
+ *     return batch by batch, so the device memory of a call does not grow with n_part.  BCHMC_PART_FORWARD: the handle's
+ *     own particles after the last forward model (x, y, z NULL, n_part = N; out[f * N + p] belongs to lattice particle p).
+ *     Neither interpolator takes min1..3 upstream: coordinates are box coordinates whatever the handle's min is.
+ *     On fp32 handles a position is converted to float first; the domain test, the cells and the weights see the float's
+ *     value (D4 of bchmc_density_particles).
+ *  I2 Fields.  BCHMC_CORR_HOST: `host`, N doubles, held as the handle's storage type like an uploaded array.
+ *     BCHMC_CORR_CHAIN_STATE: the real-space field bchmc_chain_get_state returns.  BCHMC_CORR_DELTAX and
+ *     BCHMC_INTERP_HANDLE_FIELD: what bchmc_fetch of BCHMC_F_DELTAX / of `field` would return at that moment (PSIX..Z,
+ *     VX..Z, RHO, PART_LIKE, the uploaded NOBS / NOISE / WINDOW and the rest), with bchmc_fetch's own errors.  The
+ *     sources are staged once per call into n_fields grid arrays the feature owns.  Several fields in one call are
+ *     interpolate_TSC_multi, or several interpolate_CICs: one set of cells and weights per particle serves all of them.
+ *  I3 Arithmetic.  Double, the reference's expressions in its operand order, no FMA contraction.  CIC: getCICcells /
+ *     getCICweights with both folds of pacman_coordinate, the eight terms of :92-99 each as F * a * b * c left to right,
+ *     summed in source order.  TSC: :142-188, the 27 terms in i, j, k order as wx[i] * wy[j] * wz[k] * field, with
+ *     wx[2] and wy[2] computed from dz as upstream computes them (:166-167).  A field value is read in the storage type
+ *     and widened; `out` is never rounded to float.
+ *  I4 Domain.  CIC folds: every finite coordinate is in.  TSC upstream casts xp / d to unsigned without a test (undefined
+ *     below 0, past the array from cell n on): a particle is kept if 0 <= x and (unsigned)(x / d) < n on every axis --
+ *     x < L is not enough (n = 9, L = 1: the double below 1.0 lands in cell 9).  A non-finite coordinate is lost under
+ *     either kernel.  A lost particle gets a quiet NaN in every field of `out` and counts in stats->n_lost, the others
+ *     in n_in.
+ *  I5 No result depends on another particle, on the path, on the batch or on the order inside a tile, and nothing is
+ *     added atomically to a result: every handle, deterministic or not, returns the same bits.
+ *  I6 What a call leaves alone: the chain state, the momenta, a pending proposal, deltaX, rho, Psi, pos*, the carried
+ *     gradient and -log L, and the record slots (it uses the transfer staging and buffers of its own, none of the
+ *     catalogue's: bchmc_catalogue_release and bchmc_interp_release are independent, in either order).
+ *  I7 Paths.  opts->path = 1: the particles of a batch are binned by the tile of their home cell (cell_index1 for CIC,
+ *     the particle's cell for TSC), a tile's records are cut into work items of bounded length, and a work item reads the
+ *     fields from an LDS image of tile plus halo; stats->max_per_tile is the largest tile population of a batch.
+ *     path = 0: one thread per particle reads the grid, in the same arithmetic; max_per_tile is 0.  path = -1: the engine
+ *     decides (interp_plan.hpp; DESIGN 9.8 has the figures behind the rule).  stats->path_used says which one ran.
+ * The buffers (bchmc_live_resources counts them) are built by the first call, kept for the next, and freed by
+ * bchmc_interp_release and bchmc_destroy.  n_part = 0 succeeds and writes nothing.
+ * Refused before anything is queued, the handle usable: opts NULL; kernel other than 1 / 2; path outside -1..1; n_fields
+ * outside 1..BCHMC_INTERP_MAX_FIELDS; fields NULL; a BCHMC_CORR_HOST field without its array, or an array given with
+ * another source; an unknown source or bchmc_field; out NULL with n_part > 0; a NULL column with BCHMC_PART_HOST; a column
+ * given, or n_part != N, with BCHMC_PART_FORWARD; n_part > 2^31 - 1 -- all BCHMC_ERR_ARG.  No chain state, no forward
+ * evaluation for a field or for BCHMC_PART_FORWARD, a never-uploaded input: BCHMC_ERR_STATE.  path = 1 on a handle
+ * without a tile partition (odd Nx; bchmc_tile_info): BCHMC_ERR_UNSUPPORTED. */
+enum { BCHMC_INTERP_MAX_FIELDS = 4 };
+enum { BCHMC_INTERP_HANDLE_FIELD = 3 };  /* a source beside the three of bchmc_corr_source: `field` names a bchmc_field */
+typedef struct bchmc_interp_field {
+  int32_t source;      /* bchmc_corr_source (HOST, CHAIN_STATE, DELTAX), or BCHMC_INTERP_HANDLE_FIELD = 3 */
+  int32_t field;       /* a bchmc_field when source is BCHMC_INTERP_HANDLE_FIELD, else ignored */
+  const double *host;  /* N doubles for HOST, NULL otherwise */
+} bchmc_interp_field;
+typedef struct bchmc_interp_opts {
+  int32_t kernel;      /* 1 CIC, 2 TSC (the mk numbering) */
+  int32_t path;        /* -1 the engine decides; 0 direct kernel; 1 tile kernel (BCHMC_ERR_UNSUPPORTED where the handle has no tiles) */
+  int32_t reserved[2];
+} bchmc_interp_opts;
+typedef struct bchmc_interp_stats { uint64_t n_in, n_lost, max_per_tile; int32_t path_used, reserved; } bchmc_interp_stats;
+
+int bchmc_interp_particles(bchmc_handle *h, bchmc_part_source psrc, const double *x, const double *y, const double *z,
+                           uint64_t n_part, const bchmc_interp_field *fields, int32_t n_fields,
+                           const bchmc_interp_opts *opts, double *out /* n_fields * n_part, field-major */,
+                           bchmc_interp_stats *stats /* or NULL */);
+int bchmc_interp_release(bchmc_handle *h);   /* frees the interpolation buffers; a later call rebuilds them */
 /* Lag2Eul of the resident chain state: bchmc_forward without the host array (it starts from the chain's q^, so no field
  * crosses PCIe and no transform pair is spent).  use_rsd as there.  Leaves deltaX / pos* in the handle, synchronises and
  * adapts the binning's record slots like bchmc_forward; drops a pending proposal like it.  The chain state, the momenta

@@ -18,6 +18,10 @@
 //                                                   tools/2D_powspec.cc:25-110         -> bchmc_shim::measure_spec2D
 //   void getDensity_NGP / _CIC / _TSC / _SPH(N1, N2, N3, L1, L2, L3, d1, d2, d3, min1, min2, min3, xp, yp, zp, Par_mass,
 //                        N_OBJ, delta[, weightmass[, kernel_h]])      massFunctions.cc:49-495 -> bchmc_shim::getDensity_NGP ..
+//   void interpolate_CIC(N1, N2, N3, L1, L2, L3, d1, d2, d3, xp, yp, zp, field_grid, N_OBJ, interpolation)
+//   void interpolate_TSC(N1, N2, N3, d1, d2, d3, xp, yp, zp, field_grid, N_OBJ, interpolation)
+//   void interpolate_TSC_multi(N1, N2, N3, d1, d2, d3, xp, yp, zp, N_OBJ, field_grids, interpolations, N_fields)
+//                                                   interpolate_grid.cpp:108-286       -> bchmc_shim::interpolate_CIC ..
 // Errors are std::runtime_error, like the reference's (single catch in main.cc:195-197).
 #ifndef BCHMC_SHIM_HPP
 #define BCHMC_SHIM_HPP
@@ -162,6 +166,19 @@ void getDensity_SPH(HamilView *hd, ULONG N1, ULONG N2, ULONG N3, real_prec L1, r
                     real_prec d2, real_prec d3, real_prec min1, real_prec min2, real_prec min3, const real_prec *xp,
                     const real_prec *yp, const real_prec *zp, const real_prec *Par_mass, ULONG N_OBJ, real_prec *delta,
                     bool weightmass, real_prec kernel_h);
+// interpolate_grid.cpp:108-120, 194-202, 271-286 on the device (bchmc_interp_particles): host grids read at a free list of
+// N_OBJ particles, upstream's argument lists behind the view.  The grid is the handle's (std::runtime_error otherwise).
+// A particle outside TSC's domain, or with a non-finite coordinate, gets a quiet NaN (property I4 in bchmc.h).
+// interpolate_TSC_multi takes 1 .. BCHMC_INTERP_MAX_FIELDS fields.
+void interpolate_CIC(HamilView *hd, ULONG N1, ULONG N2, ULONG N3, real_prec L1, real_prec L2, real_prec L3, real_prec d1,
+                     real_prec d2, real_prec d3, const real_prec *xp, const real_prec *yp, const real_prec *zp,
+                     const real_prec *field_grid, ULONG N_OBJ, real_prec *interpolation);
+void interpolate_TSC(HamilView *hd, ULONG N1, ULONG N2, ULONG N3, real_prec d1, real_prec d2, real_prec d3,
+                     const real_prec *xp, const real_prec *yp, const real_prec *zp, const real_prec *field_grid, ULONG N_OBJ,
+                     real_prec *interpolation);
+void interpolate_TSC_multi(HamilView *hd, ULONG N1, ULONG N2, ULONG N3, real_prec d1, real_prec d2, real_prec d3,
+                           real_prec *xp, real_prec *yp, real_prec *zp, ULONG N_OBJ, real_prec **field_grids,
+                           real_prec **interpolations, int N_fields);
 // Lag2Eul of the resident chain state (dump_deltas' second forward model, IOfunctionsGen.cc:158-169, with use_rsd = 0);
 // hd->deltaX / pos* <- this evaluation's.  use_rsd < 0: as configured.
 void chain_forward(HamilView *hd, int use_rsd);
@@ -310,6 +327,10 @@ int bchmc_shim_measure_spec2D(bchmc_shim::HamilView *hd, const double *signal, d
 int bchmc_shim_getDensity(bchmc_shim::HamilView *hd, int mk, const double *xp, const double *yp, const double *zp,
                           const double *Par_mass, unsigned long N_OBJ, double *delta, int weightmass, double kernel_h,
                           char *err, size_t errlen);
+/* interpolate_CIC (which = 1), interpolate_TSC (2) or interpolate_TSC_multi (3) with the view's own geometry; fields:
+ * n_fields grids of N doubles one after the other, out: n_fields * N_OBJ, field-major */
+int bchmc_shim_interpolate(bchmc_shim::HamilView *hd, int which, const double *xp, const double *yp, const double *zp,
+                           unsigned long N_OBJ, const double *fields, int n_fields, double *out, char *err, size_t errlen);
 int bchmc_shim_chain_forward(bchmc_shim::HamilView *hd, int use_rsd, char *err, size_t errlen);
 int bchmc_shim_chain_set_state(bchmc_shim::HamilView *hd, const double *x, char *err, size_t errlen);
 int bchmc_shim_chain_get_state(bchmc_shim::HamilView *hd, double *x, char *err, size_t errlen);
