@@ -119,7 +119,18 @@ struct bchmc_handle {
   struct Mock {
     DevBuf<unsigned long long> cnt, off, gsum, goff, res;
   } mock;
-  DevBuf<double> spec_bins;                          // measure_spectrum's 3 * n_bin accumulators
+  DevBuf<double> spec_bins;                          // measure_spectrum's 3 * n_bin accumulators, the cross-spectrum's 5 * n_bin
+  DevBytes cross_ak;                                 // Nhp complex: the first transform of bchmc_measure_cross_spectrum (the
+                                                     // second is in tC), taken by its first call and kept like spec_bins
+  // bchmc_ensemble_* (ensemble.hpp): the running accumulators.  A slot's arrays are taken by its first add or merge,
+  // kept by bchmc_ensemble_reset, freed by bchmc_ensemble_release and bchmc_destroy.
+  struct Ens {
+    struct Slot {
+      uint64_t count = 0;
+      DevBuf<double> mean, m2;                       // N doubles each on every handle, cell order k + n (j + n i)
+    } slot[BCHMC_ENS_SLOTS];
+    int ncu = 0;                                     // compute units of the device (0: not asked yet)
+  } ens;
   // measure_corr / measure_corr2d (corr.hpp): accumulators and the geometry of the last n_bin of each function, kept in
   // the handle like spec_bins (the driver measures after every sample with the same n_bin)
   struct Corr1 {
@@ -839,6 +850,53 @@ int spectrum_bins(bchmc_handle *h, const void *xk, uint64_t n_bin, double *kmode
     const double cnt = hb[2 * n_bin + l];
     kmode[l] = cnt > 0. ? hb[l] / cnt : 0.;
     power[l] = cnt > 0. ? hb[n_bin + l] / cnt * NORM : 0.;
+  }
+  return BCHMC_OK;
+}
+
+// The cross-spectrum of two half-complex transforms in measure_spectrum's bins (k_cross_spectrum): per bin kmode, nmode
+// (may be null), both auto powers normalised as spectrum_bins normalises its one, cross = the same of Re(A conj B), and
+// coeff = cross / sqrt(power_a power_b) from those three (0 for an empty bin or a zero product, NaN for a NaN one).
+// Synchronises.
+int cross_bins(bchmc_handle *h, const void *ak, const void *bk, uint64_t n_bin, double *kmode, uint64_t *nmode,
+               double *power_a, double *power_b, double *cross, double *coeff) {
+#pragma clang fp contract(off)
+  CHK(dev_reserve(h, h->spec_bins, kCrossSums * (size_t)n_bin));
+  double *bins = h->spec_bins;
+  const size_t lds = kCrossSums * (size_t)n_bin * sizeof(double);
+  HIPCHK(hipMemsetAsync(bins, 0, lds, h->stream));
+  const Geo &g = h->g;
+  const double dk = spectrum_dk(g, n_bin);
+  const int grid = std::min(nblk_stride(g.Nhp), 512);
+  if (h->f32) {
+    if (lds > ((size_t)48 << 10))  // 2048 bins are 80 KiB of the CU's 160
+      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_cross_spectrum<float>),
+                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    k_cross_spectrum<float><<<grid, 256, lds, h->stream>>>(g, reinterpret_cast<const float2 *>(ak),
+                                                           reinterpret_cast<const float2 *>(bk), (int)n_bin, dk, bins);
+  } else {
+    if (lds > ((size_t)48 << 10))
+      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_cross_spectrum<double>),
+                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    k_cross_spectrum<double><<<grid, 256, lds, h->stream>>>(g, reinterpret_cast<const double2 *>(ak),
+                                                            reinterpret_cast<const double2 *>(bk), (int)n_bin, dk, bins);
+  }
+  std::vector<double> hb(kCrossSums * n_bin);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = hipMemcpyAsync(hb.data(), bins, hb.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+  if (e != hipSuccess) return h->fail(BCHMC_ERR_HIP, "measure_cross_spectrum: %s", hipGetErrorString(e));
+  const double N = (double)g.N, NORM = g.L * g.L * g.L / N / N;  // FOURIER_DEF_2, field_statistics.cpp:73-75
+  for (uint64_t l = 0; l < n_bin; l++) {
+    const double cnt = hb[4 * n_bin + l];
+    const bool pop = cnt > 0.;
+    kmode[l] = pop ? hb[l] / cnt : 0.;
+    if (nmode) nmode[l] = pop ? (uint64_t)cnt : 0;
+    power_a[l] = pop ? hb[n_bin + l] / cnt * NORM : 0.;
+    power_b[l] = pop ? hb[2 * n_bin + l] / cnt * NORM : 0.;
+    cross[l] = pop ? hb[3 * n_bin + l] / cnt * NORM : 0.;
+    const double pp = power_a[l] * power_b[l];
+    coeff[l] = (pop && pp != 0.) ? cross[l] / std::sqrt(pp) : 0.;
   }
   return BCHMC_OK;
 }
@@ -2402,6 +2460,38 @@ struct Pipe {
     }
     CHK(upres_real(h, src));
     return fft_exec(h, h->r2c1, h->ioq, h->tC, BCHMC_K_FFT_R2C);
+  }
+
+  // One source of bchmc_measure_cross_spectrum: its transform as spectrum_source obtains it, a host signal staged here
+  // (the two sources share dstage and ioq, one after the other on the stream), a fresh R2C landing in `out`.
+  static int cross_source(bchmc_handle *h, int src, const double *signal, void *out, const void **xk) {
+    *xk = out;
+    if (src == BCHMC_CORR_HOST) {
+      CHK(h2d(h, h->dstage, signal, h->g.N * sizeof(double)));
+      return r2c_state(h, h->dstage, h->ioq, out);
+    }
+    if (src == BCHMC_CORR_CHAIN_STATE) {
+      *xk = h->cq;
+      return BCHMC_OK;
+    }
+    CHK(upres_real(h, src));
+    return fft_exec(h, h->r2c1, h->ioq, out, BCHMC_K_FFT_R2C);
+  }
+
+  // ---- bchmc_ensemble_add (ensemble.hpp) -------------------------------------------------------------------------------
+  // One Welford step of a slot from the source: a host signal from its staged doubles in dstage (an fp32 handle loses
+  // nothing of it), the chain state and deltaX as a real field of T in ioq, widened on load -- the chain state through
+  // c2r_scaled like chain_fetch's c2r_state, deltaX by k_overdens like Pipe::fetch.  Scratch only: tC, ioq.
+  static int ens_add(bchmc_handle *h, int src, double *mean, double *m2, double c, int blocks) {
+    const long long N = h->g.N;
+    if (src != BCHMC_CORR_HOST) CHK(upres_real(h, src));
+    ProfScope ps(h, BCHMC_K_OTHER);
+    if (src == BCHMC_CORR_HOST)
+      k_ens_add<double><<<blocks, kEnsBlock, 0, h->stream>>>(N, h->dstage.get(), mean, m2, c);
+    else
+      k_ens_add<T><<<blocks, kEnsBlock, 0, h->stream>>>(N, R(h->ioq), mean, m2, c);
+    HIPCHK(hipGetLastError());
+    return BCHMC_OK;
   }
 
   // ---- measure_spec2D (spec2d.hpp; spec2d_setup has run for n_bin) ----------------------------------------------------
@@ -3993,6 +4083,170 @@ int bchmc_measure_spectrum2d(bchmc_handle *h, bchmc_corr_source src, const doubl
   const void *xk = nullptr;
   CHK(DISPATCH(h, spectrum_source(h, (int)src, &xk)));
   return DISPATCH(h, spec2d_bins(h, xk, n_bin, kmode, nmode, power));
+}
+
+int bchmc_measure_cross_spectrum(bchmc_handle *h, bchmc_corr_source src_a, const double *signal_a, bchmc_corr_source src_b,
+                                 const double *signal_b, uint64_t n_bin, double *kmode, uint64_t *nmode, double *power_a,
+                                 double *power_b, double *cross, double *coeff) {
+  if (!h || !kmode || !power_a || !power_b || !cross || !coeff) return BCHMC_ERR_ARG;
+  const char *name = "measure_cross_spectrum";
+  if (n_bin == 0 || n_bin > 2048) return h->fail(BCHMC_ERR_ARG, "%s: n_bin = %llu outside 1..2048", name, (unsigned long long)n_bin);
+  CHK(source_args(h, name, src_a, signal_a));
+  CHK(source_args(h, name, src_b, signal_b));
+  ENTER(h);
+  CHK(source_state(h, src_a));
+  CHK(source_state(h, src_b));
+  if (!h->cross_ak) CHK(dev_alloc(h, h->cross_ak, 2 * (size_t)h->g.Nhp * h->esz));
+  const void *ak = nullptr, *bk = nullptr;
+  CHK(DISPATCH(h, cross_source(h, (int)src_a, signal_a, h->cross_ak, &ak)));
+  CHK(DISPATCH(h, cross_source(h, (int)src_b, signal_b, h->tC, &bk)));
+  return cross_bins(h, ak, bk, n_bin, kmode, nmode, power_a, power_b, cross, coeff);
+}
+
+// ---- bchmc_ensemble_* (ensemble.hpp) -----------------------------------------------------------------------------------
+static int ens_slot(bchmc_handle *h, const char *name, int32_t slot) {
+  if (slot < 0 || slot >= BCHMC_ENS_SLOTS)
+    return h->fail(BCHMC_ERR_ARG, "%s: slot %d outside 0..%d", name, (int)slot, BCHMC_ENS_SLOTS - 1);
+  return BCHMC_OK;
+}
+// Workgroups of the ensemble kernels: enough to cover the pairs of cells, at most kEnsBlocksPerCu per compute unit
+static int ens_blocks(bchmc_handle *h, int *blocks) {
+  if (!h->ens.ncu) {
+    int ncu = 0;
+    HIPCHK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, h->c.device));
+    h->ens.ncu = std::max(ncu, 1);
+  }
+  const long long pairs = h->g.N >> 1;
+  *blocks = (int)std::min<long long>((pairs + kEnsBlock - 1) / kEnsBlock, (long long)h->ens.ncu * kEnsBlocksPerCu);
+  return BCHMC_OK;
+}
+// The slot's two arrays, zeroed on the handle's stream, on its first add or merge; a failed allocation leaves the slot
+// empty and the handle usable.
+static int ens_take(bchmc_handle *h, bchmc_handle::Ens::Slot &s) {
+  if (s.mean && s.m2) return BCHMC_OK;
+  int rc = dev_alloc(h, s.mean, (size_t)h->g.N);
+  if (!rc) rc = dev_alloc(h, s.m2, (size_t)h->g.N);
+  if (rc) {
+    (void)s.mean.release();
+    (void)s.m2.release();
+    s.count = 0;
+  }
+  return rc;
+}
+
+int bchmc_ensemble_add(bchmc_handle *h, int32_t slot, bchmc_corr_source src, const double *signal) {
+  if (!h) return BCHMC_ERR_ARG;
+  const char *name = "ensemble_add";
+  CHK(ens_slot(h, name, slot));
+  CHK(source_args(h, name, src, signal));
+  ENTER(h);
+  CHK(source_state(h, src));
+  auto &s = h->ens.slot[slot];
+  if (s.count == UINT64_MAX) return h->fail(BCHMC_ERR_STATE, "%s: the count of slot %d is full", name, (int)slot);
+  int blocks = 0;
+  CHK(ens_blocks(h, &blocks));
+  CHK(ens_take(h, s));
+  if (signal) CHK(h2d(h, h->dstage, signal, h->g.N * sizeof(double)));
+  CHK(DISPATCH(h, ens_add(h, (int)src, s.mean, s.m2, (double)(s.count + 1), blocks)));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  s.count++;
+  return BCHMC_OK;
+}
+
+int bchmc_ensemble_count(bchmc_handle *h, int32_t slot, uint64_t *count) {
+  if (!h || !count) return BCHMC_ERR_ARG;
+  CHK(ens_slot(h, "ensemble_count", slot));
+  *count = h->ens.slot[slot].count;
+  return BCHMC_OK;
+}
+
+int bchmc_ensemble_fetch(bchmc_handle *h, int32_t slot, bchmc_ens_what what, double *out) {
+  if (!h || !out) return BCHMC_ERR_ARG;
+  const char *name = "ensemble_fetch";
+  CHK(ens_slot(h, name, slot));
+  if (what != BCHMC_ENS_MEAN && what != BCHMC_ENS_VARIANCE && what != BCHMC_ENS_STD && what != BCHMC_ENS_M2)
+    return h->fail(BCHMC_ERR_ARG, "%s: unknown quantity %d", name, (int)what);
+  ENTER(h);
+  auto &s = h->ens.slot[slot];
+  const uint64_t need = (what == BCHMC_ENS_VARIANCE || what == BCHMC_ENS_STD) ? 2 : 1;
+  if (s.count < need)
+    return h->fail(BCHMC_ERR_STATE, "%s: slot %d holds %llu samples, this needs %llu", name, (int)slot,
+                   (unsigned long long)s.count, (unsigned long long)need);
+  const size_t bytes = (size_t)h->g.N * sizeof(double);
+  if (what == BCHMC_ENS_MEAN) return d2h(h, out, s.mean, bytes);
+  if (what == BCHMC_ENS_M2) return d2h(h, out, s.m2, bytes);
+  int blocks = 0;
+  CHK(ens_blocks(h, &blocks));
+  {
+    ProfScope ps(h, BCHMC_K_OTHER);
+    const double cm1 = (double)(s.count - 1);
+    if (what == BCHMC_ENS_STD)
+      k_ens_moment<true><<<blocks, kEnsBlock, 0, h->stream>>>(h->g.N, s.m2.get(), h->dstage.get(), cm1);
+    else
+      k_ens_moment<false><<<blocks, kEnsBlock, 0, h->stream>>>(h->g.N, s.m2.get(), h->dstage.get(), cm1);
+    HIPCHK(hipGetLastError());
+  }
+  return d2h(h, out, h->dstage, bytes);
+}
+
+int bchmc_ensemble_merge(bchmc_handle *h, int32_t slot, uint64_t count_b, const double *mean_b, const double *m2_b) {
+  if (!h) return BCHMC_ERR_ARG;
+  const char *name = "ensemble_merge";
+  CHK(ens_slot(h, name, slot));
+  if (count_b == 0) return BCHMC_OK;  // nothing to fold in: the arrays are not looked at
+  if (!mean_b || !m2_b) return h->fail(BCHMC_ERR_ARG, "%s: mean_b and m2_b must be given with count_b > 0", name);
+  ENTER(h);
+  auto &s = h->ens.slot[slot];
+  if (count_b > UINT64_MAX - s.count) return h->fail(BCHMC_ERR_ARG, "%s: the two counts do not fit 64 bits", name);
+  int blocks = 0;
+  CHK(ens_blocks(h, &blocks));
+  CHK(ens_take(h, s));
+  const size_t N = (size_t)h->g.N, bytes = N * sizeof(double);
+  if (s.count == 0) {  // into an empty slot: a copy, bit for bit
+    int rc = h2d(h, s.mean, mean_b, bytes);
+    if (!rc) rc = h2d(h, s.m2, m2_b, bytes);
+    if (rc) {  // half a copy must not pass for an empty slot: the next add or merge takes zeroed arrays again
+      (void)hipStreamSynchronize(h->stream);
+      (void)s.mean.release();
+      (void)s.m2.release();
+      return rc;
+    }
+  } else {
+    CHK(h2d(h, h->dstage, mean_b, bytes));
+    CHK(h2d(h, h->dstage + N, m2_b, bytes));
+    const double na = (double)s.count, nb = (double)count_b, nab = (double)(s.count + count_b);
+    const double w = nb / nab, c = na * nb / nab;
+    ProfScope ps(h, BCHMC_K_OTHER);
+    k_ens_merge<<<blocks, kEnsBlock, 0, h->stream>>>(h->g.N, h->dstage.get(), h->dstage.get() + N, s.mean.get(), s.m2.get(), w, c);
+    HIPCHK(hipGetLastError());
+  }
+  HIPCHK(hipStreamSynchronize(h->stream));
+  s.count += count_b;
+  return BCHMC_OK;
+}
+
+int bchmc_ensemble_reset(bchmc_handle *h, int32_t slot) {
+  if (!h) return BCHMC_ERR_ARG;
+  CHK(ens_slot(h, "ensemble_reset", slot));
+  ENTER(h);
+  auto &s = h->ens.slot[slot];
+  s.count = 0;
+  if (s.mean) HIPCHK(hipMemsetAsync(s.mean, 0, (size_t)h->g.N * sizeof(double), h->stream));
+  if (s.m2) HIPCHK(hipMemsetAsync(s.m2, 0, (size_t)h->g.N * sizeof(double), h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return BCHMC_OK;
+}
+
+int bchmc_ensemble_release(bchmc_handle *h) {
+  if (!h) return BCHMC_ERR_ARG;
+  ENTER(h);
+  HIPCHK(hipStreamSynchronize(h->stream));
+  for (auto &s : h->ens.slot) {
+    (void)s.mean.release();
+    (void)s.m2.release();
+    s.count = 0;
+  }
+  return BCHMC_OK;
 }
 
 // max|w| and the first non-finite weight (*bad, -1: none) in one pass over the column, on the threads the staging copies

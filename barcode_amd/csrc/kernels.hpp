@@ -26,6 +26,8 @@
 #include "spectrum.hpp"  // measure_spectrum
 #include "corr.hpp"  // measure_corr_grid / measure_corr2D: |x^|^2, integer LDS histogram (1-D), sorted-row slices (2-D)
 #include "spec2d.hpp"  // measure_spec2D: sorted-row slices over chunks of k, Hermitian-weighted reduce
+#include "cross_spectrum.hpp"  // bchmc_measure_cross_spectrum: k_spectrum over two transforms at once
+#include "ensemble.hpp"  // bchmc_ensemble_*: Welford and Chan updates of a running mean and m2, variance / standard deviation
 #include "upres.hpp"  // interp_field (CIC gather onto another grid) and the zero-padded power spectrum of 2D_corr_fct_interp.cc
 #include "mock.hpp"  // setup_random_test / make_initial_guess: window, rank of windowed cells on the stream, noise, guesses
 #include "mass.hpp"  // Hamiltonian_mass: element-wise masses and the Jasche+13 first-order diagonal

@@ -128,7 +128,9 @@ EXPORTS = ("bchmc_create", "bchmc_destroy", "bchmc_strerror", "bchmc_last_error"
            "bchmc_comm_transport", "bchmc_garfield_walk_index", "bchmc_hamiltonian_mass",
            "bchmc_setup_random_test", "bchmc_make_initial_guess", "bchmc_measure_corr", "bchmc_chain_forward",
            "bchmc_probe_displacement", "bchmc_probe_displacement_z", "bchmc_interp_upres", "bchmc_upres_release", "bchmc_measure_spectrum_src",
-           "bchmc_density_particles", "bchmc_catalogue_release", "bchmc_interp_particles", "bchmc_interp_release")
+           "bchmc_density_particles", "bchmc_catalogue_release", "bchmc_interp_particles", "bchmc_interp_release",
+           "bchmc_measure_cross_spectrum", "bchmc_ensemble_add", "bchmc_ensemble_count", "bchmc_ensemble_fetch",
+           "bchmc_ensemble_merge", "bchmc_ensemble_reset", "bchmc_ensemble_release")
 # declared as well, listed apart: the header scan of the ABI test matches names of letters and underscores only
 EXPORTS_MT19937 = ("bchmc_chain_draw_momenta_mt19937", "bchmc_mt19937_jump")
 EXPORTS_CORR2D = ("bchmc_measure_corr2d", "bchmc_measure_corr2d_interp")  # a digit in the name, like the two above
@@ -136,6 +138,8 @@ EXPORTS_SPEC2D = ("bchmc_measure_spectrum2d",)  # likewise
 
 # bchmc_corr_source
 CORR_SOURCES = dict(host=0, chain=1, deltaX=2)
+ENS_SLOTS = 4                                         # BCHMC_ENS_SLOTS
+ENS_WHAT = dict(mean=0, variance=1, std=2, m2=3)      # bchmc_ens_what
 
 
 def load():
@@ -193,6 +197,13 @@ def load():
     lib.bchmc_upres_release.argtypes = [vp]
     lib.bchmc_measure_spectrum_src.argtypes = [vp, C.c_int, dp, C.c_uint64, dp, dp]
     lib.bchmc_measure_spectrum2d.argtypes = [vp, C.c_int, dp, C.c_uint64, dp, C.POINTER(u64), dp]
+    lib.bchmc_measure_cross_spectrum.argtypes = [vp, C.c_int, dp, C.c_int, dp, C.c_uint64, dp, C.POINTER(u64), dp, dp, dp, dp]
+    lib.bchmc_ensemble_add.argtypes = [vp, C.c_int32, C.c_int, dp]
+    lib.bchmc_ensemble_count.argtypes = [vp, C.c_int32, C.POINTER(u64)]
+    lib.bchmc_ensemble_fetch.argtypes = [vp, C.c_int32, C.c_int, dp]
+    lib.bchmc_ensemble_merge.argtypes = [vp, C.c_int32, u64, dp, dp]
+    lib.bchmc_ensemble_reset.argtypes = [vp, C.c_int32]
+    lib.bchmc_ensemble_release.argtypes = [vp]
     lib.bchmc_chain_forward.argtypes = [vp, C.c_int]
     lib.bchmc_density_particles.argtypes = [vp, C.c_int, dp, dp, dp, dp, u64, C.POINTER(DensityOpts), dp,
                                             C.POINTER(DensityStats)]
@@ -561,6 +572,71 @@ class Engine:
                                                     nmode.ctypes.data_as(C.POINTER(C.c_uint64)), _p(power)))
         shape = (n_bin, n_bin)
         return kmode.reshape(shape), nmode.reshape(shape), power.reshape(shape)
+
+    def measure_cross_spectrum(self, signal_a=None, signal_b=None, n_bin=200, source_a=None, source_b=None):
+        """The cross-spectrum of two fields in measure_spectrum's bins (bchmc_measure_cross_spectrum).  Each side is a
+        host field, the resident chain state (the default without a signal) or the handle's deltaX, sources as in
+        ``measure_corr``.  Returns (kmode, nmode, power_a, power_b, cross, coeff), n_bin each;
+        coeff = cross / sqrt(power_a power_b), 0 in an empty bin."""
+        src = [s if s is not None else ("chain" if sig is None else "host")
+               for s, sig in ((source_a, signal_a), (source_b, signal_b))]
+        n_bin = int(n_bin)
+        size = n_bin if 1 <= n_bin <= 2048 else 1  # out of range: the library refuses before it writes
+        kmode, pa, pb, cross, coeff = (np.empty(size) for _ in range(5))
+        nmode = np.empty(size, dtype=np.uint64)
+        sa = None if signal_a is None else _p(self._in(signal_a))
+        sb = None if signal_b is None else _p(self._in(signal_b))
+        self._chk(self.lib.bchmc_measure_cross_spectrum(self.h, CORR_SOURCES[src[0]], sa, CORR_SOURCES[src[1]], sb, n_bin,
+                                                        _p(kmode), nmode.ctypes.data_as(C.POINTER(C.c_uint64)), _p(pa),
+                                                        _p(pb), _p(cross), _p(coeff)))
+        return kmode, nmode, pa, pb, cross, coeff
+
+    # ---- ensemble accumulators (bchmc_ensemble_*) --------------------------------------------------
+    def ensemble_add(self, slot, signal=None, source=None):
+        """One more sample into running accumulator ``slot`` (0 .. ENS_SLOTS - 1): a host field, the resident chain
+        state (the default without a signal) or the handle's deltaX, sources as in ``measure_corr``.  One Welford step
+        per cell on the device; the sample does not cross PCIe unless it is a host field."""
+        if source is None:
+            source = "chain" if signal is None else "host"
+        sig = None if signal is None else _p(self._in(signal))
+        self._chk(self.lib.bchmc_ensemble_add(self.h, int(slot), CORR_SOURCES[source], sig))
+
+    def ensemble_count(self, slot):
+        n = C.c_uint64()
+        self._chk(self.lib.bchmc_ensemble_count(self.h, int(slot), C.byref(n)))
+        return n.value
+
+    def ensemble_fetch(self, slot, what="mean"):
+        """``what``: "mean" (needs one sample), "variance" = m2 / (count - 1) or "std" (two), "m2" (the raw sum of
+        squared deviations).  Returns N doubles."""
+        out = np.empty(self.N)
+        self._chk(self.lib.bchmc_ensemble_fetch(self.h, int(slot), ENS_WHAT[what] if isinstance(what, str) else int(what),
+                                                _p(out)))
+        return out
+
+    def ensemble_export(self, slot):
+        """(count, mean, m2) of a slot: what ``ensemble_merge`` of another handle takes.  An empty slot gives zeros."""
+        count = self.ensemble_count(slot)
+        if count == 0:
+            return 0, np.zeros(self.N), np.zeros(self.N)
+        return count, self.ensemble_fetch(slot, "mean"), self.ensemble_fetch(slot, "m2")
+
+    def ensemble_merge(self, slot, count, mean, m2):
+        """Folds another accumulator of the same grid (another chain, another GPU, an earlier run) into ``slot`` by the
+        pairwise update of Chan, Golub & LeVeque.  ``count == 0`` is a no-op; a merge into an empty slot copies."""
+        count = int(count)
+        if count == 0:
+            self._chk(self.lib.bchmc_ensemble_merge(self.h, int(slot), 0, None, None))
+            return
+        self._chk(self.lib.bchmc_ensemble_merge(self.h, int(slot), count, _p(self._in(mean)), _p(self._in(m2))))
+
+    def ensemble_reset(self, slot):
+        """count = 0 and zeroed arrays; the buffers are kept."""
+        self._chk(self.lib.bchmc_ensemble_reset(self.h, int(slot)))
+
+    def ensemble_release(self):
+        """Frees the buffers of every slot; a later ``ensemble_add`` takes them again."""
+        self._chk(self.lib.bchmc_ensemble_release(self.h))
 
     def _measure_corr(self, fn, cells, signal, n_bin, source):
         if source is None:

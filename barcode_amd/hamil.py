@@ -161,6 +161,24 @@ def measure_spec2D(hd, signal=None, N_bin=200, source=None, planepar=True):
     return hd.engine.measure_spectrum2d(signal, N_bin, source)
 
 
+def measure_cross_spectrum(hd, signal_a=None, signal_b=None, N_bin=200, source_a=None, source_b=None):
+    """The cross-spectrum of two fields in measure_spectrum's bins -> (kmode, nmode, power_a, power_b, cross, coeff).  A
+    side without a signal is the resident chain state, or with ``source_*="deltaX"`` the density of the last forward
+    model: reconstruction against truth without a field leaving the device but the truth."""
+    return hd.engine.measure_cross_spectrum(signal_a, signal_b, N_bin, source_a, source_b)
+
+
+def ensemble_add(hd, slot, signal=None, source=None):
+    """One more sample into running accumulator ``slot`` of the posterior mean and variance: ``signal`` None = the
+    resident chain state, or with ``source="deltaX"`` the density of the last forward model."""
+    hd.engine.ensemble_add(slot, signal, source)
+
+
+def ensemble_fetch(hd, slot, what="mean"):
+    """``"mean"``, ``"variance"``, ``"std"`` or ``"m2"`` of accumulator ``slot`` -> N values."""
+    return hd.engine.ensemble_fetch(slot, what)
+
+
 def getDensity(hd, mk, xp, yp, zp, Par_mass=None, weightmass=False, kernel_h=0.0, to_nobs=False):
     """getDensity_NGP / _CIC / _TSC / _SPH (massFunctions.cc:49-495; ``mk`` 0 .. 3 picks the one, None the handle's) of a
     free particle list on ``hd``'s grid, upstream's argument order from ``xp`` on -> (delta, stats).  ``weightmass``

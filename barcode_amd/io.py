@@ -148,6 +148,22 @@ def dump_density(density, fname_out="density"):
     return add_extension_if_missing(fname_out)
 
 
+def ensemble_filenames(directory, name):
+    """``<name>_mean`` and ``<name>_std`` under ``directory`` (before ``write_array``'s extension rule)."""
+    base = os.path.join(directory, name) if directory else name
+    return base + "_mean", base + "_std"
+
+
+def dump_ensemble(engine, directory, slot, name):
+    """The posterior mean and standard deviation of ensemble accumulator ``slot`` (``Engine.ensemble_add``) as raw
+    ``real_prec`` arrays of N values, ``<name>_mean`` and ``<name>_std``, like the field dumps they summarise.  Needs two
+    samples in the slot.  Returns the two paths written."""
+    names = ensemble_filenames(directory, name)
+    for path, what in zip(names, ("mean", "std")):
+        write_array(path, engine.ensemble_fetch(slot, what))
+    return tuple(add_extension_if_missing(n) for n in names)
+
+
 def dump_deltas(engine, directory, suffix=""):
     """``dump_deltas`` (IOfunctionsGen.cc:136-171) of the resident chain state: deltaLAG, then deltaEUL without
     ``rsd_model``, or deltaRSS (the configured forward model) and deltaEUL (a second Lag2Eul without RSD) with it.

@@ -312,6 +312,67 @@ int bchmc_measure_spectrum_src(bchmc_handle *h, bchmc_corr_source src, const dou
  *  S4 kmode is the mean 3-D |k| of the bin's modes, not a (k_perp, k_par) pair. */
 int bchmc_measure_spectrum2d(bchmc_handle *h, bchmc_corr_source src, const double *signal, uint64_t n_bin, double *kmode,
                              uint64_t *nmode, double *power);
+/* ---- the cross-spectrum of two fields (upstream: none; what a Barcode paper's reconstruction-against-truth figure is made
+ * of, computed there from dumped fields) ------------------------------------------------------------------------------
+ * Binning, dk, mode weights and normalisation are exactly those of bchmc_measure_spectrum_src (measure_spectrum,
+ * field_statistics.cpp:20-90: (ULONG)(ktot / dk) with IEEE sqrt and divide and no FMA contraction, Hermitian weight on the
+ * half-complex transforms, NORM = L^3 / N^2).  Per bin: kmode = mean |k|, nmode = modes (may be NULL), power_a / power_b =
+ * what bchmc_measure_spectrum_src returns for each source, cross = NORM sum hw (re_a re_b + im_a im_b) / nmode, and
+ * coeff = cross / sqrt(power_a power_b), formed on the host from those three arrays: 0 where the bin is empty or the
+ * product is 0, NaN where it is NaN.  Six arrays of n_bin; empty bins are 0.  n_bin: 1..2048.
+ * Each source's transform is obtained as bchmc_measure_spectrum_src obtains it (the chain state's q^ is used as it is);
+ * all nine pairs of sources are legal, the same source twice and two host fields included.  One kernel reads both
+ * transforms once.  The first call takes one more half-complex scratch array, which the handle keeps like the spectrum's
+ * bins (bchmc_live_resources counts it, bchmc_destroy frees it).
+ * Errors (all checked before anything is queued, for both sources) and what a call leaves untouched are those of
+ * bchmc_measure_spectrum_src.  The sums use the float atomics of bchmc_measure_spectrum: results are NOT bitwise
+ * repeatable, the last bits vary with the order in which the adds land.  fp32 handles: transforms in float, products and
+ * sums in double. */
+int bchmc_measure_cross_spectrum(bchmc_handle *h, bchmc_corr_source src_a, const double *signal_a,
+                                 bchmc_corr_source src_b, const double *signal_b, uint64_t n_bin, double *kmode,
+                                 uint64_t *nmode, double *power_a, double *power_b, double *cross, double *coeff);
+/* ---- posterior mean and variance of an ensemble of samples (upstream: left to whoever reads the deltaLAG_<i> /
+ * deltaEUL_<i> dumps of barcoderunner.cc:512-534) -----------------------------------------------------------------------
+ * BCHMC_ENS_SLOTS independent running accumulators per handle (say deltaLAG, deltaEUL in real space, deltaEUL in redshift
+ * space and a spare).  A slot is a count, kept on the host side of the handle, and two dense device arrays of N DOUBLES
+ * on every handle, fp32 ones too: mean and m2, the sum of squared deviations from the mean, in the reference's cell order
+ * k + n (j + n i).  The arrays are taken, zeroed on the handle's stream, by the slot's first add or merge, counted by
+ * bchmc_live_resources (2 buffers, 16 N bytes per used slot) and freed by bchmc_ensemble_release and bchmc_destroy; if
+ * they cannot be allocated the call returns the allocation's error, releases what it took and leaves the handle usable.
+ * Eight properties:
+ *  E1 add: one Welford step per cell from one sample of a source, in double, no FMA contraction, IEEE divide, in exactly
+ *     this operand order with c = (double)(count + 1):  d = x - mean;  mean = mean + d / c;  m2 = m2 + d * (x - mean);
+ *     so that the same lines in numpy float64 give the same bits.
+ *  E2 Sources, their argument and state errors (checked before anything is queued) are those of bchmc_measure_corr2d.
+ *     BCHMC_CORR_CHAIN_STATE: the real-space field bchmc_chain_get_state would return, through the same transform,
+ *     without the copy to the host.  BCHMC_CORR_DELTAX: what bchmc_fetch(BCHMC_F_DELTAX) would return.  BCHMC_CORR_HOST:
+ *     accumulated from the staged doubles, so an fp32 handle loses nothing of the array.  fp32 device sources are widened
+ *     to double on load.
+ *  E3 A call leaves the chain state, the momenta, the carried gradient and -log L, the uploaded inputs, deltaX / pos* AND a
+ *     pending proposal as they were (the contract of bchmc_measure_corr).
+ *  E4 A sample cell that is not finite (NaN or an infinity) makes that cell's mean and m2 NaN, for good, and touches no
+ *     other cell.
+ *  E5 fetch: BCHMC_ENS_MEAN needs count >= 1.  BCHMC_ENS_VARIANCE is m2 / (double)(count - 1), BCHMC_ENS_STD is
+ *     sqrt(m2 / (double)(count - 1)) with IEEE sqrt and divide, computed on the device into the staging array; both need
+ *     count >= 2.  BCHMC_ENS_M2 is the raw array (count >= 1); with the count and BCHMC_ENS_MEAN it is what another
+ *     handle's merge takes.  BCHMC_ERR_STATE below those counts.  out: N host doubles.
+ *  E6 merge folds another accumulator of the same grid -- another chain, another GPU, an earlier run read from disk -- into
+ *     the slot by the pairwise update of Chan, Golub & LeVeque.  With na the slot's count and nb = count_b the host forms
+ *     w = (double)nb / (double)(na + nb) and c = (double)na * (double)nb / (double)(na + nb), left to right, and the
+ *     kernel does per cell, uncontracted:  d = mean_b - mean;  mean = mean + d * w;  m2 = (m2 + m2_b) + (d * d) * c.
+ *     count_b == 0 is a no-op (the arrays may be NULL); a merge into an empty slot copies the two arrays bit for bit.  The
+ *     arrays cross PCIe through the handle's staging, one after the other.
+ *  E7 reset: count = 0, the arrays zeroed, the buffers kept.  release: every slot's buffers freed, every count 0.
+ *  E8 Results are bitwise repeatable on every handle: no cell depends on another and nothing is added atomically.
+ * slot outside 0 .. BCHMC_ENS_SLOTS - 1, an unknown quantity, a NULL array where one is needed: BCHMC_ERR_ARG. */
+enum { BCHMC_ENS_SLOTS = 4 };
+typedef enum bchmc_ens_what { BCHMC_ENS_MEAN = 0, BCHMC_ENS_VARIANCE = 1, BCHMC_ENS_STD = 2, BCHMC_ENS_M2 = 3 } bchmc_ens_what;
+int bchmc_ensemble_add(bchmc_handle *h, int32_t slot, bchmc_corr_source src, const double *signal);
+int bchmc_ensemble_count(bchmc_handle *h, int32_t slot, uint64_t *count);
+int bchmc_ensemble_fetch(bchmc_handle *h, int32_t slot, bchmc_ens_what what, double *out);
+int bchmc_ensemble_merge(bchmc_handle *h, int32_t slot, uint64_t count_b, const double *mean_b, const double *m2_b);
+int bchmc_ensemble_reset(bchmc_handle *h, int32_t slot);   /* count = 0, arrays zeroed, buffers kept */
+int bchmc_ensemble_release(bchmc_handle *h);               /* all slots: buffers freed, counts 0 */
 /* ---- a particle catalogue onto the grid (upstream: getDensity_NGP / _CIC / _TSC / _SPH, massFunctions.cc:49-495, as
  * tools/density.cc, tools/poisson_upres.cc and Lag2Eul.cc:117-126 call them) ---------------------------------------------
  * The raw density of a free list of n_part particles -- no overdens, no normalisation -- on the handle's grid, L and
