@@ -191,6 +191,22 @@ struct bchmc_handle {
     DevBuf<unsigned long long> stat;     // kCatWords
     PinnedBuf<unsigned long long> h_stat;
   } cat;
+  // bchmc_poisson_* (poisson.hpp): the resident sample is the exclusive scan of the counts and what a particle is
+  // recomputed from; the rest is the scan's scratch, the status words and one batch of positions for
+  // bchmc_poisson_positions (taken by its first call).  Built by bchmc_poisson_draw for its n_in, replaced by a draw
+  // with another one, freed by bchmc_poisson_release and bchmc_destroy.  bchmc_setup_random_test_poisson takes the
+  // status words only and leaves the sample alone.
+  struct Pois {
+    DevBuf<unsigned long long> off;                    // cells + 1
+    DevBuf<unsigned long long> cnt, boff, gsum, goff;  // workgroups, workgroups, groups, groups
+    DevBuf<unsigned long long> res, stat;              // 2, kPoisWords
+    DevBuf<double> cols;                               // 3 kCatBatch: x | y | z
+    long long cells = 0;                               // n_in^3 the scan buffers were built for (0: none)
+    bool valid = false;                                // a sample is resident
+    uint64_t seed = 0, n_part = 0;
+    uint32_t stream = 0, n_in = 0;
+    double d_in = 0.;
+  } pois;
   // bchmc_interp_particles (interp_particles.hpp): the staged sources -- n_fields grid arrays of the storage type, grown
   // when a call asks for more fields -- and one batch of kCatBatch particles at a time: the columns, the results, and for
   // the tile kernel the tile of every particle, the indexed records, the tiles' populations, offsets and cursors and the
@@ -1178,6 +1194,10 @@ int upres_setup(bchmc_handle *h, int n_out) {
 // ======================================================================================================
 // What bchmc_density_particles asks of the pipe, after its checks: the source, the kernel and scale length in force, the
 // largest |w| (1 without weights), the caller's columns
+// A source beside the two of bchmc_part_source that only bchmc_poisson_density sets (bchmc_density_particles refuses it):
+// the resident Poisson sample, whose batches k_pois_positions writes into the staged columns
+constexpr int kCatSrcPoisson = 2;
+
 struct CatCall {
   int src, mk, weighted, dest;
   double hh, max_w;
@@ -2848,6 +2868,44 @@ struct Pipe {
     return BCHMC_OK;
   }
 
+  // ---- bchmc_poisson_* (poisson.hpp) ----------------------------------------------------------------------------------
+  // The counts of an n_in^3 rate grid of `cells` cells.  The field: doubles at xd, or (xd null) the source in ioq as
+  // upres_real leaves it, read in the storage type.  cd: the counts as doubles.  resident: the scan into h->pois.off,
+  // the total in h->pois.res[0]; otherwise the counts and the status words only.
+  static int pois_counts(bchmc_handle *h, int src, long long cells, const double *xd, const bchmc_poisson_opts &o,
+                         double *cd, bool resident) {
+    auto &k = h->pois;
+    if (!xd) CHK(upres_real(h, src));
+    const long long nb = (cells + kPoisThreads - 1) / kPoisThreads, ng = (nb + kMtThreads - 1) / kMtThreads;
+    const uint2 key = make_uint2((unsigned)o.seed, (unsigned)(o.seed >> 32));
+    const T *win = o.use_window ? R(h->in_arr[BCHMC_F_WINDOW]) : nullptr;
+    unsigned long long *off = resident ? k.off.get() : nullptr, *cnt = resident ? k.cnt.get() : nullptr;
+    ProfScope ps(h, BCHMC_K_OTHER);
+    HIPCHK(hipMemsetAsync(k.stat, 0, kPoisWords * sizeof(unsigned long long), h->stream));
+    HIPCHK(hipMemsetAsync(k.stat + kPoisBad, 0xff, sizeof(unsigned long long), h->stream));
+    if (xd)
+      k_pois_counts<double, T><<<(int)nb, kPoisThreads, 0, h->stream>>>(cells, key, o.stream, o.rate_mode, o.scale, xd, win,
+                                                                        cd, off, cnt, k.stat);
+    else
+      k_pois_counts<T, T><<<(int)nb, kPoisThreads, 0, h->stream>>>(cells, key, o.stream, o.rate_mode, o.scale, R(h->ioq),
+                                                                   win, cd, off, cnt, k.stat);
+    if (resident) {
+      k_mock_scan<<<(int)ng, kMtThreads, 0, h->stream>>>(k.cnt, nb, k.boff, k.gsum);
+      k_mt_scan<<<1, kMtThreads, 0, h->stream>>>(k.gsum, (int)ng, k.goff, k.res, 0, nullptr);
+      k_pois_offsets<<<(int)nb, kPoisThreads, 0, h->stream>>>(cells, k.boff, k.goff, k.res, k.off);
+    }
+    HIPCHK(hipGetLastError());
+    return BCHMC_OK;
+  }
+
+  // particles p0 .. p0 + m - 1 of the resident sample into three device columns (m >= 1, p0 + m <= n_part)
+  static void pois_positions(bchmc_handle *h, uint64_t p0, int m, double *x, double *y, double *z) {
+    const auto &k = h->pois;
+    const uint2 key = make_uint2((unsigned)k.seed, (unsigned)(k.seed >> 32));
+    k_pois_positions<<<nblk_full(m), 256, 0, h->stream>>>(k.cells, (int)k.n_in, k.d_in, key, k.stream, k.off,
+                                                          (unsigned long long)p0, m, x, y, z);
+  }
+
   // ---- bchmc_density_particles (catalogue.hpp) ---------------------------------------------------------------------
   template <int MK, bool FIX>
   static void cat_launch(bchmc_handle *h, const SphPar &sp, bool tiled, int H, size_t lds, int m, const double *w,
@@ -2933,16 +2991,17 @@ struct Pipe {
     const PosPar pp = make_pos(h, h->last_rsd);
     for (uint64_t p0 = 0; p0 < cc.n_part; p0 += kCatBatch) {
       const int m = (int)std::min<uint64_t>(kCatBatch, cc.n_part - p0);
-      if (cc.src != BCHMC_PART_FORWARD) {
+      if (cc.src == BCHMC_PART_HOST) {
         CHK(h2d(h, x, cc.x + p0, m * sizeof(double)));
         CHK(h2d(h, y, cc.y + p0, m * sizeof(double)));
         CHK(h2d(h, z, cc.z + p0, m * sizeof(double)));
         if (w) CHK(h2d(h, w, cc.w + p0, m * sizeof(double)));
       }
-      if (cc.src == BCHMC_PART_FORWARD || tiled) {
+      if (cc.src != BCHMC_PART_HOST || tiled) {
         ProfScope ps(h, BCHMC_K_SORT);
         if (cc.src == BCHMC_PART_FORWARD)
           k_cat_positions<T><<<nblk_full(m), 256, 0, h->stream>>>(g, pp, R(h->psi), (long long)p0, m, x, y, z);
+        if (cc.src == kCatSrcPoisson) pois_positions(h, p0, m, x, y, z);
         if (tiled) {
           HIPCHK(hipMemsetAsync(c.cnt, 0, tp.ntiles * sizeof(unsigned), h->stream));
           k_cat_count<T><<<nblk_full(m), 256, 0, h->stream>>>(g, sp, tp, cc.mk, m, x, y, z, c.tile_of, c.cnt, c.stat);
@@ -4456,40 +4515,62 @@ int bchmc_hamiltonian_mass(bchmc_handle *h, const double *signal, const bchmc_ma
   return read_ctl(h, nullptr);  // synchronises; adapts the binning's record slots to the forward model just run
 }
 
-int bchmc_setup_random_test(bchmc_handle *h, const bchmc_mock_opts *o, uint32_t mt[624], int32_t *mti,
-                            uint64_t *words_used, double *delta_lag, double *delta_eul) {
-  if (!h || !o || !mt || !mti) return BCHMC_ERR_ARG;
-  ENTER(h);
-  // everything that can be refused is refused before anything is queued or the generator is touched
+// The front half of setup_random_test, shared by its two entry points.  mock_refusals: everything that can be refused
+// is refused before anything is queued or the generator is touched; `poisson` swaps the two lines about data_model 0
+// for the Poissonian mock's own.  mock_truth: the truth from 2 N Gaussians of the caller's stream, its forward model,
+// the window and the count of its cells (mock_window's layout of the staging).
+static int mock_refusals(bchmc_handle *h, const bchmc_mock_opts *o, const int32_t *mti, bool poisson, int *rsd) {
   if (*mti < 0 || *mti > 624) return h->fail(BCHMC_ERR_ARG, "mti = %d outside [0, 624]", (int)*mti);
   if (o->window_type != 1 && o->window_type != 10 && o->window_type != 23)
     return h->fail(BCHMC_ERR_ARG, "in barcoderunner: window_type = %d is not a valid choice!", (int)o->window_type);
   if (o->data_model != 0 && o->data_model != 1)
     return h->fail(BCHMC_ERR_ARG, "in barcoderunner: data_model = %d is not a valid choice!", (int)o->data_model);
-  if (o->data_model == 0 && h->c.likelihood == 0)
-    return h->fail(BCHMC_ERR_UNSUPPORTED, "Poissonian mock data: gsl_ran_poisson consumes a data-dependent number of "
-                                          "words per cell, which has no parallel form here");
-  if (o->data_model == 0 && h->c.likelihood == 2)
-    return h->fail(BCHMC_ERR_ARG, "in barcoderunner: linear data model was chosen (additive error), but incompatible "
-                                  "likelihood!");
+  if (poisson) {
+    if (o->data_model != 0 || h->c.likelihood != 0)
+      return h->fail(BCHMC_ERR_ARG, "setup_random_test_poisson: the Poissonian mock is data_model 0 under likelihood 0 "
+                                    "(data_model = %d, likelihood = %d)", (int)o->data_model, (int)h->c.likelihood);
+  } else {
+    if (o->data_model == 0 && h->c.likelihood == 0)
+      return h->fail(BCHMC_ERR_UNSUPPORTED, "Poissonian mock data: gsl_ran_poisson consumes a data-dependent number of "
+                                            "words per cell, which has no parallel form here");
+    if (o->data_model == 0 && h->c.likelihood == 2)
+      return h->fail(BCHMC_ERR_ARG, "in barcoderunner: linear data model was chosen (additive error), but incompatible "
+                                    "likelihood!");
+  }
   if (h->g.n & 1) return h->fail(BCHMC_ERR_UNSUPPORTED, "create_GARFIELD's placement needs an even Nx (%d)", h->g.n);
-  const int rsd = o->random_test_rsd ? 1 : 0;
-  if (rsd && !h->c.planepar) return h->fail(BCHMC_ERR_RSD_NOT_PLANEPAR, "non-plane-parallel RSD is not implemented");
-  CHK(need_input(h, BCHMC_F_SIGNAL_PS, "signal_PS"));
+  *rsd = o->random_test_rsd ? 1 : 0;
+  if (*rsd && !h->c.planepar) return h->fail(BCHMC_ERR_RSD_NOT_PLANEPAR, "non-plane-parallel RSD is not implemented");
+  return need_input(h, BCHMC_F_SIGNAL_PS, "signal_PS");
+}
+static int mock_truth(bchmc_handle *h, const bchmc_mock_opts *o, int rsd, uint32_t mt[624], int32_t *mti, uint64_t *used,
+                      long long *count) {
   CHK(mt_setup(h));
   CHK(DISPATCH(h, mock_alloc(h)));
   clobber_proposal(h);
   h->cg_valid = false;
   h->have[BCHMC_F_WINDOW] = h->have[BCHMC_F_NOBS] = h->have[BCHMC_F_NOISE] = false;
   const long long N = h->g.N;
-  uint64_t used1 = 0, used2 = 0;
-  CHK(mt_draw(h, mt, mti, &used1, 2 * N, false, mock_place_truth));
+  CHK(mt_draw(h, mt, mti, used, 2 * N, false, mock_place_truth));
   CHK(DISPATCH(h, mock_window(h, rsd, o->window_type)));
-  unsigned long long res[2] = {0, 0};
-  HIPCHK(hipMemcpyAsync(res, h->mock.res, sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+  unsigned long long res = 0;
+  HIPCHK(hipMemcpyAsync(&res, h->mock.res, sizeof res, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
-  const long long count = (long long)res[0];
-  if (count < 0 || count > N) return h->fail(BCHMC_ERR_STATE, "window count %lld outside [0, N]", count);
+  *count = (long long)res;
+  if (*count < 0 || *count > N) return h->fail(BCHMC_ERR_STATE, "window count %lld outside [0, N]", *count);
+  return BCHMC_OK;
+}
+
+int bchmc_setup_random_test(bchmc_handle *h, const bchmc_mock_opts *o, uint32_t mt[624], int32_t *mti,
+                            uint64_t *words_used, double *delta_lag, double *delta_eul) {
+  if (!h || !o || !mt || !mti) return BCHMC_ERR_ARG;
+  ENTER(h);
+  int rsd = 0;
+  CHK(mock_refusals(h, o, mti, false, &rsd));
+  const long long N = h->g.N;
+  uint64_t used1 = 0, used2 = 0;
+  long long count = 0;
+  CHK(mock_truth(h, o, rsd, mt, mti, &used1, &count));
+  unsigned long long res[2] = {0, 0};
   // the noise is a second draw from the state the first one returned: its size depends on the window
   if (count > 0) CHK(mt_draw(h, mt, mti, &used2, count, true, nullptr));
   MockPar mp{o->window_type, o->data_model, h->c.likelihood, o->negative_obs, o->sigma_min, o->sigma_fac,
@@ -4502,6 +4583,209 @@ int bchmc_setup_random_test(bchmc_handle *h, const bchmc_mock_opts *o, uint32_t 
   CHK(read_ctl(h, nullptr));  // synchronises; adapts the binning's record slots to the forward model just run
   if (res[1] != ~0ull)
     return h->fail(BCHMC_ERR_STATE, "in barcoderunner(): noise = 0 found! Index %llu", res[1]);
+  h->have[BCHMC_F_WINDOW] = h->have[BCHMC_F_NOBS] = h->have[BCHMC_F_NOISE] = true;
+  return BCHMC_OK;
+}
+
+// ---- bchmc_poisson_* (poisson.hpp) --------------------------------------------------------------------------------------
+// The status words of a draw: taken once, kept with the sample's buffers
+static int pois_stat_alloc(bchmc_handle *h) {
+  auto &k = h->pois;
+  if (k.stat && k.res) return BCHMC_OK;
+  int rc = dev_alloc(h, k.stat, (size_t)kPoisWords);
+  if (!rc) rc = dev_alloc(h, k.res, (size_t)2);
+  if (rc) {
+    (void)k.stat.release();
+    (void)k.res.release();
+  }
+  return rc;
+}
+// The scan's buffers for `cells` cells; all or nothing, and an earlier sample is gone either way
+static int pois_alloc(bchmc_handle *h, long long cells) {
+  auto &k = h->pois;
+  k.valid = false;
+  CHK(pois_stat_alloc(h));
+  if (k.cells == cells) return BCHMC_OK;
+  HIPCHK(hipStreamSynchronize(h->stream));
+  const long long nb = (cells + kPoisThreads - 1) / kPoisThreads, ng = (nb + kMtThreads - 1) / kMtThreads;
+  auto build = [&]() -> int {
+    CHK(dev_alloc(h, k.off, (size_t)cells + 1));
+    CHK(dev_alloc(h, k.cnt, (size_t)nb));
+    CHK(dev_alloc(h, k.boff, (size_t)nb));
+    CHK(dev_alloc(h, k.gsum, (size_t)ng));
+    return dev_alloc(h, k.goff, (size_t)ng);
+  };
+  k.cells = 0;
+  if (const int rc = build()) {
+    for (auto *b : {&k.off, &k.cnt, &k.boff, &k.gsum, &k.goff}) (void)b->release();
+    return rc;
+  }
+  k.cells = cells;
+  return BCHMC_OK;
+}
+// the status words (and the scan's total) of the draw just queued; synchronises
+static int pois_read(bchmc_handle *h, bool resident, unsigned long long st[kPoisWords], unsigned long long *total) {
+  HIPCHK(hipMemcpyAsync(st, h->pois.stat, kPoisWords * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+  if (resident) HIPCHK(hipMemcpyAsync(total, h->pois.res, sizeof *total, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return BCHMC_OK;
+}
+static int pois_opts_check(bchmc_handle *h, const char *name, const bchmc_poisson_opts *o) {
+  if (o->stream >= 0x80000000u) return h->fail(BCHMC_ERR_ARG, "%s: stream = %u is not below 2^31", name, o->stream);
+  if (o->rate_mode != 0 && o->rate_mode != 1) return h->fail(BCHMC_ERR_ARG, "%s: rate_mode = %d is neither 0 nor 1", name, (int)o->rate_mode);
+  if (!std::isfinite(o->scale)) return h->fail(BCHMC_ERR_ARG, "%s: scale = %g is not finite", name, o->scale);
+  if (o->use_window != 0 && o->use_window != 1) return h->fail(BCHMC_ERR_ARG, "%s: use_window = %d is neither 0 nor 1", name, (int)o->use_window);
+  if (o->dest != -1 && o->dest != BCHMC_F_NOBS)
+    return h->fail(BCHMC_ERR_ARG, "%s: dest = %d is neither -1 nor BCHMC_F_NOBS", name, (int)o->dest);
+  return BCHMC_OK;
+}
+
+int bchmc_poisson_draw(bchmc_handle *h, bchmc_corr_source src, const double *signal, uint32_t n_in,
+                       const bchmc_poisson_opts *opts, double *counts, bchmc_poisson_stats *stats) {
+  if (!h) return BCHMC_ERR_ARG;
+  const char *name = "poisson_draw";
+  if (!opts) return h->fail(BCHMC_ERR_ARG, "%s: opts is NULL", name);
+  CHK(source_args(h, name, src, signal));
+  CHK(pois_opts_check(h, name, opts));
+  const uint32_t Nx = (uint32_t)h->g.n;
+  if (src == BCHMC_CORR_HOST) {
+    if (n_in < 1 || n_in > Nx) return h->fail(BCHMC_ERR_ARG, "%s: n_in = %u outside 1..Nx = %u", name, n_in, Nx);
+  } else {
+    if (n_in != 0 && n_in != Nx) return h->fail(BCHMC_ERR_ARG, "%s: n_in = %u with a device source (0 or Nx = %u)", name, n_in, Nx);
+    n_in = Nx;
+  }
+  if ((opts->use_window || opts->dest == BCHMC_F_NOBS) && n_in != Nx)
+    return h->fail(BCHMC_ERR_ARG, "%s: use_window = 1 and dest = BCHMC_F_NOBS need n_in == Nx (n_in = %u, Nx = %u)", name, n_in, Nx);
+  ENTER(h);
+  CHK(source_state(h, src));
+  if (opts->use_window && !h->have[BCHMC_F_WINDOW])
+    return h->fail(BCHMC_ERR_STATE, "%s: use_window = 1, but the window was never uploaded", name);
+  const long long N = h->g.N, cells = (long long)n_in * n_in * n_in;
+  auto &k = h->pois;
+  CHK(pois_alloc(h, cells));
+  if (signal) CHK(h2d(h, h->dstage, signal, (size_t)cells * sizeof(double)));
+  double *cd = h->dstage + N;  // the counts as doubles: the upper half of the staging
+  CHK(DISPATCH(h, pois_counts(h, (int)src, cells, signal ? h->dstage.get() : nullptr, *opts, cd, true)));
+  unsigned long long st[kPoisWords], total = 0;
+  CHK(pois_read(h, true, st, &total));
+  if (st[kPoisBad] != ~0ull)
+    return h->fail(BCHMC_ERR_ARG, "%s: lambda of cell %llu is NaN, +infinity or above 2^30; nothing was written", name, st[kPoisBad]);
+  if (stats) {
+    stats->n_part = total;
+    stats->n_cells_drawn = st[kPoisDrawn];
+    stats->max_count = st[kPoisMaxCount];
+    stats->n_capped = st[kPoisCapped];
+    std::memcpy(&stats->lambda_max, &st[kPoisLambdaBits], sizeof(double));
+  }
+  if (counts) CHK(d2h(h, counts, cd, (size_t)cells * sizeof(double)));
+  if (opts->dest == BCHMC_F_NOBS) {  // exactly what bchmc_upload(BCHMC_F_NOBS) does to the handle
+    CHK(DISPATCH(h, upload(h, BCHMC_F_NOBS, cd)));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    h->have[BCHMC_F_NOBS] = true;
+    h->cg_valid = h->prop_g_valid = false;
+  }
+  k.seed = opts->seed, k.stream = opts->stream, k.n_in = n_in, k.n_part = total, k.d_in = h->g.L / (double)n_in;
+  k.valid = true;
+  return BCHMC_OK;
+}
+
+int bchmc_poisson_positions(bchmc_handle *h, uint64_t first, uint64_t m, double *x, double *y, double *z) {
+  if (!h) return BCHMC_ERR_ARG;
+  const char *name = "poisson_positions";
+  auto &k = h->pois;
+  if (!k.valid) return h->fail(BCHMC_ERR_STATE, "%s: no sample: call bchmc_poisson_draw first", name);
+  if (m > k.n_part || first > k.n_part - m)
+    return h->fail(BCHMC_ERR_ARG, "%s: particles %llu .. %llu + %llu of a sample of %llu", name, (unsigned long long)first,
+                   (unsigned long long)first, (unsigned long long)m, (unsigned long long)k.n_part);
+  if (m == 0) return BCHMC_OK;
+  if (!x || !y || !z) return h->fail(BCHMC_ERR_ARG, "%s: x, y and z must be given", name);
+  ENTER(h);
+  if (!k.cols) CHK(dev_alloc(h, k.cols, 3 * (size_t)kCatBatch));
+  double *dx = k.cols, *dy = dx + kCatBatch, *dz = dy + kCatBatch;
+  for (uint64_t p0 = 0; p0 < m; p0 += kCatBatch) {
+    const int mb = (int)std::min<uint64_t>(kCatBatch, m - p0);
+    {
+      ProfScope ps(h, BCHMC_K_OTHER);
+      Pipe<double>::pois_positions(h, first + p0, mb, dx, dy, dz);
+      HIPCHK(hipGetLastError());
+    }
+    CHK(d2h(h, x + p0, dx, mb * sizeof(double)));
+    CHK(d2h(h, y + p0, dy, mb * sizeof(double)));
+    CHK(d2h(h, z + p0, dz, mb * sizeof(double)));
+  }
+  return BCHMC_OK;
+}
+
+int bchmc_poisson_density(bchmc_handle *h, const bchmc_density_opts *opts, double *out, bchmc_density_stats *stats) {
+  if (!h || !opts) return BCHMC_ERR_ARG;
+  const char *name = "poisson_density";
+  // bchmc_density_particles' refusals, in its order, with the sample in the place of the columns
+  if (opts->weightmass != 0 && opts->weightmass != 1)
+    return h->fail(BCHMC_ERR_ARG, "%s: weightmass = %d is neither 0 nor 1", name, (int)opts->weightmass);
+  if (opts->weightmass == 1) return h->fail(BCHMC_ERR_ARG, "%s: weightmass = 1: the sample's particles carry no weights", name);
+  if (opts->mk < -1 || opts->mk > 3) return h->fail(BCHMC_ERR_ARG, "%s: mk = %d outside -1..3", name, (int)opts->mk);
+  const int mk = opts->mk < 0 ? h->c.mk : opts->mk;
+  if (!(opts->kernel_h >= 0.) || !std::isfinite(opts->kernel_h) || opts->kernel_h > h->g.L / 4)
+    return h->fail(BCHMC_ERR_ARG, "%s: kernel_h = %g is negative, not finite or above L / 4", name, opts->kernel_h);
+  const double hh = opts->kernel_h > 0. ? opts->kernel_h : h->c.particle_kernel_h;
+  if (mk == 3 && !(hh > 0. && hh <= h->g.L / 4))
+    return h->fail(BCHMC_ERR_ARG, "%s: the handle's particle_kernel_h = %g is not in (0, L / 4]", name, hh);
+  if (opts->dest != -1 && opts->dest != BCHMC_F_NOBS)
+    return h->fail(BCHMC_ERR_ARG, "%s: dest = %d is neither -1 nor BCHMC_F_NOBS", name, (int)opts->dest);
+  if (!out && opts->dest == -1) return h->fail(BCHMC_ERR_ARG, "%s: no destination (out is NULL and dest is -1)", name);
+  if (!h->pois.valid) return h->fail(BCHMC_ERR_STATE, "%s: no sample: call bchmc_poisson_draw first", name);
+  const uint64_t n_part = h->pois.n_part;
+  if (n_part > 2147483647ull) return h->fail(BCHMC_ERR_ARG, "%s: n_part = %llu > 2^31 - 1", name, (unsigned long long)n_part);
+  if (mk == 3 && (h->c.min1 < 0. || h->c.min2 < 0. || h->c.min3 < 0.))
+    return h->fail(BCHMC_ERR_UNSUPPORTED, "%s: getDensity_SPH casts x / d to an unsigned index, undefined below 0 "
+                                          "(min = %g, %g, %g)", name, h->c.min1, h->c.min2, h->c.min3);
+  ENTER(h);
+  const CatCall cc{kCatSrcPoisson, mk, 0, (int)opts->dest, hh, 1., nullptr, nullptr, nullptr, nullptr, n_part};
+  CHK(h->f32 ? Pipe<float>::density_particles(h, cc, out, stats) : Pipe<double>::density_particles(h, cc, out, stats));
+  if (opts->dest == BCHMC_F_NOBS) {  // exactly what bchmc_upload(BCHMC_F_NOBS) does to the handle
+    h->have[BCHMC_F_NOBS] = true;
+    h->cg_valid = h->prop_g_valid = false;
+  }
+  return BCHMC_OK;
+}
+
+int bchmc_poisson_release(bchmc_handle *h) {
+  if (!h) return BCHMC_ERR_ARG;
+  ENTER(h);
+  HIPCHK(hipStreamSynchronize(h->stream));
+  h->pois = bchmc_handle::Pois{};
+  return BCHMC_OK;
+}
+
+int bchmc_setup_random_test_poisson(bchmc_handle *h, const bchmc_mock_opts *o, uint32_t mt[624], int32_t *mti,
+                                    uint64_t *words_used, uint64_t seed, uint32_t stream, double *delta_lag,
+                                    double *delta_eul) {
+  if (!h || !o || !mt || !mti) return BCHMC_ERR_ARG;
+  ENTER(h);
+  int rsd = 0;
+  CHK(mock_refusals(h, o, mti, true, &rsd));
+  if (stream >= 0x80000000u) return h->fail(BCHMC_ERR_ARG, "setup_random_test_poisson: stream = %u is not below 2^31", stream);
+  CHK(pois_stat_alloc(h));
+  const long long N = h->g.N;
+  uint64_t used = 0;
+  long long count = 0;
+  CHK(mock_truth(h, o, rsd, mt, mti, &used, &count));
+  if (delta_lag) CHK(d2h(h, delta_lag, h->dstage, (size_t)N * sizeof(double)));
+  if (delta_eul) CHK(d2h(h, delta_eul, h->dstage + N, (size_t)N * sizeof(double)));
+  if (words_used) *words_used = used;
+  // nobs = Poisson(rho_c (1 + delta_eul)) inside the window (barcoderunner.cc:125-131), from the staged doubles of
+  // delta_eul into the lower half of the staging, then taken in like an uploaded array; noise = 0
+  const bchmc_poisson_opts po{seed, stream, 0, h->c.rho_c, 1, BCHMC_F_NOBS};
+  CHK(DISPATCH(h, pois_counts(h, BCHMC_CORR_HOST, N, h->dstage + N, po, h->dstage, false)));
+  unsigned long long st[kPoisWords];
+  CHK(pois_read(h, false, st, nullptr));
+  CHK(read_ctl(h, nullptr));  // synchronises; adapts the binning's record slots to the forward model just run
+  if (st[kPoisBad] != ~0ull)
+    return h->fail(BCHMC_ERR_ARG, "setup_random_test_poisson: rho_c (1 + delta_eul) of cell %llu is NaN, +infinity or "
+                                  "above 2^30", st[kPoisBad]);
+  CHK(DISPATCH(h, upload(h, BCHMC_F_NOBS, h->dstage)));
+  HIPCHK(hipMemsetAsync(h->in_arr[BCHMC_F_NOISE], 0, (size_t)N * h->esz, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
   h->have[BCHMC_F_WINDOW] = h->have[BCHMC_F_NOBS] = h->have[BCHMC_F_NOISE] = true;
   return BCHMC_OK;
 }

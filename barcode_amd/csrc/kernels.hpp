@@ -30,6 +30,7 @@
 #include "ensemble.hpp"  // bchmc_ensemble_*: Welford and Chan updates of a running mean and m2, variance / standard deviation
 #include "upres.hpp"  // interp_field (CIC gather onto another grid) and the zero-padded power spectrum of 2D_corr_fct_interp.cc
 #include "mock.hpp"  // setup_random_test / make_initial_guess: window, rank of windowed cells on the stream, noise, guesses
+#include "poisson.hpp"  // bchmc_poisson_*: Poisson counts of a rate grid (inversion / PTRS on Philox uniforms), their scan, particle positions
 #include "mass.hpp"  // Hamiltonian_mass: element-wise masses and the Jasche+13 first-order diagonal
 #include "step_boundary_x.hpp"  // Planes mode: step boundary with the x passes of both transforms fused in
 #include "alpt_x.hpp"  // Planes mode of the ALPT displacement: mix + cell-boundary average with the x passes fused in

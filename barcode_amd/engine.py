@@ -62,6 +62,18 @@ class DensityOpts(C.Structure):
                 ("reserved0", C.c_int32)]
 
 
+class PoissonOpts(C.Structure):
+    """bchmc_poisson_opts: seed and stream of the counter-based draw, the rate's form and scale, window and destination."""
+    _fields_ = [("seed", C.c_uint64), ("stream", C.c_uint32), ("rate_mode", C.c_int32), ("scale", C.c_double),
+                ("use_window", C.c_int32), ("dest", C.c_int32)]
+
+
+class PoissonStats(C.Structure):
+    """bchmc_poisson_stats."""
+    _fields_ = [("n_part", C.c_uint64), ("n_cells_drawn", C.c_uint64), ("max_count", C.c_uint64),
+                ("n_capped", C.c_uint64), ("lambda_max", C.c_double)]
+
+
 class DensityStats(C.Structure):
     """bchmc_density_stats."""
     _fields_ = [("n_in", C.c_uint64), ("n_lost", C.c_uint64), ("max_per_tile", C.c_uint64)]
@@ -130,7 +142,9 @@ EXPORTS = ("bchmc_create", "bchmc_destroy", "bchmc_strerror", "bchmc_last_error"
            "bchmc_probe_displacement", "bchmc_probe_displacement_z", "bchmc_interp_upres", "bchmc_upres_release", "bchmc_measure_spectrum_src",
            "bchmc_density_particles", "bchmc_catalogue_release", "bchmc_interp_particles", "bchmc_interp_release",
            "bchmc_measure_cross_spectrum", "bchmc_ensemble_add", "bchmc_ensemble_count", "bchmc_ensemble_fetch",
-           "bchmc_ensemble_merge", "bchmc_ensemble_reset", "bchmc_ensemble_release")
+           "bchmc_ensemble_merge", "bchmc_ensemble_reset", "bchmc_ensemble_release",
+           "bchmc_poisson_draw", "bchmc_poisson_positions", "bchmc_poisson_density", "bchmc_poisson_release",
+           "bchmc_setup_random_test_poisson")
 # declared as well, listed apart: the header scan of the ABI test matches names of letters and underscores only
 EXPORTS_MT19937 = ("bchmc_chain_draw_momenta_mt19937", "bchmc_mt19937_jump")
 EXPORTS_CORR2D = ("bchmc_measure_corr2d", "bchmc_measure_corr2d_interp")  # a digit in the name, like the two above
@@ -235,6 +249,12 @@ def load():
     lib.bchmc_mt19937_jump.argtypes = [u32p, C.c_int32, u64, u32p, i32p]
     lib.bchmc_garfield_walk_index.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(u64)]
     lib.bchmc_setup_random_test.argtypes = [vp, C.POINTER(MockOpts), u32p, i32p, C.POINTER(u64), dp, dp]
+    lib.bchmc_poisson_draw.argtypes = [vp, C.c_int, dp, C.c_uint32, C.POINTER(PoissonOpts), dp, C.POINTER(PoissonStats)]
+    lib.bchmc_poisson_positions.argtypes = [vp, u64, u64, dp, dp, dp]
+    lib.bchmc_poisson_density.argtypes = [vp, C.POINTER(DensityOpts), dp, C.POINTER(DensityStats)]
+    lib.bchmc_poisson_release.argtypes = [vp]
+    lib.bchmc_setup_random_test_poisson.argtypes = [vp, C.POINTER(MockOpts), u32p, i32p, C.POINTER(u64), u64, C.c_uint32,
+                                                    dp, dp]
     lib.bchmc_make_initial_guess.argtypes = [vp, C.c_int32, dp, C.c_int32, C.c_double, u32p, i32p, C.POINTER(u64)]
     _lib = lib
     return lib
@@ -518,6 +538,18 @@ class Engine:
             self.h, C.byref(o), mt, m, u, None if dl is None else _p(dl), None if de is None else _p(de)))
         return used, dl, de
 
+    def setup_random_test_poisson(self, rng, seed, stream=0, window_type=1, random_test_rsd=False, deltas=True):
+        """The Poissonian mock of setup_random_test (data_model 0 under likelihood 0, which ``setup_random_test``
+        refuses): truth, forward model and window from ``rng`` exactly as there, then nobs ~ Poisson(rho_c (1 + deltaX))
+        inside the window from the counter-based sampler of ``poisson_draw`` under (seed, stream), noise = 0.  Returns
+        (words used, delta_lag, delta_eul)."""
+        o = MockOpts(int(window_type), 0, 0, int(bool(random_test_rsd)), float(self.params.sigma_min), 0.0)
+        dl, de = (np.empty(self.N), np.empty(self.N)) if deltas else (None, None)
+        used = self._with_rng(rng, lambda mt, m, u: self.lib.bchmc_setup_random_test_poisson(
+            self.h, C.byref(o), mt, m, u, int(seed), int(stream), None if dl is None else _p(dl),
+            None if de is None else _p(de)))
+        return used, dl, de
+
     def make_initial_guess(self, rng, initial_guess=0, file_field=None, smoothing_type=1, smoothing_scale=0.0):
         """make_initial_guess (barcoderunner.cc:207-247): sets the resident chain state; 2, 3 and 4 draw from ``rng``
         (0 and 1 leave it alone, and ``rng`` may be None).  Returns the words used."""
@@ -721,6 +753,62 @@ class Engine:
     def catalogue_release(self):
         """Frees the catalogue buffers of ``density_particles``; a later call rebuilds them."""
         self._chk(self.lib.bchmc_catalogue_release(self.h))
+
+    def poisson_draw(self, signal=None, seed=0, stream=0, scale=1.0, rate_mode=0, n_in=None, use_window=False,
+                     to_nobs=False, source=None, counts=True):
+        """Poisson counts of a rate grid on the device (discrete_poisson_sample's draw, tools/poisson_upres.cc:23-65):
+        cell c gets Poisson(scale (1 + x_c)) (``rate_mode=0``) or Poisson(scale x_c) (1), a pure function of (seed,
+        stream, c, lambda_c).  ``signal``: n_in^3 values with n_in <= Nx (``n_in=None``: the cube root of its size);
+        without it the resident chain state (``source="chain"``) or the handle's deltaX (``"deltaX"``).  ``use_window``:
+        cells outside the uploaded window draw nothing; ``to_nobs``: the counts also become the handle's nobs.  The sample
+        stays resident for ``poisson_positions`` / ``poisson_density``.  Returns (counts or None, stats), stats =
+        dict(n_part, n_cells_drawn, max_count, n_capped, lambda_max)."""
+        if source is None:
+            source = "chain" if signal is None else "host"
+        sig = None
+        if signal is not None:
+            sig = np.ascontiguousarray(signal, dtype=np.float64).reshape(-1)
+            if n_in is None:
+                n_in = int(round(sig.size ** (1.0 / 3.0)))
+            if int(n_in) ** 3 != sig.size:
+                raise ValueError("signal of %d values is no n_in^3 grid (n_in = %s)" % (sig.size, n_in))
+        n_in = 0 if n_in is None else int(n_in)
+        cells = (n_in or self.Nx) ** 3 if 0 <= n_in <= self.Nx else 1  # out of range: the library refuses before it writes
+        out = np.empty(cells) if counts else None
+        o = PoissonOpts(int(seed), int(stream), int(rate_mode), float(scale), int(bool(use_window)),
+                        F_NOBS if to_nobs else -1)
+        st = PoissonStats()
+        self._chk(self.lib.bchmc_poisson_draw(self.h, CORR_SOURCES[source], None if sig is None else _p(sig), n_in,
+                                              C.byref(o), None if out is None else _p(out), C.byref(st)))
+        return out, dict(n_part=int(st.n_part), n_cells_drawn=int(st.n_cells_drawn), max_count=int(st.max_count),
+                         n_capped=int(st.n_capped), lambda_max=float(st.lambda_max))
+
+    def poisson_positions(self, first=0, m=None, n_part=None):
+        """Particles [first, first + m) of the resident sample, upstream's order (cells in order, then within a cell), in
+        box coordinates.  ``m=None``: up to ``n_part`` (the draw's stats).  Returns (x, y, z)."""
+        if m is None:
+            if n_part is None:
+                raise ValueError("give m, or n_part of the draw")
+            m = int(n_part) - int(first)
+        m = max(int(m), 0)
+        x, y, z = np.empty(m), np.empty(m), np.empty(m)
+        self._chk(self.lib.bchmc_poisson_positions(self.h, int(first), m, _p(x), _p(y), _p(z)))
+        return x, y, z
+
+    def poisson_density(self, mk=None, kernel_h=0.0, to_nobs=False, download=True):
+        """The resident sample onto the handle's grid through ``density_particles``' pipeline, the positions made on the
+        device batch by batch (with ``mk=1``: tools/poisson_upres.cc end to end).  Arguments and result as there."""
+        if not download and not to_nobs:
+            raise ValueError("download=False leaves the field nowhere unless to_nobs is set")
+        opts = DensityOpts(-1 if mk is None else int(mk), 0, float(kernel_h), F_NOBS if to_nobs else -1, 0)
+        st = DensityStats()
+        out = np.empty(self.N) if download else None
+        self._chk(self.lib.bchmc_poisson_density(self.h, C.byref(opts), None if out is None else _p(out), C.byref(st)))
+        return out, dict(n_in=int(st.n_in), n_lost=int(st.n_lost), max_per_tile=int(st.max_per_tile))
+
+    def poisson_release(self):
+        """Frees the resident sample and its scratch; a later ``poisson_draw`` rebuilds them."""
+        self._chk(self.lib.bchmc_poisson_release(self.h))
 
     def interp_particles(self, x=None, y=None, z=None, fields=(), kernel="cic", path=None, source="host"):
         """interpolate_CIC / interpolate_TSC / interpolate_TSC_multi (interpolate_grid.cpp:108-286) on the device: one to

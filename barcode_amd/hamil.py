@@ -190,6 +190,26 @@ def getDensity(hd, mk, xp, yp, zp, Par_mass=None, weightmass=False, kernel_h=0.0
     return hd.engine.density_particles(xp, yp, zp, w, mk=mk, kernel_h=kernel_h, to_nobs=to_nobs)
 
 
+def discrete_poisson_sample(hd, field, Nbar, seed, stream=0):
+    """discrete_poisson_sample (tools/poisson_upres.cc:23-65) of ``Nbar (1 + field)`` (:127) on the device: ``field`` is an
+    n_in^3 grid with n_in <= the handle's Nx on the handle's box.  The counts come from the engine's counter-based
+    sampler under ``(seed, stream)`` -- exact in distribution, not GSL's stream -- the particles in upstream's order.
+    Returns (x, y, z, stats); the sample stays resident in the engine."""
+    _, st = hd.engine.poisson_draw(field, seed=seed, stream=stream, scale=Nbar, counts=False)
+    x, y, z = hd.engine.poisson_positions(0, st["n_part"])
+    return x, y, z, st
+
+
+def poisson_upres(hd, field, Nbar, seed, mk=1, stream=0):
+    """tools/poisson_upres.cc end to end: a Poisson sample of ``Nbar (1 + field)`` (``field``: n_in^3, n_in <= Nx) assigned
+    to the handle's Nx^3 grid by masskernel ``mk`` (the tool's is CIC, 1), without a position leaving the device.
+    Returns (density, stats) with the draw's and the assignment's stats merged."""
+    _, st = hd.engine.poisson_draw(field, seed=seed, stream=stream, scale=Nbar, counts=False)
+    rho, ds = hd.engine.poisson_density(mk=mk)
+    st.update(ds)
+    return rho, st
+
+
 def interpolate_CIC(hd, xp, yp, zp, field_grid, path=None):
     """interpolate_CIC (interpolate_grid.cpp:108-120) of a field at a free particle list on ``hd``'s grid, upstream's
     argument order from ``xp`` on -> N_OBJ values.  ``field_grid``: an array of N values, ``"chain"``, ``"deltax"`` or a

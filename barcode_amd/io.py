@@ -148,6 +148,21 @@ def dump_density(density, fname_out="density"):
     return add_extension_if_missing(fname_out)
 
 
+def poisson_filename(fname_in, N1_out, Nbar):
+    """The default output name of ``tools/poisson_upres.cc:88``: ``<in>_poisCIC<N_out>_Nbar<Nbar>``, the two numbers as
+    they were typed (pass strings to keep a spelling such as ``8.0``)."""
+    fmt = lambda v: v if isinstance(v, str) else "%g" % v
+    return "%s_poisCIC%s_Nbar%s" % (fname_in, fmt(N1_out), fmt(Nbar))
+
+
+def dump_poisson(density, fname_in, N1_out, Nbar, fname_out=None):
+    """``quick_dump_scalar(output, N1_out, fname_out, 0, false)`` of ``tools/poisson_upres.cc:154``: the raw array under
+    ``fname_out``, by default the tool's ``<in>_poisCIC<N_out>_Nbar<Nbar>``.  Returns the path written."""
+    name = fname_out or poisson_filename(fname_in, N1_out, Nbar)
+    write_array(name, np.asarray(density))
+    return add_extension_if_missing(name)
+
+
 def ensemble_filenames(directory, name):
     """``<name>_mean`` and ``<name>_std`` under ``directory`` (before ``write_array``'s extension rule)."""
     base = os.path.join(directory, name) if directory else name

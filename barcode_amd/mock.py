@@ -2,11 +2,15 @@
 
 ``setup_random_test`` (:42-205) and ``make_initial_guess`` (:207-247) draw from the same ``GslMT19937`` the chain later
 takes its momenta, Neps, epsilon and Metropolis uniforms from (``hamil.HamiltonianMC(momenta="mt19937")``), so a run
-that starts from ``seed`` sees the arrays an upstream run seeded alike sees.  The Poissonian mock is not built
-(``BchmcError`` code 5): ``gsl_ran_poisson`` consumes a data-dependent number of words per cell.
+that starts from ``seed`` sees the arrays an upstream run seeded alike sees.  The Poissonian mock (``data_model`` 0 under
+``likelihood`` 0) has no such form: ``gsl_ran_poisson`` consumes a data-dependent number of words per cell.  With
+``MockParams.poisson_seed`` set it is drawn by the engine's counter-based sampler instead
+(``Engine.setup_random_test_poisson``: truth, forward model and window still from ``rng``, nobs exact in distribution but
+not upstream's stream); with ``None``, the default, it is refused as before (``BchmcError`` code 5).
 """
 import os
 from dataclasses import dataclass
+from typing import Optional
 
 from . import io
 
@@ -30,6 +34,7 @@ class MockParams:
     N_bin: int = 200
     likelihood: int = 1
     dir: str = ""
+    poisson_seed: Optional[int] = None   # not upstream's: seed of the counter-based Poissonian mock (None: not drawn)
 
 
 def setup_random_test(hd, rng, mock):
@@ -37,9 +42,13 @@ def setup_random_test(hd, rng, mock):
     the three arrays afterwards as if they had been uploaded.  With ``mock.dir`` the dumps upstream writes
     (deltaLAGtest / deltaEULtest via dump_deltas, win, nobs, sigma).  Returns (delta_lag, delta_eul)."""
     e = hd.engine
-    _, dl, de = e.setup_random_test(rng, window_type=mock.window_type, data_model=mock.data_model,
-                                    negative_obs=mock.negative_obs, random_test_rsd=mock.random_test_rsd,
-                                    sigma_min=mock.sigma_min, sigma_fac=mock.sigma_fac)
+    if mock.poisson_seed is not None and mock.likelihood == 0:
+        _, dl, de = e.setup_random_test_poisson(rng, mock.poisson_seed, window_type=mock.window_type,
+                                                random_test_rsd=mock.random_test_rsd)
+    else:
+        _, dl, de = e.setup_random_test(rng, window_type=mock.window_type, data_model=mock.data_model,
+                                        negative_obs=mock.negative_obs, random_test_rsd=mock.random_test_rsd,
+                                        sigma_min=mock.sigma_min, sigma_fac=mock.sigma_fac)
     if mock.dir:
         io.write_array(os.path.join(mock.dir, "deltaLAGtest"), dl)
         io.write_array(os.path.join(mock.dir, "deltaEULtest"), de)

@@ -28,7 +28,8 @@ SHIM_EXPORTS = ("bchmc_shim_Hamiltonian_EoM", "bchmc_shim_delta_Hamiltonian", "b
                 "bchmc_shim_setup_random_test", "bchmc_shim_make_initial_guess", "bchmc_shim_sizeof_mock",
                 "bchmc_shim_measure_corr_grid", "bchmc_shim_measure_corr2D", "bchmc_shim_chain_forward",
                 "bchmc_shim_interp_field", "bchmc_shim_measure_corr2D_interp", "bchmc_shim_measure_spec2D",
-                "bchmc_shim_getDensity", "bchmc_shim_interpolate")
+                "bchmc_shim_getDensity", "bchmc_shim_interpolate", "bchmc_shim_setup_random_test_poisson",
+                "bchmc_shim_discrete_poisson_sample", "bchmc_shim_poisson_positions", "bchmc_shim_poisson_upres")
 
 _dp = C.POINTER(C.c_double)
 
@@ -139,6 +140,13 @@ def load():
     lib.bchmc_shim_sizeof_mock.restype = sz
     lib.bchmc_shim_setup_random_test.argtypes = [hv, C.POINTER(MockView), MT_STATE_FN, C.c_void_p, _dp, _dp,
                                                  C.c_char_p, sz]
+    lib.bchmc_shim_setup_random_test_poisson.argtypes = [hv, C.POINTER(MockView), MT_STATE_FN, C.c_void_p, C.c_uint64,
+                                                         C.c_uint32, _dp, _dp, C.c_char_p, sz]
+    lib.bchmc_shim_discrete_poisson_sample.argtypes = [hv, _dp, C.c_uint, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64),
+                                                       C.c_char_p, sz]
+    lib.bchmc_shim_poisson_positions.argtypes = [hv, C.c_uint64, C.c_uint64, _dp, _dp, _dp, C.c_char_p, sz]
+    lib.bchmc_shim_poisson_upres.argtypes = [hv, _dp, C.c_uint, C.c_double, C.c_uint64, C.c_uint32, C.c_int, _dp,
+                                             C.c_char_p, sz]
     lib.bchmc_shim_make_initial_guess.argtypes = [hv, C.POINTER(MockView), MT_STATE_FN, C.c_void_p, C.c_char_p, sz]
     lib.bchmc_shim_HamiltonianMC_scripted.argtypes = [hv, _dp, ul, UNIFORM_FN, C.c_void_p, ul, C.POINTER(ul),
                                                       C.POINTER(AttemptLog), ul, C.POINTER(ul), C.c_char_p, sz]
@@ -420,14 +428,47 @@ class ShimHamil:
         return MT_STATE_FN(state)
 
     def setup_random_test(self, rng, window_type=1, data_model=0, negative_obs=False, random_test_rsd=False,
-                          sigma_min=1.0, sigma_fac=0.0):
-        """bchmc_shim::setup_random_test from ``rng`` (a ``GslMT19937``, advanced in place): (delta_lag, delta_eul)."""
+                          sigma_min=1.0, sigma_fac=0.0, poisson_seed=None, poisson_stream=0):
+        """bchmc_shim::setup_random_test from ``rng`` (a ``GslMT19937``, advanced in place): (delta_lag, delta_eul).
+        ``poisson_seed``: the Poissonian mock from the engine's counter-based sampler (None: refused, as upstream's
+        stream has no parallel form)."""
         m = MockView(int(window_type), int(data_model), int(bool(negative_obs)), int(bool(random_test_rsd)),
                      float(sigma_min), float(sigma_fac), 0, 1, 0.0, None)
         dl, de = np.empty(self.N), np.empty(self.N)
-        self._chk(self.lib.bchmc_shim_setup_random_test(C.byref(self.hd), C.byref(m), self._state_fn(rng), None, _p(dl),
-                                                        _p(de), self._err, len(self._err)))
+        if poisson_seed is None:
+            self._chk(self.lib.bchmc_shim_setup_random_test(C.byref(self.hd), C.byref(m), self._state_fn(rng), None, _p(dl),
+                                                            _p(de), self._err, len(self._err)))
+        else:
+            self._chk(self.lib.bchmc_shim_setup_random_test_poisson(C.byref(self.hd), C.byref(m), self._state_fn(rng), None,
+                                                                    int(poisson_seed), int(poisson_stream), _p(dl), _p(de),
+                                                                    self._err, len(self._err)))
         return dl, de
+
+    def discrete_poisson_sample(self, lam, seed, stream=0):
+        """bchmc_shim::discrete_poisson_sample of an N1^3 grid of rates (N1 <= the view's) -> (n_part, 3) positions."""
+        lam = np.ascontiguousarray(lam, dtype=np.float64).reshape(-1)
+        n1 = int(round(lam.size ** (1.0 / 3.0)))
+        if n1 ** 3 != lam.size:
+            raise ValueError("%d rates are no cube" % lam.size)
+        n = C.c_uint64(0)
+        self._chk(self.lib.bchmc_shim_discrete_poisson_sample(C.byref(self.hd), _p(lam), n1, int(seed), int(stream),
+                                                              C.byref(n), self._err, len(self._err)))
+        x, y, z = np.empty(n.value), np.empty(n.value), np.empty(n.value)
+        if n.value:  # the sample is resident: one fetch
+            self._chk(self.lib.bchmc_shim_poisson_positions(C.byref(self.hd), 0, n.value, _p(x), _p(y), _p(z), self._err,
+                                                            len(self._err)))
+        return np.stack([x, y, z], axis=1)
+
+    def poisson_upres(self, delta, Nbar, seed, mk=1, stream=0):
+        """bchmc_shim::poisson_upres: a sample of Nbar (1 + delta) (``delta``: N1^3 values) on the view's grid -> N values."""
+        delta = np.ascontiguousarray(delta, dtype=np.float64).reshape(-1)
+        n1 = int(round(delta.size ** (1.0 / 3.0)))
+        if n1 ** 3 != delta.size:
+            raise ValueError("%d values are no cube" % delta.size)
+        out = np.empty(self.N)
+        self._chk(self.lib.bchmc_shim_poisson_upres(C.byref(self.hd), _p(delta), n1, float(Nbar), int(seed), int(stream),
+                                                    int(mk), _p(out), self._err, len(self._err)))
+        return out
 
     def make_initial_guess(self, rng, initial_guess=0, file_field=None, smoothing_type=1, smoothing_scale=0.0):
         """bchmc_shim::make_initial_guess from ``rng``: sets the resident chain state."""

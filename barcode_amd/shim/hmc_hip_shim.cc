@@ -314,6 +314,62 @@ void density_on_handle(HamilView *hd, const char *name, int mk, ULONG N1, ULONG 
 }
 }  // namespace
 
+namespace {
+// The draw of both Poisson entry points: an N1^3 rate grid on the handle's box; returns the sample's size
+uint64_t poisson_draw_on_handle(HamilView *hd, const char *name, const real_prec *field, unsigned N1, unsigned N2,
+                                unsigned N3, real_prec L1, real_prec L2, real_prec L3, int rate_mode, real_prec scale,
+                                uint64_t seed, uint32_t stream) {
+  const HamilNumericalView *n = hd->numerical;
+  if (N2 != N1 || N3 != N1 || N1 < 1 || N1 > n->N1 || L1 != n->L1 || L2 != n->L1 || L3 != n->L1)
+    throw std::runtime_error(std::string(name) + ": the rate grid is not a cube of at most the handle's size on its box");
+  bchmc_handle *h = engine_for(hd);
+  bchmc_poisson_opts o{};
+  o.seed = seed;
+  o.stream = stream;
+  o.rate_mode = rate_mode;
+  o.scale = scale;
+  o.use_window = 0;
+  o.dest = -1;
+  bchmc_poisson_stats st{};
+  const int rc = bchmc_poisson_draw(h, BCHMC_CORR_HOST, field, N1, &o, nullptr, &st);
+  if (rc) fail(h, rc, name);
+  return st.n_part;
+}
+}  // namespace
+
+std::vector<std::vector<real_prec>> discrete_poisson_sample(HamilView *hd, const real_prec *lambda, unsigned N1, unsigned N2,
+                                                            unsigned N3, real_prec L1, real_prec L2, real_prec L3,
+                                                            uint64_t seed, uint32_t stream) {
+  const char *name = "discrete_poisson_sample";
+  const uint64_t n_part = poisson_draw_on_handle(hd, name, lambda, N1, N2, N3, L1, L2, L3, 1, 1., seed, stream);
+  bchmc_handle *h = engine_for(hd);
+  std::vector<std::vector<real_prec>> pos(n_part, std::vector<real_prec>(3));
+  const uint64_t batch = 1u << 20;  // the engine's own batch: three columns of it at a time
+  std::vector<real_prec> x(std::min(batch, n_part)), y(x.size()), z(x.size());
+  for (uint64_t p0 = 0; p0 < n_part; p0 += batch) {
+    const uint64_t m = std::min(batch, n_part - p0);
+    const int rc = bchmc_poisson_positions(h, p0, m, x.data(), y.data(), z.data());
+    if (rc) fail(h, rc, name);
+    for (uint64_t p = 0; p < m; p++) pos[p0 + p][0] = x[p], pos[p0 + p][1] = y[p], pos[p0 + p][2] = z[p];
+  }
+  return pos;
+}
+
+void poisson_upres(HamilView *hd, const real_prec *delta, unsigned N1, real_prec Nbar, uint64_t seed, real_prec *output,
+                   int mk, uint32_t stream) {
+  const char *name = "poisson_upres";
+  const real_prec L = hd->numerical->L1;
+  poisson_draw_on_handle(hd, name, delta, N1, N1, N1, L, L, L, 0, Nbar, seed, stream);  // lambda = Nbar (1 + delta), :127
+  bchmc_handle *h = engine_for(hd);
+  bchmc_density_opts o{};
+  o.mk = mk;
+  o.weightmass = 0;  // pmass_used = false, :150
+  o.kernel_h = 0.;
+  o.dest = -1;
+  const int rc = bchmc_poisson_density(h, &o, output, nullptr);
+  if (rc) fail(h, rc, name);
+}
+
 void getDensity_NGP(HamilView *hd, unsigned N1, unsigned N2, unsigned N3, real_prec L1, real_prec L2, real_prec L3,
                     real_prec d1, real_prec d2, real_prec d3, real_prec min1, real_prec min2, real_prec min3,
                     const real_prec *xp, const real_prec *yp, const real_prec *zp, const real_prec *Par_mass, ULONG N_OBJ,
@@ -454,7 +510,7 @@ void chain_get_state(HamilView *hd, real_prec *x) {
 }
 
 void setup_random_test(HamilView *hd, const MockView *m, mt19937_state_fn state, void *rng_state, real_prec *delta_lag,
-                       real_prec *delta_eul) {
+                       real_prec *delta_eul, const uint64_t *poisson_seed, uint32_t poisson_stream) {
   if (!m || !state) throw std::runtime_error("In setup_random_test: no parameters or no generator state hook");
   bchmc_handle *h = engine_for(hd);
   bchmc_mock_opts o;
@@ -467,7 +523,9 @@ void setup_random_test(HamilView *hd, const MockView *m, mt19937_state_fn state,
   uint32_t mt[624];
   int32_t mti = 0;
   state(rng_state, mt, &mti, 0);
-  int rc = bchmc_setup_random_test(h, &o, mt, &mti, nullptr, delta_lag, delta_eul);
+  int rc = poisson_seed && hd->likelihood == 0
+               ? bchmc_setup_random_test_poisson(h, &o, mt, &mti, nullptr, *poisson_seed, poisson_stream, delta_lag, delta_eul)
+               : bchmc_setup_random_test(h, &o, mt, &mti, nullptr, delta_lag, delta_eul);
   if (rc) fail(h, rc, "setup_random_test");
   state(rng_state, mt, &mti, 1);
   // upstream writes o->window / nobs / noise_sf, which call_hamil.cc hands to HAMIL_DATA: keep the caller's copies equal
@@ -993,6 +1051,32 @@ int bchmc_shim_setup_random_test(bchmc_shim::HamilView *hd, const bchmc_shim::Mo
                                  bchmc_shim::mt19937_state_fn state, void *rng_state, double *delta_lag,
                                  double *delta_eul, char *err, size_t errlen) {
   return guarded(err, errlen, [&] { bchmc_shim::setup_random_test(hd, m, state, rng_state, delta_lag, delta_eul); });
+}
+int bchmc_shim_setup_random_test_poisson(bchmc_shim::HamilView *hd, const bchmc_shim::MockView *m,
+                                         bchmc_shim::mt19937_state_fn state, void *rng_state, uint64_t seed,
+                                         uint32_t stream, double *delta_lag, double *delta_eul, char *err, size_t errlen) {
+  return guarded(err, errlen, [&] {
+    bchmc_shim::setup_random_test(hd, m, state, rng_state, delta_lag, delta_eul, &seed, stream);
+  });
+}
+int bchmc_shim_discrete_poisson_sample(bchmc_shim::HamilView *hd, const double *lambda, unsigned N1, uint64_t seed,
+                                       uint32_t stream, uint64_t *n_part, char *err, size_t errlen) {
+  return guarded(err, errlen, [&] {
+    const double L = hd->numerical->L1;
+    *n_part = bchmc_shim::poisson_draw_on_handle(hd, "discrete_poisson_sample", lambda, N1, N1, N1, L, L, L, 1, 1., seed, stream);
+  });
+}
+int bchmc_shim_poisson_positions(bchmc_shim::HamilView *hd, uint64_t first, uint64_t m, double *x, double *y, double *z,
+                                 char *err, size_t errlen) {
+  return guarded(err, errlen, [&] {
+    bchmc_handle *h = bchmc_shim::engine_for(hd);
+    const int rc = bchmc_poisson_positions(h, first, m, x, y, z);
+    if (rc) bchmc_shim::fail(h, rc, "poisson_positions");
+  });
+}
+int bchmc_shim_poisson_upres(bchmc_shim::HamilView *hd, const double *delta, unsigned N1, double Nbar, uint64_t seed,
+                             uint32_t stream, int mk, double *output, char *err, size_t errlen) {
+  return guarded(err, errlen, [&] { bchmc_shim::poisson_upres(hd, delta, N1, Nbar, seed, output, mk, stream); });
 }
 int bchmc_shim_make_initial_guess(bchmc_shim::HamilView *hd, const bchmc_shim::MockView *m,
                                   bchmc_shim::mt19937_state_fn state, void *rng_state, char *err, size_t errlen) {

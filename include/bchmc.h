@@ -569,6 +569,89 @@ int bchmc_setup_random_test(bchmc_handle *h, const bchmc_mock_opts *o, uint32_t 
  * (create_GARFIELD's walk), generator and chain state untouched; 0, 1 and 4 work at any Nx. */
 int bchmc_make_initial_guess(bchmc_handle *h, int32_t initial_guess, const double *file_field, int32_t smoothing_type,
                              double smoothing_scale, uint32_t mt[624], int32_t *mti, uint64_t *words_used);
+/* ---- Poisson samples of a density field (upstream: discrete_poisson_sample, tools/poisson_upres.cc:23-65, and the
+ * Poissonian mock of setup_random_test, barcoderunner.cc:117-131) -------------------------------------------------------
+ * gsl_ran_poisson consumes a data-dependent number of words of a serial stream, which no parallel form reproduces.  Like
+ * bchmc_chain_draw_momenta, these entry points draw from a counter-based Philox4x32-10 stand-in instead -- here exact in
+ * distribution: the count of cell c = k + n (j + n i) of an n_in^3 rate grid is a pure function of (seed, stream, c,
+ * lambda_c), whatever the launch shape, the handle's kind or its precision.  Eight properties:
+ *  P1 Uniforms, k_white_noise's convention.  r = philox4x32_10((c_lo, c_hi, j, 2 stream), (seed_lo, seed_hi)),
+ *     u = (((r.x << 32 | r.y) >> 11) + 0.5) 2^-53, v the same from r.z, r.w; j is the iteration.  stream < 2^31.
+ *  P2 Rate.  rate_mode 0: lambda = scale (1 + x) (poisson_upres.cc:127's Nbar (1 + delta), barcoderunner.cc:125's
+ *     rho_c (1 + delta_eul)); 1: lambda = scale x.  x is read in the storage type and widened, the product is formed in
+ *     double, uncontracted.  use_window = 1: a cell whose handle window is not > 0 gets count 0 and draws nothing
+ *     (barcoderunner.cc:126, 160).  lambda <= 0 (and -infinity): 0, as GSL.  A NaN, a +infinity or a lambda above 2^30
+ *     refuses the call with BCHMC_ERR_ARG naming the first such cell index: nothing is written to counts or made nobs,
+ *     and the handle holds no sample afterwards (an earlier one is gone: the draw had taken its buffers).
+ *  P3 0 < lambda < 10: inversion by sequential search with j = 0 and u only:
+ *       p = exp(-lambda); s = p; k = 0;  while (u > s && k < 256) { k++; p = p * lambda / (double)k; s = s + p; }
+ *     (the cap is there because u can round to 1.0).
+ *  P4 lambda >= 10: Hoermann's PTRS (1993).  b = 0.931 + 2.53 sqrt(lambda), a = -0.059 + 0.02483 b,
+ *     1/alpha = 1.1239 + 1.1328 / (b - 3.4), v_r = 0.9277 - 3.6224 / (b - 2).  Per iteration j = 0, 1, ...: U = u - 0.5,
+ *     us = 0.5 - |U|, k = floor((2 a / us + b) U + lambda + 0.43); accept if us >= 0.07 && v <= v_r; retry if k < 0 ||
+ *     (us < 0.013 && v > us); otherwise accept iff log v + log(1/alpha) - log(a / us^2 + b) <= -lambda + k log lambda -
+ *     lgamma(k + 1).  At most 64 iterations.  All of it in double, uncontracted, in this operand order: the same lines in
+ *     numpy float64 give the same counts except where a decision is closer than the last bits of exp / log / lgamma.
+ *     stats->n_capped counts the cells that ran into either cap (they return the last candidate); expected 0.
+ *  P5 The resident sample.  The handle keeps the exclusive 64-bit scan off[0 .. n_in^3] of the counts, (seed, stream,
+ *     n_in, n_part) and d_in = L / n_in -- 8 bytes per cell, nothing per particle.  Particle p lies in the cell c with
+ *     off[c] <= p < off[c + 1], found by an upper-bound search that steps over runs of empty cells, at index
+ *     kk = p - off[c]; its position is upstream's (:52-58) with gsl_rng_uniform's 32-bit resolution:
+ *     x = d_in (double)i + ((double)w.x 2^-32) d_in, y from w.y and j, z from w.z and k,
+ *     w = philox4x32_10((c_lo, c_hi, kk, 2 stream + 1), seed), uncontracted, in box coordinates (min is not added, as in
+ *     the tool).  Particle order is upstream's: cells in order, kk within a cell.
+ *  P6 bchmc_poisson_draw.  Sources, their argument and state errors: bchmc_measure_corr2d's.  BCHMC_CORR_HOST: n_in in
+ *     1..Nx, `signal` = n_in^3 doubles (staged in the lower half of the transfer staging and read as doubles on every
+ *     handle); device sources: n_in = 0 or Nx.  use_window = 1 and dest = BCHMC_F_NOBS need n_in == Nx (BCHMC_ERR_ARG),
+ *     use_window = 1 an uploaded window (BCHMC_ERR_STATE).  counts (may be NULL): n_in^3 doubles.  dest = BCHMC_F_NOBS
+ *     does to the handle exactly what bchmc_upload(BCHMC_F_NOBS) of the counts would.  A draw replaces the resident
+ *     sample and leaves alone what D6 of bchmc_density_particles lists.  The buffers are counted by
+ *     bchmc_live_resources and freed by bchmc_poisson_release and bchmc_destroy; after an allocation failure the handle
+ *     holds no sample and stays usable.  Also BCHMC_ERR_ARG: opts NULL, stream >= 2^31, rate_mode or use_window other
+ *     than 0 / 1, a scale that is not finite, dest other than -1 / BCHMC_F_NOBS.
+ *  P7 bchmc_poisson_positions: particles [first, first + m) of the resident sample as doubles on every handle --
+ *     discrete_poisson_sample's list in batches of the caller's own size.  first + m > n_part, or a NULL column with
+ *     m > 0: BCHMC_ERR_ARG; no sample: BCHMC_ERR_STATE; m = 0 succeeds.
+ *  P8 bchmc_poisson_density: the resident sample onto the handle's grid through the catalogue's pipeline, batch by batch,
+ *     the columns filled on the device: no position crosses PCIe.  With mk = 1 this is poisson_upres.cc end to end.
+ *     Options, refusals, properties D1-D7 and stats are those of bchmc_density_particles with weightmass = 0;
+ *     weightmass = 1: BCHMC_ERR_ARG; n_part > 2^31 - 1: BCHMC_ERR_ARG; no sample: BCHMC_ERR_STATE.
+ * Not built: GSL's own Poisson stream, per-particle weights, a device pointer to the positions, n_in > Nx.
+ * (Added within ABI version 4: no struct or existing entry point changed.) */
+typedef struct bchmc_poisson_opts {
+  uint64_t seed;
+  uint32_t stream;       /* < 2^31 */
+  int32_t rate_mode;     /* 0: lambda = scale (1 + x); 1: lambda = scale x */
+  double scale;
+  int32_t use_window;    /* 1: cells whose window is not > 0 draw nothing */
+  int32_t dest;          /* -1, or BCHMC_F_NOBS: the counts also become the handle's nobs, as if uploaded */
+} bchmc_poisson_opts;
+typedef struct bchmc_poisson_stats {
+  uint64_t n_part, n_cells_drawn, max_count, n_capped;  /* particles, cells with lambda > 0 inside the window, ... */
+  double lambda_max;                                    /* over the cells that drew (0: none did) */
+} bchmc_poisson_stats;
+int bchmc_poisson_draw(bchmc_handle *h, bchmc_corr_source src, const double *signal, uint32_t n_in,
+                       const bchmc_poisson_opts *opts, double *counts /* n_in^3 or NULL */,
+                       bchmc_poisson_stats *stats /* or NULL */);
+int bchmc_poisson_positions(bchmc_handle *h, uint64_t first, uint64_t m, double *x, double *y, double *z);
+int bchmc_poisson_density(bchmc_handle *h, const bchmc_density_opts *opts, double *out /* N or NULL */,
+                          bchmc_density_stats *stats /* or NULL */);
+int bchmc_poisson_release(bchmc_handle *h);   /* frees the sample and its scratch; a later draw rebuilds them */
+/* bchmc_setup_random_test with data_model = 0 on a likelihood = 0 handle, the case it refuses: the 2 N Gaussians of the
+ * truth come from the caller's mt19937 state, so the truth, its forward model and the window are bit for bit those of
+ * bchmc_setup_random_test and the generator advances by those words only; then nobs = the sampler above at
+ * scale = rho_c, rate_mode 0, use_window = 1 of the truth's deltaX under (seed, stream), 0 outside the window, and noise
+ * is 0 everywhere (upstream leaves it unwritten).  The three arrays count as uploaded; the resident sample of
+ * bchmc_poisson_draw is left alone.  Any other likelihood or data_model: BCHMC_ERR_ARG; stream >= 2^31: BCHMC_ERR_ARG;
+ * all other refusals, and their order, are those of bchmc_setup_random_test.
+ * One refusal comes after the draw, like bchmc_setup_random_test's noise == 0: a cell inside the window whose
+ * rho_c (1 + delta_eul) is NaN, +infinity or above 2^30 -> BCHMC_ERR_ARG naming the first such index.  The generator has
+ * then advanced by the truth's words, delta_lag / delta_eul and words_used are written, deltaX / pos* are the truth's and
+ * the window is built, but window, nobs and noise count as not uploaded and nobs and noise are as they were.
+ * (Added within ABI version 4: no struct or existing entry point changed.) */
+int bchmc_setup_random_test_poisson(bchmc_handle *h, const bchmc_mock_opts *o, uint32_t mt[624], int32_t *mti,
+                                    uint64_t *words_used, uint64_t seed, uint32_t stream, double *delta_lag,
+                                    double *delta_eul);
 int bchmc_philox_kat(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]); /* known-answer hook for tests */
 
 /* Diagnostic (tests, logs): how the particle-mesh path is currently set up.  out = { tile-sorted path in use, one-pass

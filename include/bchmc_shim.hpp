@@ -22,12 +22,16 @@
 //   void interpolate_TSC(N1, N2, N3, d1, d2, d3, xp, yp, zp, field_grid, N_OBJ, interpolation)
 //   void interpolate_TSC_multi(N1, N2, N3, d1, d2, d3, xp, yp, zp, N_OBJ, field_grids, interpolations, N_fields)
 //                                                   interpolate_grid.cpp:108-286       -> bchmc_shim::interpolate_CIC ..
+//   vector<vector<real_prec>> discrete_poisson_sample(lambda, N1, N2, N3, L1, L2, L3, gsl_rng*)
+//                                                   tools/poisson_upres.cc:23-65       -> bchmc_shim::discrete_poisson_sample
+//   tools/poisson_upres.cc's main (:107-157)                                           -> bchmc_shim::poisson_upres
 // Errors are std::runtime_error, like the reference's (single catch in main.cc:195-197).
 #ifndef BCHMC_SHIM_HPP
 #define BCHMC_SHIM_HPP
 #include <cstdint>
 #include <stdexcept>
 #include <string>
+#include <vector>
 
 #include "bchmc.h"
 
@@ -166,6 +170,18 @@ void getDensity_SPH(HamilView *hd, ULONG N1, ULONG N2, ULONG N3, real_prec L1, r
                     real_prec d2, real_prec d3, real_prec min1, real_prec min2, real_prec min3, const real_prec *xp,
                     const real_prec *yp, const real_prec *zp, const real_prec *Par_mass, ULONG N_OBJ, real_prec *delta,
                     bool weightmass, real_prec kernel_h);
+// tools/poisson_upres.cc:23-65 on the device (bchmc_poisson_draw + bchmc_poisson_positions): upstream's argument list
+// behind the view, with (seed, stream) of the engine's counter-based sampler in the place of the gsl_rng -- exact in
+// distribution, not GSL's stream (properties P1-P5 in bchmc.h).  lambda: N1^3 rates, N1 = N2 = N3 at most the handle's
+// grid size, on the handle's box (std::runtime_error otherwise).  Returns upstream's list of (x, y, z), in its order; the
+// sample stays resident in the engine.
+std::vector<std::vector<real_prec>> discrete_poisson_sample(HamilView *hd, const real_prec *lambda, unsigned N1, unsigned N2,
+                                                            unsigned N3, real_prec L1, real_prec L2, real_prec L3,
+                                                            uint64_t seed, uint32_t stream = 0);
+// tools/poisson_upres.cc:107-157 end to end, without a position leaving the device: a sample of Nbar (1 + delta) of the
+// N1^3 field `delta`, assigned to the handle's grid by masskernel mk (the tool's is CIC, 1).  output: N values.
+void poisson_upres(HamilView *hd, const real_prec *delta, unsigned N1, real_prec Nbar, uint64_t seed, real_prec *output,
+                   int mk = 1, uint32_t stream = 0);
 // interpolate_grid.cpp:108-120, 194-202, 271-286 on the device (bchmc_interp_particles): host grids read at a free list of
 // N_OBJ particles, upstream's argument lists behind the view.  The grid is the handle's (std::runtime_error otherwise).
 // A particle outside TSC's domain, or with a non-finite coordinate, gets a quiet NaN (property I4 in bchmc.h).
@@ -261,8 +277,10 @@ struct MockView {
 // HamiltonianMC_mt19937: read before, written back after).  The engine then holds window / nobs / noise as if they had
 // been uploaded; where the view has caller-owned arrays for them they receive the built values (so that a later
 // inputs_changed() uploads the same numbers).  delta_lag / delta_eul may be null.  Throws like the reference.
+// poisson_seed (not upstream's; null: as upstream, where the engine refuses the Poissonian mock): the mock of data_model 0
+// under the Poissonian likelihood from the engine's counter-based sampler (bchmc_setup_random_test_poisson).
 void setup_random_test(HamilView *hd, const MockView *m, mt19937_state_fn state, void *rng_state, real_prec *delta_lag,
-                       real_prec *delta_eul);
+                       real_prec *delta_eul, const uint64_t *poisson_seed = nullptr, uint32_t poisson_stream = 0);
 // make_initial_guess (barcoderunner.cc:207-247): sets the resident chain state (read it with chain_get_state)
 void make_initial_guess(HamilView *hd, const MockView *m, mt19937_state_fn state, void *rng_state);
 
@@ -349,6 +367,17 @@ int bchmc_shim_HamiltonianMC_scripted(bchmc_shim::HamilView *hd, const double *s
 int bchmc_shim_setup_random_test(bchmc_shim::HamilView *hd, const bchmc_shim::MockView *m,
                                  bchmc_shim::mt19937_state_fn state, void *rng_state, double *delta_lag,
                                  double *delta_eul, char *err, size_t errlen);
+int bchmc_shim_setup_random_test_poisson(bchmc_shim::HamilView *hd, const bchmc_shim::MockView *m,
+                                         bchmc_shim::mt19937_state_fn state, void *rng_state, uint64_t seed,
+                                         uint32_t stream, double *delta_lag, double *delta_eul, char *err, size_t errlen);
+/* discrete_poisson_sample in two steps, so that a sample is drawn once and crosses PCIe once: the draw (*n_part = the
+ * sample's size; the sample stays resident), then any slice of it as three columns (bchmc_poisson_positions) */
+int bchmc_shim_discrete_poisson_sample(bchmc_shim::HamilView *hd, const double *lambda, unsigned N1, uint64_t seed,
+                                       uint32_t stream, uint64_t *n_part, char *err, size_t errlen);
+int bchmc_shim_poisson_positions(bchmc_shim::HamilView *hd, uint64_t first, uint64_t m, double *x, double *y, double *z,
+                                 char *err, size_t errlen);
+int bchmc_shim_poisson_upres(bchmc_shim::HamilView *hd, const double *delta, unsigned N1, double Nbar, uint64_t seed,
+                             uint32_t stream, int mk, double *output, char *err, size_t errlen);
 int bchmc_shim_make_initial_guess(bchmc_shim::HamilView *hd, const bchmc_shim::MockView *m,
                                   bchmc_shim::mt19937_state_fn state, void *rng_state, char *err, size_t errlen);
 size_t bchmc_shim_sizeof_mock(void);
