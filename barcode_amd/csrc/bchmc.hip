@@ -12,6 +12,7 @@
 #include "fft_host.hpp"
 #include "owned.hpp"
 #include "pass_launch.hpp"
+#include "launch_grid.hpp"
 #include "eval_plan.hpp"
 #include "interp_plan.hpp"
 
@@ -323,7 +324,6 @@ inline bool env_on(const char *name) {
   return v && v[0] == '1';
 }
 
-inline int nblk_stride(long long n) { return (int)std::min<long long>((n + 255) / 256, 2048); }
 inline int nblk_full(long long n) { return (int)((n + 255) / 256); }
 
 // ---- profiling ------------------------------------------------------------------------------------

@@ -8,6 +8,11 @@
 // fft_host.hpp, which the engine uses too.  The only kernel of its own is k_probe_xfft, a bare wrapper around
 // xfft_inplace, on the block size of the engine's tables.
 //
+// The k-space step kernels (tests/test_gpu_kstep.py) run the same way: the planes-mode step boundary and ALPT mix through
+// launch_step_boundary_x / launch_step_boundary_x2 / launch_alpt_mix_x, their 3-D twins (grid-stride kernels, any n) on
+// nblk_stride(Nhp) x 256 and k_parseval on kRedBlocks x 256 as bchmc.hip launches them.  Their geometry takes a box
+// length, so that kfac is not 2 pi / n.
+//
 // Every device array is followed by kCanary bytes of a known pattern; an entry point copies its host arrays in,
 // launches, synchronises, copies back and checks the canaries.  Return value: 0 = ok, -1 = arguments outside the
 // engine's instantiations, -2 = HIP error, k > 0 = the canary after device array k changed (1 = the twiddle table,
@@ -15,6 +20,7 @@
 #include "kernels.hpp"
 #include "fft_host.hpp"
 #include "pass_launch.hpp"
+#include "launch_grid.hpp"
 
 #include <cmath>
 #include <cstring>
@@ -97,7 +103,7 @@ struct Probe {
   template <typename T> PassCtx<T> ctx(const Geo &g) { return {nullptr, g, ilog2(g.n), twiddles<T>(g.n)}; }
 };
 
-Geo probe_geo(int n, int esz) {
+Geo probe_geo(int n, int esz, double L = 0.) {
   Geo g;
   g.n = n;
   g.nh = n / 2 + 1;
@@ -105,8 +111,8 @@ Geo probe_geo(int n, int esz) {
   g.N = (long long)n * n * n;
   g.Nh = (long long)n * n * g.nh;
   g.Nhp = (long long)n * n * g.nhp;
-  g.L = (double)n;
-  g.d = 1.;
+  g.L = L > 0. ? L : (double)n;
+  g.d = g.L / n;
   g.kfac = 2. * M_PI / g.L;
   return g;
 }
@@ -183,6 +189,254 @@ template <typename T> int zc2r(int n, const void *ck, void *psi) {
   return pr.finish({{3, psi}});
 }
 
+// ---- the k-space step kernels ------------------------------------------------------------------------------------------
+
+// the trajectory-control words of a probe call: stop, steps_done and guard_prev live on the device and come back
+struct CtlArgs {
+  int *stop;
+  unsigned long long *steps_done;
+  const double *guard_prev;  // may be null: no guard test, as at step 0
+  double guard_limit;
+  unsigned long long step_index;
+};
+struct CtlDev {
+  StepCtl ctl{};
+  int i_stop = -1, i_done = -1;
+};
+CtlDev ctl_alloc(Probe &pr, const CtlArgs &c) {
+  CtlDev d;
+  d.ctl.stop = static_cast<int *>(pr.alloc(sizeof(int), c.stop));
+  d.i_stop = (int)pr.bufs.size() - 1;
+  d.ctl.steps_done = static_cast<unsigned long long *>(pr.alloc(sizeof(unsigned long long), c.steps_done));
+  d.i_done = (int)pr.bufs.size() - 1;
+  d.ctl.guard_prev = c.guard_prev ? static_cast<const double *>(pr.alloc(sizeof(double), c.guard_prev)) : nullptr;
+  d.ctl.guard_limit = c.guard_limit;
+  d.ctl.step_index = c.step_index;
+  return d;
+}
+
+// a device copy of a host array that may be null (then null on the device too); idx receives its device array index
+template <typename U> U *opt(Probe &pr, size_t bytes, const void *host, int *idx = nullptr) {
+  if (!host) return nullptr;
+  U *d = static_cast<U *>(pr.alloc(bytes, host));
+  if (idx) *idx = (int)pr.bufs.size() - 1;
+  return d;
+}
+
+using Outs = std::vector<std::pair<int, void *>>;
+void out(Outs &o, int idx, void *host) {
+  if (host && idx >= 0) o.push_back({idx, host});
+}
+
+// k_step_boundary_x<T, NT, PER, MODE, ALPT> / k_step_boundary_x2<T, NT, PER> as the engine launches them.
+// scal = {a, b, half_eps, eps, c_za}
+template <typename T>
+int step_boundary_x(int n, double L, int mode, int alpt, int two_tile, void *Ck, const void *q_in, const void *p_in,
+                    const void *g_in, void *q_out, void *p_out, void *g_out, const double *wS, const double *wM,
+                    const double *scal, double *guard_slot, const CtlArgs &ca) {
+  if (mode < BX_INTERIOR || mode > BX_LAST || (alpt && mode == BX_LAST)) return -1;
+  if (two_tile ? (!x2_shape(sizeof(T), n).nt || mode != BX_INTERIOR || alpt) : !x_shape(sizeof(T), n).nt) return -1;
+  const Geo g = probe_geo(n, (int)sizeof(T), L);
+  if (g.nhp % pass_kb(sizeof(T)) || !Ck || !q_in || !scal) return -1;
+  // what each mode dereferences must be there (the kernels do not test for it)
+  const bool first_kick = mode == BX_FIRST && g_in, last_kick = mode == BX_LAST && p_out;
+  if (mode == BX_INTERIOR && !(p_in && q_out && p_out && guard_slot)) return -1;
+  if (first_kick && !(p_in && q_out && p_out)) return -1;
+  if (mode == BX_LAST && (!g_out || (last_kick && !(p_in && guard_slot)))) return -1;
+  if (mode != BX_FIRST && scal[0] != 0. && !wS) return -1;
+  Probe pr;
+  const PassCtx<T> x = pr.ctx<T>(g);
+  const size_t cb = (size_t)g.Nhp * sizeof(C2<T>), db = (size_t)g.Nhp * sizeof(double);
+  int i_ck, i_qo = -1, i_po = -1, i_go = -1, i_gs = -1;
+  C2<T> *d_ck = opt<C2<T>>(pr, 3 * cb, Ck, &i_ck);
+  BoundaryX<T> a;
+  a.qi = opt<const C2<T>>(pr, cb, q_in);
+  a.pi = opt<const C2<T>>(pr, cb, p_in);
+  a.g_in = opt<const C2<T>>(pr, cb, g_in);
+  a.qo = opt<C2<T>>(pr, cb, q_out, &i_qo);
+  a.po = opt<C2<T>>(pr, cb, p_out, &i_po);
+  a.g_out = opt<C2<T>>(pr, cb, g_out, &i_go);
+  const double *d_ws = opt<const double>(pr, db, wS);
+  a.wM = opt<const double>(pr, db, wM);
+  a.a = scal[0], a.b = scal[1], a.half_eps = scal[2], a.eps = scal[3], a.c_za = scal[4];
+  a.guard_slot = opt<double>(pr, sizeof(double), guard_slot, &i_gs);
+  const CtlDev cd = ctl_alloc(pr, ca);
+  a.ctl = cd.ctl;
+  if (pr.err) return pr.err;
+  hipError_t e = hipErrorInvalidConfiguration;
+  if (two_tile) e = launch_step_boundary_x2<T>(x, d_ck, d_ws, a);
+  else if (mode == BX_INTERIOR) e = alpt ? launch_step_boundary_x<T, BX_INTERIOR, true>(x, d_ck, d_ws, a)
+                                         : launch_step_boundary_x<T, BX_INTERIOR, false>(x, d_ck, d_ws, a);
+  else if (mode == BX_FIRST) e = alpt ? launch_step_boundary_x<T, BX_FIRST, true>(x, d_ck, d_ws, a)
+                                      : launch_step_boundary_x<T, BX_FIRST, false>(x, d_ck, d_ws, a);
+  else e = launch_step_boundary_x<T, BX_LAST, false>(x, d_ck, d_ws, a);
+  pr.ok(e);
+  Outs o;
+  out(o, i_ck, Ck), out(o, i_qo, q_out), out(o, i_po, p_out), out(o, i_go, g_out), out(o, i_gs, guard_slot);
+  out(o, cd.i_stop, ca.stop), out(o, cd.i_done, ca.steps_done);
+  return pr.finish(o);
+}
+
+template <typename T> int alpt_mix_x(int n, double L, void *Ck, double smol, double inv_wtot, double inv_n) {
+  if (!x_shape(sizeof(T), n).nt) return -1;
+  const Geo g = probe_geo(n, (int)sizeof(T), L);
+  if (g.nhp % pass_kb(sizeof(T))) return -1;
+  Probe pr;
+  const PassCtx<T> x = pr.ctx<T>(g);
+  C2<T> *d = static_cast<C2<T> *>(pr.alloc((size_t)3 * g.Nhp * sizeof(C2<T>), Ck));
+  if (pr.err) return pr.err;
+  pr.ok(launch_alpt_mix_x<T>(x, d, smol, inv_wtot, inv_n));
+  return pr.finish({{1, Ck}});
+}
+
+// The 3-D twins: element-wise over the padded half-complex array, any n >= 2.
+bool ok3d(int n) { return n >= 2 && n <= 512; }
+
+// scal = {half_eps, eps, c_za}
+template <typename T>
+int kick_drift_za(int n, double L, int drift, void *qk, void *pk, const void *gk, const double *wM, const void *extra,
+                  void *Ck, const double *scal, const CtlArgs &ca) {
+  if (!ok3d(n) || !qk || !Ck || !scal || (drift && !(pk && gk))) return -1;
+  const Geo g = probe_geo(n, (int)sizeof(T), L);
+  Probe pr;
+  const size_t cb = (size_t)g.Nhp * sizeof(C2<T>);
+  int i_q, i_p = -1, i_ck;
+  C2<T> *dq = opt<C2<T>>(pr, cb, qk, &i_q), *dp = opt<C2<T>>(pr, cb, pk, &i_p);
+  const C2<T> *dg = opt<const C2<T>>(pr, cb, gk);
+  const double *dw = opt<const double>(pr, (size_t)g.Nhp * sizeof(double), wM);
+  const C2<T> *dx = opt<const C2<T>>(pr, cb, extra);
+  C2<T> *dc = opt<C2<T>>(pr, 3 * cb, Ck, &i_ck);
+  const CtlDev cd = ctl_alloc(pr, ca);
+  if (pr.err) return pr.err;
+  if (drift)
+    k_kick_drift_za<T, true><<<nblk_stride(g.Nhp), 256>>>(g, dq, dp, dg, dw, dx, dc, scal[0], scal[1], scal[2], cd.ctl);
+  else
+    k_kick_drift_za<T, false><<<nblk_stride(g.Nhp), 256>>>(g, dq, dp, dg, dw, dx, dc, scal[0], scal[1], scal[2], cd.ctl);
+  Outs o;
+  out(o, i_q, qk), out(o, i_p, pk), out(o, i_ck, Ck), out(o, cd.i_stop, ca.stop), out(o, cd.i_done, ca.steps_done);
+  return pr.finish(o);
+}
+
+// scal = {a, b, c_kick}
+template <typename T>
+int assemble(int n, double L, int kick, const void *Ck, const void *qk, const double *wS, void *gk, void *pk,
+             const double *scal, int like_mode, double *guard_slot, int *stop) {
+  if (!ok3d(n) || !Ck || !gk || !scal || like_mode < 0 || like_mode > 2 || (scal[0] != 0. && !(qk && wS))) return -1;
+  if (kick && !(pk && guard_slot && stop)) return -1;
+  const Geo g = probe_geo(n, (int)sizeof(T), L);
+  Probe pr;
+  const size_t cb = (size_t)g.Nhp * sizeof(C2<T>);
+  int i_g, i_p = -1, i_gs = -1;
+  const C2<T> *dc = opt<const C2<T>>(pr, 3 * cb, Ck), *dq = opt<const C2<T>>(pr, cb, qk);
+  const double *dw = opt<const double>(pr, (size_t)g.Nhp * sizeof(double), wS);
+  C2<T> *dg = opt<C2<T>>(pr, cb, gk, &i_g), *dp = opt<C2<T>>(pr, cb, pk, &i_p);
+  double *dgs = opt<double>(pr, sizeof(double), guard_slot, &i_gs);
+  const int *ds = opt<const int>(pr, sizeof(int), stop);
+  if (pr.err) return pr.err;
+  if (kick)
+    k_assemble<T, true><<<nblk_stride(g.Nhp), 256>>>(g, dc, dq, dw, dg, dp, scal[0], scal[1], like_mode, scal[2], dgs, ds);
+  else
+    k_assemble<T, false><<<nblk_stride(g.Nhp), 256>>>(g, dc, dq, dw, dg, dp, scal[0], scal[1], like_mode, scal[2], dgs, ds);
+  Outs o;
+  out(o, i_g, gk), out(o, i_p, pk), out(o, i_gs, guard_slot);
+  return pr.finish(o);
+}
+
+// scal = {a, b, half_eps, eps, c_za}
+template <typename T>
+int step_boundary(int n, double L, int last, void *Ck, const void *q_in, const void *p_in, void *q_out, void *p_out,
+                  void *gk, const double *wS, const double *wM, const double *scal, int like_mode, double *guard_slot,
+                  const CtlArgs &ca) {
+  if (!ok3d(n) || !Ck || !q_in || !p_in || !p_out || !scal || !guard_slot || like_mode < 0 || like_mode > 2) return -1;
+  if ((last && !gk) || (!last && !q_out) || (scal[0] != 0. && !wS)) return -1;
+  const Geo g = probe_geo(n, (int)sizeof(T), L);
+  Probe pr;
+  const size_t cb = (size_t)g.Nhp * sizeof(C2<T>), db = (size_t)g.Nhp * sizeof(double);
+  int i_ck, i_qo = -1, i_po, i_g = -1, i_gs;
+  C2<T> *dc = opt<C2<T>>(pr, 3 * cb, Ck, &i_ck);
+  const C2<T> *dqi = opt<const C2<T>>(pr, cb, q_in), *dpi = opt<const C2<T>>(pr, cb, p_in);
+  C2<T> *dqo = opt<C2<T>>(pr, cb, q_out, &i_qo), *dpo = opt<C2<T>>(pr, cb, p_out, &i_po), *dg = opt<C2<T>>(pr, cb, gk, &i_g);
+  const double *dws = opt<const double>(pr, db, wS), *dwm = opt<const double>(pr, db, wM);
+  double *dgs = opt<double>(pr, sizeof(double), guard_slot, &i_gs);
+  const CtlDev cd = ctl_alloc(pr, ca);
+  if (pr.err) return pr.err;
+  if (last)
+    k_step_boundary<T, true><<<nblk_stride(g.Nhp), 256>>>(g, dc, dqi, dpi, dqo, dpo, dg, dws, dwm, scal[0], scal[1], like_mode,
+                                                         scal[2], scal[3], scal[4], dgs, cd.ctl);
+  else
+    k_step_boundary<T, false><<<nblk_stride(g.Nhp), 256>>>(g, dc, dqi, dpi, dqo, dpo, dg, dws, dwm, scal[0], scal[1],
+                                                          like_mode, scal[2], scal[3], scal[4], dgs, cd.ctl);
+  Outs o;
+  out(o, i_ck, Ck), out(o, i_qo, q_out), out(o, i_po, p_out), out(o, i_g, gk), out(o, i_gs, guard_slot);
+  out(o, cd.i_stop, ca.stop), out(o, cd.i_done, ca.steps_done);
+  return pr.finish(o);
+}
+
+template <typename T> int alpt_poisson(int n, double L, const void *qk, void *d1k, void *phik, double scale) {
+  if (!ok3d(n) || !qk || !d1k || !phik) return -1;
+  const Geo g = probe_geo(n, (int)sizeof(T), L);
+  Probe pr;
+  const size_t cb = (size_t)g.Nhp * sizeof(C2<T>);
+  const C2<T> *dq = static_cast<const C2<T> *>(pr.alloc(cb, qk));
+  C2<T> *d1 = static_cast<C2<T> *>(pr.alloc(cb, d1k)), *dph = static_cast<C2<T> *>(pr.alloc(cb, phik));
+  if (pr.err) return pr.err;
+  k_alpt_poisson<T><<<nblk_stride(g.Nhp), 256>>>(g, dq, d1, dph, scale);
+  return pr.finish({{1, d1k}, {2, phik}});
+}
+
+template <typename T> int alpt_mix(int n, double L, void *Ck, double smol, double inv_wtot, double inv_n) {
+  if (!ok3d(n) || !Ck) return -1;
+  const Geo g = probe_geo(n, (int)sizeof(T), L);
+  Probe pr;
+  C2<T> *d = static_cast<C2<T> *>(pr.alloc((size_t)3 * g.Nhp * sizeof(C2<T>), Ck));
+  if (pr.err) return pr.err;
+  k_alpt_mix<T><<<nblk_stride(g.Nhp), 256>>>(g, d, smol, inv_wtot, inv_n);
+  return pr.finish({{0, Ck}});
+}
+
+// k_prepare_mult: corr (n^3, full grid) -> mult (n^2 nhp; goes in too, the row padding must come back as it went in)
+int prepare_mult(int n, int esz, const double *corr, double *mult, double normFS) {
+  if (!ok3d(n) || !corr || !mult) return -1;
+  const Geo g = probe_geo(n, esz);
+  Probe pr;
+  const double *dc = static_cast<const double *>(pr.alloc((size_t)g.N * sizeof(double), corr));
+  double *dm = static_cast<double *>(pr.alloc((size_t)g.Nhp * sizeof(double), mult));
+  if (pr.err) return pr.err;
+  k_prepare_mult<<<nblk_stride(g.Nhp), 256>>>(g, dc, dm, normFS);
+  return pr.finish({{1, mult}});
+}
+
+// k_parseval: kRedBlocks partials
+template <typename T> int parseval(int n, const void *xk, const double *w, double *partials) {
+  if (!ok3d(n) || !xk || !w || !partials) return -1;
+  const Geo g = probe_geo(n, (int)sizeof(T));
+  Probe pr;
+  const C2<T> *dx = static_cast<const C2<T> *>(pr.alloc((size_t)g.Nhp * sizeof(C2<T>), xk));
+  const double *dw = static_cast<const double *>(pr.alloc((size_t)g.Nhp * sizeof(double), w));
+  double *dp = static_cast<double *>(pr.alloc((size_t)kRedBlocks * sizeof(double), partials));
+  if (pr.err) return pr.err;
+  k_parseval<T><<<kRedBlocks, 256>>>(g, dx, dw, dp);
+  return pr.finish({{2, partials}});
+}
+
+// k_rollback over `count` complex elements of the two ping-pong pairs
+template <typename T>
+int rollback(long long count, const int *stop, const unsigned long long *steps_done, const void *q0, const void *p0,
+             const void *q1, const void *p1, void *q_dst, void *p_dst) {
+  if (count < 1 || count > (1ll << 28) || !stop || !steps_done || !q0 || !p0 || !q1 || !p1 || !q_dst || !p_dst) return -1;
+  if (*stop && *steps_done < 1) return -1;
+  Probe pr;
+  const size_t cb = (size_t)count * sizeof(C2<T>);
+  const int *ds = static_cast<const int *>(pr.alloc(sizeof(int), stop));
+  const unsigned long long *dd = static_cast<const unsigned long long *>(pr.alloc(sizeof(unsigned long long), steps_done));
+  const C2<T> *a0 = static_cast<const C2<T> *>(pr.alloc(cb, q0)), *b0 = static_cast<const C2<T> *>(pr.alloc(cb, p0));
+  const C2<T> *a1 = static_cast<const C2<T> *>(pr.alloc(cb, q1)), *b1 = static_cast<const C2<T> *>(pr.alloc(cb, p1));
+  C2<T> *dq = static_cast<C2<T> *>(pr.alloc(cb, q_dst)), *dp = static_cast<C2<T> *>(pr.alloc(cb, p_dst));
+  if (pr.err) return pr.err;
+  k_rollback<T><<<nblk_stride(count), 256>>>(count, ds, dd, a0, b0, a1, b1, dq, dp);
+  return pr.finish({{6, q_dst}, {7, p_dst}});
+}
+
 }  // namespace
 
 // prec: 0 = double, 1 = float (the engine's storage type T); arrays are of that type, complex ones interleaved
@@ -209,6 +463,85 @@ int fftp_zr2c(int prec, int n, const void *V, void *ck) {
 // k_zbin_direct<PSI_ONLY>: ck (3 n^2 nhp complex) -> psi (3 n^3 real)
 int fftp_zc2r(int prec, int n, const void *ck, void *psi) {
   return prec ? zc2r<float>(n, ck, psi) : zc2r<double>(n, ck, psi);
+}
+
+// ---- the k-space step kernels.  box_len: the box side L (kfac = 2 pi / L); <= 0 means L = n.  Host arrays that the engine
+// may pass as null may be null here; output arrays go in as well and come back, so what a kernel leaves alone is seen.
+
+// k_step_boundary_x (mode 0 interior, 1 first, 2 last; alpt; two_tile: k_step_boundary_x2).  scal = {a, b, half_eps, eps,
+// c_za}.  Ck: 3 n^2 nhp complex in planes space; the others n^2 nhp.  Device array numbers for a canary return: 1 twiddles,
+// then the non-null ones of Ck, q_in, p_in, g_in, q_out, p_out, g_out, wS, wM, guard_slot, stop, steps_done, guard_prev.
+int fftp_step_boundary_x(int prec, int n, double box_len, int mode, int alpt, int two_tile, void *Ck, const void *q_in,
+                         const void *p_in, const void *g_in, void *q_out, void *p_out, void *g_out, const double *wS,
+                         const double *wM, const double *scal, double *guard_slot, int *stop,
+                         unsigned long long *steps_done, const double *guard_prev, double guard_limit,
+                         unsigned long long step_index) {
+  const CtlArgs ca{stop, steps_done, guard_prev, guard_limit, step_index};
+  if (!stop || !steps_done) return -1;
+  return prec ? step_boundary_x<float>(n, box_len, mode, alpt, two_tile, Ck, q_in, p_in, g_in, q_out, p_out, g_out, wS, wM,
+                                       scal, guard_slot, ca)
+              : step_boundary_x<double>(n, box_len, mode, alpt, two_tile, Ck, q_in, p_in, g_in, q_out, p_out, g_out, wS, wM,
+                                        scal, guard_slot, ca);
+}
+
+// k_alpt_mix_x on Ck (3 n^2 nhp complex in planes space: A^, B^ in; the three displacement components out)
+int fftp_alpt_mix_x(int prec, int n, double box_len, void *Ck, double smol, double inv_wtot, double inv_n) {
+  return prec ? alpt_mix_x<float>(n, box_len, Ck, smol, inv_wtot, inv_n)
+              : alpt_mix_x<double>(n, box_len, Ck, smol, inv_wtot, inv_n);
+}
+
+// k_kick_drift_za<T, DRIFT>, in place on qk, pk.  scal = {half_eps, eps, c_za}
+int fftp_kick_drift_za(int prec, int n, double box_len, int drift, void *qk, void *pk, const void *gk, const double *wM,
+                       const void *extra, void *Ck, const double *scal, int *stop, unsigned long long *steps_done,
+                       const double *guard_prev, double guard_limit, unsigned long long step_index) {
+  const CtlArgs ca{stop, steps_done, guard_prev, guard_limit, step_index};
+  if (!stop || !steps_done) return -1;
+  return prec ? kick_drift_za<float>(n, box_len, drift, qk, pk, gk, wM, extra, Ck, scal, ca)
+              : kick_drift_za<double>(n, box_len, drift, qk, pk, gk, wM, extra, Ck, scal, ca);
+}
+
+// k_assemble<T, KICK>.  scal = {a, b, c_kick}
+int fftp_assemble(int prec, int n, double box_len, int kick, const void *Ck, const void *qk, const double *wS, void *gk,
+                  void *pk, const double *scal, int like_mode, double *guard_slot, int *stop) {
+  return prec ? assemble<float>(n, box_len, kick, Ck, qk, wS, gk, pk, scal, like_mode, guard_slot, stop)
+              : assemble<double>(n, box_len, kick, Ck, qk, wS, gk, pk, scal, like_mode, guard_slot, stop);
+}
+
+// k_step_boundary<T, LAST>.  scal = {a, b, half_eps, eps, c_za}
+int fftp_step_boundary(int prec, int n, double box_len, int last, void *Ck, const void *q_in, const void *p_in, void *q_out,
+                       void *p_out, void *gk, const double *wS, const double *wM, const double *scal, int like_mode,
+                       double *guard_slot, int *stop, unsigned long long *steps_done, const double *guard_prev,
+                       double guard_limit, unsigned long long step_index) {
+  const CtlArgs ca{stop, steps_done, guard_prev, guard_limit, step_index};
+  if (!stop || !steps_done) return -1;
+  return prec ? step_boundary<float>(n, box_len, last, Ck, q_in, p_in, q_out, p_out, gk, wS, wM, scal, like_mode, guard_slot, ca)
+              : step_boundary<double>(n, box_len, last, Ck, q_in, p_in, q_out, p_out, gk, wS, wM, scal, like_mode, guard_slot,
+                                      ca);
+}
+
+int fftp_alpt_poisson(int prec, int n, double box_len, const void *qk, void *d1k, void *phik, double scale) {
+  return prec ? alpt_poisson<float>(n, box_len, qk, d1k, phik, scale) : alpt_poisson<double>(n, box_len, qk, d1k, phik, scale);
+}
+
+int fftp_alpt_mix(int prec, int n, double box_len, void *Ck, double smol, double inv_wtot, double inv_n) {
+  return prec ? alpt_mix<float>(n, box_len, Ck, smol, inv_wtot, inv_n) : alpt_mix<double>(n, box_len, Ck, smol, inv_wtot, inv_n);
+}
+
+// k_prepare_mult: corr (n^3 doubles) -> mult (n^2 nhp doubles, nhp that of `prec`)
+int fftp_prepare_mult(int prec, int n, const double *corr, double *mult, double normFS) {
+  return prepare_mult(n, prec ? 4 : 8, corr, mult, normFS);
+}
+
+// number of partials k_parseval writes
+int fftp_parseval_blocks(void) { return kRedBlocks; }
+int fftp_parseval(int prec, int n, const void *xk, const double *w, double *partials) {
+  return prec ? parseval<float>(n, xk, w, partials) : parseval<double>(n, xk, w, partials);
+}
+
+int fftp_rollback(int prec, long long count, const int *stop, const unsigned long long *steps_done, const void *q0,
+                  const void *p0, const void *q1, const void *p1, void *q_dst, void *p_dst) {
+  return prec ? rollback<float>(count, stop, steps_done, q0, p0, q1, p1, q_dst, p_dst)
+              : rollback<double>(count, stop, steps_done, q0, p0, q1, p1, q_dst, p_dst);
 }
 
 }  // extern "C"
