@@ -2,6 +2,7 @@
 // Part of the bchmc engine's kernel set; include through kernels.hpp (definition order matters).
 #pragma once
 #include "common.hpp"
+#include "launch_grid.hpp"
 
 #include <algorithm>
 
@@ -46,29 +47,7 @@ __device__ __forceinline__ double findif_axis(const T *__restrict__ a, long long
                   (1.0 / 6) * ((double)a[o + ll * stride] - (double)a[o + rr * stride])));
 }
 
-// Workgroup -> z-rows for the two stencil passes.  Workgroups are dealt round-robin over the 8 XCDs (blocks b and b + 8
-// share one), each XCD has its own L2, and the 4th-order stencils reach two rows (j) and two planes (i) either way: with
-// consecutive rows on consecutive workgroups every XCD fetched every row of the array for its y neighbours.  Here the
-// row slots a workgroup takes (b, b + gridDim, ...; gridDim a multiple of 8) all lie in ONE slab of n / 8 consecutive j
-// -- the same slab for all workgroups of an XCD -- so the y and x neighbours of a row are rows of the same XCD, but for
-// the two rows at each slab edge.  Pure scheduling: any mapping gives the same numbers.  (Measured: the two passes
-// 0.70 -> 0.61 ms at 256^3.  Staging the rows of a group of 4 output rows in LDS instead -- 6 and 9 coalesced row loads
-// per output row, neighbours read from LDS -- was measured too and ran 1.10 ms: 72 KB of LDS per workgroup leave two
-// workgroups per CU and nothing to overlap their load phases with; profiles/r03_ab_alpt_rows.txt.)
-__device__ __forceinline__ void stencil_row(int slot, int n, int &i, int &j) {
-  if ((n & 7) == 0) {
-    const int slab = n >> 3, x = slot & 7, loc = slot >> 3;
-    j = x * slab + loc % slab;
-    i = loc / slab;
-  } else {
-    j = slot % n;
-    i = slot / n;
-  }
-}
-inline int stencil_grid(int n) {  // workgroups of the stencil passes: a multiple of 8, at most one per row
-  const long long rows = (long long)n * n;
-  return (int)std::max<long long>(std::min<long long>(rows, 4096) / 8 * 8, 8);
-}
+// Workgroup -> z-rows of the two stencil passes: stencil_row and stencil_grid, launch_grid.hpp.
 
 // First derivatives of Phi: g3[c] = d Phi / d x_c  (the `dummy` arrays of calc_m2v_mem, EqSolvers.cc:403-412)
 template <typename T>

@@ -324,8 +324,6 @@ inline bool env_on(const char *name) {
   return v && v[0] == '1';
 }
 
-inline int nblk_full(long long n) { return (int)((n + 255) / 256); }
-
 // ---- profiling ------------------------------------------------------------------------------------
 // roctx range names: the kernel ids of SURVEY.md 2.1 that each launch group replaces, so that a
 // `rocprofv3 --marker-trace --kernel-trace` timeline maps onto the reference's kernel inventory.  A push/pop pair

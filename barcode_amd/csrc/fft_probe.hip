@@ -13,6 +13,13 @@
 // nblk_stride(Nhp) x 256 and k_parseval on kRedBlocks x 256 as bchmc.hip launches them.  Their geometry takes a box
 // length, so that kfac is not 2 pi / n.
 //
+// The real-space ALPT and calc_h 0 / 3 kernels (tests/test_gpu_rs.py) run the same way: k_alpt_grad and k_alpt_sources on
+// stencil_grid(n) x 256 (k_alpt_sources with either pointer layout of alpt_middle: a_out == d1 on the planes path,
+// b_out == d1 on the 3-D path), k_alpt_kernel_table on nblk_stride(Nhp), k_gradfft_mult and k_conv_kernel on
+// nblk_stride(Nh), k_mul3 and k_findif_mul on nblk_stride(N), k_interp_tsc on nblk_full(N).  k_conv_kernel takes its table
+// F from the caller (build_conv_table is host code and not under test); k_interp_tsc takes the PosPar scalars (PosPar has
+// no lower corner: the domain of this kernel is [0, L] and periodic, as make_pos sets it).
+//
 // Every device array is followed by kCanary bytes of a known pattern; an entry point copies its host arrays in,
 // launches, synchronises, copies back and checks the canaries.  Return value: 0 = ok, -1 = arguments outside the
 // engine's instantiations, -2 = HIP error, k > 0 = the canary after device array k changed (1 = the twiddle table,
@@ -437,6 +444,116 @@ int rollback(long long count, const int *stop, const unsigned long long *steps_d
   return pr.finish({{6, q_dst}, {7, p_dst}});
 }
 
+// ---- the real-space ALPT and calc_h 0 / 3 kernels ----------------------------------------------------------------------
+
+// the stencil kernels index rows as int slots and wrap with c +- 2: the engine's smallest grid is 4
+bool ok_rs(int n) { return n >= 4 && n <= 512; }
+
+// k_alpt_grad: phi (n^3) -> g3 (3 n^3; goes in too)
+template <typename T> int alpt_grad(int n, double L, const void *phi, void *g3) {
+  if (!ok_rs(n) || !phi || !g3) return -1;
+  const Geo g = probe_geo(n, (int)sizeof(T), L);
+  Probe pr;
+  const T *dp = static_cast<const T *>(pr.alloc((size_t)g.N * sizeof(T), phi));
+  T *dg = static_cast<T *>(pr.alloc((size_t)3 * g.N * sizeof(T), g3));
+  if (pr.err) return pr.err;
+  k_alpt_grad<T><<<stencil_grid(g.n), 256>>>(g, dp, dg);
+  return pr.finish({{1, g3}});
+}
+
+// k_alpt_sources with alpt_middle's pointer layouts.  layout 0 (planes path): a_out == d1, b_out = other;
+// layout 1 (3-D path): b_out == d1, a_out = other.  d1 and other (n^3 each) go in and come back.
+template <typename T> int alpt_sources(int n, double L, int layout, const void *g3, void *d1, void *other, double D1, double D2) {
+  if (!ok_rs(n) || !g3 || !d1 || !other || (layout != 0 && layout != 1)) return -1;
+  const Geo g = probe_geo(n, (int)sizeof(T), L);
+  Probe pr;
+  const T *dg = static_cast<const T *>(pr.alloc((size_t)3 * g.N * sizeof(T), g3));
+  T *dd = static_cast<T *>(pr.alloc((size_t)g.N * sizeof(T), d1));
+  T *dx = static_cast<T *>(pr.alloc((size_t)g.N * sizeof(T), other));
+  if (pr.err) return pr.err;
+  k_alpt_sources<T><<<stencil_grid(g.n), 256>>>(g, dg, dd, layout ? dx : dd, layout ? dd : dx, D1, D2);
+  return pr.finish({{1, d1}, {2, other}});
+}
+
+// k_alpt_kernel_table: out (n^2 nhp complex; goes in too)
+template <typename T> int alpt_kernel_table(int n, double L, void *tab, double smol) {
+  if (!ok3d(n) || !tab) return -1;
+  const Geo g = probe_geo(n, (int)sizeof(T), L);
+  Probe pr;
+  C2<T> *d = static_cast<C2<T> *>(pr.alloc((size_t)g.Nhp * sizeof(C2<T>), tab));
+  if (pr.err) return pr.err;
+  k_alpt_kernel_table<T><<<nblk_stride(g.Nhp), 256>>>(g, d, smol);
+  return pr.finish({{0, tab}});
+}
+
+// k_findif_mul: dX, plike (n^3) -> V (3 n^3; goes in too)
+template <typename T>
+int findif_mul(int n, double L, int likelihood, double rho_c, double delta_min, const void *dX, const void *plike, void *V) {
+  if (!ok_rs(n) || !dX || !plike || !V || likelihood < 0 || likelihood > 2) return -1;
+  const Geo g = probe_geo(n, (int)sizeof(T), L);
+  LikePar lp{};
+  lp.rho_c = rho_c, lp.biasP = 1., lp.biasE = 1., lp.delta_min = delta_min, lp.likelihood = likelihood, lp.bias_is_identity = 1;
+  Probe pr;
+  const T *dx = static_cast<const T *>(pr.alloc((size_t)g.N * sizeof(T), dX));
+  const T *dl = static_cast<const T *>(pr.alloc((size_t)g.N * sizeof(T), plike));
+  T *dv = static_cast<T *>(pr.alloc((size_t)3 * g.N * sizeof(T), V));
+  if (pr.err) return pr.err;
+  k_findif_mul<T><<<nblk_stride(g.N), 256>>>(g, lp, dx, dl, dv);
+  return pr.finish({{2, V}});
+}
+
+// k_gradfft_mult / k_conv_kernel: one half-complex array in (n^2 nhp), three out (3 n^2 nhp; go in too)
+template <typename T> int gradfft_mult(int n, double L, const void *fk, void *Ck, double inv_n) {
+  if (!ok3d(n) || !fk || !Ck) return -1;
+  const Geo g = probe_geo(n, (int)sizeof(T), L);
+  Probe pr;
+  const C2<T> *df = static_cast<const C2<T> *>(pr.alloc((size_t)g.Nhp * sizeof(C2<T>), fk));
+  C2<T> *dc = static_cast<C2<T> *>(pr.alloc((size_t)3 * g.Nhp * sizeof(C2<T>), Ck));
+  if (pr.err) return pr.err;
+  k_gradfft_mult<T><<<nblk_stride(g.Nh), 256>>>(g, df, dc, inv_n);
+  return pr.finish({{1, Ck}});
+}
+
+template <typename T> int conv_kernel(int n, double L, const void *pl, const double *F, void *Ck, double hh, double inv_n) {
+  if (!ok3d(n) || !pl || !F || !Ck) return -1;
+  const Geo g = probe_geo(n, (int)sizeof(T), L);
+  Probe pr;
+  const C2<T> *dl = static_cast<const C2<T> *>(pr.alloc((size_t)g.Nhp * sizeof(C2<T>), pl));
+  const double *df = static_cast<const double *>(pr.alloc((size_t)g.Nhp * sizeof(double), F));
+  C2<T> *dc = static_cast<C2<T> *>(pr.alloc((size_t)3 * g.Nhp * sizeof(C2<T>), Ck));
+  if (pr.err) return pr.err;
+  k_conv_kernel<T><<<nblk_stride(g.Nh), 256>>>(g, dl, df, dc, hh, inv_n);
+  return pr.finish({{2, Ck}});
+}
+
+// k_mul3 over `count` elements: a (count), b3 (3 count) -> out3 (3 count; goes in too)
+template <typename T> int mul3(long long count, const void *a, const void *b3, void *out3) {
+  if (count < 1 || count > (1ll << 27) || !a || !b3 || !out3) return -1;
+  Probe pr;
+  const T *da = static_cast<const T *>(pr.alloc((size_t)count * sizeof(T), a));
+  const T *db = static_cast<const T *>(pr.alloc((size_t)3 * count * sizeof(T), b3));
+  T *dout = static_cast<T *>(pr.alloc((size_t)3 * count * sizeof(T), out3));
+  if (pr.err) return pr.err;
+  k_mul3<T><<<nblk_stride(count), 256>>>(count, da, db, dout);
+  return pr.finish({{2, out3}});
+}
+
+// k_interp_tsc: psi, conv (3 n^3 each) -> V (3 n^3; goes in too).  pos = {cpecvel, v_norm}; periodic as make_pos sets it.
+template <typename T>
+int interp_tsc(int n, double L, int rsd, const double *pos, double f1, const void *psi, const void *conv, void *V) {
+  if (!ok3d(n) || !pos || !psi || !conv || !V || (rsd != 0 && rsd != 1)) return -1;
+  const Geo g = probe_geo(n, (int)sizeof(T), L);
+  PosPar pp{};
+  pp.d = g.d, pp.L = g.L, pp.cpecvel = pos[0], pp.v_norm = pos[1], pp.rsd = rsd, pp.periodic = 1;
+  Probe pr;
+  const T *dp = static_cast<const T *>(pr.alloc((size_t)3 * g.N * sizeof(T), psi));
+  const T *dc = static_cast<const T *>(pr.alloc((size_t)3 * g.N * sizeof(T), conv));
+  T *dv = static_cast<T *>(pr.alloc((size_t)3 * g.N * sizeof(T), V));
+  if (pr.err) return pr.err;
+  k_interp_tsc<T><<<nblk_full(g.N), 256>>>(g, pp, f1, dp, dc, dv);
+  return pr.finish({{2, V}});
+}
+
 }  // namespace
 
 // prec: 0 = double, 1 = float (the engine's storage type T); arrays are of that type, complex ones interleaved
@@ -542,6 +659,51 @@ int fftp_rollback(int prec, long long count, const int *stop, const unsigned lon
                   const void *p0, const void *q1, const void *p1, void *q_dst, void *p_dst) {
   return prec ? rollback<float>(count, stop, steps_done, q0, p0, q1, p1, q_dst, p_dst)
               : rollback<double>(count, stop, steps_done, q0, p0, q1, p1, q_dst, p_dst);
+}
+
+// ---- the real-space ALPT and calc_h 0 / 3 kernels.  Device array numbers for a canary return: the arrays in argument order.
+
+// number of workgroups of the two stencil passes
+int fftp_stencil_grid(int n) { return stencil_grid(n); }
+
+int fftp_alpt_grad(int prec, int n, double box_len, const void *phi, void *g3) {
+  return prec ? alpt_grad<float>(n, box_len, phi, g3) : alpt_grad<double>(n, box_len, phi, g3);
+}
+
+// layout 0: a_out == d1 (planes path), b_out = other;  layout 1: b_out == d1 (3-D path), a_out = other
+int fftp_alpt_sources(int prec, int n, double box_len, int layout, const void *g3, void *d1, void *other, double D1, double D2) {
+  return prec ? alpt_sources<float>(n, box_len, layout, g3, d1, other, D1, D2)
+              : alpt_sources<double>(n, box_len, layout, g3, d1, other, D1, D2);
+}
+
+int fftp_alpt_kernel_table(int prec, int n, double box_len, void *tab, double smol) {
+  return prec ? alpt_kernel_table<float>(n, box_len, tab, smol) : alpt_kernel_table<double>(n, box_len, tab, smol);
+}
+
+int fftp_findif_mul(int prec, int n, double box_len, int likelihood, double rho_c, double delta_min, const void *dX,
+                    const void *plike, void *V) {
+  return prec ? findif_mul<float>(n, box_len, likelihood, rho_c, delta_min, dX, plike, V)
+              : findif_mul<double>(n, box_len, likelihood, rho_c, delta_min, dX, plike, V);
+}
+
+int fftp_gradfft_mult(int prec, int n, double box_len, const void *fk, void *Ck, double inv_n) {
+  return prec ? gradfft_mult<float>(n, box_len, fk, Ck, inv_n) : gradfft_mult<double>(n, box_len, fk, Ck, inv_n);
+}
+
+// F: n^2 nhp doubles (nhp that of `prec`)
+int fftp_conv_kernel(int prec, int n, double box_len, const void *pl, const double *F, void *Ck, double hh, double inv_n) {
+  return prec ? conv_kernel<float>(n, box_len, pl, F, Ck, hh, inv_n) : conv_kernel<double>(n, box_len, pl, F, Ck, hh, inv_n);
+}
+
+int fftp_mul3(int prec, long long count, const void *a, const void *b3, void *out3) {
+  return prec ? mul3<float>(count, a, b3, out3) : mul3<double>(count, a, b3, out3);
+}
+
+// pos = {cpecvel, v_norm}
+int fftp_interp_tsc(int prec, int n, double box_len, int rsd, const double *pos, double f1, const void *psi,
+                    const void *conv, void *V) {
+  return prec ? interp_tsc<float>(n, box_len, rsd, pos, f1, psi, conv, V)
+              : interp_tsc<double>(n, box_len, rsd, pos, f1, psi, conv, V);
 }
 
 }  // extern "C"
