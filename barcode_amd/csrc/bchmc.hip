@@ -76,6 +76,7 @@ struct bchmc_handle {
   DevBytes qk, pk, gk;                               // Nhp complex each
   DevBytes qk2, pk2;                                 // ping-pong partners of (qk, pk) for the fused step boundary
   DevBytes Ck;                                       // 3 Nhp: Psi^ / V^
+  bool ck_pair = false;                              // Ck holds Psi^_x | B of a boundary kernel with `pair` (psi_pair, eval_plan.hpp)
   DevBytes tC;                                       // Nhp scratch
   DevBytes psi;                                      // 3 N: displacement components
   DevBytes V;                                        // 3 N: V components
@@ -677,6 +678,7 @@ PathSwitches read_path_switches() {
   s.yfwd_f64 = env_on("BCHMC_YFWD_F64");
   s.bx_v1 = env_on("BCHMC_BX_V1");
   s.bx_v2 = env_on("BCHMC_BX_V2");
+  s.no_pair = env_on("BCHMC_NO_PAIR");
   return s;
 }
 
@@ -1270,6 +1272,7 @@ struct Pipe {
   static int displacement(bchmc_handle *h, double dq_factor, int rsd, bool *psi_planes) {
     const PathFacts f = path_facts(h, rsd);
     *psi_planes = alpt_on_planes(f, h->sw, rsd);
+    h->ck_pair = false;  // three components of Psi^, whichever model
     return uses_alpt(f, rsd) ? launch_alpt(h, dq_factor, *psi_planes) : launch_za(h, dq_factor);
   }
 
@@ -1355,9 +1358,12 @@ struct Pipe {
   static int forward_rest(bchmc_handle *h, int rsd, EvalMode m) {
     if (rsd && !h->c.planepar) return h->fail(BCHMC_ERR_RSD_NOT_PLANEPAR, "non-plane-parallel RSD is not implemented");
     const bool zbin = eval_zbin(path_facts(h, rsd), h->sw, m);  // the z pass of Psi^ is particle_stage's
+    const bool pair = h->ck_pair;  // what the boundary kernel left: Psi^_x | B (k_ypass_pair makes ky B and kz B)
+    h->ck_pair = false;
+    if (pair && !zbin) return h->fail(BCHMC_ERR_STATE, "two arrays between the x and y passes, and no y pass of the engine's own");
     if (zbin) {
       ProfScope ps(h, BCHMC_K_FFT_C2R);
-      HIPCHK(launch_ypass<T>(pass_ctx(h), C(h->Ck)));
+      HIPCHK(pair ? launch_ypass_pair<T>(pass_ctx(h), C(h->Ck)) : launch_ypass<T>(pass_ctx(h), C(h->Ck)));
     } else {
       CHK(fft_exec(h, m.planes_c2r ? h->c2r2d : h->c2r3, h->Ck, h->psi, BCHMC_K_FFT_C2R));
     }
@@ -1735,6 +1741,7 @@ struct Pipe {
     PathFacts f;
     TrajPlan p;
     double a, c_za;
+    bool pair;  // the Zel'dovich boundaries leave Psi^_x | B (psi_pair)
   };
   static Traj traj(bchmc_handle *h) {
     Traj t;
@@ -1742,6 +1749,7 @@ struct Pipe {
     t.p = traj_plan(t.f, h->sw);
     t.a = h->c.grad_psi_prior_factor;
     t.c_za = (t.p.c_za == CZa::kAlptInput ? 1. : -h->c.D1) * h->c.deltaQ_factor / (double)h->g.N;
+    t.pair = psi_pair(t.f, h->sw, t.p);
     return t;
   }
 
@@ -1749,6 +1757,7 @@ struct Pipe {
   template <int MODE, bool ALPT = false>
   static int launch_boundary_x(bchmc_handle *h, const BoundaryX<T> &bx) {
     HIPCHK((launch_step_boundary_x<T, MODE, ALPT>(pass_ctx(h), C(h->Ck), h->wS, bx)));
+    h->ck_pair = bx.pair && !ALPT && MODE != BX_LAST;  // as launch_step_boundary_x told the kernel
     return BCHMC_OK;
   }
 
@@ -1768,7 +1777,7 @@ struct Pipe {
       {
         ProfScope ps(h, BCHMC_K_KSPACE_DRIFT_ZA);
         BoundaryX<T> bx;
-        bx.qi = C(h->qk), bx.c_za = t.c_za, bx.ctl = nc;
+        bx.qi = C(h->qk), bx.c_za = t.c_za, bx.ctl = nc, bx.pair = t.pair;
         if (kind == InitialEval::kBxFirstAlpt) CHK((launch_boundary_x<BX_FIRST, true>(h, bx)));
         else CHK(launch_boundary_x<BX_FIRST>(h, bx));
       }
@@ -1862,11 +1871,12 @@ struct Pipe {
       ProfScope ps(h, BCHMC_K_KSPACE_DRIFT_ZA);
       BoundaryX<T> bx;
       bx.qi = bx.qo = C(q0), bx.pi = bx.po = C(p0), bx.wM = wM, bx.half_eps = 0.5 * eps, bx.eps = eps, bx.c_za = c_za;
-      bx.ctl = ctl, bx.g_in = C(g_first);
+      bx.ctl = ctl, bx.g_in = C(g_first), bx.pair = t.pair;
       switch (opening(t.f, h->sw, t.p)) {
         case Opening::kBxFirstAlpt: CHK((launch_boundary_x<BX_FIRST, true>(h, bx))); break;
         case Opening::kBxFirst: CHK(launch_boundary_x<BX_FIRST>(h, bx)); break;
         case Opening::kKickDriftZa:
+          h->ck_pair = false;
           k_kick_drift_za<T, true><<<nblk_stride(h->g.Nhp), 256, 0, h->stream>>>(h->g, C(q0), C(p0), C(g_first), wM,
                                                                                nullptr, C(h->Ck), 0.5 * eps, eps, c_za, ctl);
           break;
@@ -1892,7 +1902,7 @@ struct Pipe {
       ProfScope ps(h, BCHMC_K_KSPACE_FORCE_KICK);
       BoundaryX<T> bx;  // the interior boundary; the last one writes p in place, no q, and leaves the gradient in gk
       bx.qi = C(qi), bx.pi = C(pi), bx.qo = C(qo), bx.po = C(po), bx.wM = wM, bx.a = a, bx.b = b, bx.half_eps = 0.5 * eps;
-      bx.eps = eps, bx.c_za = c_za, bx.guard_slot = h->guard + s, bx.ctl = ctl;
+      bx.eps = eps, bx.c_za = c_za, bx.guard_slot = h->guard + s, bx.ctl = ctl, bx.pair = t.pair;
       switch (closing(t.f, h->sw, t.p, s, neps, like_mode)) {
         case Closing::kBxLast:
           bx.qo = nullptr, bx.po = C(pi), bx.g_out = C(h->gk);
@@ -1905,7 +1915,10 @@ struct Pipe {
           break;
         case Closing::kBxInteriorAlpt: CHK((launch_boundary_x<BX_INTERIOR, true>(h, bx))); break;
         case Closing::kBxInterior: CHK(launch_boundary_x<BX_INTERIOR>(h, bx)); break;
-        case Closing::kBxInteriorTwoTile: HIPCHK(launch_step_boundary_x2<T>(pass_ctx(h), C(h->Ck), h->wS, bx)); break;
+        case Closing::kBxInteriorTwoTile:
+          HIPCHK(launch_step_boundary_x2<T>(pass_ctx(h), C(h->Ck), h->wS, bx));
+          h->ck_pair = bx.pair;
+          break;
         case Closing::kStepBoundary:
           k_step_boundary<T, false><<<nblk_stride(h->g.Nhp), 256, 0, h->stream>>>(
               h->g, C(h->Ck), C(qi), C(pi), C(qo), C(po), C(h->gk), h->wS, wM, a, b, like_mode, 0.5 * eps, eps, c_za,

@@ -2,7 +2,8 @@
 // one-tile, two-tile or ALPT formulation, the ALPT pipeline on the 2-D plans, the z pass inside the binning, the engine's
 // own forward y / z passes.  The single statement of it, as pure functions of the path switches (PathSwitches: the
 // environment as bchmc_create read it) and of what a handle is and holds at the moment of asking (PathFacts).  Plain C++:
-// no HIP types, no getenv; tests/host/eval_plan_check.cpp proves it against literals and sweeps the whole space.
+// no HIP types, no getenv; tests/host/eval_plan_check.cpp proves it against literals and sweeps the whole space
+// (psi_pair, the two arrays between the inverse x and y passes: tests/host/two_array_check.cpp).
 //
 // Nothing here is cached and nothing should be: sort_direct changes when the record slots are given up, and the plans over
 // 2 n planes can appear late.  bchmc.hip gathers the facts when it needs a decision, asks, and switches on the answer.
@@ -22,6 +23,7 @@ struct PathSwitches {           // BCHMC_<NAME>=1, read once per handle
   bool yfwd_f64 = false;        // YFWD_F64: the engine's own forward y / z passes at 512^3 for fp64 fields too
   bool bx_v1 = false;           // BX_V1: the one-tile interior boundary for fp32 fields
   bool bx_v2 = false;           // BX_V2: the two-tile interior boundary for fp64 fields
+  bool no_pair = false;         // NO_PAIR: three arrays, not two, between the inverse x pass and the y pass
 };
 
 struct PathFacts {
@@ -132,6 +134,18 @@ struct TrajPlan {
   bool alpt_x = false, fused_za = false, fused = false;
   CZa c_za = CZa::kZeldovich;
 };
+
+// ---- two arrays, not three, between the inverse x pass and the y pass ---------------------------------------------------
+// Psi^_y = ky B and Psi^_z = kz B with one B: a Zel'dovich k_step_boundary_x (BX_FIRST, interior, one tile or two) stores
+// Psi^_x and B only, and k_ypass_pair makes the two products where it holds the column anyway: one complex array less
+// written and one less read.  Only where the engine's own y pass is what follows a boundary in planes space -- rocFFT's
+// 2-D C2R wants its three arrays, so NO_ZBIN, the fallback sort, 128^3 without ZBIN_128 and everything zbin_why_not lists
+// keep them -- and never for the ALPT boundary, whose two arrays are other fields.  The boundary kernels exist only in
+// planes mode (planes_on: calc_h 2, mk 3, not NO_PLANES).  bchmc.hip remembers what the last boundary left in Ck and
+// refuses an evaluation that would read two arrays as three.
+constexpr bool psi_pair(const PathFacts &f, const PathSwitches &s, const TrajPlan &tp) {
+  return !s.no_pair && !tp.alpt_x && planes_on(f, s) && zbin_ok(f, s) && ypair_shape(f.esz, f.n).nt;
+}
 constexpr TrajPlan traj_plan(const PathFacts &f, const PathSwitches &s) {
   TrajPlan tp;
   const bool alpt = uses_alpt(f, f.rsd_model) && f.likelihood != 3;

@@ -165,6 +165,20 @@ template <typename T> int ypass(int n, int inverse, void *ck) {
   return pr.finish({{1, ck}});
 }
 
+// k_ypass_pair as forward_rest launches it after a boundary kernel that stored Psi^_x | B: components 0 and 1 are read,
+// all three written
+template <typename T> int ypass_pair(int n, double box_len, void *ck) {
+  if (!ypair_shape(sizeof(T), n).nt) return -1;
+  const Geo g = probe_geo(n, (int)sizeof(T), box_len);
+  if (g.nhp % pass_kb(sizeof(T))) return -1;
+  Probe pr;
+  const PassCtx<T> x = pr.ctx<T>(g);
+  C2<T> *d = static_cast<C2<T> *>(pr.alloc((size_t)3 * g.Nhp * sizeof(C2<T>), ck));
+  if (pr.err) return pr.err;
+  pr.ok(launch_ypass_pair<T>(x, d));
+  return pr.finish({{1, ck}});
+}
+
 // k_zr2c as the planes-mode R2C at 512^3 launches it, and as bchmc_probe_displacement_z does at 128^3 and 256^3;
 // ck goes in as well, so that the row padding the kernel leaves alone comes back as it went in
 template <typename T> int zr2c(int n, const void *V, void *ck) {
@@ -570,6 +584,11 @@ int fftp_xfft(int prec, int n, int kb, int inverse, int groups, void *data) {
 // k_ypass over three planes-space components (3 n^2 nhp complex), in place
 int fftp_ypass(int prec, int n, int inverse, void *ck) {
   return prec ? ypass<float>(n, inverse, ck) : ypass<double>(n, inverse, ck);
+}
+
+// k_ypass_pair: components 0 (Psi^_x) and 1 (B) of ck -> the inverse y transforms of Psi^_x, ky B, kz B in components 0, 1, 2
+int fftp_ypass_pair(int prec, int n, double box_len, void *ck) {
+  return prec ? ypass_pair<float>(n, box_len, ck) : ypass_pair<double>(n, box_len, ck);
 }
 
 // k_zr2c: V (3 n^3 real) -> ck (3 n^2 nhp complex; the row padding comes back as it went in)

@@ -41,6 +41,11 @@ constexpr PassShape y_shape(int esz, int n) {
   const int nt = n == 128 ? 256 : 512;
   return n == 128 || n == 256 || n == 512 ? PassShape{nt, n * pass_kb(esz) / nt} : PassShape{};
 }
+// k_ypass_pair (the inverse y pass from the two arrays Psi^_x | B): k_ypass's tile and block; the workgroups of B make two
+// transforms on the one tile, so the grid is that of two components (ypair_grid) and the LDS that of one tile
+// (tests/host/two_array_check.cpp)
+constexpr PassShape ypair_shape(int esz, int n) { return y_shape(esz, n); }
+constexpr int ypair_comps = 2;
 // k_zr2c, k_zbin_direct: NZ = n, one lattice site along z per thread, over 6 interleaved rows
 constexpr PassShape z_shape(int /*esz*/, int n) { return n == 128 || n == 256 || n == 512 ? PassShape{n, 6} : PassShape{}; }
 
@@ -51,6 +56,7 @@ constexpr size_t zrow_lds(int esz, int n) { return ((size_t)n * 6 + n / 2) * 2 *
 // workgroups: one per column tile of `comps` components with row stride nhp (fft_row_stride), one per 2 x 2 rows
 constexpr int col_grid(int esz, int n, int nhp, int comps = 1) { return comps * n * (nhp / pass_kb(esz)); }
 constexpr int row_grid(int n) { return (n / 2) * (n / 2); }
+constexpr int ypair_grid(int esz, int n, int nhp) { return col_grid(esz, n, nhp, ypair_comps); }
 
 }  // namespace bchmc
 
@@ -117,6 +123,15 @@ hipError_t launch_ypass(const PassCtx<T> &x, C2<T> *ck) {
   else return pass_row<y_shape, T, 512>(x.g.n, go);
 }
 
+// k_ypass_pair: ck[0] = Psi^_x, ck[1] = B as a boundary kernel with `pair` left them -> the three y-transformed components
+template <typename T>
+hipError_t launch_ypass_pair(const PassCtx<T> &x, C2<T> *ck) {
+  return pass_dispatch<ypair_shape, T>(x.g.n, [&](auto nt, auto per) {
+    return launch_dyn_lds(x.stream, k_ypass_pair<T, nt, per, BCHMC_YPASS_NT>, ypair_grid(sizeof(T), x.g.n, x.g.nhp), nt,
+                          x.col_lds(), x.g, x.log2n, x.tw, ck);
+  });
+}
+
 // k_zr2c: V (3 n^3 real) -> ck
 template <typename T>
 hipError_t launch_zr2c(const PassCtx<T> &x, const T *V, C2<T> *ck) {
@@ -157,6 +172,7 @@ struct BoundaryX {
   StepCtl ctl{};
   const C2<T> *g_in = nullptr;
   C2<T> *g_out = nullptr;
+  bool pair = false;  // the Zel'dovich inverse side leaves Psi^_x | B for k_ypass_pair instead of the three Psi^ components
 };
 
 template <typename T, int MODE, bool ALPT>
@@ -164,7 +180,7 @@ hipError_t launch_step_boundary_x(const PassCtx<T> &x, C2<T> *Ck, const double *
   return pass_dispatch<x_shape, T>(x.g.n, [&](auto nt, auto per) {
     return launch_dyn_lds(x.stream, k_step_boundary_x<T, nt, per, MODE, ALPT>, x.col_grid(), nt, x.col_lds(), x.g, x.log2n,
                           x.tw, Ck, a.qi, a.pi, a.qo, a.po, wS, a.wM, a.a, a.b, a.half_eps, a.eps, a.c_za, a.guard_slot,
-                          a.ctl, a.g_in, a.g_out);
+                          a.ctl, a.g_in, a.g_out, a.pair && !ALPT && MODE != BX_LAST);
   });
 }
 
@@ -173,7 +189,7 @@ template <typename T>
 hipError_t launch_step_boundary_x2(const PassCtx<T> &x, C2<T> *Ck, const double *wS, const BoundaryX<T> &a) {
   return pass_dispatch<x2_shape, T>(x.g.n, [&](auto nt, auto per) {
     return launch_dyn_lds(x.stream, k_step_boundary_x2<T, nt, per>, x.col_grid(), nt, x.col_lds(2), x.g, x.log2n, x.tw, Ck,
-                          a.qi, a.pi, a.qo, a.po, wS, a.wM, a.a, a.b, a.half_eps, a.eps, a.c_za, a.guard_slot, a.ctl);
+                          a.qi, a.pi, a.qo, a.po, wS, a.wM, a.a, a.b, a.half_eps, a.eps, a.c_za, a.guard_slot, a.ctl, a.pair);
   });
 }
 

@@ -146,6 +146,9 @@ __device__ __forceinline__ void xfft_inplace(C2<T> *__restrict__ s, const C2<T> 
 //                g_in == nullptr: Psi^ of q_in only, nothing else read or written (launch_za), no trajectory control;
 //   BX_LAST      forward x passes of V^, g^ stored to g_out, p_out = p - (eps/2) g^ (k_step_boundary<LAST>);
 //                p_out == nullptr: g^ only (k_assemble<false>), no trajectory control.
+// `pair` (Zel'dovich BX_INTERIOR / BX_FIRST and k_step_boundary_x2; psi_pair in eval_plan.hpp): the second inverse
+// transform's output B is stored as it is into component 1 and component 2 is not written -- ky B and kz B are made by
+// k_ypass_pair (zpass.hpp), which holds the column anyway: one complex array less written here and one less read there.
 enum { BX_INTERIOR = 0, BX_FIRST = 1, BX_LAST = 2 };
 
 // ALPT = true changes what leaves through the two inverse x passes: instead of the Zel'dovich Psi^ (kx B and B, see
@@ -157,7 +160,7 @@ __global__ void __launch_bounds__(NT, BCHMC_BX_WAVES)
 k_step_boundary_x(Geo g, int log2n, const C2<T> *__restrict__ twiddle, C2<T> *Ck, const C2<T> *q_in, const C2<T> *p_in,
                   C2<T> *q_out, C2<T> *p_out, const double *__restrict__ wS, const double *__restrict__ wM, double a,
                   double b, double half_eps, double eps, double c_za, double *guard_slot, StepCtl ctl,
-                  const C2<T> *g_in = nullptr, C2<T> *g_out = nullptr) {
+                  const C2<T> *g_in = nullptr, C2<T> *g_out = nullptr, bool pair = false) {
   constexpr int KB = 128 / (int)sizeof(C2<T>);
   constexpr int kMaxPer = PER;  // elements of one component per thread: n == PER * NT / KB (checked by the host)
   extern __shared__ __attribute__((aligned(16))) unsigned char s_raw_x[];
@@ -369,6 +372,10 @@ k_step_boundary_x(Geo g, int log2n, const C2<T> *__restrict__ twiddle, C2<T> *Ck
       bx_store(Ck + col + plane * i + g.Nhp, v);
       continue;
     }
+    if (pair) {  // B itself: k_ypass_pair forms ky B and kz B (zpass.hpp)
+      bx_store(Ck + col + plane * i + g.Nhp, v);
+      continue;
+    }
     C2<T> oy, oz;
     oy.x = (T)(ky * (double)v.x);
     oy.y = (T)(ky * (double)v.y);
@@ -470,7 +477,7 @@ template <typename T, int NT, int PER>  // PER <= 4: eight elements per thread d
 __global__ void __launch_bounds__(NT, BCHMC_BX_WAVES)
 k_step_boundary_x2(Geo g, int log2n, const C2<T> *__restrict__ twiddle, C2<T> *Ck, const C2<T> *q_in, const C2<T> *p_in,
                    C2<T> *q_out, C2<T> *p_out, const double *__restrict__ wS, const double *__restrict__ wM, double a,
-                   double b, double half_eps, double eps, double c_za, double *guard_slot, StepCtl ctl) {
+                   double b, double half_eps, double eps, double c_za, double *guard_slot, StepCtl ctl, bool pair = false) {
   constexpr int KB = 128 / (int)sizeof(C2<T>);
   extern __shared__ __attribute__((aligned(16))) unsigned char s_raw_x2[];
   __shared__ double red[NT / 64];
@@ -626,6 +633,10 @@ k_step_boundary_x2(Geo g, int log2n, const C2<T> *__restrict__ twiddle, C2<T> *C
     const int i = irow + rows * m;
     bx_store(at_cw(Ck, boff[m]), sa[i * KB + c]);
     const C2<T> v = sb[i * KB + c];
+    if (pair) {
+      bx_store(at_cw(Ck1, boff[m]), v);
+      continue;
+    }
     C2<T> oy, oz;
     oy.x = (T)(ky * (double)v.x);
     oy.y = (T)(ky * (double)v.y);

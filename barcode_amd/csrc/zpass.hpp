@@ -1,5 +1,6 @@
 // zpass.hpp -- The last two passes of the planes-mode inverse transform done by the engine itself, so that the z pass
-// can end in the binning instead of in HBM: k_ypass (inverse complex FFTs along y, in place) and k_zbin_direct (inverse
+// can end in the binning instead of in HBM: k_ypass (inverse complex FFTs along y, in place; k_ypass_pair: the same from
+// the two arrays Psi^_x | B a boundary kernel leaves by default) and k_zbin_direct (inverse
 // real FFTs along z of the three displacement components, particle positions, one-pass binning).
 // Reference work these two kernels cover: the last two of the three passes of each of theta2vel's inverse transforms
 // (EqSolvers.cc:274-276 -> fftC2Rplanned, fftwrapper.cc:88-102; the x pass is in k_step_boundary_x), and everything
@@ -60,6 +61,68 @@ k_ypass(Geo g, int log2n, const C2<T> *__restrict__ twiddle, C2<T> *c) {
     const int j = jrow + rows * m;
     if (HINT == 1 || HINT == 3) bx_store(base + (long long)g.nhp * j, s[j * KB + col]);
     else base[(long long)g.nhp * j] = s[j * KB + col];
+  }
+}
+
+// ======================================================================================================
+// k_ypass_pair: the inverse y pass where k_step_boundary_x left TWO arrays (`pair` there): Psi^_x in component 0 and
+// B = (1/k^2)(Im phi^, -Re phi^), x-transformed, in component 1.  ky and kz are constants of an element from here on and
+// the x transform is linear, so Psi^_y = ky B and Psi^_z = kz B are formed where the column is already in registers: the
+// same multiply in double, rounded to T, that the boundary kernel makes on the three-array path -- the operands are
+// the same numbers, so the three arrays k_zbin_direct reads are bit for bit what k_ypass leaves there.  One complex
+// array less is written by the boundary kernel and one less read here.
+// Workgroups [0, n ntk): the column (i, :, k0 .. k0 + KB) of B, read once; ky(j) B is transformed into component 1 (in
+// place: a workgroup writes only the elements it has read) and kz B into component 2 (dead on this path until now).
+// Workgroups [n ntk, 2 n ntk): component 0, as k_ypass.  The workgroups with two transforms come first.
+// Same shapes as k_ypass (y_shape); grid col_grid(.., 2).
+// ======================================================================================================
+template <typename T, int NT, int PER, int HINT = 0>
+__global__ void __launch_bounds__(NT)
+k_ypass_pair(Geo g, int log2n, const C2<T> *__restrict__ twiddle, C2<T> *c) {
+  constexpr int KB = 128 / (int)sizeof(C2<T>);
+  extern __shared__ __attribute__((aligned(16))) unsigned char s_raw_yp[];
+  const int n = g.n;
+  C2<T> *s = reinterpret_cast<C2<T> *>(s_raw_yp);  // n * KB
+  C2<T> *tw = s + (size_t)n * KB;                  // n / 2
+  for (int t = threadIdx.x; t < n / 2; t += blockDim.x) tw[t] = twiddle[t];
+  const int ntk = g.nhp / KB;
+  const int per_comp = n * ntk;
+  const bool from_b = (int)blockIdx.x < per_comp;
+  const int b = (int)blockIdx.x % per_comp;
+  const int i = b / ntk, k0 = (b % ntk) * KB;
+  const int col = threadIdx.x % KB, jrow = threadIdx.x / KB;
+  constexpr int rows = NT / KB;
+  // element (i, 0, k0 + col) of component 0 (Psi^_x) or 1 (B)
+  C2<T> *base = c + (from_b ? g.Nhp : 0ll) + (long long)g.nhp * g.n * i + k0 + col;
+  const int shift = 32 - log2n;
+  C2<T> v[PER];
+#pragma unroll
+  for (int m = 0; m < PER; m++)
+    v[m] = (HINT == 1 || HINT == 2) ? bx_load(base + (long long)g.nhp * (jrow + rows * m))
+                                    : base[(long long)g.nhp * (jrow + rows * m)];
+  const double kz = kval(k0 + col, g.n, g.kfac);
+  for (int pass = 0; pass < (from_b ? 2 : 1); pass++) {
+    if (pass) __syncthreads();  // every thread has taken its elements of the first transform out of the tile
+#pragma unroll
+    for (int m = 0; m < PER; m++) {
+      const int j = jrow + rows * m;
+      C2<T> o = v[m];
+      if (from_b) {
+        const double f = pass ? kz : kval(j, g.n, g.kfac);
+        o.x = (T)(f * (double)v[m].x);
+        o.y = (T)(f * (double)v[m].y);
+      }
+      s[(int)(__brev((unsigned)j) >> shift) * KB + col] = o;
+    }
+    __syncthreads();
+    xfft_inplace<T>(s, tw, n, log2n, KB, true);
+    C2<T> *out = base + (pass ? g.Nhp : 0ll);
+#pragma unroll
+    for (int m = 0; m < PER; m++) {
+      const int j = jrow + rows * m;
+      if (HINT == 1 || HINT == 3) bx_store(out + (long long)g.nhp * j, s[j * KB + col]);
+      else out[(long long)g.nhp * j] = s[j * KB + col];
+    }
   }
 }
 
