@@ -133,6 +133,22 @@ struct bchmc_handle {
     } slot[BCHMC_ENS_SLOTS];
     int ncu = 0;                                     // compute units of the device (0: not asked yet)
   } ens;
+  // bchmc_tweb_* (tweb.hpp): the six real arrays of the tensor, the type map, the partials and the result of the per-type
+  // sums are taken by the first classify; the half-complex array by the first one whose source needs a transform (the
+  // chain state's q^ is read where it is), the eigenvalue staging by the first that asks for lambda, the counters by the
+  // first accumulating call or merge.  All kept until bchmc_tweb_release or bchmc_destroy.
+  struct Tweb {
+    DevBytes t[6];                       // N elements of T each: xx, xy, xz, yy, yz, zz of the last classify
+    DevBytes xk;                         // Nhp complex: x^ of a host or deltaX source (the components go through tC)
+    DevBuf<unsigned char> type;          // N
+    DevBuf<double> lam;                  // 3 N
+    DevBuf<unsigned long long> part;     // (workgroups + 1) * kTwebWords: partials, then the result
+    DevBuf<unsigned int> cnt;            // 4 N, type-major: the posterior accumulator
+    bool have_t = false;                 // t holds a tensor
+    uint64_t samples = 0;
+    bool have_par = false;               // R and lambda_th below are set (a merge brings counters, not their parameters)
+    double R = 0., lambda_th = 0.;       // of the first sample accumulated by a classify since the last reset
+  } tw;
   // measure_corr / measure_corr2d (corr.hpp): accumulators and the geometry of the last n_bin of each function, kept in
   // the handle like spec_bins (the driver measures after every sample with the same n_bin)
   struct Corr1 {
@@ -2525,6 +2541,60 @@ struct Pipe {
     return BCHMC_OK;
   }
 
+  // ---- bchmc_tweb_classify (tweb.hpp; tweb_take has run) ----------------------------------------------------------------
+  // The six components of the tensor of the source into h->tw.t: x^ as spectrum_source obtains it (a host signal is in
+  // dstage; a fresh transform lands in the feature's own half-complex array, because tC is the scratch of the
+  // components), then per component one element-wise pass into tC and one C2R.  One k-space array beyond x^ at any time.
+  static int tweb_tensor(bchmc_handle *h, int src, double half_r2) {
+    auto &w = h->tw;
+    const void *xk = w.xk;
+    if (src == BCHMC_CORR_HOST) {
+      CHK(r2c_state(h, h->dstage, h->ioq, w.xk));
+    } else if (src == BCHMC_CORR_CHAIN_STATE) {
+      xk = h->cq;
+    } else {
+      CHK(upres_real(h, src));
+      CHK(fft_exec(h, h->r2c1, h->ioq, w.xk, BCHMC_K_FFT_R2C));
+    }
+    static const int ab[6][2] = {{0, 0}, {0, 1}, {0, 2}, {1, 1}, {1, 2}, {2, 2}};
+    for (int c = 0; c < 6; c++) {
+      {
+        ProfScope ps(h, BCHMC_K_OTHER);
+        k_tweb_component<T><<<nblk_stride(h->g.Nhp), kTwebBlock, 0, h->stream>>>(h->g, C(xk), C(h->tC), ab[c][0], ab[c][1],
+                                                                                half_r2, 1. / (double)h->g.N);
+        HIPCHK(hipGetLastError());
+      }
+      CHK(fft_exec(h, h->c2r1, h->tC, w.t[c], BCHMC_K_FFT_C2R));
+    }
+    return BCHMC_OK;
+  }
+
+  // Eigenvalues, types and the per-type sums of the tensor in h->tw.t.  The mass weights 1 + x come from the unsmoothed
+  // source in real space: the staged doubles of a host signal, else the field of T that upres_real leaves in ioq (tC is
+  // free again by now).  lam: h->tw.lam or null.  The result lands in the last kTwebWords of h->tw.part.
+  static int tweb_eigen(bchmc_handle *h, int src, double lambda_th, double *lam, int nblk) {
+    auto &w = h->tw;
+    if (src != BCHMC_CORR_HOST) CHK(upres_real(h, src));
+    TwebTensor t;
+    for (int c = 0; c < 6; c++) t.c[c] = w.t[c];
+    ProfScope ps(h, BCHMC_K_OTHER);
+    if (src == BCHMC_CORR_HOST)
+      k_tweb_eigen<T, double><<<nblk, kTwebBlock, 0, h->stream>>>(h->g.N, t, h->dstage.get(), lambda_th, lam, w.type, w.part);
+    else
+      k_tweb_eigen<T, T><<<nblk, kTwebBlock, 0, h->stream>>>(h->g.N, t, R(h->ioq), lambda_th, lam, w.type, w.part);
+    k_tweb_reduce<<<kTwebWords, kWave, 0, h->stream>>>(nblk, w.part, w.part + (size_t)nblk * kTwebWords);
+    HIPCHK(hipGetLastError());
+    return BCHMC_OK;
+  }
+
+  // one component of the tensor -> N host doubles
+  static int tweb_component_fetch(bchmc_handle *h, int c, double *out) {
+    const size_t bytes = (size_t)h->g.N * sizeof(double);
+    if (kDouble) return d2h(h, out, h->tw.t[c], bytes);
+    CHK(store_real(h, R(h->tw.t[c]), h->dstage));
+    return d2h(h, out, h->dstage, bytes);
+  }
+
   // ---- measure_spec2D (spec2d.hpp; spec2d_setup has run for n_bin) ----------------------------------------------------
   template <bool GEOM>
   static int launch_spec2d(bchmc_handle *h, const CT *xk) {
@@ -4316,6 +4386,192 @@ int bchmc_ensemble_release(bchmc_handle *h) {
     (void)s.m2.release();
     s.count = 0;
   }
+  return BCHMC_OK;
+}
+
+// ---- bchmc_tweb_* (tweb.hpp) -------------------------------------------------------------------------------------------
+// Workgroups of k_tweb_eigen: a function of the grid alone, so that the order of the per-type sums, and with it every
+// bit of the masses, is the same on every handle of a kind.
+static int tweb_blocks(const bchmc_handle *h) { return nblk_stride(h->g.N); }
+
+static void tweb_drop(bchmc_handle *h) {
+  auto &w = h->tw;
+  for (auto &b : w.t) (void)b.release();
+  (void)w.xk.release();
+  (void)w.type.release();
+  (void)w.lam.release();
+  (void)w.part.release();
+  (void)w.cnt.release();
+  w.have_t = false;
+  w.samples = 0;
+  w.have_par = false;
+}
+
+// The buffers a call needs, zeroed on the handle's stream, each on its first use.  If one cannot be had the call gives
+// back those it took itself and the handle is as it was before it (the ens_take pattern).
+static int tweb_take(bchmc_handle *h, bool tensor, bool xk, bool lam, bool cnt) {
+  auto &w = h->tw;
+  const size_t N = (size_t)h->g.N;
+  bool took_t[6] = {false, false, false, false, false, false}, took_type = false, took_part = false, took_xk = false,
+       took_lam = false, took_cnt = false;
+  int rc = BCHMC_OK;
+  if (tensor) {
+    for (int c = 0; c < 6 && !rc; c++)
+      if (!w.t[c]) rc = dev_alloc(h, w.t[c], N * h->esz), took_t[c] = !rc;
+    if (!rc && !w.type) rc = dev_alloc(h, w.type, N), took_type = !rc;
+    if (!rc && !w.part) rc = dev_alloc(h, w.part, ((size_t)tweb_blocks(h) + 1) * kTwebWords), took_part = !rc;
+  }
+  if (!rc && xk && !w.xk) rc = dev_alloc(h, w.xk, 2 * (size_t)h->g.Nhp * h->esz), took_xk = !rc;
+  if (!rc && lam && !w.lam) rc = dev_alloc(h, w.lam, 3 * N), took_lam = !rc;
+  if (!rc && cnt && !w.cnt) rc = dev_alloc(h, w.cnt, 4 * N), took_cnt = !rc;
+  if (rc) {
+    (void)hipStreamSynchronize(h->stream);  // the zero fills of what goes back
+    for (int c = 0; c < 6; c++)
+      if (took_t[c]) (void)w.t[c].release();
+    if (took_type) (void)w.type.release();
+    if (took_part) (void)w.part.release();
+    if (took_xk) (void)w.xk.release();
+    if (took_lam) (void)w.lam.release();
+    if (took_cnt) (void)w.cnt.release();
+    if (took_t[0] || took_t[1] || took_t[2] || took_t[3] || took_t[4] || took_t[5]) w.have_t = false;
+  }
+  return rc;
+}
+
+int bchmc_tweb_classify(bchmc_handle *h, bchmc_corr_source src, const double *signal, const bchmc_tweb_opts *opts,
+                        double *lambda, uint8_t *type, bchmc_tweb_stats *stats) {
+  if (!h) return BCHMC_ERR_ARG;
+  const char *name = "tweb_classify";
+  if (!opts) return h->fail(BCHMC_ERR_ARG, "%s: opts is NULL", name);
+  const double Rs = opts->smoothing_scale, lth = opts->lambda_th;
+  if (!(Rs >= 0.) || !(Rs <= DBL_MAX))
+    return h->fail(BCHMC_ERR_ARG, "%s: smoothing_scale = %g is negative or not finite", name, Rs);
+  if (!(std::fabs(lth) <= DBL_MAX)) return h->fail(BCHMC_ERR_ARG, "%s: lambda_th = %g is not finite", name, lth);
+  if (opts->accumulate != 0 && opts->accumulate != 1)
+    return h->fail(BCHMC_ERR_ARG, "%s: accumulate = %d is neither 0 nor 1", name, (int)opts->accumulate);
+  CHK(source_args(h, name, src, signal));
+  ENTER(h);
+  CHK(source_state(h, src));
+  auto &w = h->tw;
+  if (opts->accumulate) {
+    if (w.have_par && (Rs != w.R || lth != w.lambda_th))
+      return h->fail(BCHMC_ERR_STATE,
+                     "%s: the accumulator holds samples of smoothing_scale = %g, lambda_th = %g; this call has %g, %g "
+                     "(bchmc_tweb_reset starts another posterior)", name, w.R, w.lambda_th, Rs, lth);
+    if (w.samples + 1 >= (1ull << 32)) return h->fail(BCHMC_ERR_STATE, "%s: the accumulator's sample count is full", name);
+  }
+  CHK(tweb_take(h, true, src != BCHMC_CORR_CHAIN_STATE, lambda != nullptr, opts->accumulate != 0));
+  const size_t N = (size_t)h->g.N;
+  const int nblk = tweb_blocks(h);
+  if (signal) CHK(h2d(h, h->dstage, signal, N * sizeof(double)));
+  w.have_t = false;
+  CHK(DISPATCH(h, tweb_tensor(h, (int)src, 0.5 * Rs * Rs)));
+  CHK(DISPATCH(h, tweb_eigen(h, (int)src, lth, lambda ? w.lam.get() : nullptr, nblk)));
+  w.have_t = true;
+  unsigned long long res[kTwebWords];
+  CHK(d2h(h, res, w.part + (size_t)nblk * kTwebWords, sizeof res));
+  if (lambda) CHK(d2h(h, lambda, w.lam, 3 * N * sizeof(double)));
+  if (type) CHK(d2h(h, type, w.type, N));
+  if (stats) {
+    for (int t = 0; t < 4; t++) {
+      stats->n_type[t] = res[t];
+      std::memcpy(&stats->mass_type[t], &res[5 + t], sizeof(double));
+    }
+    stats->n_nonfinite = res[4];
+  }
+  if (!opts->accumulate) return BCHMC_OK;
+  if (res[4])
+    return h->fail(BCHMC_ERR_ARG, "%s: %llu cells of the sample have a tensor that is not finite; nothing was accumulated",
+                   name, res[4]);
+  {
+    ProfScope ps(h, BCHMC_K_OTHER);
+    k_tweb_accumulate<<<nblk_stride((long long)((N >> 2) + 4)), kTwebBlock, 0, h->stream>>>(h->g.N, w.type, w.cnt);
+    HIPCHK(hipGetLastError());
+  }
+  HIPCHK(hipStreamSynchronize(h->stream));
+  if (!w.have_par) w.R = Rs, w.lambda_th = lth, w.have_par = true;
+  w.samples++;
+  return BCHMC_OK;
+}
+
+int bchmc_tweb_tensor(bchmc_handle *h, int32_t component, double *out) {
+  if (!h || !out) return BCHMC_ERR_ARG;
+  const char *name = "tweb_tensor";
+  if (component < 0 || component > 5) return h->fail(BCHMC_ERR_ARG, "%s: component = %d outside 0..5", name, (int)component);
+  ENTER(h);
+  if (!h->tw.have_t) return h->fail(BCHMC_ERR_STATE, "%s: no tensor in the handle: call bchmc_tweb_classify first", name);
+  return DISPATCH(h, tweb_component_fetch(h, (int)component, out));
+}
+
+int bchmc_tweb_samples(bchmc_handle *h, uint64_t *n) {
+  if (!h || !n) return BCHMC_ERR_ARG;
+  *n = h->tw.samples;
+  return BCHMC_OK;
+}
+
+int bchmc_tweb_fetch(bchmc_handle *h, int32_t type, int32_t as_probability, void *out) {
+  if (!h || !out) return BCHMC_ERR_ARG;
+  const char *name = "tweb_fetch";
+  if (type < 0 || type > 3) return h->fail(BCHMC_ERR_ARG, "%s: type = %d outside 0..3", name, (int)type);
+  ENTER(h);
+  auto &w = h->tw;
+  const size_t N = (size_t)h->g.N;
+  if (as_probability && w.samples == 0)
+    return h->fail(BCHMC_ERR_STATE, "%s: as_probability with samples = 0: the accumulator is empty", name);
+  if (!w.cnt) {  // counters never taken: every count is 0
+    std::memset(out, 0, N * sizeof(uint32_t));
+    return BCHMC_OK;
+  }
+  if (!as_probability) return d2h(h, out, w.cnt + (size_t)type * N, N * sizeof(uint32_t));
+  {
+    ProfScope ps(h, BCHMC_K_OTHER);
+    k_tweb_probability<<<nblk_stride(h->g.N), kTwebBlock, 0, h->stream>>>(h->g.N, w.cnt + (size_t)type * N, (double)w.samples,
+                                                                         h->dstage.get());
+    HIPCHK(hipGetLastError());
+  }
+  return d2h(h, out, h->dstage, N * sizeof(double));
+}
+
+int bchmc_tweb_merge(bchmc_handle *h, uint64_t n_b, const uint32_t *counts_b) {
+  if (!h) return BCHMC_ERR_ARG;
+  const char *name = "tweb_merge";
+  if (n_b == 0) return BCHMC_OK;  // nothing to fold in: the array is not looked at
+  if (!counts_b) return h->fail(BCHMC_ERR_ARG, "%s: counts_b must be given with n_b > 0", name);
+  ENTER(h);
+  auto &w = h->tw;
+  if (n_b >= (1ull << 32) || n_b + w.samples >= (1ull << 32))
+    return h->fail(BCHMC_ERR_ARG, "%s: n_b = %llu and the %llu samples held do not fit the 32-bit counters", name,
+                   (unsigned long long)n_b, (unsigned long long)w.samples);
+  CHK(tweb_take(h, false, false, false, true));
+  const size_t N = (size_t)h->g.N;
+  CHK(h2d(h, h->dstage, counts_b, 4 * N * sizeof(uint32_t)));  // 16 N bytes: exactly the staging's 2 N doubles
+  {
+    ProfScope ps(h, BCHMC_K_OTHER);
+    k_tweb_merge<<<nblk_stride(4 * h->g.N), kTwebBlock, 0, h->stream>>>(4 * h->g.N, reinterpret_cast<const unsigned int *>(h->dstage.get()),
+                                                                       w.cnt);
+    HIPCHK(hipGetLastError());
+  }
+  HIPCHK(hipStreamSynchronize(h->stream));
+  w.samples += n_b;
+  return BCHMC_OK;
+}
+
+int bchmc_tweb_reset(bchmc_handle *h) {
+  if (!h) return BCHMC_ERR_ARG;
+  ENTER(h);
+  auto &w = h->tw;
+  w.samples = 0;
+  w.have_par = false;
+  if (w.cnt) HIPCHK(hipMemsetAsync(w.cnt, 0, 4 * (size_t)h->g.N * sizeof(uint32_t), h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return BCHMC_OK;
+}
+
+int bchmc_tweb_release(bchmc_handle *h) {
+  if (!h) return BCHMC_ERR_ARG;
+  ENTER(h);
+  HIPCHK(hipStreamSynchronize(h->stream));
+  tweb_drop(h);
   return BCHMC_OK;
 }
 

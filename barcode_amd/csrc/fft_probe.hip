@@ -568,6 +568,37 @@ int interp_tsc(int n, double L, int rsd, const double *pos, double f1, const voi
   return pr.finish({{2, V}});
 }
 
+// k_tweb_eigen<T, double> and k_tweb_reduce on `count` cells as bchmc_tweb_classify launches them: t6 = six arrays of T one
+// after the other (xx, xy, xz, yy, yz, zz), x (count doubles, may be null: every mass weight is 1), lam (3 count
+// doubles, may be null), type (count bytes), res (kTwebWords 64-bit words: n_type[4], n_nonfinite, the bits of
+// mass_type[4]).  Device arrays: t6, x if given, lam if given, type, the partials.
+template <typename T>
+int tweb_eigen(long long count, const void *t6, const double *x, double lambda_th, double *lam, unsigned char *type,
+               unsigned long long *res) {
+  if (count < 1 || count > (1ll << 27) || !t6 || !type || !res) return -1;
+  Probe pr;
+  const T *dt = static_cast<const T *>(pr.alloc((size_t)6 * count * sizeof(T), t6));
+  const double *dx = opt<double>(pr, (size_t)count * sizeof(double), x);
+  int i_lam = -1;
+  double *dl = opt<double>(pr, (size_t)3 * count * sizeof(double), lam, &i_lam);
+  unsigned char *dty = static_cast<unsigned char *>(pr.alloc((size_t)count, type));
+  const int i_ty = (int)pr.bufs.size() - 1;
+  const int nblk = nblk_stride(count);
+  unsigned long long *dp = static_cast<unsigned long long *>(pr.alloc(((size_t)nblk + 1) * kTwebWords * sizeof(unsigned long long), nullptr));
+  if (pr.err) return pr.err;
+  TwebTensor t;
+  for (int c = 0; c < 6; c++) t.c[c] = dt + (size_t)c * count;
+  k_tweb_eigen<T, double><<<nblk, kTwebBlock>>>(count, t, dx, lambda_th, dl, dty, dp);
+  k_tweb_reduce<<<kTwebWords, kWave>>>(nblk, dp, dp + (size_t)nblk * kTwebWords);
+  Outs o{{i_ty, type}};
+  out(o, i_lam, lam);
+  const int rc = pr.finish(o);
+  if (rc) return rc;
+  if (!pr.ok(hipMemcpy(res, dp + (size_t)nblk * kTwebWords, kTwebWords * sizeof(unsigned long long), hipMemcpyDeviceToHost)))
+    return pr.err;
+  return 0;
+}
+
 }  // namespace
 
 // prec: 0 = double, 1 = float (the engine's storage type T); arrays are of that type, complex ones interleaved
@@ -723,6 +754,13 @@ int fftp_interp_tsc(int prec, int n, double box_len, int rsd, const double *pos,
                     const void *conv, void *V) {
   return prec ? interp_tsc<float>(n, box_len, rsd, pos, f1, psi, conv, V)
               : interp_tsc<double>(n, box_len, rsd, pos, f1, psi, conv, V);
+}
+
+// ---- the T-web's eigenvalue kernel on chosen tensors (tests/test_gpu_tweb.py)
+int fftp_tweb_eigen(int prec, long long count, const void *t6, const double *x, double lambda_th, double *lam,
+                    unsigned char *type, unsigned long long *res) {
+  return prec ? tweb_eigen<float>(count, t6, x, lambda_th, lam, type, res)
+              : tweb_eigen<double>(count, t6, x, lambda_th, lam, type, res);
 }
 
 }  // extern "C"

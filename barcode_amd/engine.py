@@ -79,6 +79,17 @@ class DensityStats(C.Structure):
     _fields_ = [("n_in", C.c_uint64), ("n_lost", C.c_uint64), ("max_per_tile", C.c_uint64)]
 
 
+class TwebOpts(C.Structure):
+    """bchmc_tweb_opts."""
+    _fields_ = [("smoothing_scale", C.c_double), ("lambda_th", C.c_double), ("accumulate", C.c_int32),
+                ("reserved0", C.c_int32)]
+
+
+class TwebStats(C.Structure):
+    """bchmc_tweb_stats."""
+    _fields_ = [("n_type", C.c_uint64 * 4), ("n_nonfinite", C.c_uint64), ("mass_type", C.c_double * 4)]
+
+
 class InterpField(C.Structure):
     """bchmc_interp_field: one source of bchmc_interp_particles."""
     _fields_ = [("source", C.c_int32), ("field", C.c_int32), ("host", C.POINTER(C.c_double))]
@@ -144,7 +155,9 @@ EXPORTS = ("bchmc_create", "bchmc_destroy", "bchmc_strerror", "bchmc_last_error"
            "bchmc_measure_cross_spectrum", "bchmc_ensemble_add", "bchmc_ensemble_count", "bchmc_ensemble_fetch",
            "bchmc_ensemble_merge", "bchmc_ensemble_reset", "bchmc_ensemble_release",
            "bchmc_poisson_draw", "bchmc_poisson_positions", "bchmc_poisson_density", "bchmc_poisson_release",
-           "bchmc_setup_random_test_poisson")
+           "bchmc_setup_random_test_poisson",
+           "bchmc_tweb_classify", "bchmc_tweb_tensor", "bchmc_tweb_samples", "bchmc_tweb_fetch", "bchmc_tweb_merge",
+           "bchmc_tweb_reset", "bchmc_tweb_release")
 # declared as well, listed apart: the header scan of the ABI test matches names of letters and underscores only
 EXPORTS_MT19937 = ("bchmc_chain_draw_momenta_mt19937", "bchmc_mt19937_jump")
 EXPORTS_CORR2D = ("bchmc_measure_corr2d", "bchmc_measure_corr2d_interp")  # a digit in the name, like the two above
@@ -154,6 +167,9 @@ EXPORTS_SPEC2D = ("bchmc_measure_spectrum2d",)  # likewise
 CORR_SOURCES = dict(host=0, chain=1, deltaX=2)
 ENS_SLOTS = 4                                         # BCHMC_ENS_SLOTS
 ENS_WHAT = dict(mean=0, variance=1, std=2, m2=3)      # bchmc_ens_what
+TWEB_TYPES = dict(void=0, sheet=1, filament=2, knot=3)  # the number of eigenvalues above lambda_th
+TWEB_COMPONENTS = dict(xx=0, xy=1, xz=2, yy=3, yz=4, zz=5)
+TWEB_NONFINITE = 255                                  # the type of a cell whose tensor is not finite
 
 
 def load():
@@ -218,6 +234,13 @@ def load():
     lib.bchmc_ensemble_merge.argtypes = [vp, C.c_int32, u64, dp, dp]
     lib.bchmc_ensemble_reset.argtypes = [vp, C.c_int32]
     lib.bchmc_ensemble_release.argtypes = [vp]
+    lib.bchmc_tweb_classify.argtypes = [vp, C.c_int, dp, C.POINTER(TwebOpts), dp, C.POINTER(C.c_uint8), C.POINTER(TwebStats)]
+    lib.bchmc_tweb_tensor.argtypes = [vp, C.c_int32, dp]
+    lib.bchmc_tweb_samples.argtypes = [vp, C.POINTER(u64)]
+    lib.bchmc_tweb_fetch.argtypes = [vp, C.c_int32, C.c_int32, vp]
+    lib.bchmc_tweb_merge.argtypes = [vp, u64, C.POINTER(C.c_uint32)]
+    lib.bchmc_tweb_reset.argtypes = [vp]
+    lib.bchmc_tweb_release.argtypes = [vp]
     lib.bchmc_chain_forward.argtypes = [vp, C.c_int]
     lib.bchmc_density_particles.argtypes = [vp, C.c_int, dp, dp, dp, dp, u64, C.POINTER(DensityOpts), dp,
                                             C.POINTER(DensityStats)]
@@ -346,6 +369,7 @@ class Engine:
         self.params = params
         self.Nx = int(params.Nx)
         self.N = self.Nx ** 3
+        self._tweb_par = None  # (smoothing_scale, lambda_th) of the samples tweb_classify has accumulated
         self.h = C.c_void_p()
         cfg = make_config(params, device, precision, deterministic)
         rc = self.lib.bchmc_create(C.byref(cfg), C.byref(self.h))
@@ -669,6 +693,81 @@ class Engine:
     def ensemble_release(self):
         """Frees the buffers of every slot; a later ``ensemble_add`` takes them again."""
         self._chk(self.lib.bchmc_ensemble_release(self.h))
+
+    # ---- the T-web of a sample (bchmc_tweb_*) ---------------------------------------------------------
+    def tweb_classify(self, signal=None, source=None, smoothing_scale=0.0, lambda_th=0.0, accumulate=False,
+                      want_lambda=True, want_type=True):
+        """The cosmic-web type of every cell of a host field, of the resident chain state (the default without a
+        signal) or of the handle's deltaX, sources as in ``measure_corr``: eigenvalues of the tidal tensor of the field
+        smoothed with a Gaussian of ``smoothing_scale`` Mpc/h, type = how many exceed ``lambda_th`` (0 void, 1 sheet,
+        2 filament, 3 knot; 255 where the tensor is not finite).  ``accumulate``: also one more sample into the
+        posterior counters.  Returns a dict: ``lambda`` (3, N) descending or None, ``type`` (N,) uint8 or None,
+        ``n_type`` (4,) uint64, ``n_nonfinite``, ``mass_type`` (4,) sums of 1 + x over each type's cells.  A sample with
+        non-finite cells raises under ``accumulate`` (nothing is added); the dict is then the exception's ``result``."""
+        if source is None:
+            source = "chain" if signal is None else "host"
+        sig = None if signal is None else _p(self._in(signal))
+        opts = TwebOpts(float(smoothing_scale), float(lambda_th), int(accumulate), 0)
+        lam = np.empty((3, self.N)) if want_lambda else None
+        typ = np.empty(self.N, dtype=np.uint8) if want_type else None
+        st = TwebStats()
+        rc = self.lib.bchmc_tweb_classify(self.h, CORR_SOURCES[source], sig, C.byref(opts),
+                                          None if lam is None else _p(lam.reshape(-1)),
+                                          None if typ is None else typ.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(st))
+        res = {"lambda": lam, "type": typ, "n_type": np.array(list(st.n_type), dtype=np.uint64),
+               "n_nonfinite": int(st.n_nonfinite), "mass_type": np.array(list(st.mass_type))}
+        if rc:
+            err = BchmcError(rc, self.lib.bchmc_strerror(rc).decode(), self.lib.bchmc_last_error(self.h).decode())
+            err.result = res if (accumulate and st.n_nonfinite) else None
+            raise err
+        if accumulate:
+            self._tweb_par = (float(smoothing_scale), float(lambda_th))
+        return res
+
+    def tweb_tensor(self, component):
+        """One component ("xx", "xy", "xz", "yy", "yz", "zz" or 0..5) of the tensor of the last ``tweb_classify``."""
+        out = np.empty(self.N)
+        c = TWEB_COMPONENTS[component] if isinstance(component, str) else int(component)
+        self._chk(self.lib.bchmc_tweb_tensor(self.h, c, _p(out)))
+        return out
+
+    def tweb_samples(self):
+        n = C.c_uint64()
+        self._chk(self.lib.bchmc_tweb_samples(self.h, C.byref(n)))
+        return n.value
+
+    def tweb_fetch(self, type, as_probability=False):
+        """The posterior counters of one type ("void", "sheet", "filament", "knot" or 0..3): N uint32, or with
+        ``as_probability`` count / samples as N doubles (needs one sample)."""
+        t = TWEB_TYPES[type] if isinstance(type, str) else int(type)
+        out = np.empty(self.N, dtype=np.float64 if as_probability else np.uint32)
+        self._chk(self.lib.bchmc_tweb_fetch(self.h, t, int(bool(as_probability)), out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def tweb_export(self):
+        """(samples, counters (4, N) uint32): what ``tweb_merge`` of another handle takes."""
+        return self.tweb_samples(), np.stack([self.tweb_fetch(t) for t in range(4)])
+
+    def tweb_merge(self, samples, counts):
+        """Adds another chain's counters (4, N), type-major, of ``samples`` samples.  ``samples == 0`` is a no-op."""
+        samples = int(samples)
+        if samples == 0:
+            self._chk(self.lib.bchmc_tweb_merge(self.h, 0, None))
+            return
+        c = np.ascontiguousarray(counts, dtype=np.uint32).reshape(-1)
+        if c.size != 4 * self.N:
+            raise ValueError("expected %d counters, got %d" % (4 * self.N, c.size))
+        self._chk(self.lib.bchmc_tweb_merge(self.h, samples, c.ctypes.data_as(C.POINTER(C.c_uint32))))
+
+    def tweb_reset(self):
+        """samples = 0 and zeroed counters; the buffers are kept."""
+        self._chk(self.lib.bchmc_tweb_reset(self.h))
+        self._tweb_par = None
+
+    def tweb_release(self):
+        """Frees every buffer of the feature, the counters included; a later ``tweb_classify`` takes them again."""
+        self._chk(self.lib.bchmc_tweb_release(self.h))
+        self._tweb_par = None
 
     def _measure_corr(self, fn, cells, signal, n_bin, source):
         if source is None:

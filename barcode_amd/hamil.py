@@ -179,6 +179,21 @@ def ensemble_fetch(hd, slot, what="mean"):
     return hd.engine.ensemble_fetch(slot, what)
 
 
+def tweb_classify(hd, signal=None, source=None, smoothing_scale=0., lambda_th=0., accumulate=False):
+    """The T-web of a sample: eigenvalues of the tidal tensor of the field smoothed with a Gaussian of
+    ``smoothing_scale`` Mpc/h and, per cell, how many exceed ``lambda_th`` (0 void, 1 sheet, 2 filament, 3 knot).
+    ``signal`` None = the resident chain state, or with ``source="deltaX"`` the density of the last forward model.
+    ``accumulate``: also one more sample of the posterior that ``tweb_probability`` reads.  Returns ``Engine.tweb_classify``'s
+    dict (lambda, type, n_type, n_nonfinite, mass_type)."""
+    return hd.engine.tweb_classify(signal, source, smoothing_scale, lambda_th, accumulate)
+
+
+def tweb_probability(hd, type):
+    """The posterior probability of ``type`` ("void", "sheet", "filament", "knot" or 0..3) per cell over the samples
+    ``tweb_classify(..., accumulate=True)`` has seen -> N values."""
+    return hd.engine.tweb_fetch(type, as_probability=True)
+
+
 def getDensity(hd, mk, xp, yp, zp, Par_mass=None, weightmass=False, kernel_h=0.0, to_nobs=False):
     """getDensity_NGP / _CIC / _TSC / _SPH (massFunctions.cc:49-495; ``mk`` 0 .. 3 picks the one, None the handle's) of a
     free particle list on ``hd``'s grid, upstream's argument order from ``xp`` on -> (delta, stats).  ``weightmass``

@@ -179,6 +179,29 @@ def dump_ensemble(engine, directory, slot, name):
     return tuple(add_extension_if_missing(n) for n in names)
 
 
+TWEB_NAMES = ("void", "sheet", "filament", "knot")
+
+
+def tweb_filenames(directory, name):
+    """``<name>_pvoid`` .. ``<name>_pknot`` and ``<name>_tweb.txt`` under ``directory`` (the four before ``write_array``'s
+    extension rule)."""
+    base = os.path.join(directory, name) if directory else name
+    return tuple(base + "_p" + t for t in TWEB_NAMES) + (base + "_tweb.txt",)
+
+
+def dump_tweb(engine, directory, name):
+    """The posterior web-type probabilities of the engine's T-web accumulator (``Engine.tweb_classify`` with
+    ``accumulate``) as four raw ``real_prec`` arrays of N values, and one text line with the sample count, the
+    smoothing scale and the threshold of the samples.  Needs one sample.  Returns the five paths written."""
+    names = tweb_filenames(directory, name)
+    for t, path in enumerate(names[:4]):
+        write_array(path, engine.tweb_fetch(t, as_probability=True))
+    R, lth = engine._tweb_par if engine._tweb_par is not None else (float("nan"), float("nan"))
+    with open(names[4], "w") as f:
+        f.write("%d %.17g %.17g\n" % (engine.tweb_samples(), R, lth))
+    return tuple(add_extension_if_missing(n) for n in names[:4]) + (names[4],)
+
+
 def dump_deltas(engine, directory, suffix=""):
     """``dump_deltas`` (IOfunctionsGen.cc:136-171) of the resident chain state: deltaLAG, then deltaEUL without
     ``rsd_model``, or deltaRSS (the configured forward model) and deltaEUL (a second Lag2Eul without RSD) with it.

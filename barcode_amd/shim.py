@@ -29,7 +29,8 @@ SHIM_EXPORTS = ("bchmc_shim_Hamiltonian_EoM", "bchmc_shim_delta_Hamiltonian", "b
                 "bchmc_shim_measure_corr_grid", "bchmc_shim_measure_corr2D", "bchmc_shim_chain_forward",
                 "bchmc_shim_interp_field", "bchmc_shim_measure_corr2D_interp", "bchmc_shim_measure_spec2D",
                 "bchmc_shim_getDensity", "bchmc_shim_interpolate", "bchmc_shim_setup_random_test_poisson",
-                "bchmc_shim_discrete_poisson_sample", "bchmc_shim_poisson_positions", "bchmc_shim_poisson_upres")
+                "bchmc_shim_discrete_poisson_sample", "bchmc_shim_poisson_positions", "bchmc_shim_poisson_upres",
+                "bchmc_shim_tweb_classify", "bchmc_shim_tweb_probability")
 
 _dp = C.POINTER(C.c_double)
 
@@ -128,6 +129,9 @@ def load():
     lib.bchmc_shim_measure_corr2D_interp.argtypes = [hv, _dp, C.c_uint, C.c_uint, C.c_double, ul, _dp, C.POINTER(ul), _dp,
                                                      C.c_int, C.c_int, C.c_char_p, sz]
     lib.bchmc_shim_measure_spec2D.argtypes = [hv, _dp, _dp, _dp, ul, C.c_int, C.c_int, C.c_char_p, sz]
+    lib.bchmc_shim_tweb_classify.argtypes = [hv, _dp, C.c_double, C.c_double, C.c_int, _dp, C.POINTER(C.c_ubyte),
+                                             C.POINTER(ul), _dp, C.c_int, C.c_char_p, sz]
+    lib.bchmc_shim_tweb_probability.argtypes = [hv, C.c_int, _dp, C.c_char_p, sz]
     lib.bchmc_shim_getDensity.argtypes = [hv, C.c_int, _dp, _dp, _dp, _dp, ul, _dp, C.c_int, C.c_double, C.c_char_p, sz]
     lib.bchmc_shim_interpolate.argtypes = [hv, C.c_int, _dp, _dp, _dp, ul, _dp, C.c_int, _dp, C.c_char_p, sz]
     lib.bchmc_shim_chain_forward.argtypes = [hv, C.c_int, C.c_char_p, sz]
@@ -340,6 +344,24 @@ class ShimHamil:
             len(self._err)))
         shape = (int(N_bin),) * 2
         return rm.reshape(shape), nm.reshape(shape), co.reshape(shape)
+
+    def tweb_classify(self, signal, smoothing_scale=0.0, lambda_th=0.0, accumulate=False, of_deltaX=False):
+        """bchmc_shim::tweb_classify at ``signal`` (None: the resident state, or deltaX) -> (lambda (3, N), type (N,)
+        uint8, n_type (4,), mass_type (4,))."""
+        lam, typ = np.empty((3, self.N)), np.empty(self.N, dtype=np.uint8)
+        nt, mt = np.zeros(4, dtype=np.uint64), np.zeros(4)
+        sig = None if signal is None else _p(self._in(signal))
+        self._chk(self.lib.bchmc_shim_tweb_classify(
+            C.byref(self.hd), sig, float(smoothing_scale), float(lambda_th), int(bool(accumulate)), _p(lam.reshape(-1)),
+            typ.ctypes.data_as(C.POINTER(C.c_ubyte)), nt.ctypes.data_as(C.POINTER(C.c_ulong)), _p(mt),
+            int(bool(of_deltaX)), self._err, len(self._err)))
+        return lam, typ, nt, mt
+
+    def tweb_probability(self, type):
+        """bchmc_shim::tweb_probability -> N values."""
+        out = np.empty(self.N)
+        self._chk(self.lib.bchmc_shim_tweb_probability(C.byref(self.hd), int(type), _p(out), self._err, len(self._err)))
+        return out
 
     def measure_spec2D(self, signal, N_bin=200, planepar=True, of_deltaX=False):
         """bchmc_shim::measure_spec2D at ``signal`` (None: the resident state, or deltaX) -> (kmode, power) shaped

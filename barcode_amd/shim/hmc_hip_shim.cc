@@ -291,6 +291,26 @@ void measure_spec2D(HamilView *hd, const real_prec *signal, real_prec *kmode, re
   if (rc) fail(h, rc, "measure_spec2D");
 }
 
+void tweb_classify(HamilView *hd, const real_prec *signal, real_prec smoothing_scale, real_prec lambda_th, bool accumulate,
+                   real_prec *lambda, unsigned char *type, ULONG *n_type, real_prec *mass_type, bool of_deltaX) {
+  bchmc_handle *h = engine_for(hd);
+  bchmc_tweb_opts o{};
+  o.smoothing_scale = smoothing_scale, o.lambda_th = lambda_th, o.accumulate = accumulate ? 1 : 0;
+  bchmc_tweb_stats st{};
+  const int rc = bchmc_tweb_classify(h, corr_source(signal, of_deltaX), signal, &o, lambda, type, &st);
+  for (int t = 0; t < 4; t++) {
+    if (n_type) n_type[t] = st.n_type[t];
+    if (mass_type) mass_type[t] = st.mass_type[t];
+  }
+  if (rc) fail(h, rc, "tweb_classify");
+}
+
+void tweb_probability(HamilView *hd, int type, real_prec *out) {
+  bchmc_handle *h = engine_for(hd);
+  const int rc = bchmc_tweb_fetch(h, type, 1, out);
+  if (rc) fail(h, rc, "tweb_probability");
+}
+
 namespace {
 // One getDensity_* call: the caller's grid must be the handle's, then bchmc_density_particles
 void density_on_handle(HamilView *hd, const char *name, int mk, ULONG N1, ULONG N2, ULONG N3, real_prec L1, real_prec L2,
@@ -952,6 +972,17 @@ int bchmc_shim_measure_spec2D(bchmc_shim::HamilView *hd, const double *signal, d
   return guarded(err, errlen, [&] {
     bchmc_shim::measure_spec2D(hd, signal, kmode, power, N_bin, planepar != 0, of_deltaX != 0);
   });
+}
+int bchmc_shim_tweb_classify(bchmc_shim::HamilView *hd, const double *signal, double smoothing_scale, double lambda_th,
+                             int accumulate, double *lambda, unsigned char *type, unsigned long *n_type, double *mass_type,
+                             int of_deltaX, char *err, size_t errlen) {
+  return guarded(err, errlen, [&] {
+    bchmc_shim::tweb_classify(hd, signal, smoothing_scale, lambda_th, accumulate != 0, lambda, type, n_type, mass_type,
+                              of_deltaX != 0);
+  });
+}
+int bchmc_shim_tweb_probability(bchmc_shim::HamilView *hd, int type, double *out, char *err, size_t errlen) {
+  return guarded(err, errlen, [&] { bchmc_shim::tweb_probability(hd, type, out); });
 }
 int bchmc_shim_getDensity(bchmc_shim::HamilView *hd, int mk, const double *xp, const double *yp, const double *zp,
                           const double *Par_mass, unsigned long N_OBJ, double *delta, int weightmass, double kernel_h,

@@ -373,6 +373,66 @@ int bchmc_ensemble_fetch(bchmc_handle *h, int32_t slot, bchmc_ens_what what, dou
 int bchmc_ensemble_merge(bchmc_handle *h, int32_t slot, uint64_t count_b, const double *mean_b, const double *m2_b);
 int bchmc_ensemble_reset(bchmc_handle *h, int32_t slot);   /* count = 0, arrays zeroed, buffers kept */
 int bchmc_ensemble_release(bchmc_handle *h);               /* all slots: buffers freed, counts 0 */
+/* ---- the cosmic web of a sample: the T-web (upstream: none; what the users of a density-posterior sampler of this family
+ * make of its samples -- Hahn et al. 2007 for the classification, Forero-Romero et al. 2009 for the threshold, Leclercq,
+ * Jasche & Wandelt 2015 for the posterior over an ensemble) ----------------------------------------------------------
+ * Let x be the source field and x^ its half-complex transform, obtained as bchmc_measure_spectrum_src obtains it (the
+ * chain state's q^ is used as it is).  Indices (i, j, k) belong to the axes (x, y, z); k_a = kval(index_a, n, kfac), the
+ * wave numbers of every k-space kernel of the engine.  Ten properties:
+ *  T1 Potential and tensor.  laplace(phi) = x and T_ab = d_a d_b phi:  T^_ab = (k_a k_b / k^2) W(k) x^, 0 at k = 0.
+ *  T2 Smoothing.  W = exp(-k^2 R^2 / 2), upstream's Gaussian kernel (convolution.cpp:286); R = smoothing_scale >= 0 in
+ *     Mpc/h, R = 0: none.
+ *  T3 Nyquist rule, even n only.  An off-diagonal component (a != b) is zero wherever the index of axis a or of axis b is
+ *     n / 2: there k_a k_b has opposite signs at a mode and at its conjugate partner, which is the same element.  The
+ *     diagonal components keep those modes (k_a^2 is even).  So all six arrays are transforms of real fields and no C2R
+ *     is handed a non-Hermitian plane (the concern of nyq_keep and of U1 above).  At odd n no mode is special.
+ *  T4 Trace.  T_xx + T_yy + T_zz = x_s - mean(x_s) in every cell, x_s the smoothed field; the three eigenvalues sum to
+ *     the same number.
+ *  T5 Eigenvalues.  Per cell lambda_1 >= lambda_2 >= lambda_3, computed in double on every handle by cyclic Jacobi
+ *     rotations (backward stable on degenerate tensors such as (lambda, 0, 0); a diagonal tensor returns its diagonal
+ *     exactly).  The tensor arrays are of the handle's storage type and widened on load.
+ *  T6 Type = the number of eigenvalues with lambda > lambda_th, strictly: 0 void, 1 sheet, 2 filament, 3 knot.  A cell
+ *     whose tensor is not finite gets type 255 and NaN eigenvalues, and counts in n_nonfinite only.
+ *  T7 Statistics.  n_type: cells per type, exact.  mass_type: the sum of 1 + x over the type's cells, x the UNSMOOTHED
+ *     source in real space (BCHMC_CORR_HOST: the staged doubles; BCHMC_CORR_CHAIN_STATE: the field
+ *     bchmc_chain_get_state would return; BCHMC_CORR_DELTAX: what bchmc_fetch(BCHMC_F_DELTAX) would return), summed in
+ *     double in a fixed order: per-workgroup partials, then one ordered reduction, no float atomics.  All outputs of a
+ *     call are bitwise repeatable on every handle.
+ *  T8 Posterior accumulator.  Four uint32 counters per cell, type-major (16 N bytes), taken zeroed by the first
+ *     accumulating call or merge.  accumulate = 1 adds 1 to the counter of each cell's type and 1 to the sample count, in
+ *     a pass of its own over the device-resident type map after the statistics have been read back; if
+ *     n_nonfinite > 0 that pass is not launched and the call returns BCHMC_ERR_ARG naming the count, with lambda, type
+ *     and stats written all the same.  The accumulator remembers the (smoothing_scale, lambda_th) of the first sample a
+ *     classify put in; an accumulating call with another pair is BCHMC_ERR_STATE until bchmc_tweb_reset (a merge brings
+ *     counters, not their parameters: keeping those equal across chains is the caller's).  bchmc_tweb_fetch returns the
+ *     counters of one type (N uint32) or, as_probability != 0, (double)count / (double)samples with IEEE divide (N
+ *     doubles).  bchmc_tweb_merge adds another chain's 4 N counters; integer addition is exact and associative, so any
+ *     merge order gives the same bits.  n_b + samples >= 2^32: BCHMC_ERR_ARG; n_b == 0: a no-op (counts_b may be NULL).
+ *  T9 Sources, their argument and state errors, and what a call leaves untouched -- the chain state, the momenta, the
+ *     carried gradient and -log L, the uploaded inputs, deltaX / pos* and a pending proposal -- are those of
+ *     bchmc_measure_corr2d.  Everything is checked before anything is queued.  Also BCHMC_ERR_ARG: opts NULL,
+ *     smoothing_scale negative or not finite, lambda_th not finite, accumulate other than 0 / 1, component outside
+ *     0..5, type outside 0..3.  BCHMC_ERR_STATE: bchmc_tweb_tensor before any classify, bchmc_tweb_fetch with
+ *     as_probability and samples == 0.  Any Nx bchmc_create accepts works, odd ones included.
+ *  T10 Buffers.  The feature owns the six real arrays of T (storage type; bchmc_tweb_tensor returns one of the last
+ *     classify as doubles), the N-byte type map, a few hundred words of partial sums, at most one half-complex array
+ *     (none for the chain state), 3 N doubles of eigenvalue staging once a caller has asked for lambda, and the
+ *     accumulator; otherwise it uses the handle's transfer staging and scratch.  Each is built on first use and kept;
+ *     bchmc_live_resources counts them, bchmc_tweb_release and bchmc_destroy free them (release also empties the
+ *     accumulator).  If one cannot be allocated the call returns the allocation's error, releases what it took and
+ *     leaves the handle usable.
+ * lambda: 3 N doubles, the lambda_1 block, then lambda_2, then lambda_3, or NULL.  type: N bytes or NULL.  stats or NULL.
+ * (Added within ABI version 4: no struct or existing entry point changed.) */
+typedef struct bchmc_tweb_opts  { double smoothing_scale, lambda_th; int32_t accumulate, reserved0; } bchmc_tweb_opts;
+typedef struct bchmc_tweb_stats { uint64_t n_type[4], n_nonfinite; double mass_type[4]; } bchmc_tweb_stats;
+int bchmc_tweb_classify(bchmc_handle *h, bchmc_corr_source src, const double *signal, const bchmc_tweb_opts *opts,
+                        double *lambda /* 3 N or NULL */, uint8_t *type /* N or NULL */, bchmc_tweb_stats *stats /* or NULL */);
+int bchmc_tweb_tensor(bchmc_handle *h, int32_t component /* 0..5 = xx, xy, xz, yy, yz, zz */, double *out /* N */);
+int bchmc_tweb_samples(bchmc_handle *h, uint64_t *n);
+int bchmc_tweb_fetch(bchmc_handle *h, int32_t type /* 0..3 */, int32_t as_probability, void *out /* N uint32, or N double */);
+int bchmc_tweb_merge(bchmc_handle *h, uint64_t n_b, const uint32_t *counts_b /* 4 N, type-major */);
+int bchmc_tweb_reset(bchmc_handle *h);     /* samples = 0, counters zeroed, buffers kept */
+int bchmc_tweb_release(bchmc_handle *h);   /* every buffer of the feature freed, samples = 0 */
 /* ---- a particle catalogue onto the grid (upstream: getDensity_NGP / _CIC / _TSC / _SPH, massFunctions.cc:49-495, as
  * tools/density.cc, tools/poisson_upres.cc and Lag2Eul.cc:117-126 call them) ---------------------------------------------
  * The raw density of a free list of n_part particles -- no overdens, no normalisation -- on the handle's grid, L and

@@ -150,6 +150,15 @@ void measure_corr2D_interp(HamilView *hd, const real_prec *signal, unsigned N_ou
 // no mode counts (bchmc_measure_spectrum2d does).  planepar == false throws like upstream.
 void measure_spec2D(HamilView *hd, const real_prec *signal, real_prec *kmode, real_prec *power, ULONG N_bin,
                     bool planepar = true, bool of_deltaX = false);
+// The T-web of a sample (bchmc_tweb_classify; upstream: none): eigenvalues of the tidal tensor of the field smoothed with
+// a Gaussian of smoothing_scale Mpc/h, and per cell how many exceed lambda_th (0 void, 1 sheet, 2 filament, 3 knot; 255
+// where the tensor is not finite).  Sources as above.  lambda: 3 N values (lambda_1 block, lambda_2, lambda_3) or NULL;
+// type: N bytes or NULL; n_type / mass_type: 4 values each or NULL.  accumulate: also one more sample of the posterior
+// that tweb_probability reads; a sample with non-finite cells throws then (nothing is added, the outputs are written).
+void tweb_classify(HamilView *hd, const real_prec *signal, real_prec smoothing_scale, real_prec lambda_th, bool accumulate,
+                   real_prec *lambda, unsigned char *type, ULONG *n_type, real_prec *mass_type, bool of_deltaX = false);
+// count / samples of one type (0..3) over the accumulated samples: N values; throws with no sample
+void tweb_probability(HamilView *hd, int type, real_prec *out);
 // massFunctions.cc:49-495 on the device (bchmc_density_particles): a free list of N_OBJ particles onto the grid, upstream's
 // argument lists behind the view.  The grid is the handle's: N1 .. min3 must be the view's own values (std::runtime_error
 // otherwise -- these functions do not assign onto another grid).  NGP and TSC always read Par_mass, like upstream; CIC and
@@ -341,6 +350,10 @@ int bchmc_shim_measure_corr2D_interp(bchmc_shim::HamilView *hd, const double *si
                                      int planepar, int of_deltaX, char *err, size_t errlen);
 int bchmc_shim_measure_spec2D(bchmc_shim::HamilView *hd, const double *signal, double *kmode, double *power,
                               unsigned long N_bin, int planepar, int of_deltaX, char *err, size_t errlen);
+int bchmc_shim_tweb_classify(bchmc_shim::HamilView *hd, const double *signal, double smoothing_scale, double lambda_th,
+                             int accumulate, double *lambda, unsigned char *type, unsigned long *n_type, double *mass_type,
+                             int of_deltaX, char *err, size_t errlen);
+int bchmc_shim_tweb_probability(bchmc_shim::HamilView *hd, int type, double *out, char *err, size_t errlen);
 /* getDensity_NGP / _CIC / _TSC / _SPH (mk 0 .. 3) with the view's own geometry */
 int bchmc_shim_getDensity(bchmc_shim::HamilView *hd, int mk, const double *xp, const double *yp, const double *zp,
                           const double *Par_mass, unsigned long N_OBJ, double *delta, int weightmass, double kernel_h,
