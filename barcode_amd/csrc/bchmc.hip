@@ -149,6 +149,19 @@ struct bchmc_handle {
     bool have_par = false;               // R and lambda_th below are set (a merge brings counters, not their parameters)
     double R = 0., lambda_th = 0.;       // of the first sample accumulated by a classify since the last reset
   } tw;
+  // bchmc_bispectrum (bispec.hpp): the n_shell real arrays (I_s while the table is built, D_s of the last call after
+  // it), the partial sums with the results behind them, and the triangle sums of the shells in `key` (sum I1 I2 I3 per
+  // triplet) are taken by the first call and replaced by a call with other shells; the half-complex array by the first
+  // call whose source needs a transform.  All kept until bchmc_bispec_release or bchmc_destroy.
+  struct Bispec {
+    DevBytes d[kBispecMaxShell];         // N elements of T each
+    DevBytes xk;                         // Nhp complex: x^ of a host or deltaX source (the shells go through tC)
+    DevBuf<double> part;                 // bispec_part_words(): partials of either kernel, then 3 n_shell + T results
+    DevBuf<double> tab;                  // T: sum over cells of I_s1 I_s2 I_s3
+    bool have_tab = false;               // tab holds the sums of the shells below
+    double k_min = 0., dk = 0.;
+    int n_shell = 0;
+  } bs;
   // measure_corr / measure_corr2d (corr.hpp): accumulators and the geometry of the last n_bin of each function, kept in
   // the handle like spec_bins (the driver measures after every sample with the same n_bin)
   struct Corr1 {
@@ -2595,6 +2608,60 @@ struct Pipe {
     return d2h(h, out, h->dstage, bytes);
   }
 
+  // ---- bchmc_bispectrum (bispec.hpp; bispec_take has run) ------------------------------------------------------------------
+  // x^ of the source as spectrum_source obtains it, but a fresh transform lands in the feature's own half-complex array:
+  // tC is the scratch of the shells.
+  static int bispec_source(bchmc_handle *h, int src, const void **xk) {
+    auto &w = h->bs;
+    *xk = w.xk;
+    if (src == BCHMC_CORR_HOST) return r2c_state(h, h->dstage, h->ioq, w.xk);
+    if (src == BCHMC_CORR_CHAIN_STATE) {
+      *xk = h->cq;
+      return BCHMC_OK;
+    }
+    CHK(upres_real(h, src));
+    return fft_exec(h, h->r2c1, h->ioq, w.xk, BCHMC_K_FFT_R2C);
+  }
+
+  // The n_shell shell fields into h->bs.d: per shell one filter pass into tC and one C2R.  xk null: I_s.
+  static int bispec_shells(bchmc_handle *h, const void *xk, double k_min, double dk, int n_shell) {
+    auto &w = h->bs;
+    for (int s = 0; s < n_shell; s++) {
+      {
+        ProfScope ps(h, BCHMC_K_OTHER);
+        if (xk)
+          k_bispec_filter<T, false><<<nblk_stride(h->g.Nhp), 256, 0, h->stream>>>(h->g, C(xk), C(h->tC), k_min, dk, n_shell, s);
+        else
+          k_bispec_filter<T, true><<<nblk_stride(h->g.Nhp), 256, 0, h->stream>>>(h->g, nullptr, C(h->tC), k_min, dk, n_shell, s);
+        HIPCHK(hipGetLastError());
+      }
+      CHK(fft_exec(h, h->c2r1, h->tC, w.d[s], BCHMC_K_FFT_C2R));
+    }
+    return BCHMC_OK;
+  }
+
+  // the contraction of the arrays in h->bs.d -> res (T doubles on the device)
+  static int bispec_triple(bchmc_handle *h, int n_shell, const BispecPlan &plan, double *res) {
+    auto &w = h->bs;
+    BispecArrays arr{};
+    for (int s = 0; s < n_shell; s++) arr.a[s] = w.d[s];
+    ProfScope ps(h, BCHMC_K_OTHER);
+    HIPCHK(launch_bispec_triple<T>(h->stream, h->g.N, n_shell, arr, plan, w.part, res));
+    return BCHMC_OK;
+  }
+
+  // the per-shell sums of x^ -> res (3 n_shell doubles on the device: sum hw, sum hw |k|, sum hw |x^|^2)
+  static int bispec_stats(bchmc_handle *h, const void *xk, double k_min, double dk, int n_shell, double *res) {
+    auto &w = h->bs;
+    const int grid = (int)std::min<long long>((h->g.Nhp + kBispecStatBlock - 1) / kBispecStatBlock, kBispecStatGrid);
+    ProfScope ps(h, BCHMC_K_OTHER);
+    k_bispec_stats<T><<<grid, kBispecStatBlock, (size_t)3 * n_shell * kWave * sizeof(double), h->stream>>>(
+        h->g, C(xk), k_min, dk, n_shell, w.part);
+    k_bispec_reduce<<<(3 * n_shell + kWave - 1) / kWave, 256, 0, h->stream>>>(grid, 3 * n_shell, w.part, res);
+    HIPCHK(hipGetLastError());
+    return BCHMC_OK;
+  }
+
   // ---- measure_spec2D (spec2d.hpp; spec2d_setup has run for n_bin) ----------------------------------------------------
   template <bool GEOM>
   static int launch_spec2d(bchmc_handle *h, const CT *xk) {
@@ -4572,6 +4639,142 @@ int bchmc_tweb_release(bchmc_handle *h) {
   ENTER(h);
   HIPCHK(hipStreamSynchronize(h->stream));
   tweb_drop(h);
+  return BCHMC_OK;
+}
+
+// ---- bchmc_bispectrum (bispec.hpp) ---------------------------------------------------------------------------------------
+// doubles of the partial buffer: the rows of the contraction or of the shell statistics, whichever are more, then the
+// results (3 n_shell sums of the statistics, T sums of the contraction)
+static size_t bispec_part_words(const bchmc_handle *h, int n_shell) {
+  const size_t T = (size_t)bispec_triplets(n_shell);
+  return std::max((size_t)bispec_grid(h->g.N) * T, (size_t)kBispecStatGrid * 3 * n_shell) + 3 * (size_t)n_shell + T;
+}
+
+static void bispec_drop(bchmc_handle *h) {
+  auto &w = h->bs;
+  for (auto &b : w.d) (void)b.release();
+  (void)w.xk.release();
+  (void)w.part.release();
+  (void)w.tab.release();
+  w.have_tab = false;
+  w.n_shell = 0;
+}
+
+// The buffers a call with n_shell shells needs, each on its first use (the tweb_take pattern): if one cannot be had
+// the call gives back those it took itself.  A handle that held another n_shell has dropped its table before.
+static int bispec_take(bchmc_handle *h, int n_shell, bool xk) {
+  auto &w = h->bs;
+  const size_t N = (size_t)h->g.N;
+  bool took_d[kBispecMaxShell] = {}, took_part = false, took_tab = false, took_xk = false;
+  int rc = BCHMC_OK;
+  for (int s = 0; s < n_shell && !rc; s++)
+    if (!w.d[s]) rc = dev_alloc(h, w.d[s], N * h->esz), took_d[s] = !rc;
+  if (!rc && !w.part) rc = dev_alloc(h, w.part, bispec_part_words(h, n_shell)), took_part = !rc;
+  if (!rc && !w.tab) rc = dev_alloc(h, w.tab, (size_t)bispec_triplets(n_shell)), took_tab = !rc;
+  if (!rc && xk && !w.xk) rc = dev_alloc(h, w.xk, 2 * (size_t)h->g.Nhp * h->esz), took_xk = !rc;
+  if (rc) {
+    (void)hipStreamSynchronize(h->stream);  // the zero fills of what goes back
+    for (int s = 0; s < n_shell; s++)
+      if (took_d[s]) (void)w.d[s].release();
+    if (took_part) (void)w.part.release();
+    if (took_tab) (void)w.tab.release(), w.have_tab = false;
+    if (took_xk) (void)w.xk.release();
+  }
+  return rc;
+}
+
+int bchmc_bispectrum(bchmc_handle *h, bchmc_corr_source src, const double *signal, const bchmc_bispec_opts *opts, double *b,
+                     double *ntri, double *q, double *kmean, uint64_t *nmode, double *power) {
+#pragma clang fp contract(off)
+  if (!h) return BCHMC_ERR_ARG;
+  const char *name = "bispectrum";
+  if (!opts) return h->fail(BCHMC_ERR_ARG, "%s: opts is NULL", name);
+  const double k_min = opts->k_min, dk = opts->dk;
+  const int n = opts->n_shell;
+  if (!(k_min >= 0.) || !(k_min <= DBL_MAX)) return h->fail(BCHMC_ERR_ARG, "%s: k_min = %g is negative or not finite", name, k_min);
+  if (!(dk > 0.) || !(dk <= DBL_MAX)) return h->fail(BCHMC_ERR_ARG, "%s: dk = %g is not > 0 or not finite", name, dk);
+  if (n < 1 || n > kBispecMaxShell) return h->fail(BCHMC_ERR_ARG, "%s: n_shell = %d outside 1..%d", name, n, kBispecMaxShell);
+  if (!b) return h->fail(BCHMC_ERR_ARG, "%s: b is NULL", name);
+  CHK(source_args(h, name, src, signal));
+  ENTER(h);
+  CHK(source_state(h, src));
+  auto &w = h->bs;
+  const Geo &g = h->g;
+  const size_t N = (size_t)g.N;
+  const int T = bispec_triplets(n);
+  // B4: with every shell below 2/3 k_Nyquist a triplet with lo(s3) >= hi(s1) + hi(s2) has no triangle and is not computed
+  const double k_nyq = g.kfac * (0.5 * (double)g.n);
+  const bool rule = k_min + (double)n * dk <= (2. / 3.) * k_nyq;
+  static_assert(kBispecMaxShell <= 255, "shell indices travel as bytes");
+  unsigned char s3_end[kBispecMaxShell][kBispecMaxShell] = {};
+  for (int s1 = 0; s1 < n; s1++)
+    for (int s2 = s1; s2 < n; s2++) {
+      int end = n;
+      if (rule) {
+        const double reach = (k_min + (double)(s1 + 1) * dk) + (k_min + (double)(s2 + 1) * dk);
+        for (end = s2; end < n && !(k_min + (double)end * dk >= reach); end++) {}
+      }
+      s3_end[s1][s2] = (unsigned char)end;
+    }
+  const BispecPlan plan = bispec_plan(n, s3_end);
+  if (w.n_shell != n) {  // other arrays and another partial buffer: what does not fit the new shells goes first
+    HIPCHK(hipStreamSynchronize(h->stream));
+    for (int s = n; s < kBispecMaxShell; s++) (void)w.d[s].release();
+    (void)w.part.release();
+    (void)w.tab.release();
+    w.have_tab = false;
+    w.n_shell = 0;
+  }
+  CHK(bispec_take(h, n, src != BCHMC_CORR_CHAIN_STATE));
+  w.n_shell = n;
+  if (!w.have_tab || w.k_min != k_min || w.dk != dk) {
+    w.have_tab = false;
+    CHK(DISPATCH(h, bispec_shells(h, nullptr, k_min, dk, n)));
+    CHK(DISPATCH(h, bispec_triple(h, n, plan, w.tab)));
+    w.k_min = k_min, w.dk = dk, w.have_tab = true;
+  }
+  if (signal) CHK(h2d(h, h->dstage, signal, N * sizeof(double)));
+  const void *xk = nullptr;
+  CHK(DISPATCH(h, bispec_source(h, (int)src, &xk)));
+  double *res = w.part + (bispec_part_words(h, n) - 3 * (size_t)n - (size_t)T);
+  CHK(DISPATCH(h, bispec_stats(h, xk, k_min, dk, n, res)));
+  CHK(DISPATCH(h, bispec_shells(h, xk, k_min, dk, n)));
+  CHK(DISPATCH(h, bispec_triple(h, n, plan, res + 3 * n)));
+  std::vector<double> hr(3 * (size_t)n + T), ht(T);
+  CHK(d2h(h, hr.data(), res, hr.size() * sizeof(double)));
+  CHK(d2h(h, ht.data(), w.tab, ht.size() * sizeof(double)));
+  const double Nd = (double)N, L3 = g.L * g.L * g.L, NORM = L3 / Nd / Nd, BNORM = L3 * L3 / (Nd * Nd * Nd);
+  std::vector<double> P(n);
+  for (int s = 0; s < n; s++) {
+    const double cnt = hr[s];
+    P[s] = cnt > 0. ? hr[2 * n + s] / cnt * NORM : 0.;
+    if (nmode) nmode[s] = (uint64_t)cnt;
+    if (kmean) kmean[s] = cnt > 0. ? hr[n + s] / cnt : 0.;
+    if (power) power[s] = P[s];
+  }
+  int t = 0;
+  for (int s1 = 0; s1 < n; s1++)
+    for (int s2 = s1; s2 < n; s2++)
+      for (int s3 = s2; s3 < n; s3++, t++) {
+        const bool computed = s3 < s3_end[s1][s2];
+        const double nt = computed ? ht[t] / Nd : 0.;
+        const bool filled = computed && !(nt < 0.5);
+        const double bt = filled ? BNORM * (hr[3 * n + t] / (Nd * nt)) : 0.;
+        b[t] = bt;
+        if (ntri) ntri[t] = nt;
+        if (q) {
+          const double den = P[s1] * P[s2] + P[s2] * P[s3] + P[s3] * P[s1];
+          q[t] = (!filled || den == 0.) ? 0. : bt / den;
+        }
+      }
+  return BCHMC_OK;
+}
+
+int bchmc_bispec_release(bchmc_handle *h) {
+  if (!h) return BCHMC_ERR_ARG;
+  ENTER(h);
+  HIPCHK(hipStreamSynchronize(h->stream));
+  bispec_drop(h);
   return BCHMC_OK;
 }
 

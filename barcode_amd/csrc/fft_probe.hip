@@ -599,6 +599,35 @@ int tweb_eigen(long long count, const void *t6, const double *x, double lambda_t
   return 0;
 }
 
+// k_bispec_triple and k_bispec_reduce on n_shell arrays of `count` cells as bchmc_bispectrum launches them: arrays = n_shell
+// arrays of T one after the other, s3_end (kBispecMaxShell x kBispecMaxShell bytes: one past the last s3 the row
+// (s1, s2) computes; null: every triplet is computed), sums (T doubles; a triplet beyond its row's end may hold anything),
+// ms (may be null): the event time of the two kernels.  Device arrays: the arrays, the partials with the sums behind them.
+template <typename T>
+int bispec_triple(int n_shell, long long count, const void *arrays, const unsigned char *s3_end, double *sums, float *ms) {
+  if (n_shell < 1 || n_shell > kBispecMaxShell || count < 1 || count > (1ll << 27) || !arrays || !sums) return -1;
+  Probe pr;
+  const T *da = static_cast<const T *>(pr.alloc((size_t)n_shell * count * sizeof(T), arrays));
+  const int grid = bispec_grid(count), W = bispec_triplets(n_shell);
+  double *dp = static_cast<double *>(pr.alloc(((size_t)grid + 1) * W * sizeof(double), nullptr));
+  if (pr.err) return pr.err;
+  const BispecPlan plan = bispec_plan(n_shell, reinterpret_cast<const unsigned char(*)[kBispecMaxShell]>(s3_end));
+  BispecArrays arr{};
+  for (int s = 0; s < n_shell; s++) arr.a[s] = da + (size_t)s * count;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  if (ms && (!pr.ok(hipEventCreate(&e0)) || !pr.ok(hipEventCreate(&e1)))) return pr.err;
+  if (ms) pr.ok(hipEventRecord(e0, nullptr));
+  pr.ok(launch_bispec_triple<T>(nullptr, count, n_shell, arr, plan, dp, dp + (size_t)grid * W));
+  if (ms) pr.ok(hipEventRecord(e1, nullptr));
+  int rc = pr.finish({});
+  if (!rc && ms && !pr.ok(hipEventElapsedTime(ms, e0, e1))) rc = pr.err;
+  if (e0) (void)hipEventDestroy(e0);
+  if (e1) (void)hipEventDestroy(e1);
+  if (rc) return rc;
+  if (!pr.ok(hipMemcpy(sums, dp + (size_t)grid * W, (size_t)W * sizeof(double), hipMemcpyDeviceToHost))) return pr.err;
+  return 0;
+}
+
 }  // namespace
 
 // prec: 0 = double, 1 = float (the engine's storage type T); arrays are of that type, complex ones interleaved
@@ -761,6 +790,13 @@ int fftp_tweb_eigen(int prec, long long count, const void *t6, const double *x, 
                     unsigned char *type, unsigned long long *res) {
   return prec ? tweb_eigen<float>(count, t6, x, lambda_th, lam, type, res)
               : tweb_eigen<double>(count, t6, x, lambda_th, lam, type, res);
+}
+
+// ---- the bispectrum's contraction kernel on chosen arrays (tests/test_gpu_bispec.py, scripts/bispec_bench.py)
+int fftp_bispec_triple(int prec, int n_shell, long long count, const void *arrays, const unsigned char *s3_end, double *sums,
+                       float *ms) {
+  return prec ? bispec_triple<float>(n_shell, count, arrays, s3_end, sums, ms)
+              : bispec_triple<double>(n_shell, count, arrays, s3_end, sums, ms);
 }
 
 }  // extern "C"

@@ -90,6 +90,11 @@ class TwebStats(C.Structure):
     _fields_ = [("n_type", C.c_uint64 * 4), ("n_nonfinite", C.c_uint64), ("mass_type", C.c_double * 4)]
 
 
+class BispecOpts(C.Structure):
+    """bchmc_bispec_opts."""
+    _fields_ = [("k_min", C.c_double), ("dk", C.c_double), ("n_shell", C.c_int32), ("reserved0", C.c_int32)]
+
+
 class InterpField(C.Structure):
     """bchmc_interp_field: one source of bchmc_interp_particles."""
     _fields_ = [("source", C.c_int32), ("field", C.c_int32), ("host", C.POINTER(C.c_double))]
@@ -157,7 +162,8 @@ EXPORTS = ("bchmc_create", "bchmc_destroy", "bchmc_strerror", "bchmc_last_error"
            "bchmc_poisson_draw", "bchmc_poisson_positions", "bchmc_poisson_density", "bchmc_poisson_release",
            "bchmc_setup_random_test_poisson",
            "bchmc_tweb_classify", "bchmc_tweb_tensor", "bchmc_tweb_samples", "bchmc_tweb_fetch", "bchmc_tweb_merge",
-           "bchmc_tweb_reset", "bchmc_tweb_release")
+           "bchmc_tweb_reset", "bchmc_tweb_release",
+           "bchmc_bispectrum", "bchmc_bispec_release")
 # declared as well, listed apart: the header scan of the ABI test matches names of letters and underscores only
 EXPORTS_MT19937 = ("bchmc_chain_draw_momenta_mt19937", "bchmc_mt19937_jump")
 EXPORTS_CORR2D = ("bchmc_measure_corr2d", "bchmc_measure_corr2d_interp")  # a digit in the name, like the two above
@@ -169,6 +175,7 @@ ENS_SLOTS = 4                                         # BCHMC_ENS_SLOTS
 ENS_WHAT = dict(mean=0, variance=1, std=2, m2=3)      # bchmc_ens_what
 TWEB_TYPES = dict(void=0, sheet=1, filament=2, knot=3)  # the number of eigenvalues above lambda_th
 TWEB_COMPONENTS = dict(xx=0, xy=1, xz=2, yy=3, yz=4, zz=5)
+BISPEC_MAX_SHELL = 32                                 # kBispecMaxShell
 TWEB_NONFINITE = 255                                  # the type of a cell whose tensor is not finite
 
 
@@ -241,6 +248,8 @@ def load():
     lib.bchmc_tweb_merge.argtypes = [vp, u64, C.POINTER(C.c_uint32)]
     lib.bchmc_tweb_reset.argtypes = [vp]
     lib.bchmc_tweb_release.argtypes = [vp]
+    lib.bchmc_bispectrum.argtypes = [vp, C.c_int, dp, C.POINTER(BispecOpts), dp, dp, dp, dp, C.POINTER(u64), dp]
+    lib.bchmc_bispec_release.argtypes = [vp]
     lib.bchmc_chain_forward.argtypes = [vp, C.c_int]
     lib.bchmc_density_particles.argtypes = [vp, C.c_int, dp, dp, dp, dp, u64, C.POINTER(DensityOpts), dp,
                                             C.POINTER(DensityStats)]
@@ -293,6 +302,12 @@ def philox_kat(ctr, key):
     if rc:
         raise BchmcError(rc, lib.bchmc_strerror(rc).decode())
     return [int(x) for x in o]
+
+
+def bispec_triplets(n_shell):
+    """All (s1, s2, s3) with s1 <= s2 <= s3 < n_shell in lexicographic order, the order of bchmc_bispectrum: (T, 3) int32."""
+    n = int(n_shell)
+    return np.array([(a, b, c) for a in range(n) for b in range(a, n) for c in range(b, n)], dtype=np.int32).reshape(-1, 3)
 
 
 def live_resources():
@@ -768,6 +783,37 @@ class Engine:
         """Frees every buffer of the feature, the counters included; a later ``tweb_classify`` takes them again."""
         self._chk(self.lib.bchmc_tweb_release(self.h))
         self._tweb_par = None
+
+    # ---- the bispectrum of a sample (bchmc_bispectrum) ---------------------------------------------------
+    def bispectrum(self, signal=None, source=None, k_min=0.0, dk=None, n_shell=8, units="h/Mpc"):
+        """The bispectrum of a host field, of the resident chain state (the default without a signal) or of the
+        handle's deltaX, sources as in ``measure_corr``, by the FFT estimator: ``n_shell`` (1..32) shells of |k| from
+        ``k_min`` in steps of ``dk``, in h/Mpc or with ``units="kf"`` in units of the fundamental 2 pi / L (``dk``
+        None: one fundamental), all triplets s1 <= s2 <= s3.  Returns a dict: ``triplets`` (T, 3) int32, ``b`` (T,),
+        ``ntri`` (T,) the number of closed mode triples, ``q`` (T,) the reduced bispectrum, and per shell ``kmean``,
+        ``nmode`` (uint64) and ``power``."""
+        if source is None:
+            source = "chain" if signal is None else "host"
+        if units not in ("h/Mpc", "kf"):
+            raise ValueError("units must be 'h/Mpc' or 'kf', got %r" % (units,))
+        kf = 2.0 * np.pi / float(self.params.L)
+        scale = kf if units == "kf" else 1.0
+        dk = kf if dk is None else float(dk) * scale
+        n = int(n_shell)
+        sig = None if signal is None else _p(self._in(signal))
+        opts = BispecOpts(float(k_min) * scale, dk, n, 0)
+        ns = min(max(n, 0), BISPEC_MAX_SHELL)  # a refused n_shell reaches the library with arrays that are never written
+        trip = bispec_triplets(ns)
+        T = len(trip)
+        b, ntri, q = np.zeros(T), np.zeros(T), np.zeros(T)
+        kmean, nmode, power = np.zeros(ns), np.zeros(ns, dtype=np.uint64), np.zeros(ns)
+        self._chk(self.lib.bchmc_bispectrum(self.h, CORR_SOURCES[source], sig, C.byref(opts), _p(b), _p(ntri), _p(q),
+                                            _p(kmean), nmode.ctypes.data_as(C.POINTER(C.c_uint64)), _p(power)))
+        return dict(triplets=trip, b=b, ntri=ntri, q=q, kmean=kmean, nmode=nmode, power=power)
+
+    def bispec_release(self):
+        """Frees every buffer of the bispectrum; a later ``bispectrum`` takes them again and rebuilds its table."""
+        self._chk(self.lib.bchmc_bispec_release(self.h))
 
     def _measure_corr(self, fn, cells, signal, n_bin, source):
         if source is None:

@@ -194,6 +194,14 @@ def tweb_probability(hd, type):
     return hd.engine.tweb_fetch(type, as_probability=True)
 
 
+def measure_bispectrum(hd, signal=None, source=None, k_min=0., dk=None, n_shell=8, units="h/Mpc"):
+    """The bispectrum of a sample by the FFT estimator (Scoccimarro 2015): ``n_shell`` shells of |k| from ``k_min`` in
+    steps of ``dk`` (h/Mpc, or fundamentals with ``units="kf"``), all triplets s1 <= s2 <= s3.  ``signal`` None = the
+    resident chain state, or with ``source="deltaX"`` the density of the last forward model.  Returns
+    ``Engine.bispectrum``'s dict (triplets, b, ntri, q, kmean, nmode, power)."""
+    return hd.engine.bispectrum(signal, source, k_min, dk, n_shell, units)
+
+
 def getDensity(hd, mk, xp, yp, zp, Par_mass=None, weightmass=False, kernel_h=0.0, to_nobs=False):
     """getDensity_NGP / _CIC / _TSC / _SPH (massFunctions.cc:49-495; ``mk`` 0 .. 3 picks the one, None the handle's) of a
     free particle list on ``hd``'s grid, upstream's argument order from ``xp`` on -> (delta, stats).  ``weightmass``

@@ -202,6 +202,26 @@ def dump_tweb(engine, directory, name):
     return tuple(add_extension_if_missing(n) for n in names[:4]) + (names[4],)
 
 
+def dump_bispec(result, directory, name):
+    """``Engine.bispectrum``'s dict as the text table ``<name>_bispec.txt`` under ``directory``: a header line, then one
+    row per triplet -- s1 s2 s3, the three shells' mean |k|, ntri, B and Q, the reals with 17 digits so that
+    ``read_bispec`` returns them bit for bit.  Returns the path."""
+    path = (os.path.join(directory, name) if directory else name) + "_bispec.txt"
+    km = result["kmean"]
+    with open(path, "w") as f:
+        f.write("# s1 s2 s3 kmean1 kmean2 kmean3 ntri B Q\n")
+        for (s1, s2, s3), nt, b, q in zip(result["triplets"], result["ntri"], result["b"], result["q"]):
+            f.write("%d %d %d %.17g %.17g %.17g %.17g %.17g %.17g\n" % (s1, s2, s3, km[s1], km[s2], km[s3], nt, b, q))
+    return path
+
+
+def read_bispec(path):
+    """The table ``dump_bispec`` wrote -> dict of ``triplets`` (T, 3) int32, ``kmean`` (T, 3), ``ntri``, ``b``, ``q``."""
+    rows = np.loadtxt(path, ndmin=2)
+    return dict(triplets=rows[:, :3].astype(np.int32), kmean=rows[:, 3:6].copy(), ntri=rows[:, 6].copy(),
+                b=rows[:, 7].copy(), q=rows[:, 8].copy())
+
+
 def dump_deltas(engine, directory, suffix=""):
     """``dump_deltas`` (IOfunctionsGen.cc:136-171) of the resident chain state: deltaLAG, then deltaEUL without
     ``rsd_model``, or deltaRSS (the configured forward model) and deltaEUL (a second Lag2Eul without RSD) with it.

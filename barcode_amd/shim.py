@@ -30,7 +30,7 @@ SHIM_EXPORTS = ("bchmc_shim_Hamiltonian_EoM", "bchmc_shim_delta_Hamiltonian", "b
                 "bchmc_shim_interp_field", "bchmc_shim_measure_corr2D_interp", "bchmc_shim_measure_spec2D",
                 "bchmc_shim_getDensity", "bchmc_shim_interpolate", "bchmc_shim_setup_random_test_poisson",
                 "bchmc_shim_discrete_poisson_sample", "bchmc_shim_poisson_positions", "bchmc_shim_poisson_upres",
-                "bchmc_shim_tweb_classify", "bchmc_shim_tweb_probability")
+                "bchmc_shim_tweb_classify", "bchmc_shim_tweb_probability", "bchmc_shim_measure_bispectrum")
 
 _dp = C.POINTER(C.c_double)
 
@@ -132,6 +132,8 @@ def load():
     lib.bchmc_shim_tweb_classify.argtypes = [hv, _dp, C.c_double, C.c_double, C.c_int, _dp, C.POINTER(C.c_ubyte),
                                              C.POINTER(ul), _dp, C.c_int, C.c_char_p, sz]
     lib.bchmc_shim_tweb_probability.argtypes = [hv, C.c_int, _dp, C.c_char_p, sz]
+    lib.bchmc_shim_measure_bispectrum.argtypes = [hv, _dp, C.c_double, C.c_double, C.c_int, _dp, _dp, _dp, _dp, C.POINTER(ul),
+                                                  _dp, C.c_int, C.c_char_p, sz]
     lib.bchmc_shim_getDensity.argtypes = [hv, C.c_int, _dp, _dp, _dp, _dp, ul, _dp, C.c_int, C.c_double, C.c_char_p, sz]
     lib.bchmc_shim_interpolate.argtypes = [hv, C.c_int, _dp, _dp, _dp, ul, _dp, C.c_int, _dp, C.c_char_p, sz]
     lib.bchmc_shim_chain_forward.argtypes = [hv, C.c_int, C.c_char_p, sz]
@@ -362,6 +364,19 @@ class ShimHamil:
         out = np.empty(self.N)
         self._chk(self.lib.bchmc_shim_tweb_probability(C.byref(self.hd), int(type), _p(out), self._err, len(self._err)))
         return out
+
+    def measure_bispectrum(self, signal, k_min, dk, n_shell, of_deltaX=False):
+        """bchmc_shim::measure_bispectrum at ``signal`` (None: the resident state, or deltaX) -> (b, ntri, q) of T values
+        and (kmean, nmode, power) of n_shell values."""
+        n = min(max(int(n_shell), 0), 32)  # out of range: refused before anything is written
+        T = n * (n + 1) * (n + 2) // 6
+        b, ntri, q = np.zeros(T), np.zeros(T), np.zeros(T)
+        km, nm, pw = np.zeros(n), np.zeros(n, dtype=np.uint64), np.zeros(n)
+        sig = None if signal is None else _p(self._in(signal))
+        self._chk(self.lib.bchmc_shim_measure_bispectrum(
+            C.byref(self.hd), sig, float(k_min), float(dk), int(n_shell), _p(b), _p(ntri), _p(q), _p(km),
+            nm.ctypes.data_as(C.POINTER(C.c_ulong)), _p(pw), int(bool(of_deltaX)), self._err, len(self._err)))
+        return b, ntri, q, km, nm, pw
 
     def measure_spec2D(self, signal, N_bin=200, planepar=True, of_deltaX=False):
         """bchmc_shim::measure_spec2D at ``signal`` (None: the resident state, or deltaX) -> (kmode, power) shaped

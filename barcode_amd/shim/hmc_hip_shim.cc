@@ -305,6 +305,18 @@ void tweb_classify(HamilView *hd, const real_prec *signal, real_prec smoothing_s
   if (rc) fail(h, rc, "tweb_classify");
 }
 
+void measure_bispectrum(HamilView *hd, const real_prec *signal, real_prec k_min, real_prec dk, int n_shell, real_prec *b,
+                        real_prec *ntri, real_prec *q, real_prec *kmean, ULONG *nmode, real_prec *power, bool of_deltaX) {
+  bchmc_handle *h = engine_for(hd);
+  bchmc_bispec_opts o{};
+  o.k_min = k_min, o.dk = dk, o.n_shell = n_shell;
+  std::vector<uint64_t> nm(nmode && n_shell > 0 && n_shell <= 32 ? n_shell : 0);
+  const int rc = bchmc_bispectrum(h, corr_source(signal, of_deltaX), signal, &o, b, ntri, q, kmean, nm.empty() ? nullptr : nm.data(),
+                                  power);
+  if (rc) fail(h, rc, "measure_bispectrum");
+  for (size_t s = 0; s < nm.size(); s++) nmode[s] = (ULONG)nm[s];
+}
+
 void tweb_probability(HamilView *hd, int type, real_prec *out) {
   bchmc_handle *h = engine_for(hd);
   const int rc = bchmc_tweb_fetch(h, type, 1, out);
@@ -979,6 +991,13 @@ int bchmc_shim_tweb_classify(bchmc_shim::HamilView *hd, const double *signal, do
   return guarded(err, errlen, [&] {
     bchmc_shim::tweb_classify(hd, signal, smoothing_scale, lambda_th, accumulate != 0, lambda, type, n_type, mass_type,
                               of_deltaX != 0);
+  });
+}
+int bchmc_shim_measure_bispectrum(bchmc_shim::HamilView *hd, const double *signal, double k_min, double dk, int n_shell,
+                                  double *b, double *ntri, double *q, double *kmean, unsigned long *nmode, double *power,
+                                  int of_deltaX, char *err, size_t errlen) {
+  return guarded(err, errlen, [&] {
+    bchmc_shim::measure_bispectrum(hd, signal, k_min, dk, n_shell, b, ntri, q, kmean, nmode, power, of_deltaX != 0);
   });
 }
 int bchmc_shim_tweb_probability(bchmc_shim::HamilView *hd, int type, double *out, char *err, size_t errlen) {

@@ -433,6 +433,61 @@ int bchmc_tweb_fetch(bchmc_handle *h, int32_t type /* 0..3 */, int32_t as_probab
 int bchmc_tweb_merge(bchmc_handle *h, uint64_t n_b, const uint32_t *counts_b /* 4 N, type-major */);
 int bchmc_tweb_reset(bchmc_handle *h);     /* samples = 0, counters zeroed, buffers kept */
 int bchmc_tweb_release(bchmc_handle *h);   /* every buffer of the feature freed, samples = 0 */
+/* ---- the bispectrum of a sample (upstream: none; the FFT estimator of Scoccimarro 2015 and Sefusatti et al. 2016: the
+ * third test of a reconstruction after P(k) and r(k) -- deltaLAG under the Gaussian prior should have none, deltaX should
+ * carry the tree-level bispectrum of the data) -------------------------------------------------------------------------
+ * Let x be the source field and x^ its half-complex transform, obtained as bchmc_measure_spectrum_src obtains it (the
+ * chain state's q^ is used as it is).  Wave numbers are kval(index, n, kfac); |k| = sqrt(kx kx + ky ky + kz kz) with IEEE
+ * sqrt and divide and no FMA contraction, as bchmc_measure_spectrum forms it.  N = n^3, L the box side.  Ten properties:
+ *  B1 Shells.  k_min >= 0 and dk > 0 in h/Mpc, n_shell in 1..32.  A mode with |k| >= k_min belongs to shell
+ *     s = (ULONG)((|k| - k_min) / dk) if s < n_shell, else to none; the mode k = 0 belongs to none whatever k_min is.  The
+ *     shell depends on |k| only, so every filtered array is the transform of a real field, Nyquist planes of an even n
+ *     included, and no C2R is handed a non-Hermitian plane.  lo(s) = k_min + s dk, hi(s) = k_min + (s + 1) dk.
+ *  B2 Shell fields.  D_s = C2R[x^ 1_s] and I_s = C2R[1_s], unnormalised inverse transforms, arrays of the storage type.
+ *  B3 Triplets.  All (s1, s2, s3) with s1 <= s2 <= s3 in lexicographic order, T = n_shell (n_shell + 1) (n_shell + 2) / 6
+ *     <= 5984.  S_t = sum over cells of D_s1 D_s2 D_s3; ntri_t = sum over cells of I_s1 I_s2 I_s3 / N, the number of
+ *     ordered mode triples (k1, k2, k3) of the three shells that close; B_t = (L^3)^2 / N^3 * S_t / (N ntri_t).  (sum over
+ *     cells of D1 D2 D3 = N times the sum of x^1 x^2 x^3 over closed triangles, and B is V^2 / N^3 times its mean:
+ *     consistent with the L^3 / N^2 of bchmc_measure_spectrum.)  Triangles close modulo the grid, k1 + k2 + k3 = 0 mod n
+ *     per axis, as in every FFT estimator: a caller who wants true triangles only keeps k_min + n_shell dk <= 2/3 k_Nyquist,
+ *     k_Nyquist = pi n / L.  The call does not refuse other shells.
+ *  B4 Empty triplets.  If k_min + n_shell dk <= 2/3 k_Nyquist, a triplet with lo(s3) >= hi(s1) + hi(s2) (evaluated in
+ *     double as written) cannot hold a triangle and is not computed: ntri = 0, B = 0.  Every other triplet is computed; if
+ *     its ntri < 0.5 then B = 0 and Q = 0.  ntri is returned as a double.  On an fp64 handle rint(ntri) is the exact count
+ *     wherever (N + 18 log2(n)) 2^-53 M^2 < 1/2, M the largest nmode of the three shells: |I_s| <= M and
+ *     ||I_s||_2 = sqrt(N M_s), each I_s carries the error of one C2R and the sum that of N terms (tests/bispec_bound.py);
+ *     that covers every shell of grids up to 32^3 and shells of up to 7 10^4 modes at 96^3.
+ *  B5 Per shell.  nmode: the exact count of full-grid modes (a stored mode counts for itself and its conjugate partner);
+ *     kmean: their mean |k|; power: L^3 / N^2 * sum hw |x^|^2 / nmode.  One k-space pass, per-workgroup partials and one
+ *     ordered reduction, no float atomics.  Empty shells give 0.
+ *  B6 Reduced bispectrum.  Q_t = B_t / (P1 P2 + P2 P3 + P3 P1) from the returned B and power; 0 where the denominator is 0
+ *     or the triplet is empty (not computed, or ntri < 0.5), NaN where it is NaN.
+ *  B7 Determinism.  Everything is summed in double on every handle and in a fixed order: a lane's cells in order, one
+ *     lane per triplet and workgroup, then one ordered reduction over the workgroups.  All outputs are bitwise
+ *     repeatable.  On an fp32 handle the transforms, D_s and I_s are float; products and sums are double.
+ *  B8 Non-finite fields.  A field that is not finite gives NaN in B of every computed triplet with ntri >= 0.5 and in
+ *     power of every populated shell; nmode, kmean and ntri do not depend on the field.  A zero field gives 0.  (Narrower
+ *     than "every computed triplet": a computed triplet with ntri < 0.5 holds no triangle and B4 sets its B to 0 whatever
+ *     the field is; B4 takes precedence.)
+ *  B9 Sources, their argument and state errors, and what a call leaves untouched -- the chain state, the momenta, the
+ *     carried gradient and -log L, the uploaded inputs, deltaX / pos* and a pending proposal -- are those of
+ *     bchmc_measure_corr2d.  Everything is checked before anything is queued.  Also BCHMC_ERR_ARG: opts NULL, k_min
+ *     negative or not finite, dk <= 0 or not finite, n_shell outside 1..32, b NULL.  Any Nx bchmc_create accepts works,
+ *     odd ones included.
+ *  B10 Buffers.  The feature owns n_shell real arrays of the storage type, the partial sums (workgroups x T doubles, at
+ *     most 512 workgroups), the table of the T triangle sums and at most one half-complex array (none for the chain
+ *     state); otherwise it uses the handle's transfer staging and scratch.  I_s and ntri depend on (grid, k_min, dk,
+ *     n_shell) only: the table is built by the first call and kept, a call with other shells replaces it, so a later
+ *     sample costs n_shell filter + C2R passes and one contraction.  bchmc_live_resources counts every buffer,
+ *     bchmc_bispec_release and bchmc_destroy free them.  If one cannot be allocated the call returns the allocation's
+ *     error, releases what it took and leaves the handle usable.
+ * b: T doubles.  ntri, q: T doubles or NULL.  kmean, power: n_shell doubles or NULL.  nmode: n_shell or NULL.
+ * (Added within ABI version 4: no struct or existing entry point changed.) */
+typedef struct bchmc_bispec_opts { double k_min, dk; int32_t n_shell, reserved0; } bchmc_bispec_opts;
+int bchmc_bispectrum(bchmc_handle *h, bchmc_corr_source src, const double *signal, const bchmc_bispec_opts *opts,
+                     double *b /* T */, double *ntri /* T or NULL */, double *q /* T or NULL */,
+                     double *kmean /* n_shell or NULL */, uint64_t *nmode /* n_shell or NULL */, double *power /* n_shell or NULL */);
+int bchmc_bispec_release(bchmc_handle *h);   /* every buffer of the feature freed */
 /* ---- a particle catalogue onto the grid (upstream: getDensity_NGP / _CIC / _TSC / _SPH, massFunctions.cc:49-495, as
  * tools/density.cc, tools/poisson_upres.cc and Lag2Eul.cc:117-126 call them) ---------------------------------------------
  * The raw density of a free list of n_part particles -- no overdens, no normalisation -- on the handle's grid, L and

@@ -159,6 +159,13 @@ void tweb_classify(HamilView *hd, const real_prec *signal, real_prec smoothing_s
                    real_prec *lambda, unsigned char *type, ULONG *n_type, real_prec *mass_type, bool of_deltaX = false);
 // count / samples of one type (0..3) over the accumulated samples: N values; throws with no sample
 void tweb_probability(HamilView *hd, int type, real_prec *out);
+// The bispectrum of a sample (bchmc_bispectrum; upstream: none) by the FFT estimator: n_shell (1..32) shells of |k| from
+// k_min in steps of dk (h/Mpc), all T = n_shell (n_shell + 1) (n_shell + 2) / 6 triplets s1 <= s2 <= s3 in lexicographic
+// order.  Sources as above.  b: T values; ntri (closed mode triples), q (the reduced bispectrum): T values or NULL;
+// kmean, nmode, power: n_shell values or NULL.
+void measure_bispectrum(HamilView *hd, const real_prec *signal, real_prec k_min, real_prec dk, int n_shell, real_prec *b,
+                        real_prec *ntri, real_prec *q, real_prec *kmean, ULONG *nmode, real_prec *power,
+                        bool of_deltaX = false);
 // massFunctions.cc:49-495 on the device (bchmc_density_particles): a free list of N_OBJ particles onto the grid, upstream's
 // argument lists behind the view.  The grid is the handle's: N1 .. min3 must be the view's own values (std::runtime_error
 // otherwise -- these functions do not assign onto another grid).  NGP and TSC always read Par_mass, like upstream; CIC and
@@ -354,6 +361,9 @@ int bchmc_shim_tweb_classify(bchmc_shim::HamilView *hd, const double *signal, do
                              int accumulate, double *lambda, unsigned char *type, unsigned long *n_type, double *mass_type,
                              int of_deltaX, char *err, size_t errlen);
 int bchmc_shim_tweb_probability(bchmc_shim::HamilView *hd, int type, double *out, char *err, size_t errlen);
+int bchmc_shim_measure_bispectrum(bchmc_shim::HamilView *hd, const double *signal, double k_min, double dk, int n_shell,
+                                  double *b, double *ntri, double *q, double *kmean, unsigned long *nmode, double *power,
+                                  int of_deltaX, char *err, size_t errlen);
 /* getDensity_NGP / _CIC / _TSC / _SPH (mk 0 .. 3) with the view's own geometry */
 int bchmc_shim_getDensity(bchmc_shim::HamilView *hd, int mk, const double *xp, const double *yp, const double *zp,
                           const double *Par_mass, unsigned long N_OBJ, double *delta, int weightmass, double kernel_h,
