@@ -195,6 +195,23 @@ struct bchmc_handle {
     std::vector<int> par_bin;              // nbin_par of populated par bin c
     std::vector<double> ksum;              // n_bin * npb sums of ktot, filled by the first measurement
   } spec2;
+  // bchmc_measure_*multipoles (multipoles.hpp): the class tables of the grid, the class sums of the last call (one table,
+  // three once the cross form has run), the segment sums of the shell pass, a half-complex array once the cross form's
+  // first source has needed a transform, and on the host the geometry of the last n_bin of each form.  Taken on first
+  // use, kept until bchmc_multipoles_release or bchmc_destroy.
+  struct Mp {
+    DevBuf<int> rows;          // kMpRows per class
+    DevBuf<int4> cls;          // { m_a, m_b, rows, 0 } per class
+    DevBuf<double> part;       // tables * ncls * nh
+    DevBuf<double> out;        // (n_bin + 1) * segments * sums
+    DevBytes xk;               // Nhp complex
+    int ncls = 0;              // 0: no tables yet
+    struct Geom {
+      uint64_t n_bin = 0;      // the arrays below are this bin count's (0: none yet)
+      std::vector<double> tmode, leg;  // n_bin, [2][n_bin]
+      std::vector<uint64_t> nmode;
+    } fourier, real;
+  } mp;
   // bchmc_interp_upres / bchmc_measure_corr2d_interp (upres.hpp): the fine grid of the last n_out, built on first use,
   // kept for the next call with the same n_out, replaced for another one, freed by bchmc_upres_release.  The work buffer
   // is declared before the execution info and the plans that point at it, like the handle's own.
@@ -1113,6 +1130,108 @@ int spec2d_setup(bchmc_handle *h, uint64_t n_bin) {
   c.ksum.clear();  // filled by the first measurement
   c.n_bin = n_bin;
   return BCHMC_OK;
+}
+
+// ---- bchmc_measure_*multipoles (multipoles.hpp) --------------------------------------------------------------------------
+void mp_drop(bchmc_handle *h) {
+  auto &w = h->mp;
+  (void)w.rows.release();
+  (void)w.cls.release();
+  (void)w.part.release();
+  (void)w.out.release();
+  (void)w.xk.release();
+  w.ncls = 0;
+}
+
+// doubles of the segment sums: the widest pass is the cross form's nine sums
+size_t mp_out_words(uint64_t n_bin) { return ((size_t)n_bin + 1) * mp_segments((int)n_bin) * 9; }
+
+// The buffers a call needs, each on its first use or when it has to grow: the class tables of the grid (the rows (i, j)
+// by class {min(i, n - i), min(j, n - j)}, ascending inside a class), `tables` class-sum tables, the segment sums for
+// n_bin and, `xk`, a half-complex array.  If one cannot be had, every buffer of the feature goes back and the handle stays
+// usable.  Synchronises when it builds the tables (they are uploaded from local vectors).
+int mp_take(bchmc_handle *h, int tables, uint64_t n_bin, bool xk) {
+  auto &w = h->mp;
+  const Geo &g = h->g;
+  const int n = g.n, m = n / 2, ncls = mp_classes(n);
+  int rc = BCHMC_OK;
+  if (!w.ncls) {
+    std::vector<int> rows((size_t)ncls * kMpRows, -1);
+    std::vector<int4> cls((size_t)ncls);
+    auto id = [&](int a, int b) { return a * (m + 1) - a * (a - 1) / 2 + (b - a); };  // a <= b <= m
+    for (int a = 0; a <= m; a++)
+      for (int b = a; b <= m; b++) cls[id(a, b)] = make_int4(a, b, 0, 0);
+    for (int i = 0; i < n; i++)
+      for (int j = 0; j < n; j++) {
+        const int mi = std::min(i, n - i), mj = std::min(j, n - j);
+        int4 &c = cls[id(std::min(mi, mj), std::max(mi, mj))];
+        rows[(size_t)id(c.x, c.y) * kMpRows + c.z++] = i * n + j;
+      }
+    rc = dev_alloc(h, w.rows, rows.size());
+    if (!rc) rc = dev_alloc(h, w.cls, cls.size());
+    if (!rc) {
+      hipError_t e = hipMemcpyAsync(w.rows, rows.data(), rows.size() * sizeof(int), hipMemcpyHostToDevice, h->stream);
+      if (e == hipSuccess) e = hipMemcpyAsync(w.cls, cls.data(), cls.size() * sizeof(int4), hipMemcpyHostToDevice, h->stream);
+      if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+      if (e != hipSuccess) rc = h->fail(BCHMC_ERR_HIP, "multipoles: class tables: %s", hipGetErrorString(e));
+    }
+    if (!rc) w.ncls = ncls;
+  }
+  if (!rc) rc = dev_reserve(h, w.part, (size_t)tables * ncls * g.nh);
+  if (!rc) rc = dev_reserve(h, w.out, mp_out_words(n_bin));
+  if (!rc && xk && !w.xk) rc = dev_alloc(h, w.xk, 2 * (size_t)g.Nhp * h->esz);
+  if (rc) {
+    (void)hipStreamSynchronize(h->stream);  // the zero fills of what goes back
+    mp_drop(h);
+  }
+  return rc;
+}
+
+// The segment sums hs[(n_bin + 1) * nseg * nacc] added per bin in ascending segment order: sums[(n_bin + 1) * nacc]
+std::vector<double> mp_bins(const std::vector<double> &hs, uint64_t n_bin, int nacc) {
+  const int nseg = mp_segments((int)n_bin);
+  std::vector<double> sums(((size_t)n_bin + 1) * nacc, 0.);
+  for (size_t b = 0; b <= n_bin; b++)
+    for (int a = 0; a < nacc; a++) {
+      double v = 0.;
+      for (int s = 0; s < nseg; s++) v += hs[(b * nseg + s) * nacc + a];
+      sums[b * nacc + a] = v;
+    }
+  return sums;
+}
+
+// nmode, the mean of t = |k| or r and the means of L_2 and L_4 per bin from the GEOM pass's segment sums
+void mp_geometry(bchmc_handle::Mp::Geom &c, const std::vector<double> &hg, uint64_t n_bin) {
+  const std::vector<double> s = mp_bins(hg, n_bin, kMpGeom);
+  c.tmode.assign(n_bin, 0.);
+  c.leg.assign(2 * n_bin, 0.);
+  c.nmode.assign(n_bin, 0);
+  for (size_t b = 0; b < n_bin; b++) {
+    const double cnt = s[b * kMpGeom];  // a sum of integers below 2^53: exact
+    c.nmode[b] = (uint64_t)cnt;
+    if (!(cnt > 0.)) continue;
+    c.tmode[b] = s[b * kMpGeom + 1] / cnt;
+    c.leg[b] = s[b * kMpGeom + 2] / cnt;
+    c.leg[n_bin + b] = s[b * kMpGeom + 3] / cnt;
+  }
+  c.n_bin = n_bin;
+}
+
+// out[l][b] = (2 l + 1) * norm * sum_l[b] / nmode[b] for table `tab` of `ntab`; 0 in an empty bin; NaN in every populated
+// one if the table's total (the elements past the last bin included) is not finite
+void mp_normalise(const bchmc_handle::Mp::Geom &c, const std::vector<double> &sums, uint64_t n_bin, int ntab, int tab,
+                  double norm, double *out) {
+#pragma clang fp contract(off)
+  const int nacc = 3 * ntab;
+  double total = 0.;
+  for (size_t b = 0; b <= n_bin; b++) total += sums[b * nacc + 3 * tab];
+  const bool finite = total - total == 0.;
+  for (int l = 0; l < 3; l++)
+    for (size_t b = 0; b < n_bin; b++) {
+      double v = 0.;
+      if (c.nmode[b]) v = finite ? (double)(4 * l + 1) * norm * sums[b * nacc + 3 * tab + l] / (double)c.nmode[b] : total - total;
+      out[(size_t)l * n_bin + b] = v;
+    }
 }
 
 // ---- the fine grid of bchmc_interp_upres / bchmc_measure_corr2d_interp (upres.hpp) ------------------------------------
@@ -2712,6 +2831,44 @@ struct Pipe {
       }
     }
     return BCHMC_OK;
+  }
+
+  // ---- bchmc_measure_*multipoles (multipoles.hpp; mp_take has run) -----------------------------------------------------
+  // The segment sums of the shell pass over the class sums of a (and b, NS = 3): hs[(n_bin + 1) * segments * 3 NS], and,
+  // `hg` not null, those of the GEOM pass: hg[(n_bin + 1) * segments * kMpGeom].  REAL: a is the real grid A(r) of T and
+  // the bins are measure_corr's; else a, b are half-complex transforms and the bins measure_spectrum's.  One synchronise.
+  template <int NS, bool REAL>
+  static int mp_sums(bchmc_handle *h, const void *a, const void *b, uint64_t n_bin, double *hg, double *hs) {
+    auto &w = h->mp;
+    const Geo &g = h->g;
+    const int nseg = mp_segments((int)n_bin);
+    const double u = REAL ? g.d : g.kfac, dt = REAL ? corr_dr(g, n_bin) : spectrum_dk(g, n_bin);
+    const long long stride = (long long)w.ncls * g.nh;
+    const size_t cells = ((size_t)n_bin + 1) * nseg;
+    const dim3 g1((unsigned)((w.ncls + kMpWaves - 1) / kMpWaves), (unsigned)((g.nh + kSpecChunk - 1) / kSpecChunk));
+    const dim3 g2((unsigned)n_bin + 1, (unsigned)nseg);
+    {
+      ProfScope ps(h, BCHMC_K_OTHER);
+      k_mp_classes<T, NS, REAL><<<g1, kSpecChunk * kMpWaves, 0, h->stream>>>(g, a, b, w.rows, w.ncls, w.part, stride);
+      if (hg) {
+        k_mp_shells<1, true><<<g2, kMpBlock, 0, h->stream>>>(g.n, g.nh, u, dt, (int)n_bin, w.ncls, w.cls, w.part, stride, REAL ? 0 : 1, w.out);
+        HIPCHK(hipMemcpyAsync(hg, w.out, cells * kMpGeom * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+      }
+      k_mp_shells<NS, false><<<g2, kMpBlock, 0, h->stream>>>(g.n, g.nh, u, dt, (int)n_bin, w.ncls, w.cls, w.part, stride, REAL ? 0 : 1, w.out);
+      HIPCHK(hipGetLastError());
+      HIPCHK(hipMemcpyAsync(hs, w.out, cells * 3 * NS * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    }
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return BCHMC_OK;
+  }
+  static int mp_auto(bchmc_handle *h, const void *xk, uint64_t n_bin, double *hg, double *hs) {
+    return mp_sums<1, false>(h, xk, nullptr, n_bin, hg, hs);
+  }
+  static int mp_cross(bchmc_handle *h, const void *ak, const void *bk, uint64_t n_bin, double *hg, double *hs) {
+    return mp_sums<3, false>(h, ak, bk, n_bin, hg, hs);
+  }
+  static int mp_corr(bchmc_handle *h, uint64_t n_bin, double *hg, double *hs) {  // A(r) is in ioq (corr_field)
+    return mp_sums<1, true>(h, h->ioq, nullptr, n_bin, hg, hs);
   }
 
   static int gradient(bchmc_handle *h, const double *d_q, double *d_g) {
@@ -4775,6 +4932,107 @@ int bchmc_bispec_release(bchmc_handle *h) {
   ENTER(h);
   HIPCHK(hipStreamSynchronize(h->stream));
   bispec_drop(h);
+  return BCHMC_OK;
+}
+
+// ---- bchmc_measure_*multipoles (multipoles.hpp) --------------------------------------------------------------------------
+// What the three entry points check after their arrays and before anything is queued
+static int mp_checks(bchmc_handle *h, const char *name, uint64_t n_bin) {
+  if (n_bin == 0 || n_bin > 2048) return h->fail(BCHMC_ERR_ARG, "%s: n_bin = %llu outside 1..2048", name, (unsigned long long)n_bin);
+  return BCHMC_OK;
+}
+// the class tables hold (n / 2 + 1)(n / 2 + 2) / 2 columns of n / 2 + 1 doubles: 0.54 GB per sum at 1024
+static int mp_grid(bchmc_handle *h, const char *name) {
+  if (h->g.n > 1024) return h->fail(BCHMC_ERR_UNSUPPORTED, "%s: n = %d > 1024", name, h->g.n);
+  return BCHMC_OK;
+}
+// the geometry of a form to the caller's arrays, from the GEOM sums `hg` if this call made them
+static void mp_geometry_out(bchmc_handle::Mp::Geom &c, const std::vector<double> &hg, uint64_t n_bin, double *tmode,
+                            uint64_t *nmode, double *leg) {
+  if (c.n_bin != n_bin) mp_geometry(c, hg, n_bin);
+  std::memcpy(tmode, c.tmode.data(), n_bin * sizeof(double));
+  std::memcpy(leg, c.leg.data(), 2 * n_bin * sizeof(double));
+  if (nmode) std::memcpy(nmode, c.nmode.data(), n_bin * sizeof(uint64_t));
+}
+
+int bchmc_measure_multipoles(bchmc_handle *h, bchmc_corr_source src, const double *signal, uint64_t n_bin, double *kmode,
+                             uint64_t *nmode, double *leg, double *p) {
+  if (!h || !kmode || !leg || !p) return BCHMC_ERR_ARG;
+  const char *name = "measure_multipoles";
+  CHK(mp_checks(h, name, n_bin));
+  CHK(source_args(h, name, src, signal));
+  ENTER(h);
+  CHK(source_state(h, src));
+  CHK(mp_grid(h, name));
+  CHK(mp_take(h, 1, n_bin, false));
+  if (signal) CHK(h2d(h, h->dstage, signal, h->g.N * sizeof(double)));
+  const void *xk = nullptr;
+  CHK(DISPATCH(h, spectrum_source(h, (int)src, &xk)));
+  auto &c = h->mp.fourier;
+  const size_t cells = ((size_t)n_bin + 1) * mp_segments((int)n_bin);
+  std::vector<double> hg(c.n_bin == n_bin ? 0 : cells * kMpGeom), hs(cells * 3);
+  CHK(DISPATCH(h, mp_auto(h, xk, n_bin, hg.empty() ? nullptr : hg.data(), hs.data())));
+  mp_geometry_out(c, hg, n_bin, kmode, nmode, leg);
+  const double N = (double)h->g.N, NORM = h->g.L * h->g.L * h->g.L / N / N;  // FOURIER_DEF_2, as spectrum_bins
+  mp_normalise(c, mp_bins(hs, n_bin, 3), n_bin, 1, 0, NORM, p);
+  return BCHMC_OK;
+}
+
+int bchmc_measure_cross_multipoles(bchmc_handle *h, bchmc_corr_source src_a, const double *signal_a, bchmc_corr_source src_b,
+                                   const double *signal_b, uint64_t n_bin, double *kmode, uint64_t *nmode, double *leg,
+                                   double *p_aa, double *p_bb, double *p_ab) {
+  if (!h || !kmode || !leg || !p_aa || !p_bb || !p_ab) return BCHMC_ERR_ARG;
+  const char *name = "measure_cross_multipoles";
+  CHK(mp_checks(h, name, n_bin));
+  CHK(source_args(h, name, src_a, signal_a));
+  CHK(source_args(h, name, src_b, signal_b));
+  ENTER(h);
+  CHK(source_state(h, src_a));
+  CHK(source_state(h, src_b));
+  CHK(mp_grid(h, name));
+  CHK(mp_take(h, 3, n_bin, src_a != BCHMC_CORR_CHAIN_STATE));
+  const void *ak = nullptr, *bk = nullptr;
+  CHK(DISPATCH(h, cross_source(h, (int)src_a, signal_a, h->mp.xk, &ak)));
+  CHK(DISPATCH(h, cross_source(h, (int)src_b, signal_b, h->tC, &bk)));
+  auto &c = h->mp.fourier;
+  const size_t cells = ((size_t)n_bin + 1) * mp_segments((int)n_bin);
+  std::vector<double> hg(c.n_bin == n_bin ? 0 : cells * kMpGeom), hs(cells * 9);
+  CHK(DISPATCH(h, mp_cross(h, ak, bk, n_bin, hg.empty() ? nullptr : hg.data(), hs.data())));
+  mp_geometry_out(c, hg, n_bin, kmode, nmode, leg);
+  const double N = (double)h->g.N, NORM = h->g.L * h->g.L * h->g.L / N / N;
+  const std::vector<double> sums = mp_bins(hs, n_bin, 9);
+  mp_normalise(c, sums, n_bin, 3, 0, NORM, p_aa);
+  mp_normalise(c, sums, n_bin, 3, 1, NORM, p_bb);
+  mp_normalise(c, sums, n_bin, 3, 2, NORM, p_ab);
+  return BCHMC_OK;
+}
+
+int bchmc_measure_corr_multipoles(bchmc_handle *h, bchmc_corr_source src, const double *signal, uint64_t n_bin, double *rmode,
+                                  uint64_t *nmode, double *leg, double *xi) {
+  if (!h || !rmode || !leg || !xi) return BCHMC_ERR_ARG;
+  const char *name = "measure_corr_multipoles";
+  CHK(mp_checks(h, name, n_bin));
+  CHK(source_args(h, name, src, signal));
+  ENTER(h);
+  CHK(source_state(h, src));
+  CHK(mp_grid(h, name));
+  CHK(mp_take(h, 1, n_bin, false));
+  if (signal) CHK(h2d(h, h->dstage, signal, h->g.N * sizeof(double)));
+  CHK(DISPATCH(h, corr_field(h, (int)src)));
+  auto &c = h->mp.real;
+  const size_t cells = ((size_t)n_bin + 1) * mp_segments((int)n_bin);
+  std::vector<double> hg(c.n_bin == n_bin ? 0 : cells * kMpGeom), hs(cells * 3);
+  CHK(DISPATCH(h, mp_corr(h, n_bin, hg.empty() ? nullptr : hg.data(), hs.data())));
+  mp_geometry_out(c, hg, n_bin, rmode, nmode, leg);
+  mp_normalise(c, mp_bins(hs, n_bin, 3), n_bin, 1, 0, 1. / (double)h->g.N, xi);
+  return BCHMC_OK;
+}
+
+int bchmc_multipoles_release(bchmc_handle *h) {
+  if (!h) return BCHMC_ERR_ARG;
+  ENTER(h);
+  HIPCHK(hipStreamSynchronize(h->stream));
+  mp_drop(h);
   return BCHMC_OK;
 }
 

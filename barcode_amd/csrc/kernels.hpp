@@ -30,6 +30,7 @@
 #include "ensemble.hpp"  // bchmc_ensemble_*: Welford and Chan updates of a running mean and m2, variance / standard deviation
 #include "tweb.hpp"  // bchmc_tweb_*: tidal-tensor components in k-space, Jacobi eigenvalues and web type per cell, posterior counters
 #include "bispec.hpp"  // bchmc_bispectrum: per-shell statistics of x^, the shell filter, the triple contraction over cells and its ordered reduce
+#include "multipoles.hpp"  // bchmc_measure_*multipoles: sums over classes of rows that share a column of |k| and mu, ordered shell sums weighted by L_0, L_2, L_4
 #include "upres.hpp"  // interp_field (CIC gather onto another grid) and the zero-padded power spectrum of 2D_corr_fct_interp.cc
 #include "mock.hpp"  // setup_random_test / make_initial_guess: window, rank of windowed cells on the stream, noise, guesses
 #include "poisson.hpp"  // bchmc_poisson_*: Poisson counts of a rate grid (inversion / PTRS on Philox uniforms), their scan, particle positions

@@ -163,7 +163,9 @@ EXPORTS = ("bchmc_create", "bchmc_destroy", "bchmc_strerror", "bchmc_last_error"
            "bchmc_setup_random_test_poisson",
            "bchmc_tweb_classify", "bchmc_tweb_tensor", "bchmc_tweb_samples", "bchmc_tweb_fetch", "bchmc_tweb_merge",
            "bchmc_tweb_reset", "bchmc_tweb_release",
-           "bchmc_bispectrum", "bchmc_bispec_release")
+           "bchmc_bispectrum", "bchmc_bispec_release",
+           "bchmc_measure_multipoles", "bchmc_measure_cross_multipoles", "bchmc_measure_corr_multipoles",
+           "bchmc_multipoles_release")
 # declared as well, listed apart: the header scan of the ABI test matches names of letters and underscores only
 EXPORTS_MT19937 = ("bchmc_chain_draw_momenta_mt19937", "bchmc_mt19937_jump")
 EXPORTS_CORR2D = ("bchmc_measure_corr2d", "bchmc_measure_corr2d_interp")  # a digit in the name, like the two above
@@ -250,6 +252,10 @@ def load():
     lib.bchmc_tweb_release.argtypes = [vp]
     lib.bchmc_bispectrum.argtypes = [vp, C.c_int, dp, C.POINTER(BispecOpts), dp, dp, dp, dp, C.POINTER(u64), dp]
     lib.bchmc_bispec_release.argtypes = [vp]
+    lib.bchmc_measure_multipoles.argtypes = [vp, C.c_int, dp, C.c_uint64, dp, C.POINTER(u64), dp, dp]
+    lib.bchmc_measure_cross_multipoles.argtypes = [vp, C.c_int, dp, C.c_int, dp, C.c_uint64, dp, C.POINTER(u64), dp, dp, dp, dp]
+    lib.bchmc_measure_corr_multipoles.argtypes = [vp, C.c_int, dp, C.c_uint64, dp, C.POINTER(u64), dp, dp]
+    lib.bchmc_multipoles_release.argtypes = [vp]
     lib.bchmc_chain_forward.argtypes = [vp, C.c_int]
     lib.bchmc_density_particles.argtypes = [vp, C.c_int, dp, dp, dp, dp, u64, C.POINTER(DensityOpts), dp,
                                             C.POINTER(DensityStats)]
@@ -814,6 +820,65 @@ class Engine:
     def bispec_release(self):
         """Frees every buffer of the bispectrum; a later ``bispectrum`` takes them again and rebuilds its table."""
         self._chk(self.lib.bchmc_bispec_release(self.h))
+
+    # ---- RSD multipoles of a sample (bchmc_measure_*multipoles) --------------------------------------------
+    def measure_multipoles(self, signal=None, source=None, n_bin=200):
+        """The Legendre multipoles P_l(k), l = 0, 2, 4, about the line of sight z of a host field, of the resident chain
+        state (the default without a signal) or of the handle's deltaX, sources as in ``measure_corr``, in
+        ``measure_spectrum``'s bins and normalisation.  Returns a dict of n_bin values each: ``k`` (mean |k|), ``nmode``
+        (uint64), ``leg2`` / ``leg4`` (the mean of L_2 / L_4 over the bin's modes: the discrete-mu leakage) and ``p0``,
+        ``p2``, ``p4``.  Bitwise repeatable."""
+        if source is None:
+            source = "chain" if signal is None else "host"
+        n_bin = int(n_bin)
+        size = n_bin if 1 <= n_bin <= 2048 else 1  # out of range: the library refuses before it writes
+        k, leg, p, nmode = np.empty(size), np.empty((2, size)), np.empty((3, size)), np.empty(size, dtype=np.uint64)
+        sig = None if signal is None else _p(self._in(signal))
+        self._chk(self.lib.bchmc_measure_multipoles(self.h, CORR_SOURCES[source], sig, n_bin, _p(k),
+                                                    nmode.ctypes.data_as(C.POINTER(C.c_uint64)), _p(leg.reshape(-1)),
+                                                    _p(p.reshape(-1))))
+        return dict(k=k, nmode=nmode, leg2=leg[0], leg4=leg[1], p0=p[0], p2=p[1], p4=p[2])
+
+    def measure_cross_multipoles(self, signal_a=None, signal_b=None, source_a=None, source_b=None, n_bin=200):
+        """The multipoles of two fields and of their cross-spectrum in one pass, each side as in ``measure_multipoles``.
+        Returns a dict: ``k, nmode, leg2, leg4`` and ``paa0, paa2, paa4``, ``pbb0 ..``, ``pab0 ..``; ``paa*`` and
+        ``pbb*`` are what ``measure_multipoles`` gives for each side, bit for bit."""
+        src = [s if s is not None else ("chain" if sig is None else "host")
+               for s, sig in ((source_a, signal_a), (source_b, signal_b))]
+        n_bin = int(n_bin)
+        size = n_bin if 1 <= n_bin <= 2048 else 1
+        k, leg, nmode = np.empty(size), np.empty((2, size)), np.empty(size, dtype=np.uint64)
+        p = {t: np.empty((3, size)) for t in ("aa", "bb", "ab")}
+        sa = None if signal_a is None else _p(self._in(signal_a))
+        sb = None if signal_b is None else _p(self._in(signal_b))
+        self._chk(self.lib.bchmc_measure_cross_multipoles(
+            self.h, CORR_SOURCES[src[0]], sa, CORR_SOURCES[src[1]], sb, n_bin, _p(k),
+            nmode.ctypes.data_as(C.POINTER(C.c_uint64)), _p(leg.reshape(-1)), _p(p["aa"].reshape(-1)),
+            _p(p["bb"].reshape(-1)), _p(p["ab"].reshape(-1))))
+        out = dict(k=k, nmode=nmode, leg2=leg[0], leg4=leg[1])
+        for t, arr in p.items():
+            for i, l in enumerate((0, 2, 4)):
+                out["p%s%d" % (t, l)] = arr[i]
+        return out
+
+    def measure_corr_multipoles(self, signal=None, source=None, n_bin=None):
+        """The multipoles xi_l(s), l = 0, 2, 4, of the correlation function in ``measure_corr``'s bins (``n_bin`` None:
+        its automatic bin count), sources as there.  Returns a dict: ``r`` (mean separation), ``nmode``, ``leg2``,
+        ``leg4``, ``xi0``, ``xi2``, ``xi4``."""
+        if source is None:
+            source = "chain" if signal is None else "host"
+        n_bin = int(n_bin) if n_bin else corr_auto_nbin(self.Nx, self.params.L)
+        size = n_bin if 1 <= n_bin <= 2048 else 1
+        r, leg, xi, nmode = np.empty(size), np.empty((2, size)), np.empty((3, size)), np.empty(size, dtype=np.uint64)
+        sig = None if signal is None else _p(self._in(signal))
+        self._chk(self.lib.bchmc_measure_corr_multipoles(self.h, CORR_SOURCES[source], sig, n_bin, _p(r),
+                                                         nmode.ctypes.data_as(C.POINTER(C.c_uint64)), _p(leg.reshape(-1)),
+                                                         _p(xi.reshape(-1))))
+        return dict(r=r, nmode=nmode, leg2=leg[0], leg4=leg[1], xi0=xi[0], xi2=xi[1], xi4=xi[2])
+
+    def multipoles_release(self):
+        """Frees every buffer of the multipoles; a later call takes them again and gives the same bits."""
+        self._chk(self.lib.bchmc_multipoles_release(self.h))
 
     def _measure_corr(self, fn, cells, signal, n_bin, source):
         if source is None:

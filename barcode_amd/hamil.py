@@ -202,6 +202,23 @@ def measure_bispectrum(hd, signal=None, source=None, k_min=0., dk=None, n_shell=
     return hd.engine.bispectrum(signal, source, k_min, dk, n_shell, units)
 
 
+def measure_multipoles(hd, signal=None, N_bin=200, source=None, planepar=True):
+    """The Legendre multipoles P_l(k), l = 0, 2, 4, about the line of sight z in measure_spectrum's bins.  ``signal``
+    None = the resident chain state, or with ``source="deltaX"`` the density of the last forward model.  Returns
+    ``Engine.measure_multipoles``'s dict (k, nmode, leg2, leg4, p0, p2, p4)."""
+    if not planepar:
+        raise RuntimeError("non-plane-parallel option not yet implemented")  # as 2D_powspec.cc:71
+    return hd.engine.measure_multipoles(signal, source, N_bin)
+
+
+def measure_corr_multipoles(hd, signal=None, N_bin=None, source=None, planepar=True):
+    """The multipoles xi_l(s), l = 0, 2, 4, of the correlation function in measure_corr_grid's bins.  Returns
+    ``Engine.measure_corr_multipoles``'s dict (r, nmode, leg2, leg4, xi0, xi2, xi4)."""
+    if not planepar:
+        raise RuntimeError("non-plane-parallel option not yet implemented")  # as 2D_corr_fct.cc:75
+    return hd.engine.measure_corr_multipoles(signal, source, N_bin)
+
+
 def getDensity(hd, mk, xp, yp, zp, Par_mass=None, weightmass=False, kernel_h=0.0, to_nobs=False):
     """getDensity_NGP / _CIC / _TSC / _SPH (massFunctions.cc:49-495; ``mk`` 0 .. 3 picks the one, None the handle's) of a
     free particle list on ``hd``'s grid, upstream's argument order from ``xp`` on -> (delta, stats).  ``weightmass``

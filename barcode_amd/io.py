@@ -222,6 +222,35 @@ def read_bispec(path):
                 b=rows[:, 7].copy(), q=rows[:, 8].copy())
 
 
+def dump_multipoles(result, directory, name):
+    """``Engine.measure_multipoles``'s or ``measure_corr_multipoles``'s dict as the text table ``<name>_multipoles.txt``
+    under ``directory``: a header line that names the columns, then one row per bin -- k or r, nmode, the means of L_2 and
+    L_4, and the three multipoles, the reals with 17 digits so that ``read_multipoles`` returns them bit for bit.
+    Returns the path."""
+    path = (os.path.join(directory, name) if directory else name) + "_multipoles.txt"
+    cols = ("k", "p0", "p2", "p4") if "k" in result else ("r", "xi0", "xi2", "xi4")
+    with open(path, "w") as f:
+        f.write("# %s nmode leg2 leg4 %s %s %s\n" % cols)
+        for row in zip(result[cols[0]], result["nmode"], result["leg2"], result["leg4"], *(result[c] for c in cols[1:])):
+            f.write("%.17g %d %.17g %.17g %.17g %.17g %.17g\n" % row)
+    return path
+
+
+def read_multipoles(path):
+    """The table ``dump_multipoles`` wrote -> the dict it was given: ``k, nmode, leg2, leg4, p0, p2, p4`` or ``r, ..., xi0,
+    xi2, xi4``, nmode as uint64."""
+    with open(path) as f:
+        names = f.readline().lstrip("#").split()
+        rows = [line.split() for line in f if line.strip()]
+    out = {}
+    for c, name in enumerate(names):
+        if name == "nmode":
+            out[name] = np.array([int(r[c]) for r in rows], dtype=np.uint64)
+        else:
+            out[name] = np.array([float(r[c]) for r in rows], dtype=np.float64)
+    return out
+
+
 def dump_deltas(engine, directory, suffix=""):
     """``dump_deltas`` (IOfunctionsGen.cc:136-171) of the resident chain state: deltaLAG, then deltaEUL without
     ``rsd_model``, or deltaRSS (the configured forward model) and deltaEUL (a second Lag2Eul without RSD) with it.

@@ -30,7 +30,8 @@ SHIM_EXPORTS = ("bchmc_shim_Hamiltonian_EoM", "bchmc_shim_delta_Hamiltonian", "b
                 "bchmc_shim_interp_field", "bchmc_shim_measure_corr2D_interp", "bchmc_shim_measure_spec2D",
                 "bchmc_shim_getDensity", "bchmc_shim_interpolate", "bchmc_shim_setup_random_test_poisson",
                 "bchmc_shim_discrete_poisson_sample", "bchmc_shim_poisson_positions", "bchmc_shim_poisson_upres",
-                "bchmc_shim_tweb_classify", "bchmc_shim_tweb_probability", "bchmc_shim_measure_bispectrum")
+                "bchmc_shim_tweb_classify", "bchmc_shim_tweb_probability", "bchmc_shim_measure_bispectrum",
+                "bchmc_shim_measure_multipoles", "bchmc_shim_measure_corr_multipoles")
 
 _dp = C.POINTER(C.c_double)
 
@@ -134,6 +135,9 @@ def load():
     lib.bchmc_shim_tweb_probability.argtypes = [hv, C.c_int, _dp, C.c_char_p, sz]
     lib.bchmc_shim_measure_bispectrum.argtypes = [hv, _dp, C.c_double, C.c_double, C.c_int, _dp, _dp, _dp, _dp, C.POINTER(ul),
                                                   _dp, C.c_int, C.c_char_p, sz]
+    lib.bchmc_shim_measure_multipoles.argtypes = [hv, _dp, ul, _dp, C.POINTER(ul), _dp, _dp, C.c_int, C.c_int, C.c_char_p, sz]
+    lib.bchmc_shim_measure_corr_multipoles.argtypes = [hv, _dp, ul, _dp, C.POINTER(ul), _dp, _dp, C.c_int, C.c_int,
+                                                       C.c_char_p, sz]
     lib.bchmc_shim_getDensity.argtypes = [hv, C.c_int, _dp, _dp, _dp, _dp, ul, _dp, C.c_int, C.c_double, C.c_char_p, sz]
     lib.bchmc_shim_interpolate.argtypes = [hv, C.c_int, _dp, _dp, _dp, ul, _dp, C.c_int, _dp, C.c_char_p, sz]
     lib.bchmc_shim_chain_forward.argtypes = [hv, C.c_int, C.c_char_p, sz]
@@ -377,6 +381,24 @@ class ShimHamil:
             C.byref(self.hd), sig, float(k_min), float(dk), int(n_shell), _p(b), _p(ntri), _p(q), _p(km),
             nm.ctypes.data_as(C.POINTER(C.c_ulong)), _p(pw), int(bool(of_deltaX)), self._err, len(self._err)))
         return b, ntri, q, km, nm, pw
+
+    def _multipoles(self, fn, signal, N_bin, planepar, of_deltaX):
+        size = int(N_bin) if 1 <= int(N_bin) <= 2048 else 1  # out of range: refused before anything is written
+        tm, nm, leg, out = np.empty(size), np.empty(size, dtype=np.uint64), np.empty((2, size)), np.empty((3, size))
+        sig = None if signal is None else _p(self._in(signal))
+        self._chk(fn(C.byref(self.hd), sig, int(N_bin), _p(tm), nm.ctypes.data_as(C.POINTER(C.c_ulong)),
+                     _p(leg.reshape(-1)), _p(out.reshape(-1)), int(bool(planepar)), int(bool(of_deltaX)), self._err,
+                     len(self._err)))
+        return tm, nm, leg, out
+
+    def measure_multipoles(self, signal, N_bin=200, planepar=True, of_deltaX=False):
+        """bchmc_shim::measure_multipoles at ``signal`` (None: the resident state, or deltaX) -> (kmode, nmode, leg (2,
+        N_bin), power (3, N_bin)), l = 0, 2, 4 along the first axis of power."""
+        return self._multipoles(self.lib.bchmc_shim_measure_multipoles, signal, N_bin, planepar, of_deltaX)
+
+    def measure_corr_multipoles(self, signal, N_bin=200, planepar=True, of_deltaX=False):
+        """bchmc_shim::measure_corr_multipoles -> (rmode, nmode, leg (2, N_bin), xi (3, N_bin))."""
+        return self._multipoles(self.lib.bchmc_shim_measure_corr_multipoles, signal, N_bin, planepar, of_deltaX)
 
     def measure_spec2D(self, signal, N_bin=200, planepar=True, of_deltaX=False):
         """bchmc_shim::measure_spec2D at ``signal`` (None: the resident state, or deltaX) -> (kmode, power) shaped

@@ -317,6 +317,24 @@ void measure_bispectrum(HamilView *hd, const real_prec *signal, real_prec k_min,
   for (size_t s = 0; s < nm.size(); s++) nmode[s] = (ULONG)nm[s];
 }
 
+void measure_multipoles(HamilView *hd, const real_prec *signal, ULONG N_bin, real_prec *kmode, ULONG *nmode, real_prec *leg,
+                        real_prec *power, bool planepar, bool of_deltaX) {
+  if (!planepar) throw std::runtime_error("non-plane-parallel option not yet implemented");  // as 2D_powspec.cc:71
+  bchmc_handle *h = engine_for(hd);
+  const int rc = bchmc_measure_multipoles(h, corr_source(signal, of_deltaX), signal, N_bin, kmode,
+                                          reinterpret_cast<uint64_t *>(nmode), leg, power);
+  if (rc) fail(h, rc, "measure_multipoles");
+}
+
+void measure_corr_multipoles(HamilView *hd, const real_prec *signal, ULONG N_bin, real_prec *rmode, ULONG *nmode,
+                             real_prec *leg, real_prec *xi, bool planepar, bool of_deltaX) {
+  if (!planepar) throw std::runtime_error("non-plane-parallel option not yet implemented");  // as 2D_corr_fct.cc:75
+  bchmc_handle *h = engine_for(hd);
+  const int rc = bchmc_measure_corr_multipoles(h, corr_source(signal, of_deltaX), signal, N_bin, rmode,
+                                               reinterpret_cast<uint64_t *>(nmode), leg, xi);
+  if (rc) fail(h, rc, "measure_corr_multipoles");
+}
+
 void tweb_probability(HamilView *hd, int type, real_prec *out) {
   bchmc_handle *h = engine_for(hd);
   const int rc = bchmc_tweb_fetch(h, type, 1, out);
@@ -983,6 +1001,20 @@ int bchmc_shim_measure_spec2D(bchmc_shim::HamilView *hd, const double *signal, d
                               unsigned long N_bin, int planepar, int of_deltaX, char *err, size_t errlen) {
   return guarded(err, errlen, [&] {
     bchmc_shim::measure_spec2D(hd, signal, kmode, power, N_bin, planepar != 0, of_deltaX != 0);
+  });
+}
+int bchmc_shim_measure_multipoles(bchmc_shim::HamilView *hd, const double *signal, unsigned long N_bin, double *kmode,
+                                  unsigned long *nmode, double *leg, double *power, int planepar, int of_deltaX, char *err,
+                                  size_t errlen) {
+  return guarded(err, errlen, [&] {
+    bchmc_shim::measure_multipoles(hd, signal, N_bin, kmode, nmode, leg, power, planepar != 0, of_deltaX != 0);
+  });
+}
+int bchmc_shim_measure_corr_multipoles(bchmc_shim::HamilView *hd, const double *signal, unsigned long N_bin, double *rmode,
+                                       unsigned long *nmode, double *leg, double *xi, int planepar, int of_deltaX,
+                                       char *err, size_t errlen) {
+  return guarded(err, errlen, [&] {
+    bchmc_shim::measure_corr_multipoles(hd, signal, N_bin, rmode, nmode, leg, xi, planepar != 0, of_deltaX != 0);
   });
 }
 int bchmc_shim_tweb_classify(bchmc_shim::HamilView *hd, const double *signal, double smoothing_scale, double lambda_th,

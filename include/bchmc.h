@@ -488,6 +488,56 @@ int bchmc_bispectrum(bchmc_handle *h, bchmc_corr_source src, const double *signa
                      double *b /* T */, double *ntri /* T or NULL */, double *q /* T or NULL */,
                      double *kmean /* n_shell or NULL */, uint64_t *nmode /* n_shell or NULL */, double *power /* n_shell or NULL */);
 int bchmc_bispec_release(bchmc_handle *h);   /* every buffer of the feature freed */
+/* ---- RSD multipoles of a sample: P_l(k) and xi_l(s), l = 0, 2, 4 (upstream: none; computed there from dumped fields; the
+ * compressed form of the maps bchmc_measure_spectrum2d and bchmc_measure_corr2d return) -----------------------------------
+ * Line of sight = z, the axis rsd.cc:52-58 displaces; plane-parallel only.  With mu^2 = z^2 / (x^2 + y^2 + z^2) of a mode's
+ * wave vector or a cell's separation:  L_0 = 1,  L_2 = 1.5 mu^2 - 0.5,  L_4 = (35 mu^4 - 30 mu^2 + 3) / 8, evaluated in
+ * double in exactly this operand order without FMA contraction.  Nine properties:
+ *  M1 Fourier space.  Bins, dk, mode weights and normalisation are exactly those of bchmc_measure_spectrum_src: bin
+ *     (ULONG)(ktot / dk), ktot = sqrt(kx kx + ky ky + kz kz) with IEEE sqrt and divide and no FMA contraction, dk =
+ *     |k|_max / n_bin, Hermitian weight hw on the half-complex transform, NORM = L^3 / N^2 (not the 1 / (4 pi) of S1).
+ *     kmode = mean |k| of the bin's modes, nmode = full-grid modes (may be NULL),
+ *     p[l / 2][b] = (2 l + 1) NORM sum hw |x^|^2 L_l(mu) / nmode[b], laid out [3][n_bin], l-major.
+ *  M2 leg[0][b], leg[1][b] = the mean of L_2 and of L_4 over the bin's modes, laid out [2][n_bin]: the leakage of the
+ *     discrete mu into l = 2, 4, which a caller subtracts to correct low-k bins.  kmode, nmode and leg depend on the grid
+ *     and n_bin only and are kept in the handle per form for the last n_bin.
+ *  M3 The mode k = 0 (the cell r = 0) has no mu: it counts in l = 0, kmode and nmode exactly as measure_spectrum
+ *     (measure_corr) counts it and contributes 0 to l = 2, 4 and to leg.
+ *  M4 Cross form.  p_aa, p_bb: what bchmc_measure_multipoles returns for each source, bit for bit; p_ab: the same with the
+ *     summand re_a re_b + im_a im_b (the imaginary parts of a mode and its partner cancel, as in
+ *     bchmc_measure_cross_spectrum).  All nine pairs of sources are legal; with the same source twice the three are equal
+ *     bit for bit.  One pass reads both transforms once.
+ *  M5 Configuration space.  A(r) is exactly the grid bchmc_measure_corr builds; cell coordinates by
+ *     pacman_center_on_origin, rmax = L/2 sqrt(3), dr = rmax / n_bin, bin (ULONG)(rtot / dr), the corner cell with
+ *     rtot == rmax dropped (C1).  xi[l / 2][b] = (2 l + 1) sum A L_l / (nmode[b] N); rmode, nmode, leg as above.  Auto only.
+ *  M6 Empty bins are 0.  A source that is not finite gives NaN in every populated bin of every l (of p_ab too if either
+ *     source is not finite); kmode, rmode, nmode and leg do not depend on the field.  A zero field gives 0.
+ *  M7 Determinism.  No atomics and a fixed order: rows that share the whole column of (ktot, mu) against kz -- the up to
+ *     eight (i, j) with the same unordered pair of |frequencies| -- are summed first, in ascending row order; then each bin
+ *     over those classes and ascending kz by a fixed partition and tree; everything in double.  All outputs are bitwise
+ *     repeatable on every handle, run to run and call to call, which bchmc_measure_spectrum's are not.  fp32 handles:
+ *     transforms in float, products and sums in double.
+ *  M8 Sources, their argument and state errors, and what a call leaves untouched -- the chain state, the momenta, the
+ *     carried gradient and -log L, the uploaded inputs, deltaX / pos* and a pending proposal -- are those of
+ *     bchmc_measure_corr2d, checked before anything is queued, for both sources of the cross form.  Also BCHMC_ERR_ARG: a
+ *     NULL array other than nmode, n_bin outside 1..2048.  Nx <= 1024 (BCHMC_ERR_UNSUPPORTED above).  Odd grids and the
+ *     smallest ones are accepted.
+ *  M9 Buffers.  The feature owns the class tables of the grid (48 bytes per class, (n/2 + 1)(n/2 + 2) / 2 classes), the
+ *     class sums (classes x (n/2 + 1) doubles per sum: 8.7 MB at 256, 0.54 GB at 1024; three sums once the cross form
+ *     has run -- accepted inside the Nx limit, not chunked), the partial sums of the bins and at most one half-complex
+ *     array (only when the cross form's first source needs a transform); otherwise it uses the handle's transfer staging
+ *     and scratch.  Each is taken on first use and kept; bchmc_live_resources counts them, bchmc_multipoles_release and
+ *     bchmc_destroy free them.  If one cannot be allocated the call returns the allocation's error, releases every buffer
+ *     of the feature and leaves the handle usable.
+ * (Added within ABI version 4: no struct or existing entry point changed.) */
+int bchmc_measure_multipoles(bchmc_handle *h, bchmc_corr_source src, const double *signal, uint64_t n_bin, double *kmode,
+                             uint64_t *nmode /* or NULL */, double *leg /* [2][n_bin] */, double *p /* [3][n_bin] */);
+int bchmc_measure_cross_multipoles(bchmc_handle *h, bchmc_corr_source src_a, const double *signal_a,
+                                   bchmc_corr_source src_b, const double *signal_b, uint64_t n_bin, double *kmode,
+                                   uint64_t *nmode /* or NULL */, double *leg, double *p_aa, double *p_bb, double *p_ab);
+int bchmc_measure_corr_multipoles(bchmc_handle *h, bchmc_corr_source src, const double *signal, uint64_t n_bin, double *rmode,
+                                  uint64_t *nmode /* or NULL */, double *leg /* [2][n_bin] */, double *xi /* [3][n_bin] */);
+int bchmc_multipoles_release(bchmc_handle *h);   /* every buffer of the feature freed */
 /* ---- a particle catalogue onto the grid (upstream: getDensity_NGP / _CIC / _TSC / _SPH, massFunctions.cc:49-495, as
  * tools/density.cc, tools/poisson_upres.cc and Lag2Eul.cc:117-126 call them) ---------------------------------------------
  * The raw density of a free list of n_part particles -- no overdens, no normalisation -- on the handle's grid, L and

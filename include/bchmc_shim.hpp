@@ -166,6 +166,14 @@ void tweb_probability(HamilView *hd, int type, real_prec *out);
 void measure_bispectrum(HamilView *hd, const real_prec *signal, real_prec k_min, real_prec dk, int n_shell, real_prec *b,
                         real_prec *ntri, real_prec *q, real_prec *kmean, ULONG *nmode, real_prec *power,
                         bool of_deltaX = false);
+// The Legendre multipoles about the line of sight z (bchmc_measure_multipoles / bchmc_measure_corr_multipoles; upstream:
+// none): P_l(k) in measure_spectrum's bins and xi_l(s) in measure_corr_grid's, l = 0, 2, 4.  Sources as above.  kmode /
+// rmode: N_bin values; nmode: N_bin or NULL; leg: 2 N_bin (the means of L_2 and L_4 per bin); power / xi: 3 N_bin, l-major.
+// planepar == false throws like upstream's 2-D tools.
+void measure_multipoles(HamilView *hd, const real_prec *signal, ULONG N_bin, real_prec *kmode, ULONG *nmode, real_prec *leg,
+                        real_prec *power, bool planepar = true, bool of_deltaX = false);
+void measure_corr_multipoles(HamilView *hd, const real_prec *signal, ULONG N_bin, real_prec *rmode, ULONG *nmode,
+                             real_prec *leg, real_prec *xi, bool planepar = true, bool of_deltaX = false);
 // massFunctions.cc:49-495 on the device (bchmc_density_particles): a free list of N_OBJ particles onto the grid, upstream's
 // argument lists behind the view.  The grid is the handle's: N1 .. min3 must be the view's own values (std::runtime_error
 // otherwise -- these functions do not assign onto another grid).  NGP and TSC always read Par_mass, like upstream; CIC and
@@ -364,6 +372,12 @@ int bchmc_shim_tweb_probability(bchmc_shim::HamilView *hd, int type, double *out
 int bchmc_shim_measure_bispectrum(bchmc_shim::HamilView *hd, const double *signal, double k_min, double dk, int n_shell,
                                   double *b, double *ntri, double *q, double *kmean, unsigned long *nmode, double *power,
                                   int of_deltaX, char *err, size_t errlen);
+int bchmc_shim_measure_multipoles(bchmc_shim::HamilView *hd, const double *signal, unsigned long N_bin, double *kmode,
+                                  unsigned long *nmode, double *leg, double *power, int planepar, int of_deltaX, char *err,
+                                  size_t errlen);
+int bchmc_shim_measure_corr_multipoles(bchmc_shim::HamilView *hd, const double *signal, unsigned long N_bin, double *rmode,
+                                       unsigned long *nmode, double *leg, double *xi, int planepar, int of_deltaX,
+                                       char *err, size_t errlen);
 /* getDensity_NGP / _CIC / _TSC / _SPH (mk 0 .. 3) with the view's own geometry */
 int bchmc_shim_getDensity(bchmc_shim::HamilView *hd, int mk, const double *xp, const double *yp, const double *zp,
                           const double *Par_mass, unsigned long N_OBJ, double *delta, int weightmass, double kernel_h,
