@@ -80,6 +80,10 @@ struct bchmc_handle {
   DevBytes tC;                                       // Nhp scratch
   DevBytes psi;                                      // 3 N: displacement components
   DevBytes V;                                        // 3 N: V components
+  DevBytes vrec;                                     // 4 N: V as records {vx, vy, vz, 0}, where v_rec holds (eval_plan.hpp); made on first use
+  bool ck_vpair = false;                             // Ck holds V^_x | W of k_ypass_fwd_pair (v_pair, eval_plan.hpp)
+  bool vrec_eval = false;                            // this evaluation's binning zeroed V records: its gather writes records
+  bool v_in_vrec = false;                            // the last evaluation's V is in vrec, not in V
   DevBytes rho, plike;                               // N each
   DevBuf<long long> rho_fix;                         // N: fixed-point density (deterministic mode only)
   DevBuf<int> fix_sat;                               // 1: set by k_fix_to_rho when a fixed-point cell came near wrapping
@@ -508,7 +512,7 @@ int need_input(bchmc_handle *h, int f, const char *name) {
 // Where bchmc_fetch takes a field from, or why it cannot: the one statement of it, for Pipe::fetch and for an entry point
 // that must refuse before anything is queued.  A field that a kernel makes first lands in ioq.
 struct FieldSource {
-  enum Made { kAsHeld, kOverdens, kPositions };
+  enum Made { kAsHeld, kOverdens, kPositions, kVrec };
   void *base = nullptr;  // the buffer, in the storage type
   size_t offset = 0;     // elements into it
   Made made = kAsHeld;
@@ -525,7 +529,10 @@ int field_source(bchmc_handle *h, int field, FieldSource *fs) {
     case BCHMC_F_POSX: case BCHMC_F_POSY: case BCHMC_F_POSZ: fs->base = h->ioq.get(), fs->made = FieldSource::kPositions; break;
     case BCHMC_F_RHO: fs->base = h->rho.get(); break;
     case BCHMC_F_PART_LIKE: fs->base = h->plike.get(); break;
-    case BCHMC_F_VX: case BCHMC_F_VY: case BCHMC_F_VZ: fs->base = h->V.get(), fs->offset = (size_t)(field - BCHMC_F_VX) * N; break;
+    case BCHMC_F_VX: case BCHMC_F_VY: case BCHMC_F_VZ:
+      if (h->v_in_vrec) fs->base = h->ioq.get(), fs->made = FieldSource::kVrec;  // the gather left records: unpacked into ioq
+      else fs->base = h->V.get(), fs->offset = (size_t)(field - BCHMC_F_VX) * N;
+      break;
     case BCHMC_F_PSIX: case BCHMC_F_PSIY: case BCHMC_F_PSIZ:
       fs->base = h->psi.get(), fs->offset = (size_t)(field - BCHMC_F_PSIX) * N;
       break;
@@ -725,6 +732,8 @@ PathSwitches read_path_switches() {
   s.bx_v1 = env_on("BCHMC_BX_V1");
   s.bx_v2 = env_on("BCHMC_BX_V2");
   s.no_pair = env_on("BCHMC_NO_PAIR");
+  s.no_vpair = env_on("BCHMC_NO_VPAIR");
+  s.no_vrec = env_on("BCHMC_NO_VREC");
   return s;
 }
 
@@ -736,7 +745,7 @@ PathFacts path_facts(bchmc_handle *h, int rsd) {
   PathFacts f;
   f.n = h->g.n, f.esz = (int)h->esz, f.Nhp = h->g.Nhp;
   f.planes_ok = h->planes_ok && h->xtw;
-  f.tiled = h->plan.tiled, f.sort_direct = h->plan.slots.sort_direct;
+  f.tiled = h->plan.tiled, f.sort_direct = h->plan.slots.sort_direct, f.std81 = h->plan.std81;
   f.mk = h->c.mk, f.calc_h = h->c.calc_h, f.likelihood = h->c.likelihood, f.sfmodel = h->c.sfmodel;
   f.rsd_model = h->c.rsd_model, f.mass_rs = h->mass_rs != 0;
   if (alpt_planes_wanted(f, h->sw, rsd) && !h->c2r2d_2 && !h->alpt_plans_failed &&
@@ -1527,6 +1536,11 @@ struct Pipe {
     bool rho_cleared = false;  // by k_bin_direct, on its way through the lattice
     const PosPar pp = make_pos(h, rsd);
     const SphPar sp = make_sph(h);
+    // this evaluation's gather will store V as records (like_force): the binning zeroes the record, not the three arrays,
+    // of a particle without a usable position
+    h->vrec_eval = eval_vrec(path_facts(h, h->c.rsd_model), h->sw, m);
+    if (h->vrec_eval && !h->vrec) CHK(dev_alloc(h, h->vrec, 4 * (size_t)h->g.N * sizeof(T)));
+    T *const vrec = h->vrec_eval ? R(h->vrec) : nullptr;
     if (h->plan.tiled) {
       // counting sort of the particles by the Eulerian tile of their home cell
       ProfScope ps(h, BCHMC_K_SORT);
@@ -1542,24 +1556,25 @@ struct Pipe {
       if (zbin) {
         HIPCHK(launch_zbin<T>(pass_ctx(h), pp, sp, h->plan.tp, C(h->Ck), cnt1, ovf, recs(h), R(h->V), h->rho_part,
                               h->fix ? nullptr : R(h->rho), h->fix ? h->rho_fix : nullptr,
-                              m.psi_unread ? nullptr : R(h->psi)));
+                              m.psi_unread ? nullptr : R(h->psi), vrec));
         // second launch (interior steps, where Psi is not stored on the way): a segment overflowed -> the two-pass sort
         // below needs Psi after all (returns at once otherwise)
         if (m.psi_unread)
           HIPCHK((launch_zbin<T, true>(pass_ctx(h), pp, sp, h->plan.tp, C(h->Ck), cnt1, ovf, nullptr, nullptr, nullptr,
-                                       nullptr, nullptr, R(h->psi))));
+                                       nullptr, nullptr, R(h->psi), nullptr)));
         rho_cleared = true;
       } else if (h->plan.slots.sort_direct) {
         const int nsuper = (nbricks + kBinPer - 1) / kBinPer;
         k_bin_direct<T><<<nsuper, BCHMC_BIN_THREADS, 0, h->stream>>>(h->g, pp, sp, h->plan.tp, nsuper, R(h->psi), cnt1, ovf,
                                                        recs(h), R(h->V), h->rho_part,
                                                        h->fix ? nullptr : R(h->rho),
-                                                       h->fix ? h->rho_fix : nullptr);
+                                                       h->fix ? h->rho_fix : nullptr, vrec);
         rho_cleared = true;
       } else {
         HIPCHK(hipMemsetAsync(ovf, 1, 1, h->stream));  // non-zero flag: two-pass sort only
       }
-      k_bin<T><<<fb_grid, 256, 0, h->stream>>>(h->g, pp, sp, h->plan.tp, nbricks, R(h->psi), cnt2, ovf, h->t_rank, R(h->V));
+      k_bin<T><<<fb_grid, 256, 0, h->stream>>>(h->g, pp, sp, h->plan.tp, nbricks, R(h->psi), cnt2, ovf, h->t_rank, R(h->V),
+                                             vrec);
       k_scan_tiles<<<(nt + 1023) / 1024, 1024, 0, h->stream>>>(h->plan.tp, cnt1, cnt2, ovf, h->t_off, h->t_end, h->t_woff,
                                                                h->t_oct, h->t_seg, ovf + 2);
       k_reorder<T><<<fb_grid, 256, 0, h->stream>>>(h->g, pp, nbricks, R(h->psi), h->t_rank, h->t_off, ovf,
@@ -1675,6 +1690,8 @@ struct Pipe {
       return h->fail(BCHMC_ERR_ARG, "calc_h = %d is not a valid value (0..3)", h->c.calc_h);
     }
     const long long N = h->g.N, Nh = h->g.Nhp;
+    const bool vrec = h->vrec_eval;  // as particle_stage decided for this evaluation
+    h->vrec_eval = h->v_in_vrec = h->ck_vpair = false;
     {
       ProfScope ps(h, BCHMC_K_MEAN_PARTIAL);
       k_partial_like<T><<<nblk_stride(N), 256, 0, h->stream>>>(h->g, make_like(h), R(h->rho), h->rho_part,
@@ -1749,7 +1766,12 @@ struct Pipe {
       HullPar hp = make_hull(h);
       if (h->plan.tiled && h->sorted_valid) {
         const int grid = tile_grid(h);
-        if (h->plan.std81)
+        if (h->plan.std81 && vrec) {
+          k_gather_tile81<T, 12, 20, true><<<grid, kTile81Threads, tile_lds(h, 0, sizeof(T)), h->stream>>>(
+              h->g, hp, h->plan.tp, h->last_rsd, recs(h), h->t_off, h->t_end, h->t_woff,
+              h->t_oct, h->t_seg, R(h->plike), R(h->vrec));
+          h->v_in_vrec = true;
+        } else if (h->plan.std81)
           k_gather_tile81<T, 12, 20><<<grid, kTile81Threads, tile_lds(h, 0, sizeof(T)), h->stream>>>(
               h->g, hp, h->plan.tp, h->last_rsd, recs(h), h->t_off, h->t_end, h->t_woff,
               h->t_oct, h->t_seg, R(h->plike), R(h->V));
@@ -1762,8 +1784,20 @@ struct Pipe {
                                                                                   R(h->psi), R(h->plike), R(h->V));
       }
       HIPCHK(hipGetLastError());
+      if (vrec && !h->v_in_vrec) return h->fail(BCHMC_ERR_STATE, "V records were zeroed and no gather writes records");
     }
+    const bool vpair = eval_vpair(path_facts(h, h->c.rsd_model), h->sw, m);
+    if (transform && h->v_in_vrec && !vpair)
+      return h->fail(BCHMC_ERR_STATE, "V was gathered as records, and a transform that reads three arrays");
     if (!transform) {
+    } else if (vpair) {
+      // the engine's own row pass (from the V records, or the three arrays with BCHMC_NO_VREC) and the column pass that
+      // leaves V^_x | W = ky V^_y + kz V^_z for the boundary kernel (zpass.hpp)
+      ProfScope ps(h, BCHMC_K_FFT_R2C);
+      if (h->v_in_vrec) HIPCHK((launch_zr2c<T, true>(pass_ctx(h), R(h->vrec), C(h->Ck))));
+      else HIPCHK(launch_zr2c<T>(pass_ctx(h), R(h->V), C(h->Ck)));
+      HIPCHK(launch_ypass_fwd_pair<T>(pass_ctx(h), C(h->Ck)));
+      h->ck_vpair = true;
     } else if (eval_yfwd(path_facts(h, h->c.rsd_model), h->sw, m)) {
       // 512^3: the engine's own row and column passes (rocFFT's length-512 column kernel runs at 2.3 TB/s, its 1-D row
       // plan alone at half the speed of the same pass inside the 2-D plan: k_zr2c + k_ypass<forward>, zpass.hpp)
@@ -1824,6 +1858,7 @@ struct Pipe {
   template <bool KICK>
   static int launch_assemble(bchmc_handle *h, double a, double b, int like_mode, double c_kick, double *guard_slot) {
     h->prop_g_valid = false;  // gk is rewritten: whatever gradient a chain proposal left there is gone
+    if (h->ck_vpair) return h->fail(BCHMC_ERR_STATE, "two arrays of V^ in Ck, and a kernel that reads three");
     ProfScope ps(h, BCHMC_K_KSPACE_FORCE_KICK);
     k_assemble<T, KICK><<<nblk_stride(h->g.Nhp), 256, 0, h->stream>>>(h->g, C(h->Ck), C(h->qk), h->wS, C(h->gk), C(h->pk),
                                                                      a, b, like_mode, c_kick, guard_slot, h->stop);
@@ -1903,7 +1938,13 @@ struct Pipe {
 
   // k_step_boundary_x for this grid, one tile per workgroup
   template <int MODE, bool ALPT = false>
-  static int launch_boundary_x(bchmc_handle *h, const BoundaryX<T> &bx) {
+  static int launch_boundary_x(bchmc_handle *h, BoundaryX<T> bx) {
+    // the forward side of this boundary reads what the last forward transform left in Ck: V^_x | W, or three arrays
+    if (MODE != BX_FIRST) {
+      if (ALPT && h->ck_vpair) return h->fail(BCHMC_ERR_STATE, "two arrays of V^ in Ck, and a boundary that reads three");
+      bx.vpair = h->ck_vpair;
+      h->ck_vpair = false;
+    }
     HIPCHK((launch_step_boundary_x<T, MODE, ALPT>(pass_ctx(h), C(h->Ck), h->wS, bx)));
     h->ck_pair = bx.pair && !ALPT && MODE != BX_LAST;  // as launch_step_boundary_x told the kernel
     return BCHMC_OK;
@@ -2057,6 +2098,7 @@ struct Pipe {
           CHK(launch_boundary_x<BX_LAST>(h, bx));
           break;
         case Closing::kStepBoundaryLast:
+          if (h->ck_vpair) return h->fail(BCHMC_ERR_STATE, "two arrays of V^ in Ck, and a boundary that reads three");
           k_step_boundary<T, true><<<nblk_stride(h->g.Nhp), 256, 0, h->stream>>>(
               h->g, C(h->Ck), C(qi), C(pi), C(qi), C(pi), C(h->gk), h->wS, wM, a, b, like_mode, 0.5 * eps, eps, c_za,
               h->guard + s, ctl);
@@ -2064,10 +2106,13 @@ struct Pipe {
         case Closing::kBxInteriorAlpt: CHK((launch_boundary_x<BX_INTERIOR, true>(h, bx))); break;
         case Closing::kBxInterior: CHK(launch_boundary_x<BX_INTERIOR>(h, bx)); break;
         case Closing::kBxInteriorTwoTile:
+          bx.vpair = h->ck_vpair;
+          h->ck_vpair = false;
           HIPCHK(launch_step_boundary_x2<T>(pass_ctx(h), C(h->Ck), h->wS, bx));
           h->ck_pair = bx.pair;
           break;
         case Closing::kStepBoundary:
+          if (h->ck_vpair) return h->fail(BCHMC_ERR_STATE, "two arrays of V^ in Ck, and a boundary that reads three");
           k_step_boundary<T, false><<<nblk_stride(h->g.Nhp), 256, 0, h->stream>>>(
               h->g, C(h->Ck), C(qi), C(pi), C(qo), C(po), C(h->gk), h->wS, wM, a, b, like_mode, 0.5 * eps, eps, c_za,
               h->guard + s, ctl);
@@ -2416,7 +2461,7 @@ struct Pipe {
     HIPCHK(hipGetLastError());
     HIPCHK(launch_zr2c<T>(pass_ctx(h), R(h->psi), C(h->Ck)));
     EvalMode m;
-    m.planes_c2r = true;
+    m.planes_c2r = m.planes_r2c = true;  // as an interior step: its gather leaves V where the handle's trajectories do
     m.psi_unread = !store_psi;
     CHK(particle_stage(h, rsd, m, true));
     int like_mode = 0;
@@ -2899,6 +2944,8 @@ struct Pipe {
     if (fs.made == FieldSource::kPositions)
       k_positions<T><<<nblk_stride(h->g.N), 256, 0, h->stream>>>(h->g, make_pos(h, h->last_rsd), R(h->psi), R(h->ioq),
                                                                  (int)field - (int)BCHMC_F_POSX);
+    if (fs.made == FieldSource::kVrec)
+      k_vrec_unpack<T><<<nblk_stride(h->g.N), 256, 0, h->stream>>>(h->g.N, R(h->vrec), (int)field - (int)BCHMC_F_VX, R(h->ioq));
     if (fs.made != FieldSource::kAsHeld) HIPCHK(hipGetLastError());
     return store_real(h, R(fs.base) + fs.offset, d_out);
   }

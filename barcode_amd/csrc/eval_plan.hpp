@@ -1,9 +1,11 @@
 // eval_plan.hpp -- which path a force evaluation takes: planes mode or the 3-D plans, the fused step boundary and its
 // one-tile, two-tile or ALPT formulation, the ALPT pipeline on the 2-D plans, the z pass inside the binning, the engine's
-// own forward y / z passes.  The single statement of it, as pure functions of the path switches (PathSwitches: the
-// environment as bchmc_create read it) and of what a handle is and holds at the moment of asking (PathFacts).  Plain C++:
-// no HIP types, no getenv; tests/host/eval_plan_check.cpp proves it against literals and sweeps the whole space
-// (psi_pair, the two arrays between the inverse x and y passes: tests/host/two_array_check.cpp).
+// own forward y / z passes, V as records and as two arrays into the forward x pass.  The single statement of it, as pure
+// functions of the path switches (PathSwitches: the environment as bchmc_create read it) and of what a handle is and holds
+// at the moment of asking (PathFacts).  Plain C++: no HIP types, no getenv; tests/host/eval_plan_check.cpp proves it
+// against literals and sweeps the whole space
+// (psi_pair, the two arrays between the inverse x and y passes: tests/host/two_array_check.cpp; v_pair / v_rec, their
+// mirror image on the forward side: tests/host/vpair_check.cpp).
 //
 // Nothing here is cached and nothing should be: sort_direct changes when the record slots are given up, and the plans over
 // 2 n planes can appear late.  bchmc.hip gathers the facts when it needs a decision, asks, and switches on the answer.
@@ -24,6 +26,8 @@ struct PathSwitches {           // BCHMC_<NAME>=1, read once per handle
   bool bx_v1 = false;           // BX_V1: the one-tile interior boundary for fp32 fields
   bool bx_v2 = false;           // BX_V2: the two-tile interior boundary for fp64 fields
   bool no_pair = false;         // NO_PAIR: three arrays, not two, between the inverse x pass and the y pass
+  bool no_vpair = false;        // NO_VPAIR: rocFFT's 2-D R2C of the three arrays of V and three arrays into the forward x pass
+  bool no_vrec = false;         // NO_VREC: the gather's V as three arrays, not one record per particle
 };
 
 struct PathFacts {
@@ -35,6 +39,7 @@ struct PathFacts {
   int mk = 3, calc_h = 2, likelihood = 1, sfmodel = 1, rsd_model = 0;
   bool mass_rs = false;      // the mass has a real-space part
   bool alpt_plans = false;   // the 2-D plans over 2 n planes exist
+  bool std81 = false;        // ... the tile-sorted path gathers with the standard 81-cell hull (k_gather_tile81)
 };
 
 struct EvalMode {             // how ONE force evaluation runs; decided by the caller
@@ -154,6 +159,32 @@ constexpr TrajPlan traj_plan(const PathFacts &f, const PathSwitches &s) {
   tp.c_za = tp.alpt_x ? CZa::kAlptInput : CZa::kZeldovich;
   tp.fused = (tp.fused_za || tp.alpt_x) && !f.mass_rs && !s.no_fuse;
   return tp;
+}
+
+// ---- V as records and two arrays, not three, into the forward x pass ----------------------------------------------------
+// The mirror image on the forward side.  V^_y and V^_z enter the boundary kernel only as W = ky V^_y + kz V^_z, and ky, kz
+// are constants of an element from the y pass on: k_zr2c makes the row pass, k_ypass_fwd_pair the column pass, storing V^_x
+// and W only, and a Zel'dovich k_step_boundary_x (interior, BX_LAST, one tile or two) with `vpair` reads the two -- one
+// complex array less written and one less read, in place of rocFFT's 2-D R2C.  Where planes mode is on and the boundary
+// is not ALPT's (whose forward side this is too, but whose builds are not measured), on the tile-sorted standard-81
+// path with the one-pass binning (zbin_ok: 128^3 follows BCHMC_ZBIN_128 as psi_pair does), where the y and z pass shapes
+// exist.  bchmc.hip remembers what the last forward side left in Ck (ck_vpair) and refuses a boundary that would read
+// two arrays as three or three as two.  BCHMC_NO_VPAIR=1: the three arrays through rocFFT.
+// Not at n = 512: measured at 256^3 only (profiles/r05_ab_vpair.txt), and 512^3 has a measured choice of its own (yfwd_ok
+// above), which stays as it is until this path is measured against it there.
+constexpr bool v_pair(const PathFacts &f, const PathSwitches &s, const TrajPlan &tp) {
+  return !s.no_vpair && !tp.alpt_x && f.n != 512 && planes_on(f, s) && zbin_ok(f, s) && f.std81 &&
+         y_shape(f.esz, f.n).nt && z_shape(f.esz, f.n).nt && yfwd_pair_shape(f.esz, f.n).nt;
+}
+// ... in an evaluation: one that wants V^ in planes space.  Never where eval_yfwd holds (n = 512).
+constexpr bool eval_vpair(const PathFacts &f, const PathSwitches &s, const EvalMode &m) {
+  return m.planes_r2c && v_pair(f, s, traj_plan(f, s));
+}
+// ... and k_gather_tile81 then stores V as one record {vx, vy, vz, 0} per particle (a whole 32-byte write instead of three
+// partial ones), which k_zr2c reads as records.  BCHMC_NO_VREC=1: the same transforms from the three arrays of V.
+constexpr bool v_rec(const PathFacts &f, const PathSwitches &s) { return v_pair(f, s, traj_plan(f, s)) && !s.no_vrec; }
+constexpr bool eval_vrec(const PathFacts &f, const PathSwitches &s, const EvalMode &m) {
+  return eval_vpair(f, s, m) && !s.no_vrec;
 }
 
 // The force evaluation before the first step: on the 3-D plans from the displacement on, or on the 2-D plans between a

@@ -152,9 +152,10 @@ template <typename T> int xfft(int n, int kb, int inverse, int groups, void *dat
   return pr.finish({{1, data}});
 }
 
-// k_ypass as forward_rest (inverse) and the planes-mode R2C at 512^3 (forward) launch it
+// k_ypass as forward_rest (inverse) and the planes-mode R2C at 512^3 (forward) launch it; forward at 128 and 256: the
+// three-array reference of k_ypass_fwd_pair
 template <typename T> int ypass(int n, int inverse, void *ck) {
-  if (!y_shape(sizeof(T), n).nt || (!inverse && n != 512)) return -1;
+  if (!y_shape(sizeof(T), n).nt) return -1;
   const Geo g = probe_geo(n, (int)sizeof(T));
   if (g.nhp % pass_kb(sizeof(T))) return -1;
   Probe pr;
@@ -179,17 +180,31 @@ template <typename T> int ypass_pair(int n, double box_len, void *ck) {
   return pr.finish({{1, ck}});
 }
 
-// k_zr2c as the planes-mode R2C at 512^3 launches it, and as bchmc_probe_displacement_z does at 128^3 and 256^3;
-// ck goes in as well, so that the row padding the kernel leaves alone comes back as it went in
-template <typename T> int zr2c(int n, const void *V, void *ck) {
+// k_ypass_fwd_pair as the planes-mode R2C launches it after k_zr2c: the three components are read, 0 (V^_x) and 1 (W) written
+template <typename T> int ypass_fwd_pair(int n, double box_len, void *ck) {
+  if (!yfwd_pair_shape(sizeof(T), n).nt) return -1;
+  const Geo g = probe_geo(n, (int)sizeof(T), box_len);
+  if (g.nhp % pass_kb(sizeof(T))) return -1;
+  Probe pr;
+  const PassCtx<T> x = pr.ctx<T>(g);
+  C2<T> *d = static_cast<C2<T> *>(pr.alloc((size_t)3 * g.Nhp * sizeof(C2<T>), ck));
+  if (pr.err) return pr.err;
+  pr.ok(launch_ypass_fwd_pair<T>(x, d));
+  return pr.finish({{1, ck}});
+}
+
+// k_zr2c as the planes-mode R2C launches it, and as bchmc_probe_displacement_z does; REC: V is n^3 records of 4 (the
+// gather's V records), else 3 n^3.  ck goes in as well, so that the row padding the kernel leaves alone comes back as it
+// went in
+template <typename T, bool REC = false> int zr2c(int n, const void *V, void *ck) {
   if (!z_shape(sizeof(T), n).nt) return -1;
   const Geo g = probe_geo(n, (int)sizeof(T));
   Probe pr;
   const PassCtx<T> x = pr.ctx<T>(g);
-  const T *dv = static_cast<const T *>(pr.alloc((size_t)3 * g.N * sizeof(T), V));
+  const T *dv = static_cast<const T *>(pr.alloc((size_t)(REC ? 4 : 3) * g.N * sizeof(T), V));
   C2<T> *dc = static_cast<C2<T> *>(pr.alloc((size_t)3 * g.Nhp * sizeof(C2<T>), ck));
   if (pr.err) return pr.err;
-  pr.ok(launch_zr2c<T>(x, dv, dc));
+  pr.ok((launch_zr2c<T, REC>(x, dv, dc)));
   return pr.finish({{2, ck}});
 }
 
@@ -206,7 +221,7 @@ template <typename T> int zc2r(int n, const void *ck, void *psi) {
   T *dp = static_cast<T *>(pr.alloc((size_t)3 * g.N * sizeof(T), nullptr));
   if (pr.err) return pr.err;
   pr.ok((launch_zbin<T, true>(x, PosPar{}, SphPar{}, TilePar{}, dc, nullptr, ovf, nullptr, nullptr, nullptr, nullptr, nullptr,
-                              dp)));
+                              dp, nullptr)));
   return pr.finish({{3, psi}});
 }
 
@@ -254,8 +269,9 @@ void out(Outs &o, int idx, void *host) {
 template <typename T>
 int step_boundary_x(int n, double L, int mode, int alpt, int two_tile, void *Ck, const void *q_in, const void *p_in,
                     const void *g_in, void *q_out, void *p_out, void *g_out, const double *wS, const double *wM,
-                    const double *scal, double *guard_slot, const CtlArgs &ca) {
+                    const double *scal, double *guard_slot, const CtlArgs &ca, int vpair = 0) {
   if (mode < BX_INTERIOR || mode > BX_LAST || (alpt && mode == BX_LAST)) return -1;
+  if (vpair && (alpt || mode == BX_FIRST)) return -1;
   if (two_tile ? (!x2_shape(sizeof(T), n).nt || mode != BX_INTERIOR || alpt) : !x_shape(sizeof(T), n).nt) return -1;
   const Geo g = probe_geo(n, (int)sizeof(T), L);
   if (g.nhp % pass_kb(sizeof(T)) || !Ck || !q_in || !scal) return -1;
@@ -283,6 +299,7 @@ int step_boundary_x(int n, double L, int mode, int alpt, int two_tile, void *Ck,
   a.guard_slot = opt<double>(pr, sizeof(double), guard_slot, &i_gs);
   const CtlDev cd = ctl_alloc(pr, ca);
   a.ctl = cd.ctl;
+  a.vpair = vpair != 0;
   if (pr.err) return pr.err;
   hipError_t e = hipErrorInvalidConfiguration;
   if (two_tile) e = launch_step_boundary_x2<T>(x, d_ck, d_ws, a);
@@ -656,6 +673,17 @@ int fftp_zr2c(int prec, int n, const void *V, void *ck) {
   return prec ? zr2c<float>(n, V, ck) : zr2c<double>(n, V, ck);
 }
 
+// k_zr2c from the gather's V records: V (n^3 records {vx, vy, vz, unused}) -> ck as fftp_zr2c
+int fftp_zr2c_rec(int prec, int n, const void *V, void *ck) {
+  return prec ? zr2c<float, true>(n, V, ck) : zr2c<double, true>(n, V, ck);
+}
+
+// k_ypass_fwd_pair: the three z-transformed components of V in ck -> the forward y transforms of component 0 in component 0
+// and W = ky V^_y + kz V^_z in component 1; component 2 comes back as it went in
+int fftp_ypass_fwd_pair(int prec, int n, double box_len, void *ck) {
+  return prec ? ypass_fwd_pair<float>(n, box_len, ck) : ypass_fwd_pair<double>(n, box_len, ck);
+}
+
 // k_zbin_direct<PSI_ONLY>: ck (3 n^2 nhp complex) -> psi (3 n^3 real)
 int fftp_zc2r(int prec, int n, const void *ck, void *psi) {
   return prec ? zc2r<float>(n, ck, psi) : zc2r<double>(n, ck, psi);
@@ -678,6 +706,21 @@ int fftp_step_boundary_x(int prec, int n, double box_len, int mode, int alpt, in
                                        scal, guard_slot, ca)
               : step_boundary_x<double>(n, box_len, mode, alpt, two_tile, Ck, q_in, p_in, g_in, q_out, p_out, g_out, wS, wM,
                                         scal, guard_slot, ca);
+}
+
+// fftp_step_boundary_x with the `vpair` flag (interior or last, Zel'dovich): Ck[0], Ck[1] hold V^_x | W of k_ypass_fwd_pair,
+// Ck[2] is not read
+int fftp_step_boundary_x_vpair(int prec, int n, double box_len, int mode, int alpt, int two_tile, void *Ck, const void *q_in,
+                               const void *p_in, const void *g_in, void *q_out, void *p_out, void *g_out, const double *wS,
+                               const double *wM, const double *scal, double *guard_slot, int *stop,
+                               unsigned long long *steps_done, const double *guard_prev, double guard_limit,
+                               unsigned long long step_index, int vpair) {
+  const CtlArgs ca{stop, steps_done, guard_prev, guard_limit, step_index};
+  if (!stop || !steps_done) return -1;
+  return prec ? step_boundary_x<float>(n, box_len, mode, alpt, two_tile, Ck, q_in, p_in, g_in, q_out, p_out, g_out, wS, wM,
+                                       scal, guard_slot, ca, vpair)
+              : step_boundary_x<double>(n, box_len, mode, alpt, two_tile, Ck, q_in, p_in, g_in, q_out, p_out, g_out, wS, wM,
+                                        scal, guard_slot, ca, vpair);
 }
 
 // k_alpt_mix_x on Ck (3 n^2 nhp complex in planes space: A^, B^ in; the three displacement components out)

@@ -5,6 +5,8 @@
 //
 // First part: the arithmetic, plain C++ (no HIP types; tests/host/pass_launch_check.cpp proves it against literals).
 // Second part, for a HIP compile only: the launchers.  Which pass runs when is not in here: eval_plan.hpp decides that.
+// The forward side of round 5 (k_zr2c from V records, k_ypass_fwd_pair, `vpair` of the boundary kernels) is launched from
+// here like the rest: yfwd_pair_shape, launch_zr2c<T, REC>, launch_ypass_fwd_pair, BoundaryX::vpair.
 #pragma once
 
 #include <cstddef>
@@ -46,6 +48,9 @@ constexpr PassShape y_shape(int esz, int n) {
 // (tests/host/two_array_check.cpp)
 constexpr PassShape ypair_shape(int esz, int n) { return y_shape(esz, n); }
 constexpr int ypair_comps = 2;
+// k_ypass_fwd_pair (the forward y pass that leaves the two arrays V^_x | W = ky V^_y + kz V^_z): k_ypass_pair's shape, grid
+// (ypair_grid) and one tile of LDS -- the workgroups of W make two transforms on the one tile too (tests/host/vpair_check.cpp)
+constexpr PassShape yfwd_pair_shape(int esz, int n) { return ypair_shape(esz, n); }
 // k_zr2c, k_zbin_direct: NZ = n, one lattice site along z per thread, over 6 interleaved rows
 constexpr PassShape z_shape(int /*esz*/, int n) { return n == 128 || n == 256 || n == 512 ? PassShape{n, 6} : PassShape{}; }
 
@@ -112,15 +117,24 @@ struct PassCtx {
   size_t col_lds(int tiles = 1) const { return bchmc::col_lds(sizeof(T), g.n, tiles); }
 };
 
-// k_ypass over the three components of ck, in place.  The forward pass exists at n = 512 only.
+// k_ypass over the three components of ck, in place, inverse or forward (the engine launches the forward pass at n = 512
+// only; 128 and 256 are the three-array reference of k_ypass_fwd_pair's test).
 template <typename T, bool INV = true>
 hipError_t launch_ypass(const PassCtx<T> &x, C2<T> *ck) {
-  auto go = [&](auto nt, auto per) {
+  return pass_dispatch<y_shape, T>(x.g.n, [&](auto nt, auto per) {
     return launch_dyn_lds(x.stream, k_ypass<T, nt, per, BCHMC_YPASS_NT, INV>, x.col_grid(3), nt, x.col_lds(), x.g, x.log2n,
                           x.tw, ck);
-  };
-  if constexpr (INV) return pass_dispatch<y_shape, T>(x.g.n, go);
-  else return pass_row<y_shape, T, 512>(x.g.n, go);
+  });
+}
+
+// k_ypass_fwd_pair: the three z-transformed components of V in ck -> ck[0] = V^_x, ck[1] = W for a boundary kernel with
+// `vpair`; ck[2] is dead afterwards
+template <typename T>
+hipError_t launch_ypass_fwd_pair(const PassCtx<T> &x, C2<T> *ck) {
+  return pass_dispatch<yfwd_pair_shape, T>(x.g.n, [&](auto nt, auto per) {
+    return launch_dyn_lds(x.stream, k_ypass_fwd_pair<T, nt, per>, ypair_grid(sizeof(T), x.g.n, x.g.nhp),
+                          nt, x.col_lds(), x.g, x.log2n, x.tw, ck);
+  });
 }
 
 // k_ypass_pair: ck[0] = Psi^_x, ck[1] = B as a boundary kernel with `pair` left them -> the three y-transformed components
@@ -132,16 +146,17 @@ hipError_t launch_ypass_pair(const PassCtx<T> &x, C2<T> *ck) {
   });
 }
 
-// k_zr2c: V (3 n^3 real) -> ck
-template <typename T>
+// k_zr2c: V (3 n^3 real; REC: n^3 records of 4) -> ck
+template <typename T, bool REC = false>
 hipError_t launch_zr2c(const PassCtx<T> &x, const T *V, C2<T> *ck) {
   return pass_dispatch<z_shape, T>(x.g.n, [&](auto nz, auto) {
-    return launch_dyn_lds(x.stream, k_zr2c<T, nz>, row_grid(x.g.n), nz, zrow_lds(sizeof(T), x.g.n), x.g, x.log2n, x.tw, V, ck);
+    return launch_dyn_lds(x.stream, k_zr2c<T, nz, REC>, row_grid(x.g.n), nz, zrow_lds(sizeof(T), x.g.n), x.g, x.log2n, x.tw, V,
+                          ck);
   });
 }
 
 // k_zbin_direct: the z pass of ck ending in the binning, or (PSI_ONLY) in psi alone and only if *ovf is set.
-// `out`: the kernel's arguments after ck (cnt, ovf, srec, V, zero_part, rho_zero, fix_zero, psi_out)
+// `out`: the kernel's arguments after ck (cnt, ovf, srec, V, zero_part, rho_zero, fix_zero, psi_out, vrec)
 template <typename T, bool PSI_ONLY = false, typename... A>
 hipError_t launch_zbin(const PassCtx<T> &x, const PosPar &pp, const SphPar &sp, const TilePar &tp, const C2<T> *ck,
                        const A &...out) {
@@ -173,6 +188,7 @@ struct BoundaryX {
   const C2<T> *g_in = nullptr;
   C2<T> *g_out = nullptr;
   bool pair = false;  // the Zel'dovich inverse side leaves Psi^_x | B for k_ypass_pair instead of the three Psi^ components
+  bool vpair = false;  // the Zel'dovich forward side reads V^_x | W as k_ypass_fwd_pair left them, not the three V^ components
 };
 
 template <typename T, int MODE, bool ALPT>
@@ -180,7 +196,8 @@ hipError_t launch_step_boundary_x(const PassCtx<T> &x, C2<T> *Ck, const double *
   return pass_dispatch<x_shape, T>(x.g.n, [&](auto nt, auto per) {
     return launch_dyn_lds(x.stream, k_step_boundary_x<T, nt, per, MODE, ALPT>, x.col_grid(), nt, x.col_lds(), x.g, x.log2n,
                           x.tw, Ck, a.qi, a.pi, a.qo, a.po, wS, a.wM, a.a, a.b, a.half_eps, a.eps, a.c_za, a.guard_slot,
-                          a.ctl, a.g_in, a.g_out, a.pair && !ALPT && MODE != BX_LAST);
+                          a.ctl, a.g_in, a.g_out, a.pair && !ALPT && MODE != BX_LAST,
+                          a.vpair && !ALPT && MODE != BX_FIRST);
   });
 }
 
@@ -189,7 +206,8 @@ template <typename T>
 hipError_t launch_step_boundary_x2(const PassCtx<T> &x, C2<T> *Ck, const double *wS, const BoundaryX<T> &a) {
   return pass_dispatch<x2_shape, T>(x.g.n, [&](auto nt, auto per) {
     return launch_dyn_lds(x.stream, k_step_boundary_x2<T, nt, per>, x.col_grid(), nt, x.col_lds(2), x.g, x.log2n, x.tw, Ck,
-                          a.qi, a.pi, a.qo, a.po, wS, a.wM, a.a, a.b, a.half_eps, a.eps, a.c_za, a.guard_slot, a.ctl, a.pair);
+                          a.qi, a.pi, a.qo, a.po, wS, a.wM, a.a, a.b, a.half_eps, a.eps, a.c_za, a.guard_slot, a.ctl, a.pair,
+                          a.vpair);
   });
 }
 

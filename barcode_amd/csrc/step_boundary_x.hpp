@@ -75,6 +75,18 @@ __device__ __forceinline__ C2<T> cmul(const C2<T> a, const C2<T> b) {
   return r;
 }
 
+// W = ky V^_y + kz V^_z of one element, in double, rounded to T: the second forward x transform's input.  The one statement
+// of it -- both boundary kernels (three arrays) and k_ypass_fwd_pair (zpass.hpp, which stores W for the boundary to read
+// as its second array) call this, so that the compiler contracts the same way in all three and the two paths hold the same
+// number (tests/test_gpu_vpair.py compares them bit for bit).
+template <typename T>
+__device__ __forceinline__ C2<T> bx_w_of(double ky, double kz, const C2<T> vy, const C2<T> vz) {
+  C2<T> w;
+  w.x = (T)(ky * (double)vy.x + kz * (double)vz.x);
+  w.y = (T)(ky * (double)vy.y + kz * (double)vz.y);
+  return w;
+}
+
 // In-place decimation-in-time FFT of KB interleaved columns: s[i * KB + c], bit-reversed input order on entry,
 // natural order on exit.  Two radix-2 stages are fused into one radix-4 pass (4 LDS reads + 4 writes per 4 points
 // per two stages); an odd log2 n gets one plain radix-2 stage first.  tw[r] = exp(-2 pi i r / n), r < n / 2.
@@ -149,6 +161,8 @@ __device__ __forceinline__ void xfft_inplace(C2<T> *__restrict__ s, const C2<T> 
 // `pair` (Zel'dovich BX_INTERIOR / BX_FIRST and k_step_boundary_x2; psi_pair in eval_plan.hpp): the second inverse
 // transform's output B is stored as it is into component 1 and component 2 is not written -- ky B and kz B are made by
 // k_ypass_pair (zpass.hpp), which holds the column anyway: one complex array less written here and one less read there.
+// `vpair` (Zel'dovich BX_INTERIOR / BX_LAST and k_step_boundary_x2; v_pair in eval_plan.hpp): the mirror image on the forward
+// side -- component 1 holds W = ky V^_y + kz V^_z as k_ypass_fwd_pair left it and component 2 is not read.
 enum { BX_INTERIOR = 0, BX_FIRST = 1, BX_LAST = 2 };
 
 // ALPT = true changes what leaves through the two inverse x passes: instead of the Zel'dovich Psi^ (kx B and B, see
@@ -160,7 +174,7 @@ __global__ void __launch_bounds__(NT, BCHMC_BX_WAVES)
 k_step_boundary_x(Geo g, int log2n, const C2<T> *__restrict__ twiddle, C2<T> *Ck, const C2<T> *q_in, const C2<T> *p_in,
                   C2<T> *q_out, C2<T> *p_out, const double *__restrict__ wS, const double *__restrict__ wM, double a,
                   double b, double half_eps, double eps, double c_za, double *guard_slot, StepCtl ctl,
-                  const C2<T> *g_in = nullptr, C2<T> *g_out = nullptr, bool pair = false) {
+                  const C2<T> *g_in = nullptr, C2<T> *g_out = nullptr, bool pair = false, bool vpair = false) {
   constexpr int KB = 128 / (int)sizeof(C2<T>);
   constexpr int kMaxPer = PER;  // elements of one component per thread: n == PER * NT / KB (checked by the host)
   extern __shared__ __attribute__((aligned(16))) unsigned char s_raw_x[];
@@ -205,10 +219,11 @@ k_step_boundary_x(Geo g, int log2n, const C2<T> *__restrict__ twiddle, C2<T> *Ck
       C2<T> v;
       if (pass == 0) {
         v = bx_load(Ck + e);
+      } else if (vpair) {  // W itself, left by k_ypass_fwd_pair
+        v = bx_load(Ck + e + g.Nhp);
       } else {
         const C2<T> vy = bx_load(Ck + e + g.Nhp), vz = bx_load(Ck + e + 2 * g.Nhp);
-        v.x = (T)(ky * (double)vy.x + kz * (double)vz.x);
-        v.y = (T)(ky * (double)vy.y + kz * (double)vz.y);
+        v = bx_w_of<T>(ky, kz, vy, vz);
       }
       s[(int)(__brev((unsigned)i) >> shift) * KB + c] = v;
     }
@@ -477,7 +492,8 @@ template <typename T, int NT, int PER>  // PER <= 4: eight elements per thread d
 __global__ void __launch_bounds__(NT, BCHMC_BX_WAVES)
 k_step_boundary_x2(Geo g, int log2n, const C2<T> *__restrict__ twiddle, C2<T> *Ck, const C2<T> *q_in, const C2<T> *p_in,
                    C2<T> *q_out, C2<T> *p_out, const double *__restrict__ wS, const double *__restrict__ wM, double a,
-                   double b, double half_eps, double eps, double c_za, double *guard_slot, StepCtl ctl, bool pair = false) {
+                   double b, double half_eps, double eps, double c_za, double *guard_slot, StepCtl ctl, bool pair = false,
+                   bool vpair = false) {
   constexpr int KB = 128 / (int)sizeof(C2<T>);
   extern __shared__ __attribute__((aligned(16))) unsigned char s_raw_x2[];
   __shared__ double red[NT / 64];
@@ -523,23 +539,20 @@ k_step_boundary_x2(Geo g, int log2n, const C2<T> *__restrict__ twiddle, C2<T> *C
   };
   C2<T> *const Ck1 = Ck + g.Nhp, *const Ck2 = Ck + 2 * g.Nhp;
   {
-    // ---- V^: all three components requested before the first one is used ----
+    // ---- V^: all three components (vpair: V^_x and W, two) requested before the first one is used ----
     C2<T> vx[PER], vy[PER], vz[PER];
 #pragma unroll
     for (int m = 0; m < PER; m++) {
       vx[m] = bx_load(at_c(Ck, boff[m]));
       vy[m] = bx_load(at_c(Ck1, boff[m]));
-      vz[m] = bx_load(at_c(Ck2, boff[m]));
+      if (!vpair) vz[m] = bx_load(at_c(Ck2, boff[m]));
     }
 #pragma unroll
     for (int m = 0; m < PER; m++) {
       const int i = irow + rows * m;
       const int r = (int)(__brev((unsigned)i) >> shift) * KB + c;
       sa[r] = vx[m];
-      C2<T> w;
-      w.x = (T)(ky * (double)vy[m].x + kz * (double)vz[m].x);
-      w.y = (T)(ky * (double)vy[m].y + kz * (double)vz[m].y);
-      sb[r] = w;
+      sb[r] = vpair ? vy[m] : bx_w_of<T>(ky, kz, vy[m], vz[m]);
     }
   }
   // ---- the operands of the boundary arithmetic are requested now and arrive while the transforms run ----

@@ -77,6 +77,32 @@ template <> __device__ __forceinline__ void rec_load<float>(const RecQuad *base,
 }
 template <typename T> constexpr int rec_quads() { return sizeof(T) == 8 ? 2 : 1; }  // 16-byte units per record
 
+// V records (v_rec, eval_plan.hpp): { vx, vy, vz, 0 } = 4 * sizeof(T) bytes at slot p = the particle's lattice index, written
+// by k_gather_tile81<.., REC> and read by k_zr2c<.., REC>.  The gather's lanes are particles of one tile in arbitrary
+// lattice order, so three 8-byte stores into three arrays are three partial writes of a 32-byte memory granule each; a
+// record is one whole granule (fp64: two 16-byte stores; fp32: one).  rec_store's twin, without the index word.
+template <typename T> __device__ __forceinline__ void vrec_store(T *rec, long long p, T vx, T vy, T vz);
+// Plain stores: with the streaming (`nt`) hint the step lost 13 % (profiles/r05_ab_vpair.txt).
+template <> __device__ __forceinline__ void vrec_store<double>(double *rec, long long p, double vx, double vy, double vz) {
+  double2 *b = reinterpret_cast<double2 *>(rec) + 2 * p;
+  b[0] = make_double2(vx, vy);
+  b[1] = make_double2(vz, 0.);
+}
+template <> __device__ __forceinline__ void vrec_store<float>(float *rec, long long p, float vx, float vy, float vz) {
+  reinterpret_cast<float4 *>(rec)[p] = make_float4(vx, vy, vz, 0.f);
+}
+// V = 0 of a particle without a usable position (it gets no record in the sort, so the gather never writes its V): into
+// its V record where this evaluation's gather writes records (vrec != nullptr), else into the three arrays
+template <typename T> __device__ __forceinline__ void v_zero(T *V, T *vrec, long long p, long long N) {
+  if (vrec) {
+    vrec_store<T>(vrec, p, T(0), T(0), T(0));
+  } else {
+    V[p] = T(0);
+    V[p + N] = T(0);
+    V[p + 2 * N] = T(0);
+  }
+}
+
 __device__ __forceinline__ int tile_of(const TilePar &tp, int n, long long ix, long long iy, long long iz) {
   const int cx = (int)(ix % n), cy = (int)(iy % n), cz = (int)(iz % n);
   return (cz / tp.tz) + tp.ntz * ((cy / tp.ty) + tp.nty * (cx / tp.tx));
@@ -189,7 +215,7 @@ template <typename T>
 __global__ void __launch_bounds__(BCHMC_BIN_THREADS) __attribute__((amdgpu_waves_per_eu(BCHMC_BIN_WAVES, BCHMC_BIN_WAVES)))
 k_bin_direct(Geo g, PosPar pp, SphPar sp, TilePar tp, int nsuper, const T *__restrict__ psi, int *__restrict__ cnt,
              int *__restrict__ ovf, RecQuad *__restrict__ srec, T *__restrict__ V, double *__restrict__ zero_part,
-             T *__restrict__ rho_zero, long long *__restrict__ fix_zero) {
+             T *__restrict__ rho_zero, long long *__restrict__ fix_zero, T *__restrict__ vrec = nullptr) {
   constexpr int kSlots = 2048;  // > kBinPer * 256 distinct counters can never occur: the probing always terminates
   __shared__ int hkey[kSlots], hcnt[kSlots], hbase[kSlots];
   // the scatter that follows accumulates sum(rho) into these partials: cleared here instead of by a fill launch
@@ -260,9 +286,7 @@ k_bin_direct(Geo g, PosPar pp, SphPar sp, TilePar tp, int nsuper, const T *__res
         slot[m] = sl;
         local[m] = atomicAdd(&hcnt[sl], 1);
       } else {
-        V[p[m]] = T(0);
-        V[p[m] + g.N] = T(0);
-        V[p[m] + 2 * g.N] = T(0);
+        v_zero<T>(V, vrec, p[m], g.N);
       }
     }
     __syncthreads();
@@ -304,7 +328,7 @@ k_bin_direct(Geo g, PosPar pp, SphPar sp, TilePar tp, int nsuper, const T *__res
 template <typename T>
 __global__ void __launch_bounds__(256)
 k_bin(Geo g, PosPar pp, SphPar sp, TilePar tp, int nbricks, const T *__restrict__ psi, int *__restrict__ cnt,
-      const int *__restrict__ ovf, int2 *__restrict__ tile_rank, T *__restrict__ V) {
+      const int *__restrict__ ovf, int2 *__restrict__ tile_rank, T *__restrict__ V, T *__restrict__ vrec = nullptr) {
   constexpr int kSlots = 512;
   __shared__ int hkey[kSlots], hcnt[kSlots], hbase[kSlots];
   if (!*ovf) return;  // the one-pass binning succeeded
@@ -335,9 +359,7 @@ k_bin(Geo g, PosPar pp, SphPar sp, TilePar tp, int nbricks, const T *__restrict_
         }
         local = atomicAdd(&hcnt[slot], 1);
       } else {
-        V[p] = T(0);
-        V[p + g.N] = T(0);
-        V[p + 2 * g.N] = T(0);
+        v_zero<T>(V, vrec, p, g.N);
       }
     }
     __syncthreads();
@@ -918,7 +940,8 @@ k_scatter_tile81(Geo g, SphPar sp, TilePar tp, const RecQuad *__restrict__ srec,
 // LZ (LY hx + hy) + hz are as good as random over the 32 eight-byte banks whatever the row stride: the 58 % bank-conflict
 // share of the LDS-active cycles (r02 SQ counters) is the birthday statistics of 16 random addresses per cycle on 32
 // banks, not a stride effect -- measured with a row stride of LZ + 1 (profiles/r03_ab_levers.txt): no change.
-template <typename T, int LY, int LZ>
+// REC: V is the record buffer (vrec_store above), not the three arrays; only the final stores differ.
+template <typename T, int LY, int LZ, bool REC = false>
 __global__ void __launch_bounds__(kTile81Threads, BCHMC_GATHER_WAVES)
 k_gather_tile81(Geo g, HullPar hp, TilePar tp, int rsd, const RecQuad *__restrict__ srec,
                 const long long *__restrict__ off,
@@ -1017,10 +1040,21 @@ k_gather_tile81(Geo g, HullPar hp, TilePar tp, int rsd, const RecQuad *__restric
     vz *= normalize;
     if (rsd) vz += (T)hp.f1 * vz;
     const long long p = rid & ~kSortFlagNoScatter;
-    V[p] = vx;
-    V[p + g.N] = vy;
-    V[p + 2 * g.N] = vz;
+    if (REC) {
+      vrec_store<T>(V, p, vx, vy, vz);
+    } else {
+      V[p] = vx;
+      V[p + g.N] = vy;
+      V[p + 2 * g.N] = vz;
+    }
   }
+}
+
+// component c of the V records into a plain array (bchmc_fetch of Vx / Vy / Vz after an evaluation that gathered records)
+template <typename T>
+__global__ void k_vrec_unpack(long long n, const T *__restrict__ vrec, int c, T *__restrict__ out) {
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
+    out[i] = vrec[4 * i + c];
 }
 
 }  // namespace bchmc

@@ -2,6 +2,9 @@
 // can end in the binning instead of in HBM: k_ypass (inverse complex FFTs along y, in place; k_ypass_pair: the same from
 // the two arrays Psi^_x | B a boundary kernel leaves by default) and k_zbin_direct (inverse
 // real FFTs along z of the three displacement components, particle positions, one-pass binning).
+// And the first two passes of the planes-mode forward transform of V: k_zr2c (real FFTs along z, from the three arrays of
+// V or from the gather's V records) and k_ypass_fwd_pair (forward FFTs along y that leave V^_x | W = ky V^_y + kz V^_z, the
+// two arrays a Zel'dovich boundary kernel reads with `vpair`); k_ypass<.., INV = false> is the three-array forward y pass.
 // Reference work these two kernels cover: the last two of the three passes of each of theta2vel's inverse transforms
 // (EqSolvers.cc:274-276 -> fftC2Rplanned, fftwrapper.cc:88-102; the x pass is in k_step_boundary_x), and everything
 // k_bin_direct covers (disp_part.cc:55-126, pacman.cpp:20-28, rsd.cc:28-68 + the tile binning, which has no counterpart
@@ -126,6 +129,94 @@ k_ypass_pair(Geo g, int log2n, const C2<T> *__restrict__ twiddle, C2<T> *c) {
   }
 }
 
+// ======================================================================================================
+// k_ypass_fwd_pair: the forward y pass that leaves TWO arrays for the step boundary (`vpair` there; v_pair in
+// eval_plan.hpp), the mirror image of k_ypass_pair.  ky and kz are constants of an element from the y pass on and the x
+// transform is linear, so W = ky V^_y + kz V^_z -- which k_step_boundary_x forms per element from two arrays that it
+// reads -- is formed here, where both columns pass through a workgroup anyway, by the same function (bx_w_of) from the
+// same operands: the same number.  One complex array less is written here and one less read by the boundary kernel.
+// Workgroups [0, n ntk): the column (i, :, k0 .. k0 + KB) of components 1 and 2 (z-transformed V_y, V_z; both requested
+// up front); component 1 is transformed forward and its results kept in registers, component 2 is transformed on the
+// same tile, W goes into component 1 (in place: a workgroup writes only elements it has read).  Component 2 is dead
+// from here to the boundary.  Workgroups [n ntk, 2 n ntk): component 0, as k_ypass<.., INV = false>.
+// No element is used as an index: any bit pattern goes through (the evaluations after a guard stop run on stale data).
+// Same shapes as k_ypass_pair (ypair_shape); grid ypair_grid, LDS of one tile.  Plain stores: its output is read once, by
+// the boundary kernel, yet the streaming hint gave nothing (profiles/r05_ab_vpair.txt).
+// ======================================================================================================
+template <typename T, int NT, int PER>
+__global__ void __launch_bounds__(NT)
+k_ypass_fwd_pair(Geo g, int log2n, const C2<T> *__restrict__ twiddle, C2<T> *c) {
+  constexpr int KB = 128 / (int)sizeof(C2<T>);
+  extern __shared__ __attribute__((aligned(16))) unsigned char s_raw_yf[];
+  const int n = g.n;
+  C2<T> *s = reinterpret_cast<C2<T> *>(s_raw_yf);  // n * KB
+  C2<T> *tw = s + (size_t)n * KB;                  // n / 2
+  for (int t = threadIdx.x; t < n / 2; t += blockDim.x) tw[t] = twiddle[t];
+  const int ntk = g.nhp / KB;
+  const int per_comp = n * ntk;
+  const bool to_w = (int)blockIdx.x < per_comp;
+  const int b = (int)blockIdx.x % per_comp;
+  const int i = b / ntk, k0 = (b % ntk) * KB;
+  const int col = threadIdx.x % KB, jrow = threadIdx.x / KB;
+  constexpr int rows = NT / KB;
+  // element (i, 0, k0 + col) of component 0 (V^_x) or 1 (V^_y -> W)
+  C2<T> *base = c + (to_w ? g.Nhp : 0ll) + (long long)g.nhp * g.n * i + k0 + col;
+  const int shift = 32 - log2n;
+  if (!to_w) {  // component 0, as k_ypass<.., INV = false>
+    C2<T> v[PER];
+#pragma unroll
+    for (int m = 0; m < PER; m++) v[m] = base[(long long)g.nhp * (jrow + rows * m)];
+#pragma unroll
+    for (int m = 0; m < PER; m++) s[(int)(__brev((unsigned)(jrow + rows * m)) >> shift) * KB + col] = v[m];
+    __syncthreads();
+    xfft_inplace<T>(s, tw, n, log2n, KB, false);
+#pragma unroll
+    for (int m = 0; m < PER; m++) {
+      const int j = jrow + rows * m;
+      base[(long long)g.nhp * j] = s[j * KB + col];
+    }
+    return;
+  }
+  // plain scalars, not C2<T>[PER]: held across the first transform as an array of the vector type, V^_z went through
+  // scratch memory (fp64: PER 16-byte stores and loads per thread)
+  T yx[PER], yy[PER], zx[PER], zy[PER];
+#pragma unroll
+  for (int m = 0; m < PER; m++) {
+    const C2<T> a = base[(long long)g.nhp * (jrow + rows * m)], b2 = base[g.Nhp + (long long)g.nhp * (jrow + rows * m)];
+    yx[m] = a.x, yy[m] = a.y, zx[m] = b2.x, zy[m] = b2.y;
+  }
+#pragma unroll
+  for (int m = 0; m < PER; m++) {
+    C2<T> a;
+    a.x = yx[m], a.y = yy[m];
+    s[(int)(__brev((unsigned)(jrow + rows * m)) >> shift) * KB + col] = a;
+  }
+  __syncthreads();
+  xfft_inplace<T>(s, tw, n, log2n, KB, false);
+#pragma unroll
+  for (int m = 0; m < PER; m++) {  // V^_y of the rows this thread stores
+    const C2<T> a = s[(jrow + rows * m) * KB + col];
+    yx[m] = a.x, yy[m] = a.y;
+  }
+  __syncthreads();  // every thread has taken its elements of the first transform out of the tile
+#pragma unroll
+  for (int m = 0; m < PER; m++) {
+    C2<T> a;
+    a.x = zx[m], a.y = zy[m];
+    s[(int)(__brev((unsigned)(jrow + rows * m)) >> shift) * KB + col] = a;
+  }
+  __syncthreads();
+  xfft_inplace<T>(s, tw, n, log2n, KB, false);
+  const double kz = kval(k0 + col, g.n, g.kfac);
+#pragma unroll
+  for (int m = 0; m < PER; m++) {
+    const int j = jrow + rows * m;
+    C2<T> a;
+    a.x = yx[m], a.y = yy[m];
+    const C2<T> w = bx_w_of<T>(kval(j, g.n, g.kfac), kz, a, s[j * KB + col]);
+    base[(long long)g.nhp * j] = w;
+  }
+}
 
 // ======================================================================================================
 // k_zbin_direct: the z pass of the inverse transform of the three displacement components fused into the one-pass
@@ -161,7 +252,7 @@ __global__ void __launch_bounds__(NZ) __attribute__((amdgpu_waves_per_eu(BCHMC_Z
 k_zbin_direct(Geo g, PosPar pp, SphPar sp, TilePar tp, int log2n, const C2<T> *__restrict__ twiddle,
               const C2<T> *__restrict__ ck, int *__restrict__ cnt, int *__restrict__ ovf, RecQuad *__restrict__ srec,
               T *__restrict__ V, double *__restrict__ zero_part, T *__restrict__ rho_zero,
-              long long *__restrict__ fix_zero, T *__restrict__ psi_out) {
+              long long *__restrict__ fix_zero, T *__restrict__ psi_out, T *__restrict__ vrec = nullptr) {
   constexpr int kSlots = 4 * NZ;  // = particles per workgroup: more distinct counters cannot occur, the probing terminates
   constexpr int kHashShift = 32 - (NZ == 128 ? 9 : (NZ == 256 ? 10 : 11));
   static_assert(NZ == 128 || NZ == 256 || NZ == 512, "k_zbin_direct: one thread per lattice site along z");
@@ -269,9 +360,7 @@ k_zbin_direct(Geo g, PosPar pp, SphPar sp, TilePar tp, int log2n, const C2<T> *_
       const int sh = (key[m] & 1) << 5;
       local[m] = (int)((atomicAdd(&hcnt[sl], 1ull << sh) >> sh) & 0xffffffffull);
     } else {
-      V[p[m]] = T(0);
-      V[p[m] + g.N] = T(0);
-      V[p[m] + 2 * g.N] = T(0);
+      v_zero<T>(V, vrec, p[m], g.N);
     }
   }
   if (PSI_ONLY) return;
@@ -310,20 +399,38 @@ k_zbin_direct(Geo g, PosPar pp, SphPar sp, TilePar tp, int log2n, const C2<T> *_
   }
 }
 
+// one V record {vx, vy, vz, unused} (vrec_store, tiles.hpp), as k_zr2c<.., REC> loads it
+template <typename T> struct VRec4 { T x, y, z, w; };
+template <typename T> __device__ __forceinline__ VRec4<T> vrec_load(const T *rec, long long p);
+template <> __device__ __forceinline__ VRec4<double> vrec_load<double>(const double *rec, long long p) {
+  const double2 *b = reinterpret_cast<const double2 *>(rec) + 2 * p;
+  const double2 lo = b[0], hi = b[1];
+  return {lo.x, lo.y, hi.x, hi.y};
+}
+template <> __device__ __forceinline__ VRec4<float> vrec_load<float>(const float *rec, long long p) {
+  const float4 v = reinterpret_cast<const float4 *>(rec)[p];
+  return {v.x, v.y, v.z, v.w};
+}
+
+
 // ======================================================================================================
 // k_zr2c: the row pass of the planes-mode R2C (unnormalised forward real transforms along z of the three components
 // of V), the mirror image of k_zbin_direct's transform part -- used where rocFFT's 2-D R2C is the slower pair
-// (512^3: its length-512 column kernel runs at 2.3 TB/s; k_zr2c + k_ypass<forward> at 5+).  One workgroup of n
-// threads per 2 x 2 x n column: thread t packs the rows (i0 + f, j0) and (i0 + f, j0 + 1) at z = t as a + i b into the
+// (512^3: its length-512 column kernel runs at 2.3 TB/s; k_zr2c + k_ypass<forward> at 5+) and wherever the column pass
+// that follows is k_ypass_fwd_pair.  One workgroup of n threads per 2 x 2 x n column: thread t packs the rows (i0 + f, j0) and (i0 + f, j0 + 1) at z = t as a + i b into the
 // six interleaved columns of the LDS tile, one radix-4 call, and the half-complex spectra come out of
 //   A[k] = (Z[k] + conj(Z[n - k])) / 2,   B[k] = (Z[k] - conj(Z[n - k])) / (2 i),   k = 0 .. n / 2.
 // Output layout: element (i, j, k) at k + nhp (j + n i) of each component, like rocFFT's row pass inside the 2-D plan;
 // the row padding k > n / 2 is left as it is (columns of the later passes are independent, reductions skip it).
 // Replaces the z part of fftR2Cplanned (fftwrapper.cc:104-119) for HMC_models.cc:342-349's three transforms of V.
-// The 128 and 256 instantiations are launched by bchmc_probe_displacement_z only (tests: a chosen displacement on its
-// way into k_zbin_direct); the hot path uses 512.
+// Launched wherever eval_vpair (256^3, 128^3 with BCHMC_ZBIN_128) or eval_yfwd (512^3) holds (eval_plan.hpp),
+// and by bchmc_probe_displacement_z (tests: a chosen displacement on its way into k_zbin_direct).  At 256^3 fp64 from
+// records: 0.97 GB in 0.173 ms.
+// REC: V is not three arrays but one record {vx, vy, vz, unused} of 4 T per lattice site, as k_gather_tile81<.., REC>
+// leaves it (v_rec, eval_plan.hpp): thread t loads the whole records of its four lattice sites (16-byte loads, lanes
+// consecutive in z) and never looks at the fourth word.  Only the loads differ.
 // ======================================================================================================
-template <typename T, int NZ>
+template <typename T, int NZ, bool REC = false>
 __global__ void __launch_bounds__(NZ)
 k_zr2c(Geo g, int log2n, const C2<T> *__restrict__ twiddle, const T *__restrict__ V, C2<T> *__restrict__ ck) {
   constexpr int KF = 6;
@@ -335,7 +442,26 @@ k_zr2c(Geo g, int log2n, const C2<T> *__restrict__ twiddle, const T *__restrict_
   const int nb = n >> 1;
   const int j0 = 2 * ((int)blockIdx.x % nb), i0 = 2 * ((int)blockIdx.x / nb);
   const int shift = 32 - log2n;
-  {
+  if (REC) {
+    const int r = (int)(__brev((unsigned)tid) >> shift) * KF;
+    VRec4<T> a[2], b[2];
+#pragma unroll
+    for (int f = 0; f < 2; f++) {
+      const long long p = tid + (long long)n * (j0 + (long long)n * (i0 + f));  // lattice site (i0 + f, j0, t)
+      a[f] = vrec_load<T>(V, p);
+      b[f] = vrec_load<T>(V, p + n);  // (i0 + f, j0 + 1, t)
+    }
+#pragma unroll
+    for (int f = 0; f < 2; f++) {
+      C2<T> v;
+      v.x = a[f].x, v.y = b[f].x;
+      s[r + f] = v;
+      v.x = a[f].y, v.y = b[f].y;
+      s[r + 2 + f] = v;
+      v.x = a[f].z, v.y = b[f].z;
+      s[r + 4 + f] = v;
+    }
+  } else {
     const int r = (int)(__brev((unsigned)tid) >> shift) * KF;
 #pragma unroll
     for (int c = 0; c < 3; c++)
