@@ -4254,6 +4254,9 @@ int bchmc_chain_set_momenta(bchmc_handle *h, const double *p) {
 int bchmc_chain_draw_momenta(bchmc_handle *h, uint64_t seed, uint64_t attempt) {
   if (!h) return BCHMC_ERR_ARG;
   ENTER(h);
+  // the attempt is one 32-bit word of the Philox counter: refuse what would wrap onto an earlier attempt's values
+  if (attempt >> 32)
+    return h->fail(BCHMC_ERR_ARG, "attempt = %llu does not fit the counter's 32-bit word", (unsigned long long)attempt);
   if (h->mass_fs && !h->have[BCHMC_F_MASS_F]) return h->fail(BCHMC_ERR_STATE, "mass_f was never uploaded");
   if (h->mass_rs && !h->have[BCHMC_F_MASS_R]) return h->fail(BCHMC_ERR_STATE, "mass_r was never uploaded");
   CHK(DISPATCH(h, chain_alloc(h)));

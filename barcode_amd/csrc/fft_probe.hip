@@ -20,6 +20,10 @@
 // F from the caller (build_conv_table is host code and not under test); k_interp_tsc takes the PosPar scalars (PosPar has
 // no lower corner: the domain of this kernel is [0, L] and periodic, as make_pos sets it).
 //
+// The Philox momentum draw's kernels (tests/test_gpu_draw.py) run the same way, as chain_draw launches them: k_white_noise
+// on nblk_stride((n + 1) / 2) x 256 over n values of any parity (seed words, attempt and stream as the kernel takes them,
+// var may be null), k_color_momenta on nblk_stride(nh) x 256 over nh complex elements (wM may be null; pk goes in too).
+//
 // Every device array is followed by kCanary bytes of a known pattern; an entry point copies its host arrays in,
 // launches, synchronises, copies back and checks the canaries.  Return value: 0 = ok, -1 = arguments outside the
 // engine's instantiations, -2 = HIP error, k > 0 = the canary after device array k changed (1 = the twiddle table,
@@ -645,6 +649,32 @@ int bispec_triple(int n_shell, long long count, const void *arrays, const unsign
   return 0;
 }
 
+// k_white_noise over n values as chain_draw launches it: var (n values of T, may be null), out (n values; goes in too)
+template <typename T>
+int white_noise(long long n, unsigned seed_lo, unsigned seed_hi, unsigned attempt, unsigned stream, const void *var, void *out_) {
+  if (n < 1 || n > (1ll << 27) || !out_) return -1;
+  Probe pr;
+  const T *dv = opt<const T>(pr, (size_t)n * sizeof(T), var);
+  T *dout = static_cast<T *>(pr.alloc((size_t)n * sizeof(T), out_));
+  const int i_out = (int)pr.bufs.size() - 1;
+  if (pr.err) return pr.err;
+  k_white_noise<T><<<nblk_stride((n + 1) / 2), 256>>>(n, make_uint2(seed_lo, seed_hi), attempt, stream, dv, dout);
+  return pr.finish({{i_out, out_}});
+}
+
+// k_color_momenta over nh complex elements: wk (nh complex), wM (nh doubles, may be null), pk (nh complex; goes in too)
+template <typename T> int color_momenta(long long nh, const void *wk, const double *wM, void *pk, int accumulate) {
+  if (nh < 1 || nh > (1ll << 27) || !wk || !pk) return -1;
+  Probe pr;
+  const C2<T> *dw = static_cast<const C2<T> *>(pr.alloc((size_t)nh * sizeof(C2<T>), wk));
+  const double *dm = opt<const double>(pr, (size_t)nh * sizeof(double), wM);
+  C2<T> *dp = static_cast<C2<T> *>(pr.alloc((size_t)nh * sizeof(C2<T>), pk));
+  const int i_pk = (int)pr.bufs.size() - 1;
+  if (pr.err) return pr.err;
+  k_color_momenta<T><<<nblk_stride(nh), 256>>>(nh, dw, dm, dp, accumulate);
+  return pr.finish({{i_pk, pk}});
+}
+
 }  // namespace
 
 // prec: 0 = double, 1 = float (the engine's storage type T); arrays are of that type, complex ones interleaved
@@ -840,6 +870,17 @@ int fftp_bispec_triple(int prec, int n_shell, long long count, const void *array
                        float *ms) {
   return prec ? bispec_triple<float>(n_shell, count, arrays, s3_end, sums, ms)
               : bispec_triple<double>(n_shell, count, arrays, s3_end, sums, ms);
+}
+
+// ---- the Philox momentum draw's two kernels (tests/test_gpu_draw.py).  Device arrays: the non-null ones in argument order.
+int fftp_white_noise(int prec, long long n, unsigned seed_lo, unsigned seed_hi, unsigned attempt, unsigned stream,
+                     const void *var, void *out) {
+  return prec ? white_noise<float>(n, seed_lo, seed_hi, attempt, stream, var, out)
+              : white_noise<double>(n, seed_lo, seed_hi, attempt, stream, var, out);
+}
+
+int fftp_color_momenta(int prec, long long nh, const void *wk, const double *wM, void *pk, int accumulate) {
+  return prec ? color_momenta<float>(nh, wk, wM, pk, accumulate) : color_momenta<double>(nh, wk, wM, pk, accumulate);
 }
 
 }  // extern "C"

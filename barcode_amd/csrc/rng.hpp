@@ -27,13 +27,19 @@ __device__ __forceinline__ uint4 philox4x32_10(uint4 c, uint2 k) {
 
 __global__ void k_philox_kat(uint4 ctr, uint2 key, uint4 *out) { *out = philox4x32_10(ctr, key); }
 
+// The engine's Philox counters, one map for both consumers (include/bchmc.h states it above bchmc_chain_draw_momenta):
+//   momentum draw     (i_lo, i_hi | kMomentumDomain, attempt, stream)     i: pair index, stream 0 Fourier / 1 real part
+//   Poisson sampler   (c_lo, c_hi, j or kk, 2 stream [+ 1])               c: cell index (poisson.hpp)
+// The high word of a pair or cell index never reaches bit 31, so the two can share no counter under any seed.
+constexpr unsigned kMomentumDomain = 0x80000000u;
+
 // out[2i], out[2i+1] = two independent N(0,1) (Box-Muller on two 53-bit uniforms), optionally times sqrt(var[.]).
 template <typename T>
 __global__ void __launch_bounds__(256)
 k_white_noise(long long n, uint2 key, unsigned attempt, unsigned stream, const T *__restrict__ var, T *__restrict__ out) {
   const long long pairs = (n + 1) / 2;
   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < pairs; i += (long long)gridDim.x * blockDim.x) {
-    const uint4 r = philox4x32_10(make_uint4((unsigned)i, (unsigned)(i >> 32), attempt, stream), key);
+    const uint4 r = philox4x32_10(make_uint4((unsigned)i, (unsigned)(i >> 32) | kMomentumDomain, attempt, stream), key);
     const double u1 = ((double)((((unsigned long long)r.x << 32) | r.y) >> 11) + 0.5) * (1.0 / 9007199254740992.0);
     const double u2 = ((double)((((unsigned long long)r.z << 32) | r.w) >> 11) + 0.5) * (1.0 / 9007199254740992.0);
     const double rad = sqrt(-2.0 * log(u1));

@@ -186,8 +186,21 @@ int bchmc_chain_set_state(bchmc_handle *h, const double *q);   /* hd->x -> HBM *
 int bchmc_chain_get_state(bchmc_handle *h, double *q);
 int bchmc_chain_set_momenta(bchmc_handle *h, const double *p); /* host-drawn momenta (reference RNG order) */
 int bchmc_chain_get_momenta(bchmc_handle *h, double *p);
-/* p ~ N(0, M) on the device: counter-based Philox4x32-10, a pure function of (seed, attempt, cell).  Statistical
- * stand-in for draw_momenta (HMC_momenta.cc:42-94), whose serial GSL stream it does not reproduce. */
+/* p ~ N(0, M) on the device: counter-based Philox4x32-10.  Statistical stand-in for draw_momenta (HMC_momenta.cc:42-94),
+ * whose serial GSL stream it does not reproduce.
+ * The values.  Pair i = 0 .. (N + 1) / 2 - 1 of white-noise array s (s = 0: the Fourier-space part, s = 1: the real-space
+ * part) takes r = philox4x32_10((i_lo, i_hi | 0x80000000, attempt, s), (seed_lo, seed_hi)), the two 53-bit uniforms
+ * u1 = (((r.x << 32 | r.y) >> 11) + 0.5) 2^-53 and u2 the same from r.z, r.w, and Box-Muller in double:
+ * w_s[2 i] = sqrt(-2 ln u1) cos(2 pi u2), w_s[2 i + 1] = sqrt(-2 ln u1) sin(2 pi u2) (the last one is dropped at odd N).
+ * Then p = IFFT[ FFT[w_0] sqrt(mass_f N / L^3) ] (0 where mass_f <= 0) + sqrt(mass_r) w_1 (0 where mass_r <= 0), each part
+ * only where mass_type has it: a pure function of (seed, attempt, cell), not of the launch shape or the handle's kind.
+ * The counter map of the engine's Philox4x32-10, every consumer, key = (seed_lo, seed_hi) throughout:
+ *     momentum draw, array s          (i_lo, i_hi | 0x80000000, attempt, s)      i: pair index, s in {0, 1}
+ *     Poisson counts (P1 below)       (c_lo, c_hi, j, 2 stream)                  c: cell index, j: iteration < 64
+ *     Poisson positions (P5 below)    (c_lo, c_hi, kk, 2 stream + 1)             kk: index of the particle in its cell
+ * A pair or cell index stays below 2^63, so bit 31 of the second word is set for the momentum draw and clear for the
+ * Poisson sampler: the two share no counter under any seed, attempt or stream, and one seed may serve both.
+ * attempt is one counter word: attempt >= 2^32 is BCHMC_ERR_ARG, the resident momenta untouched. */
 int bchmc_chain_draw_momenta(bchmc_handle *h, uint64_t seed, uint64_t attempt);
 /* draw_momenta (HMC_momenta.cc:42-94) on the device from the caller's GSL mt19937 state; mt/mti in: state before the
  * draw, out: the state GSL holds after it.  words_used may be NULL.
