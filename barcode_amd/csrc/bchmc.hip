@@ -14,6 +14,7 @@
 #include "pass_launch.hpp"
 #include "launch_grid.hpp"
 #include "eval_plan.hpp"
+#include "xtile_kernels.hpp"
 #include "interp_plan.hpp"
 
 #include <rocfft/rocfft.h>
@@ -71,10 +72,14 @@ struct bchmc_handle {
   DevBytes in_arr[6];
   bool have[6] = {false, false, false, false, false, false};
   DevBuf<double> wS, wM;  // normFS / signal_PS, normFS / mass_f on the half-complex layout
+  DevBuf<double2> wpair;  // Nhp: {wS, wM} in x-column tiles (xtile.hpp), made by trajectory_fused where x_tiles holds ...
+  unsigned long long w_gen = 1, wpair_gen = 0;  // ... and made again when upload() has written wS or wM since (w_gen moved)
 
   // state and scratch (T / C2<T>)
   DevBytes qk, pk, gk;                               // Nhp complex each
   DevBytes qk2, pk2;                                 // ping-pong partners of (qk, pk) for the fused step boundary
+  XLayout qk_layout = XLayout::kNatural;             // what (qk, pk) hold: tiled only between the opening and the closing
+                                                     // boundary of trajectory_fused (XPairs, xtile.hpp), natural on every return
   DevBytes Ck;                                       // 3 Nhp: Psi^ / V^
   bool ck_pair = false;                              // Ck holds Psi^_x | B of a boundary kernel with `pair` (psi_pair, eval_plan.hpp)
   DevBytes tC;                                       // Nhp scratch
@@ -734,6 +739,7 @@ PathSwitches read_path_switches() {
   s.no_pair = env_on("BCHMC_NO_PAIR");
   s.no_vpair = env_on("BCHMC_NO_VPAIR");
   s.no_vrec = env_on("BCHMC_NO_VREC");
+  s.no_xtile = env_on("BCHMC_NO_XTILE");
   return s;
 }
 
@@ -747,7 +753,7 @@ PathFacts path_facts(bchmc_handle *h, int rsd) {
   f.planes_ok = h->planes_ok && h->xtw;
   f.tiled = h->plan.tiled, f.sort_direct = h->plan.slots.sort_direct, f.std81 = h->plan.std81;
   f.mk = h->c.mk, f.calc_h = h->c.calc_h, f.likelihood = h->c.likelihood, f.sfmodel = h->c.sfmodel;
-  f.rsd_model = h->c.rsd_model, f.mass_rs = h->mass_rs != 0;
+  f.rsd_model = h->c.rsd_model, f.mass_rs = h->mass_rs != 0, f.mass_fs = h->mass_fs != 0;
   if (alpt_planes_wanted(f, h->sw, rsd) && !h->c2r2d_2 && !h->alpt_plans_failed &&
       make_plans_2d(h, 2 * (size_t)h->g.n, h->r2c2d_2, h->c2r2d_2) != BCHMC_OK)
     h->alpt_plans_failed = true;
@@ -1873,21 +1879,26 @@ struct Pipe {
     return fft_exec(h, h->r2c1, staging, out, BCHMC_K_FFT_R2C);
   }
 
-  // xk / N -> C2R -> T array
-  static int c2r_scaled(bchmc_handle *h, const void *xk, void *out_T) {
+  // xk / N -> C2R -> T array.  xtiled: xk is in x-column tiles (the early q of a tiled trajectory); the scaling pass
+  // un-tiles it on the way.
+  static int c2r_scaled(bchmc_handle *h, const void *xk, void *out_T, bool xtiled = false) {
     {
       ProfScope ps(h, BCHMC_K_OTHER);
-      k_scale_c<T><<<nblk_stride(h->g.Nhp), 256, 0, h->stream>>>(h->g.Nhp, reinterpret_cast<const CT *>(xk), C(h->tC),
-                                                                1. / (double)h->g.N);
+      if (xtiled)
+        k_xtile_scale_c<T><<<nblk_stride(h->g.Nhp), 256, 0, h->stream>>>(h->g, reinterpret_cast<const CT *>(xk), C(h->tC),
+                                                                        1. / (double)h->g.N);
+      else
+        k_scale_c<T><<<nblk_stride(h->g.Nhp), 256, 0, h->stream>>>(h->g.Nhp, reinterpret_cast<const CT *>(xk), C(h->tC),
+                                                                  1. / (double)h->g.N);
       HIPCHK(hipGetLastError());
     }
     return fft_exec(h, h->c2r1, h->tC, out_T, BCHMC_K_FFT_C2R);
   }
 
   // C2R of a k-space state into an ABI (double) device array; `scratch_T` is used when T != double.
-  static int c2r_state(bchmc_handle *h, const void *xk, void *scratch_T, double *d_out) {
-    if (kDouble) return c2r_scaled(h, xk, d_out);
-    CHK(c2r_scaled(h, xk, scratch_T));
+  static int c2r_state(bchmc_handle *h, const void *xk, void *scratch_T, double *d_out, bool xtiled = false) {
+    if (kDouble) return c2r_scaled(h, xk, d_out, xtiled);
+    CHK(c2r_scaled(h, xk, scratch_T, xtiled));
     return store_real(h, R(scratch_T), d_out);
   }
 
@@ -1925,6 +1936,7 @@ struct Pipe {
     TrajPlan p;
     double a, c_za;
     bool pair;  // the Zel'dovich boundaries leave Psi^_x | B (psi_pair)
+    bool xt;    // a fused trajectory keeps its state and weights in x-column tiles (x_tiles, xtile.hpp)
   };
   static Traj traj(bchmc_handle *h) {
     Traj t;
@@ -1933,11 +1945,12 @@ struct Pipe {
     t.a = h->c.grad_psi_prior_factor;
     t.c_za = (t.p.c_za == CZa::kAlptInput ? 1. : -h->c.D1) * h->c.deltaQ_factor / (double)h->g.N;
     t.pair = psi_pair(t.f, h->sw, t.p);
+    t.xt = x_tiles(t.f, h->sw, t.p);
     return t;
   }
 
   // k_step_boundary_x for this grid, one tile per workgroup
-  template <int MODE, bool ALPT = false>
+  template <int MODE, bool ALPT = false, bool XT = false>
   static int launch_boundary_x(bchmc_handle *h, BoundaryX<T> bx) {
     // the forward side of this boundary reads what the last forward transform left in Ck: V^_x | W, or three arrays
     if (MODE != BX_FIRST) {
@@ -1945,7 +1958,7 @@ struct Pipe {
       bx.vpair = h->ck_vpair;
       h->ck_vpair = false;
     }
-    HIPCHK((launch_step_boundary_x<T, MODE, ALPT>(pass_ctx(h), C(h->Ck), h->wS, bx)));
+    HIPCHK((launch_step_boundary_x<T, MODE, ALPT, XT>(pass_ctx(h), C(h->Ck), h->wS, bx)));
     h->ck_pair = bx.pair && !ALPT && MODE != BX_LAST;  // as launch_step_boundary_x told the kernel
     return BCHMC_OK;
   }
@@ -2051,22 +2064,34 @@ struct Pipe {
       CHK(dev_alloc(h, h->qk2, 2 * (size_t)h->g.Nhp * sizeof(T)));
       CHK(dev_alloc(h, h->pk2, 2 * (size_t)h->g.Nhp * sizeof(T)));
     }
-    void *const q0 = h->qk, *const p0 = h->pk, *const q1 = h->qk2, *const p1 = h->pk2;
+    // Between the opening and the closing boundary the pairs may hold the x-column tile layout (xtile.hpp): `xp` follows
+    // which pair holds what, launch by launch, and a kernel that would read one layout as the other is refused.
+    const bool xt = t.xt;
+    const char *const wrong_layout = "a k-space state pair in one layout, and a kernel that reads the other";
+    if (h->qk_layout != XLayout::kNatural) return h->fail(BCHMC_ERR_STATE, wrong_layout);
+    if (xt) CHK(tiled_weights(h));
+    XPairs xp;
+    void *const qb[2] = {h->qk, h->qk2}, *const pb[2] = {h->pk, h->pk2};
     int like_mode = 2;
     double b = 0.;
-    int cur = 0;  // boundary j reads pair j % 2
     {
+      const Opening op = opening(t.f, h->sw, t.p);
+      if (!xp.open(xt, op == Opening::kBxFirst)) return h->fail(BCHMC_ERR_STATE, wrong_layout);
       StepCtl ctl{h->stop, h->steps_done, nullptr, guard_limit, 0};
       ProfScope ps(h, BCHMC_K_KSPACE_DRIFT_ZA);
-      BoundaryX<T> bx;
-      bx.qi = bx.qo = C(q0), bx.pi = bx.po = C(p0), bx.wM = wM, bx.half_eps = 0.5 * eps, bx.eps = eps, bx.c_za = c_za;
+      BoundaryX<T> bx;  // natural: in place; tiled: pair 0 natural -> pair 1 tiled
+      bx.qi = C(qb[0]), bx.pi = C(pb[0]), bx.qo = C(qb[xp.cur]), bx.po = C(pb[xp.cur]), bx.wM = wM, bx.wpair = h->wpair;
+      bx.half_eps = 0.5 * eps, bx.eps = eps, bx.c_za = c_za;
       bx.ctl = ctl, bx.g_in = C(g_first), bx.pair = t.pair;
-      switch (opening(t.f, h->sw, t.p)) {
+      switch (op) {
         case Opening::kBxFirstAlpt: CHK((launch_boundary_x<BX_FIRST, true>(h, bx))); break;
-        case Opening::kBxFirst: CHK(launch_boundary_x<BX_FIRST>(h, bx)); break;
+        case Opening::kBxFirst:
+          if (xt) CHK((launch_boundary_x<BX_FIRST, false, true>(h, bx)));
+          else CHK(launch_boundary_x<BX_FIRST>(h, bx));
+          break;
         case Opening::kKickDriftZa:
           h->ck_pair = false;
-          k_kick_drift_za<T, true><<<nblk_stride(h->g.Nhp), 256, 0, h->stream>>>(h->g, C(q0), C(p0), C(g_first), wM,
+          k_kick_drift_za<T, true><<<nblk_stride(h->g.Nhp), 256, 0, h->stream>>>(h->g, C(qb[0]), C(pb[0]), C(g_first), wM,
                                                                                nullptr, C(h->Ck), 0.5 * eps, eps, c_za, ctl);
           break;
       }
@@ -2078,7 +2103,7 @@ struct Pipe {
         // the last boundary only kicks p: this is the final q (unless the runaway guard stops the trajectory, which the
         // caller checks).  Its real-space copy is made now, so that its transfer to the host runs beside the force
         // evaluation that follows.
-        CHK(c2r_state(h, cur ? q1 : q0, h->ioq, h->early_q_dev));
+        CHK(c2r_state(h, qb[xp.cur], h->ioq, h->early_q_dev, xp.q[xp.cur] == XLayout::kTiled));
         HIPCHK(hipEventRecord(h->ev_q, h->stream));
         h->early_q_done = true;
       }
@@ -2087,15 +2112,19 @@ struct Pipe {
       CHK(force_sources(h, true, step_mode(t.f, h->sw, t.p, s, neps), &like_mode, &b));
       if (tap && tap->like_f && last) CHK(tap_loglike(h, tap->like_f));
       StepCtl ctl{h->stop, h->steps_done, s > 0 ? h->guard + (s - 1) : nullptr, guard_limit, s};
-      void *qi = cur ? q1 : q0, *pi = cur ? p1 : p0, *qo = cur ? q0 : q1, *po = cur ? p0 : p1;
+      const Closing cl = closing(t.f, h->sw, t.p, s, neps, like_mode);
+      const int src = xp.cur, dst = xp.dst(xt, last);
+      if (!xp.close(xt, cl, last)) return h->fail(BCHMC_ERR_STATE, wrong_layout);
+      void *qi = qb[src], *pi = pb[src], *qo = qb[src ^ 1], *po = pb[src ^ 1];
       ProfScope ps(h, BCHMC_K_KSPACE_FORCE_KICK);
-      BoundaryX<T> bx;  // the interior boundary; the last one writes p in place, no q, and leaves the gradient in gk
+      BoundaryX<T> bx;  // the interior boundary; the last one writes p (natural: in place), no q, and leaves the gradient in gk
       bx.qi = C(qi), bx.pi = C(pi), bx.qo = C(qo), bx.po = C(po), bx.wM = wM, bx.a = a, bx.b = b, bx.half_eps = 0.5 * eps;
-      bx.eps = eps, bx.c_za = c_za, bx.guard_slot = h->guard + s, bx.ctl = ctl, bx.pair = t.pair;
-      switch (closing(t.f, h->sw, t.p, s, neps, like_mode)) {
+      bx.eps = eps, bx.c_za = c_za, bx.guard_slot = h->guard + s, bx.ctl = ctl, bx.pair = t.pair, bx.wpair = h->wpair;
+      switch (cl) {
         case Closing::kBxLast:
-          bx.qo = nullptr, bx.po = C(pi), bx.g_out = C(h->gk);
-          CHK(launch_boundary_x<BX_LAST>(h, bx));
+          bx.qo = nullptr, bx.po = C(pb[dst]), bx.g_out = C(h->gk);
+          if (xt) CHK((launch_boundary_x<BX_LAST, false, true>(h, bx)));
+          else CHK(launch_boundary_x<BX_LAST>(h, bx));
           break;
         case Closing::kStepBoundaryLast:
           if (h->ck_vpair) return h->fail(BCHMC_ERR_STATE, "two arrays of V^ in Ck, and a boundary that reads three");
@@ -2104,11 +2133,15 @@ struct Pipe {
               h->guard + s, ctl);
           break;
         case Closing::kBxInteriorAlpt: CHK((launch_boundary_x<BX_INTERIOR, true>(h, bx))); break;
-        case Closing::kBxInterior: CHK(launch_boundary_x<BX_INTERIOR>(h, bx)); break;
+        case Closing::kBxInterior:
+          if (xt) CHK((launch_boundary_x<BX_INTERIOR, false, true>(h, bx)));
+          else CHK(launch_boundary_x<BX_INTERIOR>(h, bx));
+          break;
         case Closing::kBxInteriorTwoTile:
           bx.vpair = h->ck_vpair;
           h->ck_vpair = false;
-          HIPCHK(launch_step_boundary_x2<T>(pass_ctx(h), C(h->Ck), h->wS, bx));
+          if (xt) HIPCHK((launch_step_boundary_x2<T, true>(pass_ctx(h), C(h->Ck), h->wS, bx)));
+          else HIPCHK(launch_step_boundary_x2<T>(pass_ctx(h), C(h->Ck), h->wS, bx));
           h->ck_pair = bx.pair;
           break;
         case Closing::kStepBoundary:
@@ -2118,19 +2151,42 @@ struct Pipe {
               h->guard + s, ctl);
           break;
       }
-      if (buffers_flip(s, neps)) cur ^= 1;
       HIPCHK(hipGetLastError());
     }
+    const int fin = xp.cur, res = xp.result(xt);
+    if (!xp.finish(xt)) return h->fail(BCHMC_ERR_STATE, wrong_layout);
     {
       ProfScope ps(h, BCHMC_K_OTHER);
-      k_rollback<T><<<nblk_stride(h->g.Nhp), 256, 0, h->stream>>>(h->g.Nhp, h->stop, h->steps_done, C(q0), C(p0), C(q1),
-                                                                 C(p1), C(cur ? q1 : q0), C(cur ? p1 : p0));
+      if (xt) {
+        // the final q, or the state a guard stop rolls back to, out of the tiles: natural in pair `res`.  Ck is dead after
+        // the last boundary; its first two components are the stop path's scratch.
+        CT *const sq = C(h->Ck), *const sp = C(h->Ck) + h->g.Nhp;
+        k_xtile_finish<T><<<nblk_stride(h->g.Nhp), 256, 0, h->stream>>>(h->g, h->stop, h->steps_done, C(qb[0]), C(pb[0]),
+                                                                       C(qb[1]), C(pb[1]), fin, C(qb[res]), sq, sp);
+        HIPCHK(hipGetLastError());
+        k_xtile_restore<T><<<nblk_stride(h->g.Nhp), 256, 0, h->stream>>>(h->g.Nhp, h->stop, sq, sp, C(qb[res]), C(pb[res]));
+      } else {
+        k_rollback<T><<<nblk_stride(h->g.Nhp), 256, 0, h->stream>>>(h->g.Nhp, h->stop, h->steps_done, C(qb[0]), C(pb[0]),
+                                                                   C(qb[1]), C(pb[1]), C(qb[res]), C(pb[res]));
+      }
       HIPCHK(hipGetLastError());
     }
-    if (cur) {
+    h->qk_layout = xp.q[res];  // natural: finish() has checked it
+    if (res) {
       std::swap(h->qk, h->qk2);
       std::swap(h->pk, h->pk2);
     }
+    return BCHMC_OK;
+  }
+
+  // {wS, wM} in x-column tiles for the tiled boundary kernels: made on first use and again after an upload of either
+  static int tiled_weights(bchmc_handle *h) {
+    if (!h->wpair) CHK(dev_alloc(h, h->wpair, (size_t)h->g.Nhp));
+    else if (h->wpair_gen == h->w_gen) return BCHMC_OK;
+    ProfScope ps(h, BCHMC_K_OTHER);
+    k_xtile_weights<<<nblk_stride(h->g.Nhp), 256, 0, h->stream>>>(h->g, pass_kb((int)sizeof(T)), h->wS, h->wM, h->wpair);
+    HIPCHK(hipGetLastError());
+    h->wpair_gen = h->w_gen;
     return BCHMC_OK;
   }
 
@@ -3066,6 +3122,7 @@ struct Pipe {
       double *w = field == BCHMC_F_SIGNAL_PS ? h->wS : h->wM;
       k_prepare_mult<<<nblk_stride(h->g.Nhp), 256, 0, h->stream>>>(h->g, d_src, w, normFS);
       HIPCHK(hipGetLastError());
+      h->w_gen++;  // the tiled pair {wS, wM} is stale (trajectory_fused makes it again)
     }
     return BCHMC_OK;
   }

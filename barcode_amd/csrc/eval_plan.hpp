@@ -6,6 +6,9 @@
 // against literals and sweeps the whole space
 // (psi_pair, the two arrays between the inverse x and y passes: tests/host/two_array_check.cpp; v_pair / v_rec, their
 // mirror image on the forward side: tests/host/vpair_check.cpp).
+// Whether a fused trajectory keeps its k-space state and weights in x-column tiles between its opening and its closing
+// boundary (BCHMC_NO_XTILE=1: never) is decided next door, in xtile.hpp (x_tiles; tests/host/xtile_check.cpp), from the same
+// switches and facts.
 //
 // Nothing here is cached and nothing should be: sort_direct changes when the record slots are given up, and the plans over
 // 2 n planes can appear late.  bchmc.hip gathers the facts when it needs a decision, asks, and switches on the answer.
@@ -28,6 +31,7 @@ struct PathSwitches {           // BCHMC_<NAME>=1, read once per handle
   bool no_pair = false;         // NO_PAIR: three arrays, not two, between the inverse x pass and the y pass
   bool no_vpair = false;        // NO_VPAIR: rocFFT's 2-D R2C of the three arrays of V and three arrays into the forward x pass
   bool no_vrec = false;         // NO_VREC: the gather's V as three arrays, not one record per particle
+  bool no_xtile = false;        // NO_XTILE: the natural layout for the trajectory's k-space state and weights (xtile.hpp)
 };
 
 struct PathFacts {
@@ -40,6 +44,7 @@ struct PathFacts {
   bool mass_rs = false;      // the mass has a real-space part
   bool alpt_plans = false;   // the 2-D plans over 2 n planes exist
   bool std81 = false;        // ... the tile-sorted path gathers with the standard 81-cell hull (k_gather_tile81)
+  bool mass_fs = false;      // the mass has a k-space part (wM exists)
 };
 
 struct EvalMode {             // how ONE force evaluation runs; decided by the caller

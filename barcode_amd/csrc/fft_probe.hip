@@ -32,6 +32,7 @@
 #include "fft_host.hpp"
 #include "pass_launch.hpp"
 #include "launch_grid.hpp"
+#include "xtile_kernels.hpp"
 
 #include <cmath>
 #include <cstring>
@@ -273,8 +274,10 @@ void out(Outs &o, int idx, void *host) {
 template <typename T>
 int step_boundary_x(int n, double L, int mode, int alpt, int two_tile, void *Ck, const void *q_in, const void *p_in,
                     const void *g_in, void *q_out, void *p_out, void *g_out, const double *wS, const double *wM,
-                    const double *scal, double *guard_slot, const CtlArgs &ca, int vpair = 0) {
+                    const double *scal, double *guard_slot, const CtlArgs &ca, int vpair = 0, const void *wpair = nullptr) {
   if (mode < BX_INTERIOR || mode > BX_LAST || (alpt && mode == BX_LAST)) return -1;
+  const bool xt = wpair != nullptr;  // the XT instantiations: state and weights in x-column tiles (xtile.hpp)
+  if (xt && (alpt || !wM || !p_in || (mode != BX_LAST && !q_out) || !p_out || (mode == BX_FIRST && !g_in))) return -1;
   if (vpair && (alpt || mode == BX_FIRST)) return -1;
   if (two_tile ? (!x2_shape(sizeof(T), n).nt || mode != BX_INTERIOR || alpt) : !x_shape(sizeof(T), n).nt) return -1;
   const Geo g = probe_geo(n, (int)sizeof(T), L);
@@ -304,9 +307,14 @@ int step_boundary_x(int n, double L, int mode, int alpt, int two_tile, void *Ck,
   const CtlDev cd = ctl_alloc(pr, ca);
   a.ctl = cd.ctl;
   a.vpair = vpair != 0;
+  a.wpair = opt<const double2>(pr, (size_t)g.Nhp * sizeof(double2), wpair);
   if (pr.err) return pr.err;
   hipError_t e = hipErrorInvalidConfiguration;
-  if (two_tile) e = launch_step_boundary_x2<T>(x, d_ck, d_ws, a);
+  if (xt && two_tile) e = launch_step_boundary_x2<T, true>(x, d_ck, d_ws, a);
+  else if (xt && mode == BX_INTERIOR) e = launch_step_boundary_x<T, BX_INTERIOR, false, true>(x, d_ck, d_ws, a);
+  else if (xt && mode == BX_FIRST) e = launch_step_boundary_x<T, BX_FIRST, false, true>(x, d_ck, d_ws, a);
+  else if (xt) e = launch_step_boundary_x<T, BX_LAST, false, true>(x, d_ck, d_ws, a);
+  else if (two_tile) e = launch_step_boundary_x2<T>(x, d_ck, d_ws, a);
   else if (mode == BX_INTERIOR) e = alpt ? launch_step_boundary_x<T, BX_INTERIOR, true>(x, d_ck, d_ws, a)
                                          : launch_step_boundary_x<T, BX_INTERIOR, false>(x, d_ck, d_ws, a);
   else if (mode == BX_FIRST) e = alpt ? launch_step_boundary_x<T, BX_FIRST, true>(x, d_ck, d_ws, a)
@@ -751,6 +759,38 @@ int fftp_step_boundary_x_vpair(int prec, int n, double box_len, int mode, int al
                                        scal, guard_slot, ca, vpair)
               : step_boundary_x<double>(n, box_len, mode, alpt, two_tile, Ck, q_in, p_in, g_in, q_out, p_out, g_out, wS, wM,
                                         scal, guard_slot, ca, vpair);
+}
+
+// fftp_step_boundary_x_vpair through the XT instantiations (Zel'dovich; wM required): wpair = n^2 nhp {wS, wM} in x-column
+// tiles (xtile.hpp), and of the state arrays q_in, p_in (interior, last), q_out, p_out (interior, first) are tiled too -- Ck,
+// g_in, g_out and the last boundary's p_out natural.  wS is not read.  wpair is the last device array of a canary return.
+int fftp_step_boundary_x_xtile(int prec, int n, double box_len, int mode, int two_tile, void *Ck, const void *q_in,
+                               const void *p_in, const void *g_in, void *q_out, void *p_out, void *g_out, const double *wS,
+                               const double *wM, const double *scal, double *guard_slot, int *stop,
+                               unsigned long long *steps_done, const double *guard_prev, double guard_limit,
+                               unsigned long long step_index, int vpair, const void *wpair) {
+  const CtlArgs ca{stop, steps_done, guard_prev, guard_limit, step_index};
+  if (!stop || !steps_done || !wpair) return -1;
+  return prec ? step_boundary_x<float>(n, box_len, mode, 0, two_tile, Ck, q_in, p_in, g_in, q_out, p_out, g_out, wS, wM,
+                                       scal, guard_slot, ca, vpair, wpair)
+              : step_boundary_x<double>(n, box_len, mode, 0, two_tile, Ck, q_in, p_in, g_in, q_out, p_out, g_out, wS, wM,
+                                        scal, guard_slot, ca, vpair, wpair);
+}
+
+// k_xtile_weights as trajectory_fused launches it: wS, wM (n^2 nhp doubles, natural) -> pair (n^2 nhp {wS, wM}, tiled for
+// the storage type's KB).  Device arrays: 1 wS, 2 wM, 3 pair.
+int fftp_xtile_weights(int prec, int n, const double *wS, const double *wM, void *pair) {
+  const int esz = prec ? 4 : 8;
+  if (!x_shape(esz, n).nt || !wS || !wM || !pair) return -1;
+  const Geo g = probe_geo(n, esz);
+  if (g.nhp % pass_kb(esz)) return -1;
+  Probe pr;
+  const size_t db = (size_t)g.Nhp * sizeof(double);
+  const double *d_ws = static_cast<const double *>(pr.alloc(db, wS)), *d_wm = static_cast<const double *>(pr.alloc(db, wM));
+  double2 *d_pair = static_cast<double2 *>(pr.alloc(2 * db, pair));
+  if (pr.err) return pr.err;
+  k_xtile_weights<<<nblk_stride(g.Nhp), 256>>>(g, pass_kb(esz), d_ws, d_wm, d_pair);
+  return pr.finish({{2, pair}});
 }
 
 // k_alpt_mix_x on Ck (3 n^2 nhp complex in planes space: A^, B^ in; the three displacement components out)

@@ -189,25 +189,30 @@ struct BoundaryX {
   C2<T> *g_out = nullptr;
   bool pair = false;  // the Zel'dovich inverse side leaves Psi^_x | B for k_ypass_pair instead of the three Psi^ components
   bool vpair = false;  // the Zel'dovich forward side reads V^_x | W as k_ypass_fwd_pair left them, not the three V^ components
+  const double2 *wpair = nullptr;  // XT launches: {wS, wM} in x-column tiles (xtile.hpp); wS is not read then
 };
 
-template <typename T, int MODE, bool ALPT>
+// XT: the state (and a.wpair) in x-column tiles, as the kernel's comment says for each MODE; it needs a.wpair and, where
+// the mode writes p, a p_out that is not p_in
+template <typename T, int MODE, bool ALPT, bool XT = false>
 hipError_t launch_step_boundary_x(const PassCtx<T> &x, C2<T> *Ck, const double *wS, const BoundaryX<T> &a) {
+  if (XT && (!a.wpair || !a.wM || a.po == a.pi || a.qo == a.qi)) return hipErrorInvalidValue;
   return pass_dispatch<x_shape, T>(x.g.n, [&](auto nt, auto per) {
-    return launch_dyn_lds(x.stream, k_step_boundary_x<T, nt, per, MODE, ALPT>, x.col_grid(), nt, x.col_lds(), x.g, x.log2n,
-                          x.tw, Ck, a.qi, a.pi, a.qo, a.po, wS, a.wM, a.a, a.b, a.half_eps, a.eps, a.c_za, a.guard_slot,
-                          a.ctl, a.g_in, a.g_out, a.pair && !ALPT && MODE != BX_LAST,
-                          a.vpair && !ALPT && MODE != BX_FIRST);
+    return launch_dyn_lds(x.stream, k_step_boundary_x<T, nt, per, MODE, ALPT, XT>, x.col_grid(), nt, x.col_lds(), x.g,
+                          x.log2n, x.tw, Ck, a.qi, a.pi, a.qo, a.po, wS, a.wM, a.a, a.b, a.half_eps, a.eps, a.c_za,
+                          a.guard_slot, a.ctl, a.g_in, a.g_out, a.pair && !ALPT && MODE != BX_LAST,
+                          a.vpair && !ALPT && MODE != BX_FIRST, a.wpair);
   });
 }
 
 // the two-tile formulation of the interior Zel'dovich boundary (no g_in / g_out)
-template <typename T>
+template <typename T, bool XT = false>
 hipError_t launch_step_boundary_x2(const PassCtx<T> &x, C2<T> *Ck, const double *wS, const BoundaryX<T> &a) {
+  if (XT && (!a.wpair || !a.wM || a.po == a.pi || a.qo == a.qi)) return hipErrorInvalidValue;
   return pass_dispatch<x2_shape, T>(x.g.n, [&](auto nt, auto per) {
-    return launch_dyn_lds(x.stream, k_step_boundary_x2<T, nt, per>, x.col_grid(), nt, x.col_lds(2), x.g, x.log2n, x.tw, Ck,
-                          a.qi, a.pi, a.qo, a.po, wS, a.wM, a.a, a.b, a.half_eps, a.eps, a.c_za, a.guard_slot, a.ctl, a.pair,
-                          a.vpair);
+    return launch_dyn_lds(x.stream, k_step_boundary_x2<T, nt, per, XT>, x.col_grid(), nt, x.col_lds(2), x.g, x.log2n, x.tw,
+                          Ck, a.qi, a.pi, a.qo, a.po, wS, a.wM, a.a, a.b, a.half_eps, a.eps, a.c_za, a.guard_slot, a.ctl,
+                          a.pair, a.vpair, a.wpair);
   });
 }
 

@@ -67,6 +67,16 @@ __device__ __forceinline__ double bx_load(const double *p) {
   return BCHMC_BX_NT >= 2 ? __builtin_nontemporal_load(p) : *p;
 }
 
+// base + a 32-bit byte offset: a uniform base pointer and a lane offset are the `saddr` form of the global instructions
+template <typename U>
+__device__ __forceinline__ const U *bx_at(const U *base, unsigned off) {
+  return reinterpret_cast<const U *>(reinterpret_cast<const char *>(base) + off);
+}
+template <typename U>
+__device__ __forceinline__ U *bx_at(U *base, unsigned off) {
+  return reinterpret_cast<U *>(reinterpret_cast<char *>(base) + off);
+}
+
 template <typename T>
 __device__ __forceinline__ C2<T> cmul(const C2<T> a, const C2<T> b) {
   C2<T> r;
@@ -169,12 +179,24 @@ enum { BX_INTERIOR = 0, BX_FIRST = 1, BX_LAST = 2 };
 // below) the two fields Lag2Eul_non_zeldovich starts from -- delta(1)^ = c_za q^' into component 0 and the Poisson
 // solution Phi^ = -delta(1)^ / k^2 (0 at k = 0; PoissonSolver, EqSolvers.cc:29-64: no Nyquist zeroing) into component 1
 // of Ck, with c_za = deltaQ_factor / N.  The ALPT model's own pipeline (alpt_x.hpp) takes over from there.
-template <typename T, int NT, int PER, int MODE = BX_INTERIOR, bool ALPT = false>
+//
+// XT = true (Zel'dovich, inside trajectory_fused only; x_tiles in xtile.hpp): the state and the weights in x-column tiles.
+// This workgroup's tile t = j (nhp / KB) + k0 / KB is the contiguous run of n KB elements at t n KB, element (i, c) of it at
+// i KB + c (xtile_index): whole lines in sequence instead of 128-byte segments one plane apart, behind a uniform base with a
+// 32-bit lane offset.  The weights come as ONE load from wpair = {wS, wM} in the same layout (wS is not read; wM only says
+// that a mass exists).  Which arrays are tiled:
+//   BX_INTERIOR  q_in, p_in, q_out, p_out;
+//   BX_FIRST     q_out, p_out (q_in, p_in and g_in natural: the opening converts, so it cannot update in place);
+//   BX_LAST      q_in, p_in (p_out and g_out natural: the closing converts, so p_out must not be p_in).
+// Ck, g_in and g_out are natural always.  The arithmetic per element and its order are those of XT = false.
+template <typename T, int NT, int PER, int MODE = BX_INTERIOR, bool ALPT = false, bool XT = false>
 __global__ void __launch_bounds__(NT, BCHMC_BX_WAVES)
 k_step_boundary_x(Geo g, int log2n, const C2<T> *__restrict__ twiddle, C2<T> *Ck, const C2<T> *q_in, const C2<T> *p_in,
                   C2<T> *q_out, C2<T> *p_out, const double *__restrict__ wS, const double *__restrict__ wM, double a,
                   double b, double half_eps, double eps, double c_za, double *guard_slot, StepCtl ctl,
-                  const C2<T> *g_in = nullptr, C2<T> *g_out = nullptr, bool pair = false, bool vpair = false) {
+                  const C2<T> *g_in = nullptr, C2<T> *g_out = nullptr, bool pair = false, bool vpair = false,
+                  const double2 *__restrict__ wpair = nullptr) {
+  static_assert(!(XT && ALPT), "the ALPT boundary has no tiled form");
   constexpr int KB = 128 / (int)sizeof(C2<T>);
   constexpr int kMaxPer = PER;  // elements of one component per thread: n == PER * NT / KB (checked by the host)
   extern __shared__ __attribute__((aligned(16))) unsigned char s_raw_x[];
@@ -207,6 +229,11 @@ k_step_boundary_x(Geo g, int log2n, const C2<T> *__restrict__ twiddle, C2<T> *Ck
   const long long col = k + (long long)g.nhp * j;  // element (0, j, k)
   const double ky = kval(j, g.n, g.kfac), kz = kval(k, g.n, g.kfac);
   const int shift = 32 - log2n;
+  // XT: the tile's base in elements (uniform), for the state arrays and the weight pair alike
+  const long long tbase = XT ? (long long)bid * n * KB : 0;
+  const C2<T> *const qt_in = q_in + tbase, *const pt_in = p_in + tbase;
+  C2<T> *const qt_out = q_out + tbase, *const pt_out = p_out + tbase;
+  const double2 *const wt = wpair + tbase;
   double2 hk[kMaxPer];
   // ---- forward x passes.  ky and kz are constants of a column, so V^_y and V^_z go through ONE transform as
   // ky V_y + kz V_z:  h^ = (1/k^2) [ kx (Im V^_x, -Re V^_x) + (Im W^, -Re W^) ],  W = ky V_y + kz V_z ----
@@ -255,24 +282,41 @@ k_step_boundary_x(Geo g, int log2n, const C2<T> *__restrict__ twiddle, C2<T> *Ck
     const double kx = kval(i, g.n, g.kfac);
     const double ksq = kx * kx + ky * ky + kz * kz;
     const bool nyq = (i == g.n / 2) || (j == g.n / 2) || (k == g.n / 2);
+    const unsigned te = (unsigned)(i * KB + c);                        // XT: element (i, c) of the tile ...
+    const unsigned tb = te * (unsigned)sizeof(C2<T>), wb = te * 16u;  // ... as byte offsets into state and weight pair
     double2 q;
     if (MODE == BX_INTERIOR) {
-      const C2<T> t = bx_load(q_in + idx);
+      const C2<T> t = XT ? bx_load(bx_at(qt_in, tb)) : bx_load(q_in + idx);
+      q = make_double2((double)t.x, (double)t.y);
+    } else if (XT && MODE == BX_LAST) {
+      const C2<T> t = *bx_at(qt_in, tb);
       q = make_double2((double)t.x, (double)t.y);
     } else q = ld2<T>(q_in, idx);
+    double2 w2 = make_double2(0., 0.);  // XT: {wS, wM} of the element
+    if (XT && MODE == BX_INTERIOR) w2 = bx_load(bx_at(wt, wb));
     if (MODE == BX_FIRST) {
       if (g_in) {  // k_kick_drift_za<DRIFT>: the drift uses the kicked momentum before it is rounded to T
         double2 p = ld2<T>(p_in, idx);
         const double2 g0 = ld2<T>(g_in, idx);
         p.x -= half_eps * g0.x;
         p.y -= half_eps * g0.y;
-        st2<T>(p_out, idx, p.x, p.y);
+        if (XT) {
+          C2<T> t;
+          t.x = (T)p.x;
+          t.y = (T)p.y;
+          *bx_at(pt_out, tb) = t;
+        } else st2<T>(p_out, idx, p.x, p.y);
         if (wM) {
-          const double w = wM[idx];
+          const double w = XT ? bx_at(wt, wb)->y : wM[idx];
           q.x += eps * (w * p.x);
           q.y += eps * (w * p.y);
         }
-        st2<T>(q_out, idx, q.x, q.y);
+        if (XT) {
+          C2<T> t;
+          t.x = (T)q.x;
+          t.y = (T)q.y;
+          *bx_at(qt_out, tb) = t;
+        } else st2<T>(q_out, idx, q.x, q.y);
       }
     } else {
       double2 gg = make_double2(0., 0.);
@@ -280,8 +324,8 @@ k_step_boundary_x(Geo g, int log2n, const C2<T> *__restrict__ twiddle, C2<T> *Ck
         const double f = b * (1 / ksq);
         gg = make_double2(f * hk[m].x, f * hk[m].y);
       }
-      if (a != 0.) {
-        const double w = a * bx_load(wS + idx);
+      if (a != 0.) {  // 0 * wS is never formed: wS is infinite where the spectrum is 0
+        const double w = a * (XT ? (MODE == BX_INTERIOR ? w2.x : bx_load(&bx_at(wt, wb)->x)) : bx_load(wS + idx));
         gg.x += w * q.x;
         gg.y += w * q.y;
       }
@@ -291,7 +335,11 @@ k_step_boundary_x(Geo g, int log2n, const C2<T> *__restrict__ twiddle, C2<T> *Ck
       if (MODE == BX_LAST) {
         g_out[idx] = gs;
         if (p_out) {
-          const double2 p = ld2<T>(p_in, idx);
+          double2 p;
+          if (XT) {
+            const C2<T> t = *bx_at(pt_in, tb);
+            p = make_double2((double)t.x, (double)t.y);
+          } else p = ld2<T>(p_in, idx);
           C2<T> pe;
           pe.x = (T)(p.x - half_eps * gg.x);
           pe.y = (T)(p.y - half_eps * gg.y);
@@ -301,7 +349,7 @@ k_step_boundary_x(Geo g, int log2n, const C2<T> *__restrict__ twiddle, C2<T> *Ck
         }
         continue;
       }
-      const C2<T> pt = bx_load(p_in + idx);
+      const C2<T> pt = XT ? bx_load(bx_at(pt_in, tb)) : bx_load(p_in + idx);
       double2 p = make_double2((double)pt.x, (double)pt.y);
       C2<T> pe;
       pe.x = (T)(p.x - half_eps * gg.x);
@@ -314,10 +362,11 @@ k_step_boundary_x(Geo g, int log2n, const C2<T> *__restrict__ twiddle, C2<T> *Ck
         C2<T> t;
         t.x = (T)p.x;
         t.y = (T)p.y;
-        bx_store(p_out + idx, t);
+        if (XT) bx_store(bx_at(pt_out, tb), t);
+        else bx_store(p_out + idx, t);
       }
       if (wM) {
-        const double w = bx_load(wM + idx);
+        const double w = XT ? w2.y : bx_load(wM + idx);
         q.x += eps * (w * p.x);
         q.y += eps * (w * p.y);
       }
@@ -325,7 +374,8 @@ k_step_boundary_x(Geo g, int log2n, const C2<T> *__restrict__ twiddle, C2<T> *Ck
         C2<T> t;
         t.x = (T)q.x;
         t.y = (T)q.y;
-        bx_store(q_out + idx, t);
+        if (XT) bx_store(bx_at(qt_out, tb), t);
+        else bx_store(q_out + idx, t);
       }
     }
     qkeep[m].x = (T)q.x;
@@ -488,12 +538,13 @@ __device__ __forceinline__ void xfft_inplace2(C2<T> *__restrict__ sa, C2<T> *__r
   }
 }
 
-template <typename T, int NT, int PER>  // PER <= 4: eight elements per thread do not fit 128 registers with their operands
+// XT = true: q_in, p_in, q_out, p_out and the weights in x-column tiles, as k_step_boundary_x<BX_INTERIOR, XT> takes them.
+template <typename T, int NT, int PER, bool XT = false>  // PER <= 4: eight elements per thread do not fit 128 registers with their operands
 __global__ void __launch_bounds__(NT, BCHMC_BX_WAVES)
 k_step_boundary_x2(Geo g, int log2n, const C2<T> *__restrict__ twiddle, C2<T> *Ck, const C2<T> *q_in, const C2<T> *p_in,
                    C2<T> *q_out, C2<T> *p_out, const double *__restrict__ wS, const double *__restrict__ wM, double a,
                    double b, double half_eps, double eps, double c_za, double *guard_slot, StepCtl ctl, bool pair = false,
-                   bool vpair = false) {
+                   bool vpair = false, const double2 *__restrict__ wpair = nullptr) {
   constexpr int KB = 128 / (int)sizeof(C2<T>);
   extern __shared__ __attribute__((aligned(16))) unsigned char s_raw_x2[];
   __shared__ double red[NT / 64];
@@ -538,6 +589,14 @@ k_step_boundary_x2(Geo g, int log2n, const C2<T> *__restrict__ twiddle, C2<T> *C
     return reinterpret_cast<const double *>(reinterpret_cast<const char *>(base) + off);
   };
   C2<T> *const Ck1 = Ck + g.Nhp, *const Ck2 = Ck + 2 * g.Nhp;
+  // XT: the state arrays and the weight pair behind the tile's base (uniform), element (i, c) at byte toff[m]
+  const long long tbase = XT ? (long long)bid * n * KB : 0;
+  const C2<T> *const qt_in = q_in + tbase, *const pt_in = p_in + tbase;
+  C2<T> *const qt_out = q_out + tbase, *const pt_out = p_out + tbase;
+  const double2 *const wt = wpair + tbase;
+  unsigned toff[PER];
+#pragma unroll
+  for (int m = 0; m < PER; m++) toff[m] = XT ? (unsigned)(((irow + rows * m) * KB + c) * (int)sizeof(C2<T>)) : boff[m];
   {
     // ---- V^: all three components (vpair: V^_x and W, two) requested before the first one is used ----
     C2<T> vx[PER], vy[PER], vz[PER];
@@ -561,10 +620,15 @@ k_step_boundary_x2(Geo g, int log2n, const C2<T> *__restrict__ twiddle, C2<T> *C
 #pragma unroll
   for (int m = 0; m < PER; m++) {
     const unsigned woff = sizeof(C2<T>) == 16 ? boff[m] / 2 : boff[m];  // doubles at the same element index
-    qv[m] = bx_load(at_c(q_in, boff[m]));
-    pv[m] = bx_load(at_c(p_in, boff[m]));
-    ws[m] = (a != 0.) ? bx_load(at_d(wS, woff)) : 0.;
-    wm[m] = wM ? bx_load(at_d(wM, woff)) : 0.;
+    qv[m] = bx_load(at_c(qt_in, toff[m]));
+    pv[m] = bx_load(at_c(pt_in, toff[m]));
+    if (XT) {  // one load of {wS, wM}; 0 * wS is not formed below (a != 0. guards the use)
+      const double2 w2 = bx_load(bx_at(wt, sizeof(C2<T>) == 16 ? toff[m] : toff[m] * 2));
+      ws[m] = w2.x, wm[m] = w2.y;
+    } else {
+      ws[m] = (a != 0.) ? bx_load(at_d(wS, woff)) : 0.;
+      wm[m] = wM ? bx_load(at_d(wM, woff)) : 0.;
+    }
   }
   __syncthreads();
   xfft_inplace2<T, false>(sa, sb, tw, n, log2n, KB);
@@ -613,7 +677,7 @@ k_step_boundary_x2(Geo g, int log2n, const C2<T> *__restrict__ twiddle, C2<T> *C
       C2<T> t;
       t.x = (T)p.x;
       t.y = (T)p.y;
-      bx_store(at_cw(p_out, boff[m]), t);
+      bx_store(at_cw(pt_out, toff[m]), t);
     }
     if (wM) {
       q.x += eps * (wm[m] * p.x);
@@ -622,7 +686,7 @@ k_step_boundary_x2(Geo g, int log2n, const C2<T> *__restrict__ twiddle, C2<T> *C
     C2<T> qs;
     qs.x = (T)q.x;
     qs.y = (T)q.y;
-    bx_store(at_cw(q_out, boff[m]), qs);
+    bx_store(at_cw(qt_out, toff[m]), qs);
     // Psi^_j = k_j B, B = (1/k^2)(Im phi^, -Re phi^), phi^ = c_za q^': kx B from the stored q' as computed, B from q'
     // as stored (rounded to T) -- the two inputs the first formulation feeds its inverse passes
     C2<T> o, o2;
