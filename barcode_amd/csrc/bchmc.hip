@@ -103,6 +103,7 @@ struct bchmc_handle {
   DevBytes cq, cp;                                   // Nhp complex each
   DevBuf<double> part6;                              // 6 * kRedBlocks doubles
   bool have_cq = false, have_cp = false, have_prop = false;
+  bool cp_draw_rs = false;  // cp is a draw for a real-space mass alone, and mass_r is still the array it was drawn with
   // Force carried along the chain: g^ = FFT-space gradient_psi at the chain state cq, with its -log L.  The end of an
   // accepted trajectory (or the start of a rejected one) IS the next trajectory's start, so the gradient HMC.cc:279
   // evaluates there is already known; only the fast attempt mode uses it.  Any new input or state invalidates it.
@@ -2240,6 +2241,18 @@ struct Pipe {
     return BCHMC_OK;
   }
 
+  // dstage = the real-space copy of the resident momenta; after a draw for a real-space mass alone, exactly 0 where that
+  // mass is not positive, as the draw itself was (the resident form is k-space, and the way back leaves round-off there)
+  static int momenta_to_stage(bchmc_handle *h) {
+    CHK(c2r_state(h, h->cp, h->ioq, h->dstage));
+    if (h->cp_draw_rs) {
+      ProfScope ps(h, BCHMC_K_OTHER);
+      k_zero_closed<T><<<nblk_stride(h->g.N), 256, 0, h->stream>>>(h->g.N, R(h->in_arr[BCHMC_F_MASS_R]), h->dstage);
+      HIPCHK(hipGetLastError());
+    }
+    return BCHMC_OK;
+  }
+
   // log_like's forward model equals the force's one iff these hold (gaussian_independent.cpp:57-76 vs
   // poissonian.cpp:54-56, lognormal_independent.cpp:105-107); then the -log L of both trajectory ends can be tapped
   // from the trajectory's own first and last force evaluation, and K, psi_prior are Parseval sums of the k-space
@@ -4044,6 +4057,7 @@ int bchmc_upload(bchmc_handle *h, bchmc_field field, const double *host, size_t 
   CHK(DISPATCH(h, upload(h, field, h->dstage)));
   HIPCHK(hipStreamSynchronize(h->stream));
   h->have[field] = true;
+  if (field == BCHMC_F_MASS_R) h->cp_draw_rs = false;
   // gradient_psi and -log L do not involve the mass (it enters the kinetic term and the drift only)
   if (field != BCHMC_F_MASS_F && field != BCHMC_F_MASS_R) h->cg_valid = h->prop_g_valid = false;
   return BCHMC_OK;
@@ -4305,6 +4319,7 @@ int bchmc_chain_set_momenta(bchmc_handle *h, const double *p) {
   CHK(DISPATCH(h, r2c_state(h, h->dstage, h->iop, h->cp)));
   HIPCHK(hipStreamSynchronize(h->stream));
   h->have_cp = true;
+  h->cp_draw_rs = false;
   return BCHMC_OK;
 }
 
@@ -4319,6 +4334,7 @@ int bchmc_chain_draw_momenta(bchmc_handle *h, uint64_t seed, uint64_t attempt) {
   CHK(DISPATCH(h, chain_alloc(h)));
   CHK(DISPATCH(h, chain_draw(h, seed, attempt)));
   h->have_cp = true;
+  h->cp_draw_rs = h->mass_rs && !h->mass_fs;
   return BCHMC_OK;
 }
 
@@ -4336,6 +4352,7 @@ int bchmc_chain_draw_momenta_mt19937(bchmc_handle *h, uint32_t mt[624], int32_t 
   CHK(mt_setup(h));
   CHK(mt_draw(h, mt, mti, words_used, h->mt.G, false, mt_place_momenta));
   h->have_cp = true;
+  h->cp_draw_rs = h->mass_rs && !h->mass_fs;
   return BCHMC_OK;
 }
 
@@ -4367,7 +4384,8 @@ int bchmc_chain_get_momenta(bchmc_handle *h, double *p) {
   if (!h || !p) return BCHMC_ERR_ARG;
   ENTER(h);
   if (!h->have_cp) return h->fail(BCHMC_ERR_STATE, "no momenta set or drawn");
-  return chain_fetch(h, h->cp, p);
+  CHK(DISPATCH(h, momenta_to_stage(h)));
+  return d2h(h, p, h->dstage, h->g.N * sizeof(double));
 }
 
 int bchmc_chain_get_proposal(bchmc_handle *h, double *q1, double *p1) {
@@ -5343,6 +5361,7 @@ int bchmc_hamiltonian_mass(bchmc_handle *h, const double *signal, const bchmc_ma
   const size_t N = (size_t)h->g.N, bytes = N * sizeof(double);
   if (state && signal) CHK(h2d(h, h->dstage, signal, bytes));
   CHK(DISPATCH(h, mass_build(h, state && !signal, *opts, force, jasche)));
+  if (h->mass_rs) h->cp_draw_rs = false;
   if (h->mass_fs) h->have[BCHMC_F_MASS_F] = true;
   if (h->mass_rs) h->have[BCHMC_F_MASS_R] = true;
   if (mass_f && h->mass_fs) CHK(d2h(h, mass_f, h->dstage, bytes));

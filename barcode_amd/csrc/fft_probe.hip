@@ -24,6 +24,10 @@
 // on nblk_stride((n + 1) / 2) x 256 over n values of any parity (seed words, attempt and stream as the kernel takes them,
 // var may be null), k_color_momenta on nblk_stride(nh) x 256 over nh complex elements (wM may be null; pk goes in too).
 //
+// The generic trajectory's real-space mass and GRF kernels (tests/test_gpu_massrs.py) run the same way over `count`
+// elements: k_div_mass_r (in place too, as the engine calls it), k_grf_grad, k_scale_c and k_add_r on nblk_stride(count) x
+// 256, k_kin_rs and k_grf_loglike on kRedBlocks x 256 with every partial handed back.
+//
 // Every device array is followed by kCanary bytes of a known pattern; an entry point copies its host arrays in,
 // launches, synchronises, copies back and checks the canaries.  Return value: 0 = ok, -1 = arguments outside the
 // engine's instantiations, -2 = HIP error, k > 0 = the canary after device array k changed (1 = the twiddle table,
@@ -683,6 +687,79 @@ template <typename T> int color_momenta(long long nh, const void *wk, const doub
   return pr.finish({{i_pk, pk}});
 }
 
+// ---- the generic trajectory's real-space mass and GRF kernels ----------------------------------------------------------
+
+// what a probe over `count` elements accepts (the engine's largest grid is 512^3 = 2^27 cells)
+bool ok_count(long long count) { return count >= 1 && count <= (1ll << 27); }
+
+// k_div_mass_r over `count` cells: p, mass_r -> out (goes in too).  out == p is the engine's call (in place on iop): then
+// one device array holds both.
+template <typename T> int div_mass_r(long long count, const void *p, const void *mass_r, void *out_) {
+  if (!ok_count(count) || !p || !mass_r || !out_) return -1;
+  Probe pr;
+  const size_t rb = (size_t)count * sizeof(T);
+  const bool in_place = out_ == p;
+  T *dp = static_cast<T *>(pr.alloc(rb, p));
+  const T *dm = static_cast<const T *>(pr.alloc(rb, mass_r));
+  T *dout = in_place ? dp : static_cast<T *>(pr.alloc(rb, out_));
+  if (pr.err) return pr.err;
+  k_div_mass_r<T><<<nblk_stride(count), 256>>>(count, dp, dm, dout);
+  return pr.finish({{in_place ? 0 : 2, out_}});
+}
+
+// k_kin_rs over `count` cells: kRedBlocks partials (go in too)
+template <typename T> int kin_rs(long long count, const void *p, const void *mass_r, double *partials) {
+  if (!ok_count(count) || !p || !mass_r || !partials) return -1;
+  Probe pr;
+  const size_t rb = (size_t)count * sizeof(T);
+  const T *dp = static_cast<const T *>(pr.alloc(rb, p)), *dm = static_cast<const T *>(pr.alloc(rb, mass_r));
+  double *dpart = static_cast<double *>(pr.alloc((size_t)kRedBlocks * sizeof(double), partials));
+  if (pr.err) return pr.err;
+  k_kin_rs<T><<<kRedBlocks, 256>>>(count, dp, dm, dpart);
+  return pr.finish({{2, partials}});
+}
+
+// k_grf_grad / k_grf_loglike over `count` cells: q, nobs, noise, window -> out (goes in too) / kRedBlocks partials (go in too)
+template <typename T, bool ENERGY>
+int grf(long long count, const void *q, const void *nobs, const void *noise, const void *window, void *out_) {
+  if (!ok_count(count) || !q || !nobs || !noise || !window || !out_) return -1;
+  Probe pr;
+  const size_t rb = (size_t)count * sizeof(T);
+  const T *dq = static_cast<const T *>(pr.alloc(rb, q)), *dn = static_cast<const T *>(pr.alloc(rb, nobs));
+  const T *ds = static_cast<const T *>(pr.alloc(rb, noise)), *dw = static_cast<const T *>(pr.alloc(rb, window));
+  void *dout = pr.alloc(ENERGY ? (size_t)kRedBlocks * sizeof(double) : rb, out_);
+  if (pr.err) return pr.err;
+  if (ENERGY)
+    k_grf_loglike<T><<<kRedBlocks, 256>>>(count, dq, dn, ds, dw, static_cast<double *>(dout));
+  else
+    k_grf_grad<T><<<nblk_stride(count), 256>>>(count, dq, dn, ds, dw, static_cast<T *>(dout));
+  return pr.finish({{4, out_}});
+}
+
+// k_scale_c over `count` complex elements: in -> out (goes in too)
+template <typename T> int scale_c(long long count, const void *in, void *out_, double s) {
+  if (!ok_count(count) || !in || !out_) return -1;
+  Probe pr;
+  const size_t cb = (size_t)count * sizeof(C2<T>);
+  const C2<T> *din = static_cast<const C2<T> *>(pr.alloc(cb, in));
+  C2<T> *dout = static_cast<C2<T> *>(pr.alloc(cb, out_));
+  if (pr.err) return pr.err;
+  k_scale_c<T><<<nblk_stride(count), 256>>>(count, din, dout, s);
+  return pr.finish({{1, out_}});
+}
+
+// k_add_r over `count` cells: a, b -> out (goes in too)
+template <typename T> int add_r(long long count, const void *a, const void *b, void *out_) {
+  if (!ok_count(count) || !a || !b || !out_) return -1;
+  Probe pr;
+  const size_t rb = (size_t)count * sizeof(T);
+  const T *da = static_cast<const T *>(pr.alloc(rb, a)), *db = static_cast<const T *>(pr.alloc(rb, b));
+  T *dout = static_cast<T *>(pr.alloc(rb, out_));
+  if (pr.err) return pr.err;
+  k_add_r<T><<<nblk_stride(count), 256>>>(count, da, db, dout);
+  return pr.finish({{2, out_}});
+}
+
 }  // namespace
 
 // prec: 0 = double, 1 = float (the engine's storage type T); arrays are of that type, complex ones interleaved
@@ -921,6 +998,38 @@ int fftp_white_noise(int prec, long long n, unsigned seed_lo, unsigned seed_hi, 
 
 int fftp_color_momenta(int prec, long long nh, const void *wk, const double *wM, void *pk, int accumulate) {
   return prec ? color_momenta<float>(nh, wk, wM, pk, accumulate) : color_momenta<double>(nh, wk, wM, pk, accumulate);
+}
+
+// ---- the generic trajectory's real-space mass and GRF kernels (tests/test_gpu_massrs.py).  Device arrays: the arrays in
+// argument order; output arrays go in as well.  `partials`: fftp_parseval_blocks() doubles.
+
+// out == p runs the kernel in place, as the engine does on iop (device arrays then: 1 p and out, 2 mass_r)
+int fftp_div_mass_r(int prec, long long count, const void *p, const void *mass_r, void *out) {
+  return prec ? div_mass_r<float>(count, p, mass_r, out) : div_mass_r<double>(count, p, mass_r, out);
+}
+
+int fftp_kin_rs(int prec, long long count, const void *p, const void *mass_r, double *partials) {
+  return prec ? kin_rs<float>(count, p, mass_r, partials) : kin_rs<double>(count, p, mass_r, partials);
+}
+
+int fftp_grf_grad(int prec, long long count, const void *q, const void *nobs, const void *noise, const void *window,
+                  void *out) {
+  return prec ? grf<float, false>(count, q, nobs, noise, window, out) : grf<double, false>(count, q, nobs, noise, window, out);
+}
+
+int fftp_grf_loglike(int prec, long long count, const void *q, const void *nobs, const void *noise, const void *window,
+                     double *partials) {
+  return prec ? grf<float, true>(count, q, nobs, noise, window, partials)
+              : grf<double, true>(count, q, nobs, noise, window, partials);
+}
+
+// `count` complex elements
+int fftp_scale_c(int prec, long long count, const void *in, void *out, double s) {
+  return prec ? scale_c<float>(count, in, out, s) : scale_c<double>(count, in, out, s);
+}
+
+int fftp_add_r(int prec, long long count, const void *a, const void *b, void *out) {
+  return prec ? add_r<float>(count, a, b, out) : add_r<double>(count, a, b, out);
 }
 
 }  // extern "C"

@@ -211,6 +211,15 @@ __global__ void k_div_mass_r(long long n, const T *__restrict__ p, const T *__re
   }
 }
 
+// A momentum draw for a real-space mass alone is exactly 0 wherever mass_r is not positive (k_white_noise, k_mt_real_space).
+// Its real-space copy that went through the chain's resident k-space form and back holds the transform pair's round-off
+// there instead: put the zeros back.
+template <typename T>
+__global__ void k_zero_closed(long long n, const T *__restrict__ mass_r, double *__restrict__ x) {
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
+    if (!((double)mass_r[i] > 0.0)) x[i] = 0.;
+}
+
 // sum 0.5 * p * (p / mass_r): real-space part of kinetic_term (HMC.cc:88-110)
 template <typename T>
 __global__ void __launch_bounds__(256)

@@ -185,6 +185,9 @@ void *bchmc_stream(bchmc_handle *h); /* hipStream_t the engine launches on */
 int bchmc_chain_set_state(bchmc_handle *h, const double *q);   /* hd->x -> HBM */
 int bchmc_chain_get_state(bchmc_handle *h, double *q);
 int bchmc_chain_set_momenta(bchmc_handle *h, const double *p); /* host-drawn momenta (reference RNG order) */
+/* The resident momenta live in k-space; what comes back went through a transform pair.  After a draw (either kind below)
+ * for a real-space mass alone (mass_type 0, 6, 60) the cells where mass_r is not positive (<= 0 or NaN) come back exactly 0,
+ * as they were drawn, for as long as mass_r is the array of the draw. */
 int bchmc_chain_get_momenta(bchmc_handle *h, double *p);
 /* p ~ N(0, M) on the device: counter-based Philox4x32-10.  Statistical stand-in for draw_momenta (HMC_momenta.cc:42-94),
  * whose serial GSL stream it does not reproduce.
